@@ -10,6 +10,10 @@ per-rank frame sizes to stitch the global seek table + variable-length gather of
 
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps and prints the line. --full adds everything else the line reports, outside the timed
+region: the CPU baseline and bit-exactness gate, the RA spot check, other RA sizes and modes, RA latency, the host-pointer calls, BASELINE
+config 4's share and the GPU clocks. --dump-outputs DIR writes what the last timed step computed (see dump_outputs()).
 """
 import argparse
 import ctypes
@@ -404,6 +408,37 @@ def ra_latency_probe(Z, eng, d_arc, arc_size, d_in, N, qb, torch):
     return out
 
 
+def dump_outputs(path, d_arc, arc_size, d_ra, ra_bytes, torch):
+    """--dump-outputs: what a caller of the timed path receives from its last step — the archive and the random-access answers — for comparing
+    two builds output for output (bytes as float32, sums as float64, about 40 MB in all): archive_size; the archive's first 2 MiB (header and
+    seek table); 4 Mi bytes of each output at positions drawn from a fixed seed; the byte sum of every 1 MiB chunk of each, which every byte enters."""
+    os.makedirs(path, exist_ok=True)
+    dev = d_ra.device
+    MiB = 1 << 20
+
+    def chunk_sums(t):
+        out = []
+        for a in range(0, t.numel(), 256 * MiB):                # int64 sums of at most 256 MiB at a time
+            c = t[a: a + 256 * MiB]
+            full = c.numel() // MiB * MiB
+            out.append(c[:full].view(-1, MiB).sum(dim=1, dtype=torch.int64))
+            if full < c.numel():
+                out.append(c[full:].sum(dtype=torch.int64).view(1))
+        return torch.cat(out).cpu().numpy().astype(np.float64)
+
+    def sample(t, seed):
+        idx = np.sort(np.random.RandomState(seed).randint(0, t.numel(), size=min(t.numel(), 4 * MiB)))
+        return t[torch.from_numpy(idx).to(dev)].cpu().numpy().astype(np.float32)
+
+    torch.cuda.synchronize()
+    arc, ra = d_arc[:arc_size], d_ra[:ra_bytes]
+    for name, a in (("archive_size", np.array([arc_size], dtype=np.float64)),
+                    ("archive_head", arc[: 2 * MiB].cpu().numpy().astype(np.float32)),
+                    ("archive_sample", sample(arc, 1)), ("archive_chunk_sums", chunk_sums(arc)),
+                    ("ra_sample", sample(ra, 2)), ("ra_chunk_sums", chunk_sums(ra))):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def choose_comm(eng, rank, world, one_gpu, dev, dist, sharding, torch, want, group=None):
     """The communicator of a multi-rank run: RCCL called by the library itself (ncclAllGather / grouped ncclSend+ncclRecv on the engine's
     stream), or the host transport over torch.distributed — the fallback, and the only choice when every rank sits on one GPU (RCCL
@@ -440,6 +475,8 @@ def main():
     ap.add_argument("--timed-only", action="store_true", help="nothing but the timed steps (PMC passes: tools/pmc_bench.sh)")
     ap.add_argument("--no-host-calls", action="store_true", help="skip the host-pointer extras (4 GiB through zratool_amd b, outside the timed region)")
     ap.add_argument("--no-c4", action="store_true", help="skip BASELINE config 4's one-GPU share (2 GiB log-like, level 9 @ 256 KiB, outside the timed region)")
+    ap.add_argument("--full", action="store_true", help="also run the baselines, checks and extra measurements outside the timed region (the --no-* options above leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     # stdout carries exactly one line, the JSON: libraries that print banners on first use (RCCL's version block, gloo's rank lines)
@@ -510,7 +547,7 @@ def main():
     # ---- bit-exactness gate + CPU baseline (rank 0): first 1 GiB of the same corpus through the CPU path
     cpu = None
     gate = "skipped"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # N=1 only (bench contract); N>1 runs reuse the N=1 gate
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # N=1 only (bench contract); N>1 runs reuse the N=1 gate
         samp = min(N, 1 << 30)
         # the CPU sample keeps the step's own blend of compressed bytes to queries (16 GiB : 1 M -> 1 GiB : 62.5 k)
         cpu_nq = max(1000, int(round(q * samp / float(N))))
@@ -597,21 +634,25 @@ def main():
     for _ in range(args.warmup):
         step()
     comp_ms.clear(); ra_ms.clear(); mf_ms.clear(); dec_stats.clear(); dec_stage.clear()
-    clocks_before = gpu_clocks() if rank == 0 else None
+    clocks_before = gpu_clocks() if rank == 0 and args.full else None
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     sync_all()
     elapsed = time.perf_counter() - t0
-    clocks_after = gpu_clocks() if rank == 0 else None
+    clocks_after = gpu_clocks() if rank == 0 and args.full else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # before anything below reuses the buffers (the RA extras answer into d_ra)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_arc if world == 1 else step.root, arc_size, d_ra, q * qb, torch)
+
     # spot-check RA output of the last step against the resident input
-    chk = rng.randint(0, q, size=64)
+    chk = rng.randint(0, q, size=64) if args.full else []
     other = {}                                            # N>1: the corpus of the rank that owns the bytes, regenerated on the host
     for i in chk:
         o = int(offs[i])
@@ -630,7 +671,7 @@ def main():
 
     # SURVEY §8d RA size classes (outside the timed region, single rank): 64 KiB unaligned (touches 2 frames) and 1 MiB queries
     ra_classes = {}
-    if world == 1 and not args.timed_only:
+    if world == 1 and args.full and not args.timed_only:
         for qsz, nq2 in ((65536, 100000), (1 << 20, 8000)):
             o2 = rng.randint(0, N - qsz - 1, size=nq2).astype(np.uint64)
             s2 = np.full(nq2, qsz, dtype=np.uint64); oo2 = (np.arange(nq2, dtype=np.uint64) * qsz)
@@ -648,7 +689,7 @@ def main():
     # the other RA mode, outside the timed region: the same 1 M queries with the option flipped (whole frames when the timed leg stopped
     # early, early stop when the timed leg — the default since round 6 — decoded whole frames)
     ra_other = None
-    if world == 1 and not args.timed_only:
+    if world == 1 and args.full and not args.timed_only:
         lib_opts.ZraHipSetOptions((opts_before & ~8) if ra_whole_timed else (opts_before | 8))
         try:
             eng.decompress_ra_batch(d_arc.data_ptr(), arc_size, d_ra.data_ptr(), offs, sizes, oofs)     # warm
@@ -666,16 +707,16 @@ def main():
 
     lib_opts.ZraHipSetOptions(opts_before)              # (the probes below measure the library's defaults)
     ra_latency = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         ra_latency = ra_latency_probe(Z, eng, d_arc, arc_size, d_in, N, qb, torch)
 
     host_calls = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_host_calls:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.no_host_calls:
         host_calls = host_pointer_calls(args.level, fs)
 
     # BASELINE config 4's one-GPU share (level 9 @ 256 KiB, log-like), outside the timed region; needs the oracle for its gate + CPU leg
     c4 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.timed_only and not args.no_c4:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.timed_only and not args.no_c4:
         c4 = c4_share(Z, eng, torch, dev)
 
     # compressed bytes of the frames the timed queries touch (for the random-access leg's roofline): the archive's own seek table
