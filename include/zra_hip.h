@@ -65,6 +65,55 @@ ZRA_EXPORT ZraStatus ZraHipDecompressBuffer(ZraHipEngine* engine, const void* dI
 ZRA_EXPORT ZraStatus ZraHipDecompressRABatch(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dOut,
                                              const uint64_t* hOffsets, const uint64_t* hSizes, const uint64_t* hOutOffsets, size_t nQueries);
 
+/* ---- archive handle: a device-resident archive opened once, with a cache of whole decoded frames in HBM ----
+ * The reference's Decompressor holds the parsed header and takes a maxCacheSize (zra.h); this is its device-pointer counterpart.
+ * A read whose frames are all resident costs one query upload, one copy kernel and one small read-back — no decode. */
+typedef struct ZraHipArchive ZraHipArchive;
+
+/** Opens the archive at dArchive (archiveSize bytes, device memory) on `engine`.
+ *  - Validation and statuses are ZraHipDecompressRABatch's: archiveSize <= 38 or < the header size -> OutOfBoundsAccess; a fixed-header
+ *    problem -> that status (HeaderInvalid / ZraVersionLow); a seek table outside the header or ceil(uncompressedSize / frameSize) !=
+ *    frames -> HeaderInvalid.
+ *  - The header is read from the device here, once; no read copies it again.
+ *  - Slots = min(cacheBytes / frameSize, frames), each one frame of frameSize bytes in an arena of the handle's own (not engine scratch:
+ *    ZraHipReleaseScratch does not touch it). An arena or tables that cannot be allocated -> {ZStdError, 64} (memory_allocation); no
+ *    handle is written and nothing is kept.
+ *  - engine NULL, dArchive NULL with archiveSize != 0, or archive NULL -> {ZStdError, 42}.
+ *  - The archive's bytes must stay valid and unchanged until ZraHipArchiveClose; a caller that rewrites them calls ZraHipArchiveDropCache.
+ *  Threading is the engine's: one call at a time per engine. Several handles may share one engine, each with its own arena; close every
+ *  handle before destroying its engine. */
+ZRA_EXPORT ZraStatus ZraHipArchiveOpen(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, size_t cacheBytes,
+                                       ZraHipArchive** archive);
+/** Releases the handle and its arena. NULL is a no-op. */
+ZRA_EXPORT void ZraHipArchiveClose(ZraHipArchive* archive);
+/** Query i returns bytes [hOffsets[i], hOffsets[i] + hSizes[i]) of the content at dOut + hOutOffsets[i] (host arrays, as
+ *  ZraHipDecompressRABatch). Synchronous.
+ *  - Bounds: the reference's rule, offset + size >= uncompressedSize -> OutOfBoundsAccess (zra.cpp:260). A refused call changes no
+ *    counter and no resident frame.
+ *  - 0 slots: exactly ZraHipDecompressRABatch on the same archive (bytes, statuses, partial decode, the ZRA_HIP_OPT_RA_WHOLE_FRAMES
+ *    opt-in); only the header read is gone.
+ *  - At least 1 slot: every frame the handle decodes is decoded whole and its content checksum verified if it has one. On a valid archive
+ *    the answers equal ZraHipDecompressRABatch's, and dOut bytes outside them are not touched. On a damaged archive the status is that of
+ *    ZraHipDecompressRABatch under ZRA_HIP_OPT_RA_WHOLE_FRAMES, whatever the process-wide option says.
+ *  - Residency: a frame becomes resident only if it decoded with status 0 and regenerated exactly min(frameSize, uncompressedSize -
+ *    f * frameSize) bytes. A read that returns an error leaves every slot it claimed for decoding empty; frames resident before it that it
+ *    did not claim stay. A frame that failed is never served from the cache: the next read decodes it again and fails again alike.
+ *  - Counting: for each accepted read, hits + misses = the distinct frames its non-empty queries touch (duplicate and overlapping queries
+ *    share a frame). When the missed frames outnumber the slots they are decoded in passes of at most `slots` frames into the same slots:
+ *    every answer is still right, and at most `slots` frames are resident afterwards.
+ *  - Eviction is CLOCK (second chance): a frame is inserted with its reference bit clear and a hit sets it; the hand clears set bits and
+ *    passes those slots, and takes clear or empty slots as victims, in hand order. So with S slots, if every read touches one hot frame
+ *    H and K < S/2 frames never touched before, H is a hit on every read after the first.
+ *  - ZraHipGetKernelStats / ZraHipGetDecodeStageStats describe the read afterwards, like any call on the engine; a read whose frames were
+ *    all resident reports 0 decode launches. */
+ZRA_EXPORT ZraStatus ZraHipArchiveRead(ZraHipArchive* archive, void* dOut, const uint64_t* hOffsets, const uint64_t* hSizes,
+                                       const uint64_t* hOutOffsets, size_t nQueries);
+/** Forgets every resident frame (the counters stay). */
+ZRA_EXPORT ZraStatus ZraHipArchiveDropCache(ZraHipArchive* archive);
+/** out8 = {cache slots, frames resident now, reads accepted, frame hits, frame misses (= frames decoded), evictions,
+ *  uncompressed size, frame size}; counters 2-5 are cumulative since the handle was opened. */
+ZRA_EXPORT void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8);
+
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody
  *  (capacity nFrames*ZSTD_compressBound(frameSize)); writes the nFrames local frame sizes (u64, device) to dSizes and the

@@ -118,6 +118,12 @@ def load():
         "ZraHipDecompressRABatch": (S, [vp, vp, sz, vp, u64p, u64p, u64p, sz]),
         "ZraHipCompressFrames": (S, [vp, vp, sz, vp, vp, szp, ctypes.c_int8, u32, ctypes.c_bool]),
         "ZraHipStitchHeader": (S, [u64p, sz, ctypes.c_uint64, u32, vp, szp]),
+        # archive handle
+        "ZraHipArchiveOpen": (S, [vp, vp, sz, sz, ctypes.POINTER(vp)]),
+        "ZraHipArchiveClose": (None, [vp]),
+        "ZraHipArchiveRead": (S, [vp, vp, u64p, u64p, u64p, sz]),
+        "ZraHipArchiveDropCache": (S, [vp]),
+        "ZraHipArchiveGetStats": (None, [vp, u64p]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -160,7 +166,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCompressBuffer", "ZraHipDecompressBuffer", "ZraHipDecompressRABatch", "ZraHipCompressFrames", "ZraHipStitchHeader", "ZraHipDebugReadSeqs", "ZraHipSetOptions", "ZraHipGetOptions",
                    "ZraHipShardRange", "ZraHipOwnerOfFrame", "ZraHipRouteQueries", "ZraHipCommGetUniqueId", "ZraHipCommCreateRccl", "ZraHipCommCreateHost", "ZraHipCommLoopback", "ZraHipCommDestroy",
                    "ZraHipCommCompress", "ZraHipCommStitchSizes", "ZraHipShardDestroy", "ZraHipShardHeaderSize", "ZraHipShardGetHeader", "ZraHipShardArchiveSize", "ZraHipShardGetBody",
-                   "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe"]
+                   "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe",
+                   "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats"]
 
 
 def _chk(st, what=""):
@@ -323,6 +330,58 @@ class Engine:
         self._order()
         _chk(self.L.ZraHipCompressFrames(self.h, d_in, in_size, d_body, d_sizes, ctypes.byref(bsz), level, frame_size, checksum))
         return bsz.value
+
+
+ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
+
+
+class Archive:
+    """Archive handle (include/zra_hip.h: ZraHipArchive*): a device-resident archive opened once on `engine`, with a cache of whole
+    decoded frames in an HBM arena of `cache_bytes` (0: no cache, reads are ZraHipDecompressRABatch). The archive's bytes must stay
+    valid and unchanged until close(). Keeps its Engine alive: the engine is not destroyed before the handle."""
+
+    def __init__(self, engine, d_archive_ptr, size, cache_bytes=0):
+        self.engine = engine
+        self.L = engine.L
+        self.h = None
+        h = ctypes.c_void_p()
+        engine._order()
+        _chk(self.L.ZraHipArchiveOpen(engine.h, d_archive_ptr, size, cache_bytes, ctypes.byref(h)), "ZraHipArchiveOpen")
+        self.h = h
+
+    def read(self, d_out, offsets, sizes, out_offsets):
+        import numpy as np
+        o = np.ascontiguousarray(offsets, dtype=np.uint64)
+        s = np.ascontiguousarray(sizes, dtype=np.uint64)
+        oo = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveRead(self.h, d_out, p(o), p(s), p(oo), len(o)), "ZraHipArchiveRead")
+
+    def stats(self):
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipArchiveGetStats(self.h, a)
+        return dict(zip(ARCHIVE_STATS, (int(v) for v in a)))
+
+    def drop_cache(self):
+        _chk(self.L.ZraHipArchiveDropCache(self.h), "ZraHipArchiveDropCache")
+
+    def close(self):
+        if self.h:
+            self.L.ZraHipArchiveClose(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def stitch_header(frame_sizes, uncompressed_size, frame_size):

@@ -1,0 +1,43 @@
+// zra_amd — archive handle: a device-resident archive opened once (header parsed a single time) with a cache of whole decoded frames
+// in an HBM arena of its own (zra_hip.h: ZraHipArchive*). The engine's streams and decoder do the work; zra_archive.hip.
+#pragma once
+#include "zra_engine.h"
+
+namespace zra_eng {
+
+class ArchiveCache {
+ public:
+  // the archive checks of ZraHipDecompressRABatch; slots = min(cacheBytes / frameSize, frames); memory_allocation (64) when the arena
+  // or the tables cannot be had (nothing is kept then)
+  static Status open(Engine* e, const uint8_t* dArc, size_t arcSize, size_t cacheBytes, ArchiveCache** out);
+  ~ArchiveCache();
+  // query i: bytes [hOff[i], hOff[i] + hSize[i]) of the content at dOut + hOutOff[i]; wholeFramesOpt: the process-wide
+  // ZRA_HIP_OPT_RA_WHOLE_FRAMES (what a handle without slots follows, like the batch call)
+  Status read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt);
+  // forget every resident frame (the cumulative counters stay)
+  Status drop();
+  // {slots, resident, reads, hits, misses, evictions, uncompressed size, frame size}
+  void stats(uint64_t out[8]) const;
+
+ private:
+  ArchiveCache() = default;
+  Status read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
+  Engine* e_ = nullptr;
+  const uint8_t* dArc_ = nullptr;
+  size_t arcSize_ = 0;
+  HeaderInfo h_{};
+  uint32_t nFrames_ = 0, slots_ = 0, maxPass_ = 0;
+  // device state, one allocation: slotOf[nFrames] | frameOf[slots] | victim[maxPass] (u32) | ref[slots] (u8) | hand (u32) + counters (u64)
+  void* state_ = nullptr;
+  uint8_t* arena_ = nullptr;            // slots x frameSize
+  uint32_t* slotOf_ = nullptr;          // frame -> slot, kNone when not resident
+  uint32_t* frameOf_ = nullptr;         // slot -> frame, kEmpty when free
+  uint32_t* victim_ = nullptr;          // the slots the current read decodes into
+  uint8_t* ref_ = nullptr;              // CLOCK reference bit (2: claimed by the running read)
+  uint32_t* hand_ = nullptr;
+  unsigned long long* dctr_ = nullptr;  // {evictions, resident}
+  uint64_t* pin_ = nullptr;             // page-locked read-back words
+  uint64_t reads_ = 0, hits_ = 0, misses_ = 0, evictions_ = 0, resident_ = 0;
+};
+
+}  // namespace zra_eng

@@ -1,0 +1,300 @@
+// zra_amd — archive handle with a cache of decoded frames (zra_archive.h, zra_hip.h: ZraHipArchive*).
+//
+// A read whose frames are all resident costs the query upload, ONE launch (zra_cache_lookup_kernel: every slice of a resident frame
+// is copied out of the arena, every other frame is counted as a miss) and one 8-byte read-back. Misses go through the batch's own
+// planner and decoder, whole frames, into arena slots chosen by CLOCK (zra_cache_victims_kernel), and are published by
+// zra_cache_commit_kernel once they have decoded cleanly.
+//
+// Ordering conditions of a read (all on the engine's stream):
+//  (a) hit or miss is decided ONCE per frame, by the lookup kernel, before anything in the read changes slotOf. The planner and the
+//      fill kernel go by that snapshot (RaPlan::cnt != 0), never by slotOf: a frame hit earlier in the read and evicted as a victim
+//      afterwards has no job, and must get no piece.
+//  (b) the lookup kernel (every hit copy) runs before the victims kernel and the decoder: no hit can read a slot that is being
+//      overwritten.
+//  (c) a frame is mapped (slotOf / frameOf) only by the commit kernel, after its decode pass: no lookup can find a half-decoded slot.
+#include "zra_archive.h"
+#include "zra_dev.h"
+#include "zra_kernels.h"
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+using namespace zra_dev;
+
+namespace {
+constexpr u32 kNone = 0xFFFFFFFFu;    // slotOf: the frame is not resident
+constexpr u32 kEmpty = 0xFFFFFFFFu;   // frameOf: the slot holds no frame
+constexpr u8 kClaimed = 2;            // ref: the slot is being decoded into by the running read (neither a victim again nor skipped)
+constexpr u32 kMaxPass = 1u << 16;    // frames of one decode pass: well inside one internal pass of Engine::decode_jobs (>= 128 Ki frames)
+
+// one wave copies one slice: 16-byte moves when source and destination share their alignment modulo 16, copy_bytes' 8-byte ones otherwise
+__device__ __forceinline__ void copy_slice(u8* dst, const u8* src, u32 n, int lane) {
+  if ((((uintptr_t)dst ^ (uintptr_t)src) & 15u) || n < 64) { copy_bytes(dst, src, n, lane, 64); return; }
+  const u32 head = (u32)((16u - ((uintptr_t)dst & 15u)) & 15u);
+  if ((u32)lane < head) dst[lane] = src[lane];
+  const u32 n16 = (n - head) >> 4;
+  const uint4* s4 = (const uint4*)(src + head);
+  uint4* d4 = (uint4*)(dst + head);
+  for (u32 i = lane; i < n16; i += 64) d4[i] = s4[i];
+  for (u32 i = head + (n16 << 4) + lane; i < n; i += 64) dst[i] = src[i];
+}
+}  // namespace
+
+// Wave per slice (slice = the part of a query inside one frame; q[4i + 3] = the first slice of query i, as the batch's direct kernel
+// reads it). Resident frame: the slice is copied from the arena to out and the slot's reference bit set; the frame counts as a hit
+// once (seen[]). Otherwise the slice is counted into cnt[f] (the planner's piece count) and the frame as a miss once.
+// words[0] = distinct missed frames, words[1] = distinct hit frames.
+extern "C" __global__ void __launch_bounds__(256) zra_cache_lookup_kernel(const u64* q, u32 nq, u64 nSlices, u64 fs, const u32* slotOf, u8* ref,
+                                                                        const u8* arena, u8* out, u32* cnt, u32* seen, u32* words) {
+  const int lane = (int)(threadIdx.x & 63);
+  for (u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); s < nSlices; s += (u64)gridDim.x * 4) {
+    // the query that holds slice s: the last one whose first slice is <= s (a query of size 0 owns no slice)
+    u32 lo = 0, hi = nq - 1;
+    while (lo < hi) {
+      const u32 mid = lo + (hi - lo + 1) / 2;
+      if (q[4 * (size_t)mid + 3] <= s) lo = mid; else hi = mid - 1;
+    }
+    const u64 off = q[4 * (size_t)lo], size = q[4 * (size_t)lo + 1], dst = q[4 * (size_t)lo + 2], k = s - q[4 * (size_t)lo + 3];
+    const u64 f0 = off / fs, f = f0 + k, head = off - f0 * fs;
+    const u32 srcOff = k ? 0u : (u32)head;
+    const u64 done = k ? (fs - head) + (k - 1) * fs : 0;
+    const u32 len = (u32)min<u64>(fs - srcOff, size - done);
+    const u32 v = slotOf[f];
+    if (v != kNone) {
+      copy_slice(out + dst + done, arena + (u64)v * fs + srcOff, len, lane);
+      if (lane == 0) {
+        if (!ref[v]) ref[v] = 1;
+        if (atomicExch(&seen[f], 1u) == 0) atomicAdd(&words[1], 1u);
+      }
+    } else if (lane == 0) {
+      if (atomicAdd(&cnt[f], 1u) == 0) atomicAdd(&words[0], 1u);
+    }
+  }
+}
+
+// One workgroup. reuse == 0: CLOCK from *hand — a slot whose reference bit is set has it cleared and is passed over, an empty slot or one
+// with a clear bit becomes the next victim, until V are chosen; the hand stops behind the last. reuse != 0: the V slots in victim[]
+// again (a later decode pass of the same read). Either way every victim's frame is unmapped (counted as an eviction) and the slot
+// claimed. ctr = {evictions, resident}.
+extern "C" __global__ void __launch_bounds__(1024) zra_cache_victims_kernel(u32* slotOf, u32* frameOf, u8* ref, u32* hand, unsigned long long* ctr,
+                                                                         u32 slots, u32 V, u32* victim, u32 reuse) {
+  __shared__ u32 sWave[16], sCut, sEvict;
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) sEvict = 0;
+  __syncthreads();
+  auto claim = [&](u32 v) {
+    const u32 old = frameOf[v];
+    if (old != kEmpty) { slotOf[old] = kNone; frameOf[v] = kEmpty; atomicAdd(&sEvict, 1u); }
+    ref[v] = kClaimed;
+  };
+  if (reuse) {
+    for (u32 i = tid; i < V; i += 1024) claim(victim[i]);
+  } else {
+    const u32 C = min(slots, 1024u);                         // a chunk never holds one slot twice
+    u32 pos = *hand, taken = 0;
+    // (terminates: V <= slots, a claimed slot is never a candidate again, and one turn of the hand clears every reference bit)
+    while (taken < V) {
+      const bool in = tid < C;
+      const u32 p = in ? (pos + tid < slots ? pos + tid : pos + tid - slots) : 0u;
+      const u8 r = in ? ref[p] : kClaimed;
+      const bool cand = in && r != kClaimed && (r == 0 || frameOf[p] == kEmpty);
+      const u64 m = __ballot(cand);
+      const u32 rank = (u32)__popcll(m & ((1ull << lane) - 1));
+      if (lane == 0) sWave[wave] = (u32)__popcll(m);
+      __syncthreads();
+      u32 before = 0, total = 0;
+      for (u32 w = 0; w < 16; w++) { const u32 c = sWave[w]; before += w < wave ? c : 0u; total += c; }
+      const u32 need = V - taken, r2 = before + rank;
+      if (cand && total >= need && r2 == need - 1) sCut = tid;          // the hand stops behind the last victim it needs
+      __syncthreads();
+      const u32 cut = total >= need ? sCut : C - 1;
+      if (in && tid <= cut) {
+        if (cand) { victim[taken + r2] = p; claim(p); }
+        else if (r == 1) ref[p] = 0;                                  // second chance
+      }
+      taken += min(total, need);
+      pos = pos + cut + 1 < slots ? pos + cut + 1 : pos + cut + 1 - slots;
+      __syncthreads();                                                // (sWave, sCut of the next chunk)
+    }
+    if (tid == 0) *hand = pos;
+  }
+  __syncthreads();
+  if (tid == 0 && sEvict) { ctr[0] += sEvict; ctr[1] -= sEvict; }
+}
+
+// After decode pass [s0, s0 + n) of the planned jobs (jobOf = RaPlan::slot, job numbers in frame order): a frame of the pass that decoded
+// with status 0 and exactly its size is published in its slot (reference bit clear); any other leaves its slot empty, and so does every
+// slot of a pass that failed (passOk == 0). Claimed slots the pass did not need (its last, short pass) are released empty.
+extern "C" __global__ void __launch_bounds__(256) zra_cache_commit_kernel(const u32* cnt, const u32* jobOf, u32 nFrames, u32 s0, u32 n, const u32* victim,
+                                                                        u32 V, const u32* status, const u32* produced, u32 passOk, u64 fs, u64 total,
+                                                                        u32* slotOf, u32* frameOf, u8* ref, unsigned long long* ctr) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < nFrames && cnt[t]) {
+    const u32 st = jobOf[t];
+    if (st >= s0 && st - s0 < n) {
+      const u32 j = st - s0, v = victim[j];
+      const u64 o = (u64)t * fs;
+      const u32 expect = o >= total ? 0u : (u32)min<u64>(fs, total - o);
+      if (passOk && status[j] == 0 && produced[j] == expect) { slotOf[t] = v; frameOf[v] = t; atomicAdd(&ctr[1], 1ull); }
+      ref[v] = 0;
+    }
+  }
+  if (t >= n && t < V) ref[victim[t]] = 0;
+}
+
+// =================================================================================================
+namespace zra_eng {
+
+#define ACHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return zerr(1); } } while (0)
+
+Status ArchiveCache::open(Engine* e, const uint8_t* dArc, size_t arcSize, size_t cacheBytes, ArchiveCache** out) {
+  ACHK(hipSetDevice(e->device_));
+  HeaderInfo h;
+  { Status st = e->ra_header(dArc, arcSize, &h); if (st.zra) return st; }
+  ArchiveCache* c = new ArchiveCache();
+  c->e_ = e; c->dArc_ = dArc; c->arcSize_ = arcSize; c->h_ = h;
+  c->nFrames_ = h.frames();
+  const uint64_t fs = h.frameSize;
+  c->slots_ = fs ? (uint32_t)std::min<uint64_t>(cacheBytes / fs, c->nFrames_) : 0u;
+  c->maxPass_ = std::min(c->slots_, kMaxPass);
+  const size_t S = c->slots_, F = c->nFrames_;
+  const size_t u32Bytes = (F + S + c->maxPass_) * 4, stateBytes = ((u32Bytes + S + 7) & ~(size_t)7) + 8 + 16;
+  auto fail = [&]() { (void)hipGetLastError(); delete c; return zerr(64); };
+  if (hipHostMalloc((void**)&c->pin_, 64, hipHostMallocDefault) != hipSuccess) { c->pin_ = nullptr; return fail(); }
+  if (S) {
+    if (hipMalloc((void**)&c->arena_, S * fs) != hipSuccess) { c->arena_ = nullptr; return fail(); }
+    if (hipMalloc(&c->state_, stateBytes) != hipSuccess) { c->state_ = nullptr; return fail(); }
+    uint8_t* b = (uint8_t*)c->state_;
+    c->slotOf_ = (uint32_t*)b; c->frameOf_ = c->slotOf_ + F; c->victim_ = c->frameOf_ + S;
+    c->ref_ = b + u32Bytes;
+    c->hand_ = (uint32_t*)(b + ((u32Bytes + S + 7) & ~(size_t)7));
+    c->dctr_ = (unsigned long long*)((uint8_t*)c->hand_ + 8);
+    if (hipMemsetAsync(b, 0xFF, u32Bytes, e->stream_) != hipSuccess ||
+        hipMemsetAsync(c->ref_, 0, stateBytes - u32Bytes, e->stream_) != hipSuccess || hipStreamSynchronize(e->stream_) != hipSuccess) {
+      (void)hipGetLastError(); delete c; return zerr(1);
+    }
+  }
+  *out = c;
+  return ok();
+}
+
+ArchiveCache::~ArchiveCache() {
+  if (e_) { (void)hipSetDevice(e_->device_); (void)hipStreamSynchronize(e_->stream_); }
+  if (arena_) (void)hipFree(arena_);
+  if (state_) (void)hipFree(state_);
+  if (pin_) (void)hipHostFree(pin_);
+}
+
+void ArchiveCache::stats(uint64_t out[8]) const {
+  const uint64_t v[8] = {slots_, resident_, reads_, hits_, misses_, evictions_, h_.uncompressedSize, h_.frameSize};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+
+Status ArchiveCache::drop() {
+  ACHK(hipSetDevice(e_->device_));
+  if (!slots_) return ok();
+  ACHK(hipMemsetAsync(slotOf_, 0xFF, ((size_t)nFrames_ + slots_) * 4, e_->stream_));
+  ACHK(hipMemsetAsync(ref_, 0, slots_, e_->stream_));
+  ACHK(hipMemsetAsync(dctr_ + 1, 0, 8, e_->stream_));
+  ACHK(hipStreamSynchronize(e_->stream_));
+  resident_ = 0;
+  return ok();
+}
+
+Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt) {
+  Engine& E = *e_;
+  ACHK(hipSetDevice(E.device_));
+  if (!slots_) {
+    // no cache: the batch call itself, header read and checked at open
+    E.set_ra_verify_whole_frames(wholeFramesOpt);
+    Status st = E.ra_batch_body(dArc_, h_, dArc_ + h_.size, arcSize_ - h_.size, 0, dOut, hOff, hSize, hOutOff, nq);
+    if (st.zra == kOutOfBounds) return st;
+    reads_++;
+    const uint64_t fs = h_.frameSize;
+    if (fs && nFrames_) {
+      std::vector<uint8_t> seen(nFrames_, 0);
+      for (size_t i = 0; i < nq; i++) {
+        if (!hSize[i]) continue;
+        for (uint64_t f = hOff[i] / fs, f1 = (hOff[i] + hSize[i] - 1) / fs; f <= f1; f++) {
+          if (!seen[f]) misses_++;
+          seen[f] = 1;
+        }
+      }
+    }
+    return st;
+  }
+  E.kstats_[4] = E.kstats_[5] = 0; for (auto& d : E.dstats_) d = 0;
+  return read_cached(dOut, hOff, hSize, hOutOff, nq);
+}
+
+Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+  Engine& E = *e_;
+  hipStream_t s = E.stream_;
+  const uint64_t fs = h_.frameSize, U = h_.uncompressedSize;
+  const uint32_t nF = nFrames_;
+  if (nq == 0) { reads_++; return ok(); }
+  uint64_t nSlices = 0;
+  { Status st = E.ra_walk_queries(h_, hOff, hSize, hOutOff, nq, &nSlices); if (st.zra) return st; }
+  reads_++;
+  if (nSlices == 0) { ACHK(hipStreamSynchronize(s)); return ok(); }
+  // the batch's planner arrays (RaPlan: cnt, need, slot, cursor, then its totals in 16 words), the lookup's two result words inside those
+  // 16, then seen[nFrames]: one memset
+  const size_t planWords = 4 * (size_t)nF + 16;
+  if (!E.raPlan_.reserve((planWords + nF) * 4)) return zerr(64);
+  uint32_t* plan = E.raPlan_.as<uint32_t>();
+  uint32_t* words = plan + 4 * (size_t)nF + 8;
+  ACHK(hipMemsetAsync(plan, 0, (planWords + nF) * 4, s));
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((nSlices + 3) / 4, 1u << 20);
+  hipLaunchKernelGGL(zra_cache_lookup_kernel, dim3(grid), dim3(256), 0, s, E.qmeta_.as<uint64_t>(), (u32)nq, (u64)nSlices, (u64)fs, slotOf_, ref_,
+                     arena_, dOut, plan, plan + planWords, words);
+  ACHK(hipMemcpyAsync(pin_, words, 8, hipMemcpyDeviceToHost, s));
+  ACHK(hipStreamSynchronize(s));
+  ACHK(hipGetLastError());
+  const uint32_t missed = ((const uint32_t*)pin_)[0], hit = ((const uint32_t*)pin_)[1];
+  hits_ += hit; misses_ += missed;
+  if (!missed) return ok();
+
+  // ---- misses: whole frames into CLOCK victims, passes of at most maxPass_ frames through the batch's planner and decoder
+  if (!E.frameOff_.reserve(((size_t)nF + 1) * 16) || !E.outOff_.reserve((size_t)nF * 8) || !E.expect_.reserve((size_t)nF * 4) ||
+      !E.raLimit_.reserve((size_t)nF * 4) || !E.raPieceBase_.reserve(((size_t)nF + 1) * 4) || !E.raPieces_.reserve((size_t)nSlices * sizeof(ZraRaPiece) + 64))
+    return zerr(64);
+  const uint32_t V = std::min(missed, maxPass_);
+  hipLaunchKernelGGL(zra_cache_victims_kernel, dim3(1), dim3(1024), 0, s, slotOf_, frameOf_, ref_, hand_, dctr_, slots_, V, victim_, 0u);
+  uint32_t totals[2];
+  Status fail = E.ra_plan_fill(plan, nq, nF, dArc_ + h_.seekTableOffset, 0, fs, U, V, true, victim_, totals);
+  const uint32_t jobs = fail.zra ? 0u : totals[0];
+  const uint8_t* dBody = dArc_ + h_.size;
+  const uint64_t bodyBytes = arcSize_ - h_.size;
+  ZraDecodeArgs ra{};
+  ra.pieces = E.raPieces_.as<ZraRaPiece>(); ra.raOut = dOut;
+  const uint32_t commitGrid = (std::max(nF, V) + 255) / 256;
+  for (uint32_t s0 = 0; s0 < jobs && !fail.zra; s0 += V) {
+    const uint32_t n = std::min(V, jobs - s0);
+    if (s0) hipLaunchKernelGGL(zra_cache_victims_kernel, dim3(1), dim3(1024), 0, s, slotOf_, frameOf_, ref_, hand_, dctr_, slots_, V, victim_, 1u);
+    ra.limit = E.raLimit_.as<uint32_t>() + s0; ra.pieceBase = E.raPieceBase_.as<uint32_t>() + s0;
+    fail = E.decode_jobs(dBody, bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)s0, arena_, E.outOff_.as<uint64_t>() + s0,
+                         E.expect_.as<uint32_t>() + s0, n, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2, 0, &ra);
+    hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, plan, plan + 2 * (size_t)nF, nF, s0, n, victim_, V,
+                       E.status_.as<uint32_t>(), E.produced_.as<uint32_t>(), fail.zra ? 0u : 1u, (u64)fs, (u64)U, slotOf_, frameOf_, ref_, dctr_);
+  }
+  if (!jobs)   // (the planner failed: the claimed slots are released all the same)
+    hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, plan, plan + 2 * (size_t)nF, 0u, 0u, 0u, victim_, V,
+                       E.status_.as<uint32_t>(), E.produced_.as<uint32_t>(), 0u, (u64)fs, (u64)U, slotOf_, frameOf_, ref_, dctr_);
+  ACHK(hipMemcpyAsync(pin_ + 2, dctr_, 16, hipMemcpyDeviceToHost, s));
+  ACHK(hipStreamSynchronize(s));
+  ACHK(hipGetLastError());
+  evictions_ = pin_[2]; resident_ = pin_[3];
+  if (fail.zra == kZStdError) {
+    // Damage: the status is the batch call's under ZRA_HIP_OPT_RA_WHOLE_FRAMES. Which of several failing frames that call reports
+    // depends on how it lays out its jobs (one per slice for small batches, one per frame otherwise), so on this cold path the batch
+    // itself is asked; the frames it decodes are the same, whole.
+    const bool was = E.ra_verify_whole_frames();
+    E.set_ra_verify_whole_frames(true);
+    const Status st2 = E.ra_batch_body(dArc_, h_, dBody, bodyBytes, 0, dOut, hOff, hSize, hOutOff, nq);
+    E.set_ra_verify_whole_frames(was);
+    if (st2.zra) return st2;
+  }
+  return fail;
+}
+
+}  // namespace zra_eng

@@ -5,6 +5,7 @@
 #include "zra.h"
 #include "zra_hip.h"
 #include "zra_engine.h"
+#include "zra_archive.h"
 #include "zra_format.h"
 
 #include <atomic>
@@ -712,6 +713,26 @@ ZraStatus ZraHipDecompressRABatch(ZraHipEngine* engine, const void* dIn, size_t 
                                   const uint64_t* hOutOffsets, size_t nQueries) {
   engine->e->set_ra_verify_whole_frames((g_options.load() & kOptRaWholeFrames) != 0);
   return mk(engine->e->decompress_ra_batch((const uint8_t*)dIn, inSize, (uint8_t*)dOut, hOffsets, hSizes, hOutOffsets, nQueries));
+}
+
+struct ZraHipArchive { zra_eng::ArchiveCache* c; };
+ZraStatus ZraHipArchiveOpen(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, size_t cacheBytes, ZraHipArchive** archive) {
+  if (!engine || !archive || (!dArchive && archiveSize)) return mk(ZStdError, 42);
+  zra_eng::ArchiveCache* c = nullptr;
+  const zra_eng::Status s = zra_eng::ArchiveCache::open(engine->e, (const uint8_t*)dArchive, archiveSize, cacheBytes, &c);
+  if (s.zra) return mk(s);
+  *archive = new ZraHipArchive{c};
+  return mk(Success);
+}
+void ZraHipArchiveClose(ZraHipArchive* archive) { if (archive) { delete archive->c; delete archive; } }
+ZraStatus ZraHipArchiveRead(ZraHipArchive* archive, void* dOut, const uint64_t* hOffsets, const uint64_t* hSizes, const uint64_t* hOutOffsets, size_t nQueries) {
+  if (!archive || (nQueries && (!hOffsets || !hSizes || !hOutOffsets))) return mk(ZStdError, 42);
+  return mk(archive->c->read((uint8_t*)dOut, hOffsets, hSizes, hOutOffsets, nQueries, (g_options.load() & kOptRaWholeFrames) != 0));
+}
+ZraStatus ZraHipArchiveDropCache(ZraHipArchive* archive) { return archive ? mk(archive->c->drop()) : mk(ZStdError, 42); }
+void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8) {
+  if (!out8) return;
+  if (archive) archive->c->stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {

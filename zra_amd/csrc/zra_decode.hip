@@ -306,12 +306,7 @@ __device__ __forceinline__ void build_fse_dtable(u32* stage, const short* norm, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// cooperative byte copy global->global by the calling group of `nthreads` threads (rank `t`)
-__device__ __forceinline__ void copy_bytes(u8* dst, const u8* src, u32 n, int t, int nthreads) {
-  u32 n8 = n >> 3;
-  for (u32 i = t; i < n8; i += nthreads) st64(dst + 8 * i, ld64(src + 8 * i));
-  for (u32 i = (n8 << 3) + t; i < n; i += nthreads) dst[i] = src[i];
-}
+// (copy_bytes, the cooperative global->global copy: zra_dev.h)
 __device__ __forceinline__ void fill_bytes(u8* dst, u8 v, u32 n, int t, int nthreads) {
   u64 vv = 0x0101010101010101ull * v;
   u32 n8 = n >> 3;

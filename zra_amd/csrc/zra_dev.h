@@ -49,6 +49,13 @@ __device__ __forceinline__ void lds_st128(u8* p, uint4 q) { zra_v4u32_t v = {q.x
 __device__ __forceinline__ void lds_st64(u8* p, u64 v) { *(zra_lds_u64_t*)p = v; }
 __device__ __forceinline__ void st32(u8* p, u32 v) { *(u32_u*)p = v; }
 __device__ __forceinline__ void st64(u8* p, u64 v) { *(u64_u*)p = v; }
+// cooperative byte copy global->global by the calling group of `nthreads` threads (rank `t`): the decoder's random-access slices and
+// the archive handle's cache hits (zra_archive.hip)
+__device__ __forceinline__ void copy_bytes(u8* dst, const u8* src, u32 n, int t, int nthreads) {
+  u32 n8 = n >> 3;
+  for (u32 i = t; i < n8; i += nthreads) st64(dst + 8 * i, ld64(src + 8 * i));
+  for (u32 i = (n8 << 3) + t; i < n; i += nthreads) dst[i] = src[i];
+}
 struct __attribute__((packed, aligned(1))) u128_u { u32 a, b, c, d; };
 __device__ __forceinline__ void st128(u8* p, u32 a, u32 b, u32 c, u32 d) { u128_u v; v.a = a; v.b = b; v.c = c; v.d = d; *(u128_u*)p = v; }
 

@@ -84,6 +84,14 @@ class Engine {
                              const uint64_t* hOutOff, size_t nq);
   Status decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
                                    const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
+  // pieces of the batch, shared with the archive handle (zra_archive.hip): the header read + checks, the walk over the host query
+  // arrays (bounds, tuples uploaded to the device), the planner of the decode jobs, and the batch behind an already checked header
+  Status ra_header(const uint8_t* dArc, size_t arcSize, HeaderInfo* h);
+  Status ra_walk_queries(const HeaderInfo& h, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces);
+  Status ra_plan_fill(uint32_t* plan, size_t nq, uint32_t nFrames, const uint8_t* table, uint64_t bodyBase, uint64_t fs, uint64_t U,
+                      uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]);
+  Status ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
+                       const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
   // Host-walked frame list (reference semantics of DecompressBuffer: seek table not consulted). hFrameOff has nFrames+1 entries
   // relative to dBody; frames are assumed to regenerate frameSize bytes each (last: the remainder of total).
   Status decompress_frames_host_list(const uint8_t* dBody, uint64_t bodySize, const std::vector<uint64_t>& hFrameOff,
@@ -119,6 +127,7 @@ class Engine {
   // batched random access: false (default) = a frame is decoded up to the last byte a query needs, so damage behind that byte
   // and the frame's content checksum go unnoticed; true = whole frames + checksums, the reference's error behaviour
   void set_ra_verify_whole_frames(bool on) { raVerifyWholeFrames_ = on; }
+  bool ra_verify_whole_frames() const { return raVerifyWholeFrames_; }
   int device() const { return device_; }
   int num_cus() const { return numCUs_; }
 
@@ -161,6 +170,7 @@ class Engine {
   void* encCounters_ = nullptr; size_t encCountersBytes_ = 0;   // sub-batch counters stream B may be waiting on (drain_after_error)
   int waitValueOk_ = 0;                    // 0 unknown, 1 hipStreamWaitValue32 works on device memory, -1 it does not (batch path)
   friend struct EncodeImpl;
+  friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 
 }  // namespace zra_eng

@@ -132,7 +132,7 @@ __device__ __forceinline__ void ra_frame_span(const u8* table, u64 f, u64 bodyBa
   else { *so = a - bodyBase; *se = b - bodyBase; }
 }
 __global__ void __launch_bounds__(1024) zra_ra_plan_kernel(RaPlan P, u32 nFrames, const u8* table, u64 bodyBase, u64 fs, u64 total, u32 passSlots, u32 fullFrames,
-                                                           u64* frameOff, u64* outOff, u32* outCap, u32* limit, u32* pieceBase) {
+                                                           u64* frameOff, u64* outOff, u32* outCap, u32* limit, u32* pieceBase, const u32* victim) {
   __shared__ u32 sT[1024], sP[1024];
   const u32 tid = threadIdx.x;
   const u32 per = (nFrames + 1023) / 1024;
@@ -155,7 +155,8 @@ __global__ void __launch_bounds__(1024) zra_ra_plan_kernel(RaPlan P, u32 nFrames
     ra_frame_span(table, f, bodyBase, &frameOff[2 * (size_t)st], &frameOff[2 * (size_t)st + 1]);
     const u64 o = (u64)f * fs;
     const u32 expect = o >= total ? 0u : (u32)(total - o < fs ? total - o : fs);
-    outOff[st] = (u64)(st % passSlots) * fs;
+    // (victim: the archive handle's arena slots, zra_archive.hip — job st of a pass decodes into slot victim[st % passSlots])
+    outOff[st] = (u64)(victim ? victim[st % passSlots] : st % passSlots) * fs;
     outCap[st] = expect;
     limit[st] = fullFrames ? expect : min(P.need[f], expect);
     pieceBase[st] = sp;
@@ -174,9 +175,13 @@ __global__ void zra_ra_fill_kernel(const u64* q, u32 nq, u64 fs, RaPlan P, const
   for (u64 f = f0; f <= f1; f++) {
     const u32 srcOff = f == f0 ? (u32)(off % fs) : 0u;
     const u64 len = min<u64>(fs - srcOff, size - done);
-    const u32 at = pieceBase[P.slot[f]] + atomicAdd(&P.cursor[f], 1u);
-    ZraRaPiece pc; pc.dstOff = dst + done; pc.srcOff = srcOff; pc.len = (u32)len;
-    pieces[at] = pc;
+    // a frame with no count has no job: the archive handle counts only the frames its lookup missed (a hit's slice has been copied
+    // already); that count is the only test — P.slot of such a frame is not set
+    if (P.cnt[f]) {
+      const u32 at = pieceBase[P.slot[f]] + atomicAdd(&P.cursor[f], 1u);
+      ZraRaPiece pc; pc.dstOff = dst + done; pc.srcOff = srcOff; pc.len = (u32)len;
+      pieces[at] = pc;
+    }
     done += len;
   }
 }
@@ -824,41 +829,33 @@ Status Engine::decompress_ra_batch(const uint8_t* dArc, size_t arcSize, uint8_t*
   return decompress_ra_batch_shard(dArc, arcSize, nullptr, 0, 0, dOut, hOff, hSize, hOutOff, nq);
 }
 
-// dBody == nullptr: a whole archive at dArc (header, table, body). Otherwise dArc holds header + table only and dBody the bytes
-// [bodyBase, bodyBase + bodyBytes) of the archive's body — the frames one rank of a distributed archive owns (zra_comm.hip).
-Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
-                                         const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
-  // bring-up: ZRA_RA_TRACE=1 prints the host microseconds between the marks of a call
-  static const bool trace = std::getenv("ZRA_RA_TRACE") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "  ra %-14s %7.1f us\n", what, std::chrono::duration<double, std::micro>(t - t_last).count());
-    t_last = t;
-  };
-  HIPCHK(hipSetDevice(device_));
-  kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0;
+// the fixed header of a device-resident archive, read back and checked: the statuses of ZraHipDecompressRABatch (the archive handle
+// opens with the same ones, zra_archive.hip)
+Status Engine::ra_header(const uint8_t* dArc, size_t arcSize, HeaderInfo* h) {
   if (arcSize <= zra_fmt::kFixedSize) return {kOutOfBounds, 0};
   uint8_t fixed[zra_fmt::kFixedSize];
   HIPCHK(hipMemcpyAsync(fixed, dArc, sizeof(fixed), hipMemcpyDeviceToHost, stream_));
   HIPCHK(hipStreamSynchronize(stream_));
-  mark("header read");
-  HeaderInfo h;
-  if (int e = parse_fixed_header(fixed, &h)) return {e, 0};
-  if (arcSize < h.size) return {kOutOfBounds, 0};
-  if (!dBody) { dBody = dArc + h.size; bodyBytes = arcSize - h.size; bodyBase = 0; }
-  const uint32_t nFrames = h.frames();
-  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  if (int e = parse_fixed_header(fixed, h)) return {e, 0};
+  if (arcSize < h->size) return {kOutOfBounds, 0};
+  const uint32_t nFrames = h->frames();
+  const uint64_t fs = h->frameSize, U = h->uncompressedSize;
   // the reference indexes the table with offset / frameSize without looking at tableSize (zra.cpp:265-268); a header whose fields
   // disagree (size beyond what the table covers, table outside the header) would send it out of bounds — here it is HeaderInvalid
-  if ((uint64_t)h.seekTableOffset + h.seekTableSize > h.size) return {kHeaderInvalid, 0};
+  if ((uint64_t)h->seekTableOffset + h->seekTableSize > h->size) return {kHeaderInvalid, 0};
   if (fs && U && (U + fs - 1) / fs != nFrames) return {kHeaderInvalid, 0};
-  if (nq == 0) return ok();
+  return ok();
+}
+
+// one walk over the queries: the reference's bound (offset + size >= uncompressedSize is refused: the ">=" quirk, zra.cpp:260;
+// overflow-safe), the slices (one per frame a query touches) and the (offset, size, destination, first slice) tuples the device
+// kernels read — written straight into page-locked memory, so that their copy (into qmeta_) runs at bus speed beside the launches that
+// follow. *maxPieces = the slices; 0 when there is nothing to decode (the copies may still be in flight: the caller synchronises).
+Status Engine::ra_walk_queries(const HeaderInfo& h, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces) {
+  const uint32_t nFrames = h.frames();
+  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  *maxPieces = 0;
   if (nq > 0xFFFFFFF0ull) return zerr(64);
-  // one walk over the queries: the reference's bound (offset + size >= uncompressedSize is refused: the ">=" quirk, zra.cpp:260;
-  // overflow-safe), the slices (one per frame a query touches) and the (offset, size, destination, first slice) tuples the device
-  // kernels read — written straight into page-locked memory, so that their copy runs at bus speed beside the launches that follow
   if (pinQCap_ < 4 * nq) {
     if (pinQ_) (void)hipHostFree(pinQ_);
     pinQ_ = nullptr; pinQCap_ = 0;
@@ -868,7 +865,7 @@ Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, co
     pinQ_ = (uint64_t*)pq; pinQCap_ = cap;
   }
   uint64_t* const hq = pinQ_;
-  uint64_t maxPieces = 0;
+  uint64_t pieces = 0;
   const bool pow2 = fs && !(fs & (fs - 1));
   const unsigned fsLog = pow2 ? (unsigned)__builtin_ctzll(fs) : 0u;
   if (fs == 0 || nFrames == 0) {
@@ -882,11 +879,66 @@ Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, co
     for (size_t q = q0; q < q1; q++) {
       const uint64_t o = hOff[q], z = hSize[q];
       if (z >= U || o >= U - z) { (void)hipStreamSynchronize(stream_); return {kOutOfBounds, 0}; }
-      hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = hOutOff[q]; hq[4 * q + 3] = maxPieces;
-      if (z) maxPieces += pow2 ? ((o + z - 1) >> fsLog) - (o >> fsLog) + 1 : (o + z - 1) / fs - o / fs + 1;
+      hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = hOutOff[q]; hq[4 * q + 3] = pieces;
+      if (z) pieces += pow2 ? ((o + z - 1) >> fsLog) - (o >> fsLog) + 1 : (o + z - 1) / fs - o / fs + 1;
     }
     HIPCHK(hipMemcpyAsync(qmeta_.as<uint64_t>() + 4 * q0, hq + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, stream_));
   }
+  *maxPieces = pieces;
+  return ok();
+}
+
+// dense job numbers, decode jobs and piece lists of the frames counted in plan (RaPlan layout: cnt, need, slot, cursor [nFrames] each,
+// then totals) from the query tuples in qmeta_; totals = {jobs, pieces}. victim: see zra_ra_plan_kernel (nullptr: scratch window).
+Status Engine::ra_plan_fill(uint32_t* plan, size_t nq, uint32_t nFrames, const uint8_t* table, uint64_t bodyBase, uint64_t fs, uint64_t U,
+                            uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]) {
+  RaPlan P;
+  P.cnt = plan; P.need = P.cnt + nFrames; P.slot = P.need + nFrames; P.cursor = P.slot + nFrames; P.totals = P.cursor + nFrames;
+  hipLaunchKernelGGL(zra_ra_plan_kernel, dim3(1), dim3(1024), 0, stream_, P, nFrames, table, (u64)bodyBase, (u64)fs, (u64)U, passSlots,
+                     fullFrames ? 1u : 0u, frameOff_.as<uint64_t>(), outOff_.as<uint64_t>(), expect_.as<uint32_t>(), raLimit_.as<uint32_t>(),
+                     raPieceBase_.as<uint32_t>(), victim);
+  hipLaunchKernelGGL(zra_ra_fill_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, qmeta_.as<uint64_t>(), (u32)nq, (u64)fs, P,
+                     raPieceBase_.as<uint32_t>(), raPieces_.as<ZraRaPiece>());
+  totals[0] = totals[1] = 0;
+  HIPCHK(hipMemcpyAsync(totals, P.totals, 8, hipMemcpyDeviceToHost, stream_));
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipGetLastError());
+  return ok();
+}
+
+// dBody == nullptr: a whole archive at dArc (header, table, body). Otherwise dArc holds header + table only and dBody the bytes
+// [bodyBase, bodyBase + bodyBytes) of the archive's body — the frames one rank of a distributed archive owns (zra_comm.hip).
+Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
+                                         const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+  HIPCHK(hipSetDevice(device_));
+  kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0;
+  HeaderInfo h;
+  { Status st = ra_header(dArc, arcSize, &h); if (st.zra) return st; }
+  if (!dBody) { dBody = dArc + h.size; bodyBytes = arcSize - h.size; bodyBase = 0; }
+  return ra_batch_body(dArc, h, dBody, bodyBytes, bodyBase, dOut, hOff, hSize, hOutOff, nq);
+}
+
+// the batch behind a header that has been read and checked (ra_header): the archive handle without slots comes here directly
+Status Engine::ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
+                             const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+  // bring-up: ZRA_RA_TRACE=1 prints the host microseconds between the marks of a call
+  static const bool trace = std::getenv("ZRA_RA_TRACE") != nullptr;
+  auto t_last = std::chrono::steady_clock::now();
+  auto mark = [&](const char* what) {
+    if (!trace) return;
+    const auto t = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "  ra %-14s %7.1f us\n", what, std::chrono::duration<double, std::micro>(t - t_last).count());
+    t_last = t;
+  };
+  HIPCHK(hipSetDevice(device_));
+  kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0;
+  mark("header read");
+  const uint32_t nFrames = h.frames();
+  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  if (nq == 0) return ok();
+  uint64_t maxPieces = 0;
+  { Status st = ra_walk_queries(h, hOff, hSize, hOutOff, nq, &maxPieces); if (st.zra) return st; }
+  if (fs == 0 || nFrames == 0) return ok();
   if (maxPieces == 0) { HIPCHK(hipStreamSynchronize(stream_)); return ok(); }
   mark("queries");
   const uint64_t tempBudget = 16ull << 30;
@@ -909,17 +961,10 @@ Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, co
     HIPCHK(hipMemsetAsync(raPlan_.p, 0, planWords * 4, stream_));
     RaPlan P;
     P.cnt = raPlan_.as<uint32_t>(); P.need = P.cnt + nFrames; P.slot = P.need + nFrames; P.cursor = P.slot + nFrames; P.totals = P.cursor + nFrames;
-    const uint64_t* dQ = qmeta_.as<uint64_t>();
-    hipLaunchKernelGGL(zra_ra_count_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, dQ, (u32)nq, (u64)fs, P);
-    hipLaunchKernelGGL(zra_ra_plan_kernel, dim3(1), dim3(1024), 0, stream_, P, nFrames, dArc + h.seekTableOffset, (u64)bodyBase, (u64)fs, (u64)U, passSlots,
-                       raVerifyWholeFrames_ ? 1u : 0u, frameOff_.as<uint64_t>(), outOff_.as<uint64_t>(), expect_.as<uint32_t>(), raLimit_.as<uint32_t>(),
-                       raPieceBase_.as<uint32_t>());
-    hipLaunchKernelGGL(zra_ra_fill_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, dQ, (u32)nq, (u64)fs, P, raPieceBase_.as<uint32_t>(),
-                       raPieces_.as<ZraRaPiece>());
-    uint32_t totals[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(totals, P.totals, 8, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(zra_ra_count_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, qmeta_.as<uint64_t>(), (u32)nq, (u64)fs, P);
+    uint32_t totals[2];
+    Status st = ra_plan_fill(raPlan_.as<uint32_t>(), nq, nFrames, dArc + h.seekTableOffset, bodyBase, fs, U, passSlots, raVerifyWholeFrames_, nullptr, totals);
+    if (st.zra) return st;
     touched = totals[0];
     mark("plan");
   }
