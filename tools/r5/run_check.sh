@@ -2,7 +2,7 @@
 # round 5: compress-side parity selection, then the headline call (16 GiB, level 3, 64 KiB) once per variant of EXTRA_VARIANTS in a process
 # of its own, with the stream timeline (ZRA_ENC_TRACE) and the launch telemetry (waves per CU / XCD, entropy workgroups): the script behind
 # most of profiles/r05_experiments.md. EXTRA_VARIANTS = words of '+'-joined environment settings, e.g.
-#   EXTRA_VARIANTS="ZRA_PIPE=0 ZRA_PIPE=2 ZRA_MF_WAVES=20+ZRA_ENT_WGS=8" tools/r5/gpu.sh 1500 /tmp/c.log tools/r5/run_check.sh
+#   EXTRA_VARIANTS="ZRA_MF_WAVES=18+ZRA_ENT_WGS=1 ZRA_MF_WAVES=20+ZRA_ENT_WGS=8" tools/r5/gpu.sh 1500 /tmp/c.log tools/r5/run_check.sh
 # REPS (default 1) processes per variant (the process-to-process spread); SKIP_PARITY=1 leaves the tests out.
 root=$(pwd); out=$root/gpurun_out; mkdir -p $out; export TMPDIR=/tmp
 sel="compress_buffer_bit_exact and (3-65536 or 4-65536 or 3-16384 or 0-16384 or 9-65536 or 1-65536 or 13-) or sub_batch_boundaries or short_last_frame or randomised_differential_compress or streaming or match_finder_sequences and (3-65536 or 3-16384)"

@@ -7,6 +7,7 @@
 #include "zra_engine.h"
 #include "zra_archive.h"
 #include "zra_format.h"
+#include "zra_env.h"
 
 #include <atomic>
 #include <algorithm>
@@ -41,8 +42,7 @@ class EnginePool {
       if (created_ < limit()) {
         created_++;
         lk.unlock();
-        int dev = 0;
-        if (const char* s = std::getenv("ZRA_DEVICE")) dev = std::atoi(s);
+        const int dev = zra_env::env_int("ZRA_DEVICE", 0);
         Engine* e = nullptr;
         zra_eng::Status st = Engine::create(&e, dev);
         if (st.zra) {
@@ -70,11 +70,11 @@ class EnginePool {
   }
  private:
   static int limit() {
-    static const int n = [] { const char* s = std::getenv("ZRA_ENGINES"); int v = s ? std::atoi(s) : 4; return v < 1 ? 1 : v > 64 ? 64 : v; }();
+    static const int n = [] { const int v = zra_env::env_int("ZRA_ENGINES", 4); return v < 1 ? 1 : v > 64 ? 64 : v; }();
     return n;
   }
   static uint64_t cap() {
-    static const uint64_t c = [] { const char* s = std::getenv("ZRA_SCRATCH_CAP_GIB"); long long v = s ? std::atoll(s) : 48; return (uint64_t)(v < 1 ? 1 : v) << 30; }();
+    static const uint64_t c = [] { const long long v = zra_env::env_i64("ZRA_SCRATCH_CAP_GIB", 48); return (uint64_t)(v < 1 ? 1 : v) << 30; }();
     return c;
   }
   std::mutex mu_; std::condition_variable cv_;
@@ -539,8 +539,7 @@ namespace zra {
     const size_t first = entryIndex, count = stop - entryIndex;
     const u64 firstByte = (u64)first * header.frameSize;
     const size_t produced = count ? (size_t)std::min<u64>((u64)count * header.frameSize, header.uncompressedSize > firstByte ? header.uncompressedSize - firstByte : 0) : 0;
-    const char* aheadEnv = std::getenv("ZRA_STREAM_AHEAD_MIB");
-    const size_t aheadBytes = (aheadEnv ? (size_t)std::atoll(aheadEnv) : 256) << 20;
+    const size_t aheadBytes = (size_t)zra_env::env_i64("ZRA_STREAM_AHEAD_MIB", 256) << 20;   // (read per call: tests change it)
     if (!ahead) ahead = std::make_shared<Ahead>();
     Ahead& A = *ahead;
     if (count && aheadBytes && !A.disabled && header.frameSize) {

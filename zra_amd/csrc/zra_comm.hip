@@ -12,6 +12,7 @@
 #include "zra_format.h"
 #include "zra_dev.h"
 #include "zra_hip.h"
+#include "zra_env.h"
 #include <rccl/rccl.h>
 #include <algorithm>
 #include <cstdlib>
@@ -104,8 +105,8 @@ struct ZraHipComm {
       // a rank's frames are 5.6 GiB in ONE send to the root, and nothing says a single ncclSend takes that. Both sides cut a message
       // the same way (they know its length), all pieces of all peers inside the one group: transfers to different peers still run side
       // by side, each on its own xGMI link.
-      static const size_t chunk = (std::getenv("ZRA_COMM_CHUNK_MIB") ? (size_t)std::max(1, std::atoi(std::getenv("ZRA_COMM_CHUNK_MIB"))) : (size_t)1024) << 20;
-      static const size_t chunkB = std::getenv("ZRA_COMM_CHUNK_BYTES") ? (size_t)std::max(64, std::atoi(std::getenv("ZRA_COMM_CHUNK_BYTES"))) : chunk;   // (test hook: pieces of a few KiB)
+      static const size_t chunk = (size_t)std::max(1, zra_env::env_int("ZRA_COMM_CHUNK_MIB", 1024)) << 20;
+      static const size_t chunkB = zra_env::env_set("ZRA_COMM_CHUNK_BYTES") ? (size_t)std::max(64, zra_env::env_int("ZRA_COMM_CHUNK_BYTES", 0)) : chunk;   // (test hook: pieces of a few KiB)
       if (R.GroupStart() != ncclSuccess) return false;
       bool good = true;
       for (auto& x : r) for (size_t o = 0; o < x.bytes; o += chunkB) good &= R.Recv((uint8_t*)x.buf + o, std::min(chunkB, x.bytes - o), ncclUint8, x.peer, nccl, st) == ncclSuccess;
@@ -542,7 +543,7 @@ ZraStatus ZraHipCommServe(ZraHipComm* c, const ZraHipShard* s, const uint64_t* o
       if (hipStreamSynchronize(stream) != hipSuccess) st = zra_eng::zerr(1);
     }
   }
-  if (st.zra && std::getenv("ZRA_COMM_TRACE")) std::fprintf(stderr, "ZraHipCommServe: rank %d local status {%d, %d}\n", me, st.zra, st.zstd);
+  if (st.zra && zra_env::env_set("ZRA_COMM_TRACE")) std::fprintf(stderr, "ZraHipCommServe: rank %d local status {%d, %d}\n", me, st.zra, st.zstd);
   return c->agree(st);
 }
 

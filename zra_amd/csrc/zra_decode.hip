@@ -1709,7 +1709,7 @@ __device__ __forceinline__ ExecCtx exec_begin(const ZraDecodeArgs& a, const u32 
 }
 // up to 64 sequences, lane = sequence (act: the lane has one; oStart / lStart: where its literals go and come from)
 __device__ __forceinline__ void exec_step_global(const ExecCtx& c, ExecShared& S, const u32 ll, const u32 ml, const u32 off, const u32 oStart, const u32 lStart,
-                                                 const bool act, const int lane, const u32 debugSkip) {
+                                                 const bool act, const int lane) {
   u8* const out = c.out; const u8* const lit = c.lit; const u32 litKind = c.litKind; const u8 rleByte = c.rleByte;
   const u32 mdst = oStart + ll;
 #ifdef ZRA_DEC_PROFILE
@@ -1719,11 +1719,11 @@ __device__ __forceinline__ void exec_step_global(const ExecCtx& c, ExecShared& S
   {
     u8* op = out + oStart;
     const bool longLit = ll > 32;
-    if (!longLit && ll && !(debugSkip & 1)) {
+    if (!longLit && ll) {
       if (litKind == 1) for (u32 b = 0; b < ll; b++) op[b] = rleByte;
       else copy_le64(op, lit + lStart, ll);
     }
-    u64 lm = (debugSkip & 8) ? 0ull : __ballot(longLit);
+    u64 lm = __ballot(longLit);
     while (lm) {
       const u32 k = (u32)__builtin_ctzll(lm); lm &= lm - 1;
       const u32 jl = bcast_u32(ll, k), jo = bcast_u32(oStart, k), js = bcast_u32(lStart, k);
@@ -1761,7 +1761,7 @@ __device__ __forceinline__ void exec_step_global(const ExecCtx& c, ExecShared& S
       const bool mine = (pending >> lane) & 1;
       const bool ready = mine && !(deps & pending);
       const bool longM = ready && ml > 64;
-      if (ready && !longM && !(debugSkip & 2)) {
+      if (ready && !longM) {
         u8* dp = out + mdst; const u8* sp = dp - off;
         if (off >= ml) copy_le64(dp, sp, ml);      // no overlap: all loads, then all stores
         else copy_periodic_le64(dp, sp, ml, off, S.slot[lane]);  // overlapping match = period `off`: only the bytes in front of the destination are read
@@ -1775,7 +1775,7 @@ __device__ __forceinline__ void exec_step_global(const ExecCtx& c, ExecShared& S
         else { for (u32 k = lane; k < jml; k += WAVE) dp[k] = sp[k % jof]; }
       }
       pending &= ~__ballot(ready);
-      if (!(debugSkip & 4)) wsync();
+      wsync();
       XCNT(12, 1)
     }
   }
@@ -1793,9 +1793,9 @@ __device__ __forceinline__ void lsync() {
 // step lies in the window entirely; one that begins further back lies in finished output entirely), the rounds cost LDS round trips,
 // and the window goes out in 16-byte stores, followed by the step's ONE drain. Steps larger than the window take exec_step_global.
 __device__ __forceinline__ void exec_step(ExecCtx& c, ExecShared& S, const u32 ll, const u32 ml, const u32 off, const u32 oStart, const u32 lStart,
-                                          const bool act, const int lane, const u32 debugSkip) {
+                                          const bool act, const int lane) {
   const u32 stepStart = bcast_u32(oStart, 0), stepLen = bcast_u32(oStart + ll + ml, 63) - stepStart;
-  if (stepLen > XWIN || debugSkip) { exec_step_global(c, S, ll, ml, off, oStart, lStart, act, lane, debugSkip); c.preValid = false; return; }
+  if (stepLen > XWIN) { exec_step_global(c, S, ll, ml, off, oStart, lStart, act, lane); c.preValid = false; return; }
   u8* const out = c.out; const u8* const lit = c.lit; const u32 litKind = c.litKind; const u8 rleByte = c.rleByte;
   u8* const W = S.win;                                    // output byte x of the window sits at W[x + wb] (x >= stepStart - XPRE; plain indices:
   const u32 wb = XPRE - stepStart;                        //  a biased LDS pointer would not survive being widened to a flat one)
@@ -1936,7 +1936,7 @@ __device__ __forceinline__ u32 exec_job(const ZraDecodeArgs& a, const u32 j, Exe
     const u32 tot = ll + ml;
     const u32 incT = dpp_scan_add(tot), incL = dpp_scan_add(ll);
     XTIME(0) XCNT(9, 1) XCNT(10, cnt)
-    exec_step(c, S, ll, ml, off, c.outBase + incT - tot, c.litBase + incL - ll, act, lane, a.debugSkip);
+    exec_step(c, S, ll, ml, off, c.outBase + incT - tot, c.litBase + incL - ll, act, lane);
 #ifdef ZRA_DEC_PROFILE
     xpt_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -2011,7 +2011,7 @@ __device__ __forceinline__ void exec_frame_all(const ZraDecodeArgs& a, const u32
       const u32 oStart = c.outBase + incT - tot;
       const u32 off = resolve(offRaw);
       if (__ballot(act && offRaw >= ZRA_REP_MARK_LO && off > c.produced0 + oStart + ll)) { bad = true; break; }
-      exec_step(c, S, ll, ml, off, oStart, c.litBase + incL - ll, act, lane, a.debugSkip);
+      exec_step(c, S, ll, ml, off, oStart, c.litBase + incL - ll, act, lane);
       c.outBase += bcast_u32(incT, 63); c.litBase += bcast_u32(incL, 63);
     }
     if (bad) { bail = true; break; }
@@ -2299,7 +2299,7 @@ __device__ __forceinline__ void chain_consume(const ZraDecodeArgs& a, const u32 
     // a step cut short at the query's last byte ends where its last validated sequence ends: the lanes behind it carry that position
     // (exec_step takes the step's length from lane 63; the lengths of the unexecuted, unchecked sequences must not be in it)
     const u32 endOut = outPos + bcast_u32(sOut, nb - 1), endLit = litPos + bcast_u32(sLit, nb - 1);
-    c.outBase = outPos; exec_step(c, X, on2 ? ll : 0u, on2 ? ml : 0u, on2 ? min(off, 0x0FFFFFFFu) : 1u, on2 ? outBefore : endOut, on2 ? litBefore : endLit, on2, lane, a.debugSkip);
+    c.outBase = outPos; exec_step(c, X, on2 ? ll : 0u, on2 ? ml : 0u, on2 ? min(off, 0x0FFFFFFFu) : 1u, on2 ? outBefore : endOut, on2 ? litBefore : endLit, on2, lane);
     outPos += bcast_u32(sOut, nb - 1); litPos += bcast_u32(sLit, nb - 1);
     t += nb;
     if (lane == 0) ring_st(&R.tail, t);

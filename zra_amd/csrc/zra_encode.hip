@@ -6,6 +6,7 @@
 #include "zra_engine.h"
 #include "zra_dev.h"
 #include "zra_format.h"
+#include "zra_env.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -23,11 +24,9 @@ extern "C" __global__ void zra_entropy_front_kernel(ZraEncArgs a, uint32_t block
 extern "C" __global__ void zra_entropy_back_kernel(ZraEncArgs a, uint32_t block);
 extern "C" __global__ void zra_ent_chain_kernel(ZraEncArgs a);
 extern "C" __global__ void zra_ent_chain5_kernel(ZraEncArgs a);
-extern "C" __global__ void zra_ent_chain3_kernel(ZraEncArgs a);
-extern "C" __global__ void zra_ent_chain2_kernel(ZraEncArgs a);
-extern "C" __global__ void zra_ent_chain1_kernel(ZraEncArgs a);
 
 using namespace zra_dev;
+using namespace zra_env;
 
 namespace {
 
@@ -204,7 +203,7 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
   // gather of a sub-batch are released on stream B by hipStreamWaitValue32 on that counter — no per-batch launch tails in the
   // DRAM-bound match finder, and the entropy stage runs under it in small pieces.
   {
-    bool persist = maxBlocksPerFrame == 1 && full.strategy == 2 && !std::getenv("ZRA_MF_NOPERSIST");   // (one block: the frame fits any window)
+    bool persist = maxBlocksPerFrame == 1 && full.strategy == 2;   // (one block: the frame fits any window)
     if (persist && waitValueOk_ == 0) {
       // the pipeline needs stream memory operations on plain device memory; probe once (a wait that is already satisfied), and
       // use the batch path below on runtimes without them
@@ -223,9 +222,9 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
   // Two scratch contexts: the match finder of batch k+1 (stream A) overlaps the entropy stage + gather of batch k (stream B);
   // both kernels are latency-bound, so they share the CUs almost for free. 8 GiB of scratch per context.
   // scratch per context: enough for one frame per resident wave (32 per CU) of the one-lane finders, whose throughput is frames in
-  // flight / frame latency (level 9 @ 256 KiB needs 6 MiB of tables per frame); bring-up knob ZRA_ENC_BUDGET_GIB
+  // flight / frame latency (level 9 @ 256 KiB needs 6 MiB of tables per frame); test hook ZRA_ENC_BUDGET_GIB
   uint64_t budget = 8ull << 30;
-  if (const char* e = std::getenv("ZRA_ENC_BUDGET_GIB")) budget = (uint64_t)std::atoi(e) << 30;
+  if (env_set("ZRA_ENC_BUDGET_GIB")) budget = (uint64_t)env_int("ZRA_ENC_BUDGET_GIB", 0) << 30;
   else if (full.strategy != 2) {
     // measured at level 9 @ 256 KiB (4 GiB input): 8 GiB -> 0.33 GiB/s, 16 -> 0.58, 32 -> 0.71, 64 -> 0.93 (all frames resident)
     size_t freeB = 0, totalB = 0;
@@ -239,13 +238,12 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
   // b's entropy stage (the confirmed repcodes: a block stored raw does not move them), so ONE batch runs finder and entropy stage strictly
   // in turns; two contexts fill each other's gaps — as long as half a batch still fills the chip (16 frames per CU). Measured on one box
   // (profiles/r05_experiments.md §9; log-like data, 256 KiB frames): 8,192 frames at level 9 3.69-3.80 -> 3.89-3.98 GiB/s, at level 5
-  // 8.14-8.18 -> 8.94-8.99; 4,096 frames at level 3 12.8 -> 10.6 (hence the bound). ZRA_ENC_SPLIT=0: off.
+  // 8.14-8.18 -> 8.94-8.99; 4,096 frames at level 3 12.8 -> 10.6 (hence the bound).
   // And batches of EQUAL size whenever there are several: a call of 8,192 frames with room for 7,168 ran as 7,168 + 1,024 (the bench's
   // c4_share, where the timed buffers leave less free memory than a lone call finds), and the small batch left its context idle.
-  { static const bool split = !(std::getenv("ZRA_ENC_SPLIT") && std::atoi(std::getenv("ZRA_ENC_SPLIT")) == 0);
-    uint64_t nBatches = (nFramesTotal + B - 1) / B;
-    if (split && maxBlocksPerFrame > 1 && nBatches == 1 && nFramesTotal >= 32ull * (uint64_t)numCUs_) nBatches = 2;
-    if (split && nBatches > 1) B = (uint32_t)std::min<uint64_t>(B, ((nFramesTotal + nBatches - 1) / nBatches + 63) & ~63ull); }
+  { uint64_t nBatches = (nFramesTotal + B - 1) / B;
+    if (maxBlocksPerFrame > 1 && nBatches == 1 && nFramesTotal >= 32ull * (uint64_t)numCUs_) nBatches = 2;
+    if (nBatches > 1) B = (uint32_t)std::min<uint64_t>(B, ((nFramesTotal + nBatches - 1) / nBatches + 63) & ~63ull); }
   // the entropy stage: workgroups that take the batch's frames from a queue — as many as the device holds at once (5 waves per SIMD by
   // registers), each with its own literal buffer and sequence work area
   const uint32_t entGridB = (uint32_t)std::min<uint64_t>(B, (uint64_t)numCUs_ * 5);
@@ -282,9 +280,9 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
   };
   std::vector<std::pair<hipEvent_t, hipEvent_t>> mfSpans, entSpans;
   hipEvent_t entDone[2] = {nullptr, nullptr};
-  // the second context's match-finder stream (ZRA_MF_ONE_STREAM: bring-up knob, everything on stream A as before)
+  // the second context's match-finder stream
   hipStream_t mfStream2 = nullptr;
-  if (nCtx == 2 && !std::getenv("ZRA_MF_ONE_STREAM")) {
+  if (nCtx == 2) {
     if (!pipeStreams_[0] && hipStreamCreateWithFlags(&pipeStreams_[0], hipStreamNonBlocking) != hipSuccess) { pipeStreams_[0] = nullptr; (void)hipGetLastError(); }
     mfStream2 = pipeStreams_[0];
   }
@@ -320,21 +318,18 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
     if (entDone[c]) HIPCHK(hipStreamWaitEvent(sA, entDone[c], 0));
     // test knob: the table scratch filled with a pattern before a batch — whatever a finder does not clear itself (the wave-cooperative
     // hash-chain finder leaves its chain slots alone) must not matter (tests/test_gpu_parity.py::test_opt_in_kernels_are_bit_exact_too)
-    { static const bool poison = std::getenv("ZRA_ENC_POISON") != nullptr;
+    { static const bool poison = env_set("ZRA_ENC_POISON");
       if (poison) HIPCHK(hipMemsetAsync(x.tables.p, 0xA5, (size_t)nb * tableWords * 4, sA)); }
     for (uint32_t blk = 0; blk < rounds; blk++) {
       hipEvent_t m0 = ev(), m1 = ev(), e1 = ev();
       if (!m0 || !m1 || !e1) return zerr(1);
       HIPCHK(hipEventRecord(m0, sA));
       {
-        // occupancy experiment knob (bring-up): extra dynamic LDS per workgroup caps the frames in flight per CU
-        static const int dynLds = std::getenv("ZRA_MF_LDS") ? std::atoi(std::getenv("ZRA_MF_LDS")) : 0;
         // dfast batches (levels 3-4) run the lean window-resolve kernel; a short last frame whose cparams select another
         // strategy is parsed by the generic kernel in a second single-frame launch
         const bool hasTail = tailSize && f0 + nb == nFramesTotal;
         // LDS geometry of the dfast kernel's bucket filter (see compress_persistent)
-        uint32_t shL = 1, shS = 2, dupLog = 8;
-        if (const char* f = std::getenv("ZRA_MF_FILTER")) { unsigned x = 1, y = 1, z = 8; if (std::sscanf(f, "%u,%u,%u", &x, &y, &z) >= 1) { shL = x & 15; shS = y & 15; dupLog = z & 15; } }
+        const uint32_t shL = 1, shS = 2, dupLog = 8;
         a.mfFilter = shL | (shS << 4) | (dupLog << 8);
         const uint32_t hl = std::max(full.hashLog, tail.hashLog), cl = std::max(full.chainLog, tail.chainLog);
         const size_t filterBytes = (8u << dupLog) + (((size_t)1 << hl) >> shL) / 8 + (((size_t)1 << cl) >> shS) / 8 + 64;
@@ -348,28 +343,25 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
           else hipLaunchKernelGGL(mfGeneric, dim3(1), dim3(64), 0, sA, a, blk, only, slot, 1u);
         };
         if (full.strategy == 2 && !serialAll) {
-          hipLaunchKernelGGL(zra_mf_dfast_kernel, dim3(nb), dim3(64), filterBytes + dynLds, sA, a, blk, 0xFFFFFFFFu, 0u);
+          hipLaunchKernelGGL(zra_mf_dfast_kernel, dim3(nb), dim3(64), filterBytes, sA, a, blk, 0xFFFFFFFFu, 0u);
           if (oddTail) launchLone((uint32_t)(nb - 1), (uint32_t)(nb - 1));
         } else {
           // frames per wave: as many as it takes to have every frame of the batch resident at once (32 waves per CU)
-          static const int pwEnv = std::getenv("ZRA_MF_PERWAVE") ? std::atoi(std::getenv("ZRA_MF_PERWAVE")) : 0;
           // hash-chain strategies (greedy / lazy / lazy2): one frame per wave, the wave-cooperative finder; fast gains 9.4 -> 14.5 from 8
           const bool hashChain = full.strategy >= 3 && full.strategy <= 5 && !serialAll;
-          uint32_t perWave = pwEnv > 0 ? (uint32_t)pwEnv : hashChain ? 1u
-                           : std::min<uint32_t>(8u, std::max<uint32_t>(1u, (nb + (uint32_t)numCUs_ * 32 - 1) / ((uint32_t)numCUs_ * 32)));
+          const uint32_t perWave = hashChain ? 1u : std::min<uint32_t>(8u, std::max<uint32_t>(1u, (nb + (uint32_t)numCUs_ * 32 - 1) / ((uint32_t)numCUs_ * 32)));
           // the hash-chain kernel and the fast kernel hold their own finder only (lean register budgets); a short last frame with any
           // other strategy goes to the generic kernel (or the dfast kernel) in a second, single-frame launch
-          const bool lean = pwEnv <= 0 && (hashChain || full.strategy == 1);
+          const bool lean = hashChain || full.strategy == 1;
           // resident waves of the hash-chain finder: 32 per CU (all the hardware holds) — except for the deep searches over big tables
           // (search log >= 5 with >= 4 MiB of tables per frame: levels 9-10 at 256 KiB frames), which run faster with 20, five per SIMD
           // (level 9 @ 256 KiB: 3.53 GiB/s at 32, 3.48 at 22, 3.74 at 20, 3.70 at 16, 3.21 at 14; level 10: 2.11 -> 2.29 at 16; level 6 @
           // 256 KiB with the same tables and search log 3: 7.16 -> 6.55 at 16; level 9 @ 64 KiB: 5.20 -> 4.53 at 16 — profiles/
           // r04_experiments.md §9). Padding each wave's LDS (3 KiB of its own) to 8 KiB sets it.
-          uint32_t hcPad = (uint32_t)dynLds;
-          if (!std::getenv("ZRA_MF_LDS") && hashChain && full.searchLog >= 5 && tableWords * 4 >= (4ull << 20)) hcPad = 5120;
-          if (hashChain && pwEnv <= 0) hipLaunchKernelGGL(zra_mf_hc_kernel, dim3(nb), dim3(64), hcPad, sA, a, blk, 0xFFFFFFFFu, 0u);
-          else if (lean) hipLaunchKernelGGL(zra_mf_fast_kernel, dim3((nb + perWave - 1) / perWave), dim3(64), dynLds, sA, a, blk, perWave);
-          else hipLaunchKernelGGL(mfGeneric, dim3((nb + perWave - 1) / perWave), dim3(64), dynLds, sA, a, blk, 0xFFFFFFFFu, 0u, perWave);
+          const uint32_t hcPad = hashChain && full.searchLog >= 5 && tableWords * 4 >= (4ull << 20) ? 5120u : 0u;
+          if (hashChain) hipLaunchKernelGGL(zra_mf_hc_kernel, dim3(nb), dim3(64), hcPad, sA, a, blk, 0xFFFFFFFFu, 0u);
+          else if (lean) hipLaunchKernelGGL(zra_mf_fast_kernel, dim3((nb + perWave - 1) / perWave), dim3(64), 0, sA, a, blk, perWave);
+          else hipLaunchKernelGGL(mfGeneric, dim3((nb + perWave - 1) / perWave), dim3(64), 0, sA, a, blk, 0xFFFFFFFFu, 0u, perWave);
           if (oddTail) hipLaunchKernelGGL(zra_mf_dfast_kernel, dim3(1), dim3(64), filterBytes, sA, a, blk, (uint32_t)(nb - 1), (uint32_t)(nb - 1));
           else if (lean && hasTail && (hashChain ? (tail.strategy < 3 || tail.strategy > 5) : tail.strategy != 1))
             launchLone((uint32_t)(nb - 1), (uint32_t)(nb - 1));
@@ -393,9 +385,7 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
     HIPCHK(hipEventRecord(done, stream2_));
     entDone[c] = done;
     // test hook: give up behind batch ZRA_ENC_FAIL_BATCH with its kernels in flight (the error exit must drain every stream: tests/test_gpu_parity.py)
-    if (const char* fb = std::getenv("ZRA_ENC_FAIL_BATCH")) if ((uint64_t)std::atoll(fb) == batchIdx) return zerr(1);
-    { static const bool serial = std::getenv("ZRA_ENC_SERIAL") != nullptr;   // bring-up knob: no mf/entropy overlap (per-kernel timing in isolation)
-      if (serial) { HIPCHK(hipStreamWaitEvent(stream_, done, 0)); if (mfStream2) HIPCHK(hipStreamWaitEvent(mfStream2, done, 0)); } }
+    if ((uint64_t)env_i64("ZRA_ENC_FAIL_BATCH", -1) == batchIdx) return zerr(1);
   }
   uint64_t total = 0;
   HIPCHK(hipMemcpyAsync(&total, dRunning, 8, hipMemcpyDeviceToHost, stream2_));
@@ -418,33 +408,27 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
   const uint64_t nFramesTotal = (inSize + frameSize - 1) / frameSize;
   const size_t tailSize = inSize % frameSize;
   const auto mfGeneric = (full.strategy >= 7 || tail.strategy >= 7) ? zra_mf_opt_kernel : zra_mf_kernel;
-  // How the entropy stage shares the device with the match finder (ZRA_PIPE; one box, 16 GiB, round 4's library 997-999 ms in its slower
-  // state on that box — profiles/r05_experiments.md):
-  //   1 (default)  round 4's overlap: per sub-batch of 8192 frames one entropy launch + scan + gather on stream B, released by the
-  //                finder's count of finished frames; 18 finder waves per CU leave room for one entropy workgroup.  938 ms
-  //   0            the entropy stage behind the whole finder launch: 22 finder waves per CU (842 ms) + 190 ms.       1038 ms
-  //   2            the entropy stage resident beside the finder, one queue-driven workgroup per CU, scanning and gathering itself:
-  //                the finder loses what the stage gains.                                                      988-1075 ms
+  // How the entropy stage shares the device with the match finder (round 4's overlap): per sub-batch of 8192 frames one entropy launch +
+  // scan + gather on stream B, released by the finder's count of finished frames; the finder leaves each CU room for one entropy
+  // workgroup (DESIGN.md lists the two other arrangements that were measured and retired).
   // With the bucket flags fewer table requests queue up and more finder waves pay again (alone: 18 waves 880-897 ms, 20 waves 855-862,
   // 22 and 24 waves 824-846; without the flags 18 = 24 waves, round 4) — but the entropy stage needs its room: at 20 waves it falls behind.
-  static const int pipeMode = std::getenv("ZRA_PIPE") ? std::atoi(std::getenv("ZRA_PIPE")) : 1;
   // (round 6: 19 beside the entropy stage — its workgroup takes 14 of the CU's 128 LDS pieces since the histograms share storage with the
   //  tables, a finder wave 6: 19 x 6 + 14 = 128; it was 18 x 6 + 19)
-  static const uint32_t wavesPerCU = std::getenv("ZRA_MF_WAVES") ? (uint32_t)std::atoi(std::getenv("ZRA_MF_WAVES")) : (pipeMode == 0 ? 22u : 19u);
-  static const uint32_t SB = std::getenv("ZRA_ENC_SUB") ? (uint32_t)std::atoi(std::getenv("ZRA_ENC_SUB")) : 8192u;   // frames per sub-batch
+  static const uint32_t wavesPerCU = (uint32_t)env_int("ZRA_MF_WAVES", 19);
+  constexpr uint32_t SB = 8192;                  // frames per sub-batch
   const uint32_t nSlots = (uint32_t)std::min<uint64_t>((uint64_t)numCUs_ * wavesPerCU, nFramesTotal);
   // per-frame scratch that lives from the match finder to the entropy stage: sequences + block record + checksum + size/offset
   const uint64_t perFrame = seqStride * 8 + sizeof(ZraEncFrameState) + sizeof(ZraEncBlockOut) + 4 + 16 + 8;
   // per context (two of them); every launch boundary costs the pipeline about 7 ms (A/B on one box: 8 launches instead of 5 per 16 GiB
-  // = -2 %), so the launches are as long as a scratch budget allows; bring-up knob ZRA_ENC_PBUDGET_GIB
+  // = -2 %), so the launches are as long as a scratch budget allows.
   // Round 3: the boundary costs more than that once everything else is tuned — at 16 GiB one launch instead of five is 11-13 % of the
   // match finder's time (A/B on one box: 5 x 200 ms vs 1 x 867-897 ms; every launch ends with a tail of straggling frames and starts
   // with all waves in step). So the budget is what the device can spare: a third of its free memory, between 8 and 64 GiB (46 GiB of
   // sequence scratch take 16 GiB of 64 KiB frames through in one launch; the scratch is grow-only and given back by
   // ZraHipReleaseScratch / the engine pool's cap).
   uint64_t budget;
-  if (const char* e = std::getenv("ZRA_ENC_PBUDGET_GIB")) budget = (uint64_t)std::max(1, std::atoi(e)) << 30;
-  else {
+  {
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = 24ull << 30;
     // what this engine already holds for the purpose counts as free (the reservation below reuses it)
@@ -454,32 +438,26 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
   // the budget is a wish (other engines of the pool, other ranks on the device and the caller's own buffers read the same free-memory
   // figure): a reservation that fails is tried again with half of it, down to 1 GiB, before the call gives up with memory_allocation
   uint64_t SBIG = 0, nSuper = 0, subsPerSuper = 0; int nCtx = 1;
-  EncCtx& sh = encCtx_[0];                       // shared: table slots, the entropy workgroups' literal buffers, the ring of encoded-frame slots
-  // entropy stage: queue-driven workgroups. Behind the match finder (pipeMode 0, the default): as many as the device holds, five per CU
-  // by registers. Resident beside it (ZRA_PIPE=2): ONE per CU — what fits next to 18 match-finder waves; workgroups that find no room
-  // would keep the launch's hardware queue busy until the finder leaves.
-  // Round 5 measured both on one box (16 GiB, profiles/r05_experiments.md): beside the finder the stage keeps up (0.92-0.97 ms per frame
-  // and workgroup), and slows the finder from 846-970 ms to 1020-1075 ms: its work is ALU and LDS work, not idle latency, and costs about
-  // what it costs alone. Behind the finder: 846 + 187 ms.
-  static const uint32_t entPerCU = std::getenv("ZRA_ENT_WGS") ? (uint32_t)std::max(1, std::atoi(std::getenv("ZRA_ENT_WGS"))) : (pipeMode == 0 ? 5u : pipeMode == 1 ? 8u : 1u);
+  EncCtx& sh = encCtx_[0];                       // shared: table slots, the entropy workgroups' literal buffers, the encoded-frame slots
+  // entropy stage: queue-driven workgroups, launched per sub-batch; they sit where a CU has room beside the finder's waves
+  static const uint32_t entPerCU = (uint32_t)std::max(1, env_int("ZRA_ENT_WGS", 8));
   const uint32_t entGrid = (uint32_t)std::min<uint64_t>((uint64_t)numCUs_ * entPerCU, nFramesTotal);
   const uint64_t entWorkStride = (9 * seqStride + 255) & ~255ull;
-  // round 6: the split entropy stage (pipeMode 1 only): per sub-batch a FRONT launch (literals, tables), zra_ent_chain_kernel (the state chains,
+  // round 6: the split entropy stage: per sub-batch a FRONT launch (literals, tables), zra_ent_chain_kernel (the state chains,
   // lane = (frame, stream)), a BACK launch (sequence bitstream, block / frame end). The work area and a record are then per FRAME of the
   // sub-batch. ZRA_ENT_SPLIT: 0 never, 1 (default) calls of at least 256 frames, 2 always.
-  static const int splitEnv = std::getenv("ZRA_ENT_SPLIT") ? std::atoi(std::getenv("ZRA_ENT_SPLIT")) : 1;
-  const bool entSplit = pipeMode == 1 && (splitEnv >= 2 || (splitEnv == 1 && nFramesTotal >= 256));
-  static const uint32_t ringSubsEnv = std::getenv("ZRA_ENC_RING") ? (uint32_t)std::max(2, std::atoi(std::getenv("ZRA_ENC_RING"))) : 4u;   // sub-batches the slot ring holds
+  static const int splitEnv = env_int("ZRA_ENT_SPLIT", 1);
+  const bool entSplit = splitEnv >= 2 || (splitEnv == 1 && nFramesTotal >= 256);
+  // encoded-frame slots: one sub-batch's worth (each sub-batch's entropy launch encodes into slots 0 .. its frames - 1, and its scan and
+  // gather follow it in stream order before the next sub-batch's launch)
   uint64_t slotRing = 0;
   for (;; budget /= 2) {
     SBIG = std::max<uint64_t>(1, std::min<uint64_t>(nFramesTotal, budget / perFrame));
-    if (const char* e = std::getenv("ZRA_ENC_SUPER")) SBIG = std::max<uint64_t>(1, std::min<uint64_t>(SBIG, (uint64_t)std::atoll(e)));   // bring-up knob
     if (SBIG > SB) SBIG -= SBIG % SB;
     nCtx = nFramesTotal > SBIG ? 2 : 1;
     nSuper = (nFramesTotal + SBIG - 1) / SBIG;
     subsPerSuper = (SBIG + SB - 1) / SB;
-    slotRing = std::min<uint64_t>((uint64_t)ringSubsEnv * SB, subsPerSuper * (uint64_t)SB);
-    if (SBIG <= SB) slotRing = SBIG;
+    slotRing = std::min<uint64_t>(SB, SBIG);
     const uint64_t workUnits = entSplit ? std::min<uint64_t>(SB, nFramesTotal) : entGrid;
     bool okR = sh.tables.reserve((size_t)nSlots * tableWords * 4) && sh.lits.reserve((size_t)entGrid * litStride) && sh.work.reserve((size_t)workUnits * entWorkStride) &&
                sh.slots.reserve(slotRing * slotStride) && (!entSplit || sh.rec.reserve((size_t)workUnits * sizeof(ZraEntRec)));
@@ -492,19 +470,18 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
     if (budget <= (1ull << 30) || SBIG <= SB) return zerr(64);
     (void)hipGetLastError();
   }
-  // counters: [u64 running offset][pad][abort + 3 pad][per super-batch 8: mf queue, mf started, entropy queue, scanned, handing out,
-  // gathered, 2 pad][per sub-batch 4: encoded, handed out for copying, copied, finished by the match finder]
+  // counters: [u64 running offset][pad][4 unused][per super-batch 8: mf queue, mf started, 6 unused][per sub-batch 4: the entropy
+  // (FRONT) launch's frame queue, the BACK launch's frame queue, unused, finished by the match finder]
   const size_t nCnt = 4 + 8 * (size_t)nSuper + 4 * (size_t)(nSuper * subsPerSuper) + 4;
   const size_t cntCore = (16 + 4 * nCnt + 15) & ~(size_t)15;
   const size_t cntBytes = cntCore + 8 * (size_t)ZRA_TELE_WORDS;      // + the launch telemetry (ZraEncArgs::mfTele)
   if (!encScan_.reserve(cntBytes)) return zerr(64);
   uint64_t* dRunning = encScan_.as<uint64_t>();
   uint32_t* dCnt = (uint32_t*)(encScan_.as<uint8_t>() + 16);
-  uint32_t* dAbort = dCnt;                       // [0]
   uint32_t* dPerSuper = dCnt + 4;                // 8 words per super-batch
   uint32_t* dPerSub = dPerSuper + 8 * nSuper;    // 4 x subsPerSuper words per super-batch
   HIPCHK(hipMemsetAsync(encScan_.as<uint8_t>(), 0, cntBytes, stream_));
-  encCounters_ = dCnt; encCountersBytes_ = 4 * (4 + 8 * (size_t)nSuper + 4 * (size_t)(nSuper * subsPerSuper));   // (... the per-sub-batch words too: stream B waits on the finder's mfDone counts)   // (an error exit fills them with 0x7F: the abort word is set, the queues are past their ends, every wait of the two kernels and of stream B ends)
+  encCounters_ = dCnt; encCountersBytes_ = 4 * (4 + 8 * (size_t)nSuper + 4 * (size_t)(nSuper * subsPerSuper));   // (an error exit fills them with 0x7F: the queues are past their ends, every wait of stream B on the finder's counts ends)
 
   ZraEncArgs base{};
   base.in = dIn; base.inSize = inSize; base.frameSize = frameSize; base.checksum = checksum ? 1 : 0;
@@ -515,26 +492,24 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
   base.entWorkStride = entWorkStride;
   // issue priority of the entropy stage's waves beside the finder: 1 (one box, alternating processes: priority 3 -> 903-911 ms, 1 -> 879-880,
   // 0 -> 919 with the stage falling behind)
-  { static const int ep = std::getenv("ZRA_ENT_PRIO") ? std::atoi(std::getenv("ZRA_ENT_PRIO")) : 1; base.entPrio = (uint32_t)ep; }
-  base.pipeAbort = dAbort; base.entSubFrames = SB; base.slotRing = (uint32_t)slotRing; base.readyStamp = 1u;
-  base.running = dRunning; base.gBody = dBody + bodyBase0; base.gEntries = dEntries; base.gSizesOut = dSizes;
+  base.entPrio = 1;
+  base.entSubFrames = SB; base.slotRing = (uint32_t)slotRing; base.readyStamp = 1u;
   // LDS geometry of the match finder's wave: the bucket filter — 1 bit per 2^shL long-table buckets, 1 bit per 2^shS short-table buckets —
   // and the duplicate-detection slots: 2 KiB + 4 KiB + 0.5 KiB = 6.5 KiB at hashLog 16 / chainLog 15 (one bit per 2 long buckets, per 8
   // short buckets). The flag sweep ahead of a frame's parse (df_later_flags) runs over the same bytes. What fits a CU beside the entropy
   // stage's workgroup is decided by LDS in pieces of 1,280 bytes (below): 18 waves of <= 7,680 bytes, or 20 of <= 6,400 — and 20 were
   // measured slower whichever part paid for it (128 duplicate slots: + 9 %; 1 filter bit per 16 short buckets: + 3 %).
-  uint32_t shL = 1, shS = 3, dupLog = 8;
-  if (const char* f = std::getenv("ZRA_MF_FILTER")) { unsigned x = 1, y = 1, z = 8; if (std::sscanf(f, "%u,%u,%u", &x, &y, &z) >= 1) { shL = x & 15; shS = y & 15; dupLog = z & 15; } }
+  const uint32_t shL = 1, shS = 3, dupLog = 8;
   base.mfFilter = shL | (shS << 4) | (dupLog << 8);
   const uint32_t hl = std::max(full.hashLog, tail.hashLog), cl = std::max(full.chainLog, tail.chainLog);
   const size_t filterBytes = (8u << dupLog) + (((size_t)1 << hl) >> shL) / 8 + (((size_t)1 << cl) >> shS) / 8;
 
   // ---- latency mode (round 4): calls of at most ZRA_MF_LS_MAX frames (default: two per CU, what LDS holds at 64 KiB) run the dfast parse over
   // a copy of the frame in LDS (zra_mf_dfast_ls_kernel). ZRA_MF_LS=0 turns it off.
-  static const int lsEnv = std::getenv("ZRA_MF_LS") ? std::atoi(std::getenv("ZRA_MF_LS")) : 1;
+  static const int lsEnv = env_int("ZRA_MF_LS", 1);
   const uint32_t lsBytes = (uint32_t)((std::min<uint64_t>(frameSize, inSize) + 64 + 63) & ~63ull);
   const uint32_t lsPerCu = (uint32_t)((160u << 10) / (lsBytes + filterBytes));
-  static const int lsMaxEnv = std::getenv("ZRA_MF_LS_MAX") ? std::atoi(std::getenv("ZRA_MF_LS_MAX")) : -1;
+  static const int lsMaxEnv = env_int("ZRA_MF_LS_MAX", -1);
   bool useLs = lsEnv != 0 && full.strategy == 2 && lsPerCu >= 1 &&
                nFramesTotal <= (lsMaxEnv >= 0 ? (uint64_t)lsMaxEnv : (uint64_t)lsPerCu * (uint64_t)numCUs_);
   if (useLs && lsAttr_ == 0) {
@@ -545,8 +520,8 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
   if (lsAttr_ < 0) useLs = false;
 
   // ---- round 5: bucket flags computed by the match finder's own waves, ahead of each frame's parse (df_later_flags): one flag slot per
-  // resident wave. ZRA_MF_FLAGS=0 turns them off (bring-up A/B).
-  static const int flEnv = std::getenv("ZRA_MF_FLAGS") ? std::atoi(std::getenv("ZRA_MF_FLAGS")) : 1;
+  // resident wave. ZRA_MF_FLAGS=0 turns them off (test hook).
+  static const int flEnv = env_int("ZRA_MF_FLAGS", 1);
   const bool useFlagsWave = flEnv != 0 && !useLs && full.strategy == 2;
   ZraFlagArgs fw{};
   if (useFlagsWave) {
@@ -556,14 +531,11 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
     // the parse's source span in LDS behind the filter (mf_dfast_lean): 768 bytes + their flags = 992 bytes per wave. LDS is handed out
     // in pieces of 1,280 bytes on this chip (measured, profiles/r05_experiments.md §6: 21 waves of 6.5 KiB fit a CU, not 24), so a wave
     // holds 7,680 bytes with or without the span, and 18 waves + the entropy stage's workgroup (24,320) fill the CU's 163,840 to within
-    // 1,280 bytes. ZRA_MF_SPAN=<bytes> (multiple of 64, <= 1024; 0: none)
-    static const int spEnv = std::getenv("ZRA_MF_SPAN") ? std::atoi(std::getenv("ZRA_MF_SPAN")) : 768;
-    fw.spanBytes = (uint32_t)std::min(1024, std::max(0, spEnv)) & ~63u;
-    // (advisor, round 5: the parse needs 15 bytes of alignment slack + a window's 64 + 7 bytes in the span; a shorter one could never be filled)
-    if (fw.spanBytes < 128) fw.spanBytes = 0;
+    // 1,280 bytes. (A multiple of 64, at most 1024; the parse needs 15 bytes of alignment slack + a window's 64 + 7 bytes in it.)
+    fw.spanBytes = 768;
     // round 6: epoch bits in the cells' tag field — a wave clears its 384 KiB table slot once per 2^epochBits frames instead of per frame.
     // The tag keeps >= 10 hash bits (position + 1 takes 16-17 bits of a cell at 64-128 KiB frames). ZRA_MF_EPOCH=<bits> (0: clear per frame)
-    static const int epEnv = std::getenv("ZRA_MF_EPOCH") ? std::atoi(std::getenv("ZRA_MF_EPOCH")) : 4;
+    static const int epEnv = env_int("ZRA_MF_EPOCH", 4);
     const uint32_t ibMax = 32u - (uint32_t)__builtin_clz((uint32_t)std::max<uint64_t>(2, std::min<uint64_t>(frameSize, inSize)) - 1u);
     fw.epochBits = (uint32_t)std::max(0, std::min(epEnv, (int)(32u - ibMax) - 10));   // (the kernel holds ZRA_DF_EPOCH_BITS = 4 of them)
   }
@@ -575,7 +547,7 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
     return evPool_[evNext++];
   };
   std::vector<std::pair<hipEvent_t, hipEvent_t>> mfSpans, entSpans;
-  static const bool traceOn = std::getenv("ZRA_ENC_TRACE") != nullptr;   // bring-up: timeline of the launches on stderr
+  static const bool traceOn = env_set("ZRA_ENC_TRACE");   // diagnostics: timeline of the launches on stderr
   hipEvent_t superDone[2] = {nullptr, nullptr};
   // stream B starts after the counters are cleared and after whatever the caller queued on the engine stream
   { hipEvent_t e0 = ev(); if (!e0) return zerr(1); HIPCHK(hipEventRecord(e0, stream_)); HIPCHK(hipStreamWaitEvent(stream2_, e0, 0)); }
@@ -593,10 +565,9 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
     a.blockOut = (ZraEncBlockOut*)(x.misc.as<uint8_t>() + (size_t)SBIG * sizeof(ZraEncFrameState));
     a.contentCk = x.ck.as<uint32_t>();
     a.sizes = x.sizes.as<uint64_t>();
-    a.mfQueue = dPerSuper + 8 * S; a.mfStarted = a.mfQueue + 1; a.entQueue = a.mfQueue + 2; a.scanDone = a.mfQueue + 3; a.gatherJ = a.mfQueue + 4; a.gatherDone = a.mfQueue + 5;
-    a.entDone = dPerSub + 4 * S * subsPerSuper; a.gQueue = a.entDone + subsPerSuper; a.gCopied = a.gQueue + subsPerSuper;
-    a.mfDone = pipeMode == 1 ? a.gCopied + subsPerSuper : nullptr;
-    a.offsets = x.sizes.as<uint64_t>() + SBIG;
+    a.mfQueue = dPerSuper + 8 * S; a.mfStarted = a.mfQueue + 1;
+    uint32_t* const entQ = dPerSub + 4 * S * subsPerSuper;          // per sub-batch: FRONT / whole-stage queue, BACK queue, -, mf done
+    a.mfDone = entQ + 3 * subsPerSuper;
     // the context's per-frame scratch is free once the last sub-batch that used it has been gathered
     if (superDone[c]) HIPCHK(hipStreamWaitEvent(stream_, superDone[c], 0));
     // no frame of this launch is published yet (the stamps of an earlier call may still sit in the block records)
@@ -613,95 +584,66 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
     HIPCHK(hipGetLastError());                        // (a launch that failed would leave stream B waiting for waves that never start)
     HIPCHK(hipEventRecord(m1, stream_));
     mfSpans.push_back({m0, m1});
-    // a short last frame whose cparams select another strategy: parsed by the generic kernel (table slot 0 is free by then), then published
+    // a short last frame whose cparams select another strategy: parsed by the generic kernel (table slot 0 is free by then); stream B waits
+    // for it through an event
     const bool oddTail = tailSize && F0 + n == nFramesTotal && tail.strategy != 2;
     if (oddTail) {
       ZraEncArgs at = a; at.mfQueue = nullptr;
       if (tail.strategy >= 3 && tail.strategy <= 5) hipLaunchKernelGGL(zra_mf_hc_kernel, dim3(1), dim3(64), 0, stream_, at, 0u, (uint32_t)(n - 1), 0u);
       else hipLaunchKernelGGL(mfGeneric, dim3(1), dim3(64), 0, stream_, at, 0u, (uint32_t)(n - 1), 0u, 1u);
-      HIPCHK(hipStreamWriteValue32(stream_, &a.blockOut[n - 1].ready, a.readyStamp, 0));
     }
-    if (pipeMode == 1) {
-      // ---- round 4's overlap, with this round's kernels: per sub-batch of 8192 frames, released by the match finder's own count of
-      // finished frames, one entropy launch + scan + gather on stream B. The stage's workgroups come and go: they sit where a CU has
-      // room beside the finder's waves, and nowhere when there is nothing to do.
-      // (round 6: the checksum kernel — 4 x n lanes, ~2 ms of the whole chip — only once every wave of the finder is resident. Queued at once it
-      //  could reach the CUs first, the dispatcher then placed the finder's waves unevenly (20 on most CUs, 12-18 on the ones the checksum
-      //  blocks were leaving), and a CU with 20 has no room for the entropy workgroup: one process of the round ended 31 ms behind that way,
-      //  profiles/r06_experiments.md §0)
-      // (no wait of the finder depends on stream B inside a super-batch, so this cannot hang; with a bring-up ZRA_MF_WAVES beyond what a CU
-      //  holds — 21 by LDS — the last waves start when the first ones leave, and the stage then runs BEHIND the finder instead of beside it)
-      HIPCHK(hipStreamWaitValue32(stream2_, a.mfStarted, mfGrid, hipStreamWaitValueGte, 0xFFFFFFFFu));
-      if (checksum)
-        hipLaunchKernelGGL(zra_content_ck_kernel, dim3((n * 4 + 255) / 256), dim3(256), 0, stream2_, dIn, (u64)inSize, frameSize, (u32)F0, n, a.contentCk);
-      const uint32_t nSub1 = (n + SB - 1) / SB;
-      hipEvent_t eLast = nullptr;
-      for (uint32_t j = 0; j < nSub1; j++) {
-        const uint32_t j0 = j * SB, nbj = std::min<uint32_t>(SB, n - j0);
-        const bool hasOdd = oddTail && j == nSub1 - 1;
-        HIPCHK(hipStreamWaitValue32(stream2_, a.mfDone + j, nbj - (hasOdd ? 1u : 0u), hipStreamWaitValueGte, 0xFFFFFFFFu));
-        if (hasOdd) { hipEvent_t te = ev(); if (!te) return zerr(1); HIPCHK(hipEventRecord(te, stream_)); HIPCHK(hipStreamWaitEvent(stream2_, te, 0)); }
-        ZraEncArgs aj = a;
-        aj.firstFrame = (uint32_t)(F0 + j0); aj.nFrames = nbj;
-        aj.seqs = a.seqs + (size_t)j0 * seqStride; aj.state = a.state + j0; aj.blockOut = a.blockOut + j0;
-        aj.contentCk = a.contentCk + j0; aj.sizes = a.sizes + j0;
-        aj.readyStamp = 0; aj.slotRing = (uint32_t)std::min<uint64_t>(SB, slotRing); aj.entSubFrames = SB;
-        aj.entQueue = a.entDone + j;                     // (a zeroed word per sub-batch: the launch's frame queue)
-        uint64_t* dOffsets = x.sizes.as<uint64_t>() + SBIG + j0;
-        hipEvent_t e0 = ev(), e1 = ev(); if (!e0 || !e1) return zerr(1);
-        HIPCHK(hipEventRecord(e0, stream2_));
-        if (entSplit) {
-          aj.entRec = sh.rec.as<ZraEntRec>();
-          hipLaunchKernelGGL(zra_entropy_front_kernel, dim3(std::min<uint32_t>(nbj, entGrid)), dim3(256), 0, stream2_, aj, 0u);
-          // frames per wave of the chain kernel (6 / 3 / 2 / 1: the same LDS per CU as 1 / 2 / 3 / 6 waves)
-          // (5 by default: 17,640 B of LDS, what is left of a CU beside 19 finder waves; 6 needs the room 18 waves leave)
-          static const uint32_t chainG = std::getenv("ZRA_CHAIN_G") ? (uint32_t)std::atoi(std::getenv("ZRA_CHAIN_G")) : (wavesPerCU >= 19 ? 5u : 6u);
-          const uint32_t cg = chainG <= 1 ? 1u : chainG == 2 ? 2u : chainG <= 4 ? 3u : chainG == 5 ? 5u : 6u;
-          const auto chainK = cg == 1 ? zra_ent_chain1_kernel : cg == 2 ? zra_ent_chain2_kernel : cg == 3 ? zra_ent_chain3_kernel : cg == 5 ? zra_ent_chain5_kernel : zra_ent_chain_kernel;
-          hipLaunchKernelGGL(chainK, dim3((nbj + cg - 1) / cg), dim3(64), 0, stream2_, aj);
-          ZraEncArgs ab = aj; ab.entQueue = a.gQueue + j;   // (another zeroed word of the sub-batch: the BACK launch's frame queue)
-          hipLaunchKernelGGL(zra_entropy_back_kernel, dim3(std::min<uint32_t>(nbj, entGrid)), dim3(256), 0, stream2_, ab, 0u);
-        } else
-          hipLaunchKernelGGL(zra_entropy_kernel, dim3(std::min<uint32_t>(nbj, entGrid)), dim3(256), 0, stream2_, aj, 0u);
-        HIPCHK(hipEventRecord(e1, stream2_));
-        entSpans.push_back({e0, e1});
-        hipLaunchKernelGGL(zra_scan_sizes_kernel, dim3(1), dim3(64), 0, stream2_, aj.sizes, nbj, dOffsets, dRunning, (const u32*)nullptr);
-        hipLaunchKernelGGL(zra_gather_frames_kernel, dim3(nbj), dim3(256), 0, stream2_, aj.slots, slotStride, aj.sizes, dOffsets, dBody,
-                           bodyBase0, dEntries ? dEntries : nullptr, (u32)(F0 + j0), dSizes, (const u32*)nullptr);
-        eLast = e1;
-      }
-      hipEvent_t done = ev(); if (!done) return zerr(1);
-      HIPCHK(hipEventRecord(done, stream2_));
-      superDone[c] = done;
-      (void)eLast;
-      continue;
-    }
-    // stream B: once every wave of the match finder is resident (they are placed first, side by side: what is left of each CU is one
-    // contiguous piece), the content checksums, then the queue-driven entropy stage. pipeMode 0: only behind the whole match-finder
-    // launch, with as many workgroups as the device holds; pipeMode 2: at once, resident beside the finder
-    if (pipeMode == 0) HIPCHK(hipStreamWaitEvent(stream2_, m1, 0));
-    else HIPCHK(hipStreamWaitValue32(stream2_, a.mfStarted, mfGrid, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    // ---- per sub-batch of 8192 frames, released by the match finder's own count of finished frames, one entropy launch + scan +
+    // gather on stream B. The stage's workgroups come and go: they sit where a CU has room beside the finder's waves, and nowhere when
+    // there is nothing to do.
+    // (round 6: the checksum kernel — 4 x n lanes, ~2 ms of the whole chip — only once every wave of the finder is resident. Queued at once it
+    //  could reach the CUs first, the dispatcher then placed the finder's waves unevenly (20 on most CUs, 12-18 on the ones the checksum
+    //  blocks were leaving), and a CU with 20 has no room for the entropy workgroup: one process of the round ended 31 ms behind that way,
+    //  profiles/r06_experiments.md §0)
+    // (no wait of the finder depends on stream B inside a super-batch, so this cannot hang; with a test hook ZRA_MF_WAVES beyond what a CU
+    //  holds — 21 by LDS — the last waves start when the first ones leave, and the stage then runs BEHIND the finder instead of beside it)
+    HIPCHK(hipStreamWaitValue32(stream2_, a.mfStarted, mfGrid, hipStreamWaitValueGte, 0xFFFFFFFFu));
     if (checksum)
       hipLaunchKernelGGL(zra_content_ck_kernel, dim3((n * 4 + 255) / 256), dim3(256), 0, stream2_, dIn, (u64)inSize, frameSize, (u32)F0, n, a.contentCk);
-    hipEvent_t e0 = ev(), e1 = ev(); if (!e0 || !e1) return zerr(1);
-    HIPCHK(hipEventRecord(e0, stream2_));
-    hipLaunchKernelGGL(zra_entropy_kernel, dim3(std::min<uint32_t>(n, entGrid)), dim3(256), 0, stream2_, a, 0u);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, stream2_));
-    entSpans.push_back({e0, e1});
-    // (the entropy launch ends when every frame of the super-batch sits in the archive: the context's scratch and the slot ring are free)
-    superDone[c] = e1;
+    const uint32_t nSub1 = (n + SB - 1) / SB;
+    for (uint32_t j = 0; j < nSub1; j++) {
+      const uint32_t j0 = j * SB, nbj = std::min<uint32_t>(SB, n - j0);
+      const bool hasOdd = oddTail && j == nSub1 - 1;
+      HIPCHK(hipStreamWaitValue32(stream2_, a.mfDone + j, nbj - (hasOdd ? 1u : 0u), hipStreamWaitValueGte, 0xFFFFFFFFu));
+      if (hasOdd) { hipEvent_t te = ev(); if (!te) return zerr(1); HIPCHK(hipEventRecord(te, stream_)); HIPCHK(hipStreamWaitEvent(stream2_, te, 0)); }
+      ZraEncArgs aj = a;
+      aj.firstFrame = (uint32_t)(F0 + j0); aj.nFrames = nbj;
+      aj.seqs = a.seqs + (size_t)j0 * seqStride; aj.state = a.state + j0; aj.blockOut = a.blockOut + j0;
+      aj.contentCk = a.contentCk + j0; aj.sizes = a.sizes + j0;
+      aj.entQueue = entQ + j;                          // (a zeroed word per sub-batch: the launch's frame queue)
+      uint64_t* dOffsets = x.sizes.as<uint64_t>() + SBIG + j0;
+      hipEvent_t e0 = ev(), e1 = ev(); if (!e0 || !e1) return zerr(1);
+      HIPCHK(hipEventRecord(e0, stream2_));
+      if (entSplit) {
+        aj.entRec = sh.rec.as<ZraEntRec>();
+        hipLaunchKernelGGL(zra_entropy_front_kernel, dim3(std::min<uint32_t>(nbj, entGrid)), dim3(256), 0, stream2_, aj, 0u);
+        // frames per wave of the chain kernel: 5 at 19 or more finder waves (17,640 B of LDS, what is left of a CU beside 19 of them), else
+        // 6 (the room 18 waves leave)
+        const uint32_t cg = wavesPerCU >= 19 ? 5u : 6u;
+        hipLaunchKernelGGL(cg == 5 ? zra_ent_chain5_kernel : zra_ent_chain_kernel, dim3((nbj + cg - 1) / cg), dim3(64), 0, stream2_, aj);
+        ZraEncArgs ab = aj; ab.entQueue = entQ + subsPerSuper + j;   // (another zeroed word of the sub-batch: the BACK launch's frame queue)
+        hipLaunchKernelGGL(zra_entropy_back_kernel, dim3(std::min<uint32_t>(nbj, entGrid)), dim3(256), 0, stream2_, ab, 0u);
+      } else
+        hipLaunchKernelGGL(zra_entropy_kernel, dim3(std::min<uint32_t>(nbj, entGrid)), dim3(256), 0, stream2_, aj, 0u);
+      HIPCHK(hipEventRecord(e1, stream2_));
+      entSpans.push_back({e0, e1});
+      hipLaunchKernelGGL(zra_scan_sizes_kernel, dim3(1), dim3(64), 0, stream2_, aj.sizes, nbj, dOffsets, dRunning, (const u32*)nullptr);
+      hipLaunchKernelGGL(zra_gather_frames_kernel, dim3(nbj), dim3(256), 0, stream2_, aj.slots, slotStride, aj.sizes, dOffsets, dBody,
+                         bodyBase0, dEntries ? dEntries : nullptr, (u32)(F0 + j0), dSizes, (const u32*)nullptr);
+    }
+    hipEvent_t done = ev(); if (!done) return zerr(1);
+    HIPCHK(hipEventRecord(done, stream2_));
+    superDone[c] = done;
   }
   uint64_t total = 0;
   HIPCHK(hipMemcpyAsync(&total, dRunning, 8, hipMemcpyDeviceToHost, stream2_));
   HIPCHK(hipStreamSynchronize(stream2_));
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipGetLastError());
-  {
-    uint32_t aborted = 0;
-    HIPCHK(hipMemcpy(&aborted, dAbort, 4, hipMemcpyDeviceToHost));
-    if (aborted) return zerr(1);                      // a wait between the two persistent kernels ran out of patience
-  }
   double kernelMs = 0;
   kstats_[0] = kstats_[1] = kstats_[2] = kstats_[3] = 0;
   for (auto& sp : mfSpans) { float m = 0; if (hipEventElapsedTime(&m, sp.first, sp.second) == hipSuccess) { kstats_[0] += m; kstats_[1] += 1; kernelMs += m; } }
@@ -815,8 +757,7 @@ Status Engine::decode_host(const uint8_t* hSpan, size_t spanSize, const std::vec
   // ~40 % of such a call. Here the job arrays and the compressed span travel in ONE copy from page-locked memory, the kernel is queued
   // straight behind it, and the answer comes back through page-locked memory: one copy in, one launch, one copy out, one wait.
   constexpr size_t kSmallSpan = 768u << 10, kSmallOut = 1u << 20, kSmallJobs = 16;
-  static const bool smallHostOff = std::getenv("ZRA_HOST_SMALL") && std::atoi(std::getenv("ZRA_HOST_SMALL")) == 0;
-  if (!smallHostOff && !wholeArchive && nFrames <= kSmallJobs && spanSize <= kSmallSpan && size <= kSmallOut && (uint64_t)nFrames * frameSize <= (64ull << 20)) {
+  if (!wholeArchive && nFrames <= kSmallJobs && spanSize <= kSmallSpan && size <= kSmallOut && (uint64_t)nFrames * frameSize <= (64ull << 20)) {
     const size_t metaBytes = (size_t)kSmallJobs * (16 + 8 + 4 + 4);                   // frameOff pairs, outOff, expect (padded)
     const size_t inBytes = metaBytes + ((spanSize + 63) & ~(size_t)63);
     if (!pinSmall_) {

@@ -1222,72 +1222,25 @@ __device__ __attribute__((noinline)) void entropy_frame_call(KArgs& a, u32 block
   entropy_frame<PHASE>(au, block, f, pin(lits), pin(slot), pin(work), S, (ZraEntRec*)pin((u8*)rec));
 }
 
-// The entropy stage: workgroups that take frames from a queue, each with its own literal buffer and sequence work area.
-//  * Batch path (multi-block frames, the other strategies): launched per block round behind the batch's match-finder launch; the queue
-//    hands out the batch's frames, nothing to wait for (readyStamp == 0), a slot per frame.
-//  * Persistent pipeline (round 5; single-block dfast frames): the workgroups stay resident BESIDE the persistent match finder — one
-//    per CU is what a CU's LDS and registers hold next to 18-20 match-finder waves — and take frames in frame order: wait until the
-//    match finder has published the frame (its stamp in the block record), encode it into the slot ring, count it for the host's scan +
-//    gather of the sub-batch. Rounds 1-4 launched one workgroup per frame and sub-batch instead; whether a workgroup found room on a CU
-//    then depended on how the match finder's waves had happened to land, and at one workgroup per CU the stage could not keep up.
-//    Every wait gives up after ~10 s of the 100 MHz clock (pipeAbort): the call fails, the GPU does not hang.
-// ---- the pipeline's seek-table build, done by the entropy stage's own workgroups (round 5: launches of a scan / gather kernel on a
-// third stream were not placed while the two persistent kernels held the device — the first gather ran until the match finder left)
-// exclusive scan of the sizes of sub-batch j -> a.offsets (absolute inside the body), *a.running += the sub-batch's bytes
-__device__ __forceinline__ void pipe_scan_subbatch(KArgs& a, u32 j, EncShared& S) {
-  const u32 j0 = j * a.entSubFrames, nbj = min(a.entSubFrames, a.nFrames - j0);
-  const u32 per = (nbj + ENT_THREADS - 1) / ENT_THREADS, i0 = j0 + per * threadIdx.x, i1 = min(i0 + per, j0 + nbj);
-  u32 sum = 0;
-  for (u32 i = i0; i < i1; i++) sum += (u32)a.sizes[i];
-  u32 tot;
-  const u32 ex = block_excl_scan(S, sum, &tot);
-  u64 off = *a.running + ex;
-  for (u32 i = i0; i < i1; i++) { a.offsets[i] = off; off += a.sizes[i]; }
-  __syncthreads();
-  if (threadIdx.x == 0) *a.running += tot;
-}
-// frame `fi` of the launch: from its slot to body + offsets[fi]; seek-table entry and size
-__device__ __forceinline__ void pipe_gather_frame(KArgs& a, u32 fi) {
-  const u64 n = a.sizes[fi], off = a.offsets[fi];
-  const u8* s = a.slots + (size_t)(fi % a.slotRing) * a.slotStride; u8* d = a.gBody + off;
-  const u64 n16 = n >> 4;
-  for (u64 i = threadIdx.x; i < n16; i += ENT_THREADS) {
-    const uint4 v = ((const uint4*)s)[i];
-    st64(d + 16 * i, (u64)v.x | ((u64)v.y << 32)); st64(d + 16 * i + 8, (u64)v.z | ((u64)v.w << 32));
-  }
-  for (u64 i = (n16 << 4) + threadIdx.x; i < n; i += ENT_THREADS) d[i] = s[i];
-  if (threadIdx.x == 0) {
-    if (a.gEntries) { u8* e = a.gEntries + (size_t)(a.firstFrame + fi) * 5; st32(e, (u32)off); e[4] = (u8)(off >> 32); }
-    if (a.gSizesOut) a.gSizesOut[a.firstFrame + fi] = n;
-  }
-}
-
-// The entropy stage: workgroups that take frames from a queue, each with its own literal buffer and sequence work area.
-//  * Batch path (multi-block frames, the other strategies): launched per block round behind the batch's match-finder launch; the queue
-//    hands out the batch's frames, nothing to wait for (readyStamp == 0), a slot per frame; the host launches scan and gather.
-//  * Persistent pipeline (round 5; single-block dfast frames): the workgroups stay resident BESIDE the persistent match finder — one
-//    per CU is what a CU's LDS and registers hold next to 18-20 match-finder waves — and take frames in frame order: wait until the
-//    match finder has published the frame (its stamp in the block record), encode it into the slot ring, count it; the workgroup that
-//    completes a sub-batch scans its sizes, and everybody copies encoded frames of scanned sub-batches into the archive between two
-//    frames of their own. Rounds 1-4 launched one workgroup per frame and sub-batch instead; whether a workgroup found room on a CU
-//    then depended on how the match finder's waves had happened to land, and at one workgroup per CU the stage could not keep up.
-//    Nothing waits without doing the other work that is ready, and every wait gives up after ~10 s of the 100 MHz clock (pipeAbort):
-//    the call fails, the GPU does not hang.
+// The entropy stage: workgroups that take frames from a queue (`entQueue`), each with its own literal buffer and sequence work area,
+// and leave when the queue is dry. The host launches scan and gather behind it.
+//  * Batch path (multi-block frames, the other strategies): launched per block round behind the batch's match-finder launch, a slot per
+//    frame.
+//  * Persistent pipeline (single-block dfast frames): launched per sub-batch once the match finder has finished the sub-batch's frames;
+//    its workgroups sit where a CU has room beside the finder's waves, frame f of the sub-batch in slot f.
 template <int PHASE>
 __device__ __forceinline__ void entropy_kernel_body(u32 block) {
   KArgs& a = *(KArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // (the kernel's first argument, where it arrived)
   __shared__ EncShared S;
   // This stage runs beside the match finder, which fills most issue slots; the one-lane serial sections here are latency-critical.
-  // Raise the wave's issue priority so they are not queued behind match-finder waves (a.entPrio: bring-up knob ZRA_ENT_PRIO, default 3).
+  // Raise the wave's issue priority so they are not queued behind match-finder waves (a.entPrio: 1 in the persistent pipeline, 3 in the
+  // batch path).
   switch (a.entPrio) { case 0: __builtin_amdgcn_s_setprio(0); break; case 1: __builtin_amdgcn_s_setprio(1); break; case 2: __builtin_amdgcn_s_setprio(2); break; default: __builtin_amdgcn_s_setprio(3); break; }
   const int tid = threadIdx.x;
   u8* const lits = a.lits + (size_t)blockIdx.x * a.litStride;
   u8* const workWg = a.entWork + (size_t)blockIdx.x * a.entWorkStride;      // (split stage: a work area per FRAME, below)
-  const bool pipe = a.readyStamp != 0;
-  const u32 SBF = a.entSubFrames, nSub = pipe ? (a.nFrames + SBF - 1) / SBF : 0u, ringSubs = max(1u, a.slotRing / SBF);
   // thread 0's bookkeeping
-  u32 pend = 0xFFFFFFFFu; bool dry = false;
-  u64 tStart = 0, tWait = 0, idleSince = 0; u32 nDone = 0;
+  u64 tStart = 0; u32 nDone = 0;
   if (tid == 0 && a.mfTele) {
     const u32 hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;
     atomicAdd((unsigned long long*)&a.mfTele[ZRA_TELE_ENT + 8 + ((xcc << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 15u))], 1ull);
@@ -1296,97 +1249,23 @@ __device__ __forceinline__ void entropy_kernel_body(u32 block) {
   for (;;) {
     __syncthreads();                                   // (S.sc of the step before is no longer read)
     if (tid == 0) {
-      u32 act = 0, arg = 0;                            // 0 nothing ready (slept), 1 copy frame arg, 2 encode frame arg, 4 leave
-      if (pipe) {
-        // 1. an encoded frame of a scanned sub-batch to copy?
-        u32 j = __hip_atomic_load(a.gatherJ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (j < nSub && j < __hip_atomic_load(a.scanDone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {
-          const u32 nbj = min(SBF, a.nFrames - j * SBF);
-          const u32 g = __hip_atomic_load(&a.gQueue[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nbj ? atomicAdd(&a.gQueue[j], 1u) : nbj;
-          if (g < nbj) { act = 1; arg = j * SBF + g; break; }
-          atomicCAS(a.gatherJ, j, j + 1);
-          j = __hip_atomic_load(a.gatherJ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      if (!act) {
-        // 2. a frame to encode: the next of the queue, once its slot is free and the match finder has published it
-        if (pend == 0xFFFFFFFFu && !dry) { const u32 f = atomicAdd(a.entQueue, 1u); if (f < a.nFrames) pend = f; else dry = true; }
-        if (pend != 0xFFFFFFFFu) {
-          bool okF = true;
-          if (pipe) {
-            const u32 j = pend / SBF;
-            if (j >= ringSubs && __hip_atomic_load(a.gatherDone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) + ringSubs <= j) okF = false;
-            else if (__hip_atomic_load(&a.blockOut[pend].ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != a.readyStamp) okF = false;
-          }
-          if (okF) { act = 2; arg = pend; pend = 0xFFFFFFFFu; nDone++; }
-        } else if (!pipe || __hip_atomic_load(a.gatherDone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= nSub) act = 4;   // nothing left anywhere
-      }
-      if (pipe && __hip_atomic_load(a.pipeAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) act = 4;
-      if (!act) {
-        const u64 t = wall_clock64();
-        if (!idleSince) idleSince = t;
-        else if (t - idleSince > 1000000000ull) { atomicExch(a.pipeAbort, 2u); act = 4; }
-        __builtin_amdgcn_s_sleep(64);
-        tWait += wall_clock64() - t;
-      } else idleSince = 0;
-      S.sc[15] = act; S.sc[14] = arg;
+      const u32 f = atomicAdd(a.entQueue, 1u);
+      if (f < a.nFrames) nDone++;
+      S.sc[14] = f;
     }
     __syncthreads();
-    const u32 act = (u32)__builtin_amdgcn_readfirstlane((int)S.sc[15]), arg = (u32)__builtin_amdgcn_readfirstlane((int)S.sc[14]);
-    if (act == 4) {
+    const u32 f = (u32)__builtin_amdgcn_readfirstlane((int)S.sc[14]);
+    if (f >= a.nFrames) {
+      // (telemetry word [2], ticks spent waiting, stays 0: nothing here waits)
       if (tid == 0 && a.mfTele && nDone > 0) {
         u64* const t = a.mfTele + ZRA_TELE_ENT;
         atomicAdd((unsigned long long*)&t[0], 1ull); atomicAdd((unsigned long long*)&t[1], wall_clock64() - tStart);
-        atomicAdd((unsigned long long*)&t[2], tWait); atomicAdd((unsigned long long*)&t[3], (unsigned long long)nDone);
+        atomicAdd((unsigned long long*)&t[3], (unsigned long long)nDone);
       }
       return;
     }
-    if (act == 0) continue;
-    if (act == 1) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");             // the frame's slot, size and offset (other workgroups wrote them)
-      pipe_gather_frame(a, arg);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");             // (the slot has been read: it may be written again once the sub-batch is through)
-      __syncthreads();
-      if (tid == 0) {
-        const u32 j = arg / SBF, nbj = min(SBF, a.nFrames - j * SBF);
-        if (atomicAdd(&a.gCopied[j], 1u) + 1 == nbj) {
-          // sub-batches finish in any order: move the count of finished ones over every one that is complete
-          for (;;) {
-            const u32 d = __hip_atomic_load(a.gatherDone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            if (d >= nSub || __hip_atomic_load(&a.gCopied[d], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != min(SBF, a.nFrames - d * SBF)) break;
-            atomicCAS(a.gatherDone, d, d + 1);
-          }
-        }
-      }
-      continue;
-    }
-    // act == 2: encode frame `arg`
-    if (pipe) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // what the match finder wrote for this frame (sequences, block record)
-    entropy_frame_call<PHASE>(a, block, arg, lits, a.slots + (size_t)(arg % a.slotRing) * a.slotStride,
-                              PHASE ? a.entWork + (size_t)arg * a.entWorkStride : workWg, S, PHASE ? a.entRec + arg : nullptr);
-    if (pipe) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");             // the slot and the frame's size, before the count
-      __syncthreads();
-      const u32 j = arg / SBF, nbj = min(SBF, a.nFrames - j * SBF);
-      if (tid == 0) S.sc[13] = atomicAdd(&a.entDone[j], 1u) + 1 == nbj ? 1u : 0u;
-      __syncthreads();
-      if (S.sc[13]) {
-        // this workgroup encoded the sub-batch's last frame: it scans the sizes, behind the scan of the sub-batch before
-        if (tid == 0) {
-          const u64 t0 = wall_clock64();
-          while (__hip_atomic_load(a.scanDone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != j) {
-            __builtin_amdgcn_s_sleep(16);
-            if (__hip_atomic_load(a.pipeAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || wall_clock64() - t0 > 1000000000ull) { atomicExch(a.pipeAbort, 2u); break; }
-          }
-        }
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // every frame size of the sub-batch, the running offset
-        pipe_scan_subbatch(a, j, S);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(a.scanDone, j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    entropy_frame_call<PHASE>(a, block, f, lits, a.slots + (size_t)(f % a.slotRing) * a.slotStride,
+                              PHASE ? a.entWork + (size_t)f * a.entWorkStride : workWg, S, PHASE ? a.entRec + f : nullptr);
   }
 }
 
@@ -1406,7 +1285,7 @@ zra_entropy_back_kernel(ZraEncArgs a_, u32 block) { (void)a_; entropy_kernel_bod
 // beside the match finder's 18 waves, as many as fit otherwise.
 #define ZRA_CHAIN_TBL_BYTES 3528u      /* per frame: state tables LL 512 + OF 256 + ML 512 u16; {deltaNbBits, deltaFindState} LL 36 + OF 32 + ML 53 */
 // (G frames per wave. Beside the match finder a lone wave's step is bound by its issue slots, not by lanes: fewer frames per wave and more
-//  waves per CU — same LDS — buy issue share; zra_encode.hip picks the instantiation: ZRA_CHAIN_G)
+//  waves per CU — same LDS — buy issue share; zra_encode.hip picks 5 or 6 by the match finder's waves per CU)
 template <u32 ZRA_CHAIN_FRAMES>
 __device__ __forceinline__ void ent_chain_body() {
   KArgs& a = *(KArgs*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1495,9 +1374,6 @@ __device__ __forceinline__ void ent_chain_body() {
 }
 extern "C" __global__ void __launch_bounds__(64) zra_ent_chain_kernel(ZraEncArgs a_) { (void)a_; ent_chain_body<6>(); }
 extern "C" __global__ void __launch_bounds__(64) zra_ent_chain5_kernel(ZraEncArgs a_) { (void)a_; ent_chain_body<5>(); }   // 17,640 B: beside 19 finder waves
-extern "C" __global__ void __launch_bounds__(64) zra_ent_chain3_kernel(ZraEncArgs a_) { (void)a_; ent_chain_body<3>(); }
-extern "C" __global__ void __launch_bounds__(64) zra_ent_chain2_kernel(ZraEncArgs a_) { (void)a_; ent_chain_body<2>(); }
-extern "C" __global__ void __launch_bounds__(64) zra_ent_chain1_kernel(ZraEncArgs a_) { (void)a_; ent_chain_body<1>(); }
 
 #ifdef ZRA_MF_PROFILE
 extern "C" __attribute__((visibility("default"))) void ZraHipDebugReadEntProfile(unsigned long long* out16, int reset) {

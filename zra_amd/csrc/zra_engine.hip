@@ -2,6 +2,7 @@
 #include "zra_engine.h"
 #include "zra_dev.h"
 #include "zra_format.h"
+#include "zra_env.h"
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -222,6 +223,9 @@ namespace zra_eng {
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { last_hip_error = e_; return zerr(1); } } while (0)
 static thread_local hipError_t last_hip_error = hipSuccess;
 
+// diagnostics: ZRA_RA_TRACE prints the host microseconds between the marks of a random-access call
+static bool ra_trace() { static const bool on = zra_env::env_set("ZRA_RA_TRACE"); return on; }
+
 // bytes of device scratch all engines of the process hold (what the engine pool's cap looks at)
 static std::atomic<uint64_t> g_scratchBytes{0};
 uint64_t scratch_bytes_in_use() { return g_scratchBytes.load(); }
@@ -230,12 +234,9 @@ bool DevBuf::reserve(size_t n) {
   if (n <= cap) return true;
   if (p) { (void)hipFree(p); g_scratchBytes -= cap; p = nullptr; cap = 0; }
   size_t want = n + n / 8 + 256;
-  // bring-up / test knob: ZRA_ALLOC_LIMIT_MIB makes any single reservation above the limit fail (memory_allocation paths without a full device)
-  static const uint64_t limit = std::getenv("ZRA_ALLOC_LIMIT_MIB") ? (uint64_t)std::atoll(std::getenv("ZRA_ALLOC_LIMIT_MIB")) << 20 : ~0ull;
-  // bring-up knob ZRA_ALLOC_MODE (round 5, the launch-time states of the match finder): 1 = hipDeviceMallocUncached, 2 = fine-grained
-  static const int mode = std::getenv("ZRA_ALLOC_MODE") ? std::atoi(std::getenv("ZRA_ALLOC_MODE")) : 0;
-  const hipError_t ea = want > limit ? hipErrorOutOfMemory : mode == 1 ? hipExtMallocWithFlags(&p, want, hipDeviceMallocUncached)
-                        : mode == 2 ? hipExtMallocWithFlags(&p, want, hipDeviceMallocFinegrained) : hipMalloc(&p, want);
+  // test hook: ZRA_ALLOC_LIMIT_MIB makes any single reservation above the limit fail (memory_allocation paths without a full device)
+  static const uint64_t limit = zra_env::env_set("ZRA_ALLOC_LIMIT_MIB") ? (uint64_t)zra_env::env_i64("ZRA_ALLOC_LIMIT_MIB", 0) << 20 : ~0ull;
+  const hipError_t ea = want > limit ? hipErrorOutOfMemory : hipMalloc(&p, want);
   if (ea != hipSuccess) { p = nullptr; cap = 0; (void)hipGetLastError(); return false; }
   cap = want; g_scratchBytes += cap;
   return true;
@@ -357,7 +358,7 @@ Status Engine::decode_scratch(ZraDecodeArgs& a, uint32_t maxFrameBytes) {
 Status Engine::decode_small(const ZraDecodeArgs& a0, const uint32_t* dExpect, uint32_t maxFrameBytes, uint32_t jobBase, unsigned long long* hResult, uint32_t* bailed) {
   ZraDecodeArgs a = a0;
   const uint32_t n = a.nFrames;
-  static const bool trace = std::getenv("ZRA_RA_TRACE") != nullptr;
+  const bool trace = ra_trace();
   auto t_last = std::chrono::steady_clock::now();
   auto mark = [&](const char* what) {
     if (!trace) return;
@@ -368,7 +369,6 @@ Status Engine::decode_small(const ZraDecodeArgs& a0, const uint32_t* dExpect, ui
   { Status st = decode_scratch(a, maxFrameBytes); if (st.zra) return st; }
   mark("scratch");
   a.active = nullptr; a.nActive = n; a.round = 0; a.nextActive = decLists_.as<uint32_t>();
-  { static const int skip = std::getenv("ZRA_DEC_SKIP") ? std::atoi(std::getenv("ZRA_DEC_SKIP")) : 0; a.debugSkip = (uint32_t)skip; }
   // the round counters are zero whenever this path finds them (zeroed behind the previous use, off the caller's wait); the result
   // word and the kernel's bail counter (counting down) were preset together by decode_jobs' one memset; frame-end checks and the
   // first-error reduction happen inside the kernel: one launch, one copy back, one synchronisation
@@ -407,23 +407,19 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
   { Status st = decode_scratch(a, maxFrameBytes); if (st.zra) return st; }
   decCountersClean_ = false;
   uint32_t* listA = decLists_.as<uint32_t>(); uint32_t* listB = listA + n;
-  static const int wavesCap = std::getenv("ZRA_DEC_WAVES") ? std::atoi(std::getenv("ZRA_DEC_WAVES")) : 0;   // bring-up: occupancy sweep
   if (!decOccParse_) {
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&decOccParse_, zra_dec_parse_kernel, 64, 0));
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&decOccExec_, zra_dec_exec_kernel, 64, 0));
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&decOccHuf_, zra_dec_huf_kernel, 64, 0));
     decOccParse_ = std::max(1, decOccParse_); decOccExec_ = std::max(1, decOccExec_); decOccHuf_ = std::max(1, decOccHuf_);
   }
-  int perCUParse = decOccParse_, perCUExec = decOccExec_;
-  if (wavesCap > 0) { perCUParse = std::min(perCUParse, wavesCap); perCUExec = std::min(perCUExec, wavesCap); }
-  { static const int skip = std::getenv("ZRA_DEC_SKIP") ? std::atoi(std::getenv("ZRA_DEC_SKIP")) : 0; a.debugSkip = (uint32_t)skip; }
+  const int perCUParse = decOccParse_, perCUExec = decOccExec_;
   HIPCHK(hipEventRecord(ev0_, stream_));
-  static const uint32_t chainWaves = std::getenv("ZRA_DEC_CHAIN_WAVES") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_CHAIN_WAVES")) : 2u;
+  constexpr uint32_t chainWaves = 2;
   // (ZRA_DEC_CHAIN_LDS_MIN: jobs from which the LDS-table chain kernel runs beside the other one; the tests set it to 1)
-  static const uint32_t chainLdsMin = std::getenv("ZRA_DEC_CHAIN_LDS_MIN") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_CHAIN_LDS_MIN")) : (uint32_t)numCUs_ * 96u;
-  static const int chainLdsMode = std::getenv("ZRA_DEC_CHAIN_LDS") ? std::atoi(std::getenv("ZRA_DEC_CHAIN_LDS")) : 1;   // 0: without the LDS-table kernel; 2 (bring-up): that kernel alone
+  static const uint32_t chainLdsMin = (uint32_t)zra_env::env_int("ZRA_DEC_CHAIN_LDS_MIN", numCUs_ * 96);
+  static const int chainLdsMode = zra_env::env_int("ZRA_DEC_CHAIN_LDS", 1);   // 0: without the LDS-table kernel; 2 (test hook): that kernel alone
   static const bool chainLdsOn = chainLdsMode != 0;
-  static const uint32_t chainGrid = std::getenv("ZRA_DEC_CHAIN_GRID") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_CHAIN_GRID")) : 0u;        // bring-up: absolute wave count
   // the rounds of one set of jobs, one stage after the other on the engine's stream (resident waves per CU of the chain kernel — lane =
   // frame, 64 frames' tables per wave: fewer frames in flight keep more of their table cells in the caches; A/B on one box, round 3,
   // 8 GiB decode, chain stage 2 / 3 / 4 / 6 / 8 waves per CU -> 26.0 / 26.6 / 30.1 / 35.2 / 32.9 ms; 16 GiB, 1 / 1.5 / 2 / 2.5: 74.1 / 58.2 / 51.9 / 53.0 ms)
@@ -432,7 +428,7 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
   // counted on the device). Grids are sized by the previous burst's job count (an upper bound: jobs only drop out). One copy back and
   // one synchronisation per burst; frames that still go on afterwards (foreign archives with more, smaller blocks; scratch deferrals)
   // take further bursts of one round.
-  static const uint32_t aheadCap = std::getenv("ZRA_DEC_AHEAD") ? (uint32_t)std::max(1, std::atoi(std::getenv("ZRA_DEC_AHEAD"))) : 16u;
+  constexpr uint32_t aheadCap = 16;
   if (!roundN_.reserve(4 * (aheadCap + 2) + 64)) return zerr(64);
   auto run_rounds = [&](ZraDecodeArgs& x, uint32_t nActive, const uint32_t* active, uint32_t round, uint32_t* lA, uint32_t* lB, uint32_t ahead) -> Status {
     uint32_t* const dN = roundN_.as<uint32_t>();
@@ -445,7 +441,7 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
         x.nActivePtr = bi ? dN + bi : nullptr;
         x.nextActive = (active == lA) ? lB : lA;
         const uint32_t gridParse = (uint32_t)std::min<uint64_t>(nActive, (uint64_t)numCUs_ * perCUParse);
-        const uint32_t gridChain = (uint32_t)std::min<uint64_t>((nActive + 63) / 64, chainGrid ? chainGrid : (uint64_t)numCUs_ * chainWaves);
+        const uint32_t gridChain = (uint32_t)std::min<uint64_t>((nActive + 63) / 64, (uint64_t)numCUs_ * chainWaves);
         const uint32_t gridExec = (uint32_t)std::min<uint64_t>(nActive, (uint64_t)numCUs_ * perCUExec);
         // per-stage spans (HIP events on the engine's stream; summed into dstats_ once the burst has synchronised)
         hipEvent_t se[5];
@@ -497,80 +493,6 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
     }
     return ok();
   };
-  // Stage pipeline (round 3, opt-in: ZRA_DEC_PIPE=K). With the jobs cut into K slices, slice k's parse, Huffman + chain, and execute
-  // kernels run on four streams with grids that leave room for each other, so that slice k executes while slice k+1 decodes its literals
-  // and chains and slice k+2 parses. Same kernels, same per-job results; only the first block round is pipelined (frames with more blocks
-  // finish slice by slice in the classic way afterwards). Measured, 8 GiB decode on one box: off 105 GiB/s, K = 4 / 8 / 16: 108 / 96 / 66 —
-  // the stages do not hide each other (they queue on the same request path), and slices below one chain grid (32 Ki frames) starve
-  // the lane-per-frame chain kernel. Not the default.
-  static const uint32_t pipeK = std::getenv("ZRA_DEC_PIPE") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_PIPE")) : 0u;
-  static const uint32_t pipeMin = std::getenv("ZRA_DEC_PIPE_MIN") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_PIPE_MIN")) : 16384u;
-  bool piped = false;
-  if (pipeK >= 2 && n >= pipeMin && n >= pipeK * 1024u) {
-    for (auto& st : pipeStreams_) if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { st = nullptr; (void)hipGetLastError(); }   // (each on its own: the encode side creates [0], the LDS chain kernel [1])
-    if (pipeStreams_[0] && pipeStreams_[1] && pipeStreams_[2] && decCounters_.reserve((size_t)(pipeK + 1) * ZRA_DC_WORDS * 4 + 64)) {
-      piped = true;
-      a.counters = decCounters_.as<uint32_t>();
-      static const uint32_t wP = std::getenv("ZRA_DEC_PIPE_PARSE") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_PIPE_PARSE")) : 8u;
-      static const uint32_t wH = std::getenv("ZRA_DEC_PIPE_HUF") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_PIPE_HUF")) : 8u;
-      static const uint32_t wX = std::getenv("ZRA_DEC_PIPE_EXEC") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_PIPE_EXEC")) : 12u;
-      const uint32_t B = ((n + pipeK - 1) / pipeK + 63u) & ~63u;
-      const uint32_t K = (n + B - 1) / B;
-      hipStream_t sP = stream_, sH = pipeStreams_[0], sC = pipeStreams_[1], sX = pipeStreams_[2];
-      HIPCHK(hipMemsetAsync(a.counters, 0, (size_t)(K + 1) * ZRA_DC_WORDS * 4, stream_));
-      hipEvent_t e0 = stage_event(); if (!e0) return zerr(1);
-      HIPCHK(hipEventRecord(e0, stream_));
-      HIPCHK(hipStreamWaitEvent(sH, e0, 0)); HIPCHK(hipStreamWaitEvent(sC, e0, 0)); HIPCHK(hipStreamWaitEvent(sX, e0, 0));
-      std::vector<ZraDecodeArgs> sub(K);
-      hipEvent_t eX = nullptr;
-      for (uint32_t k = 0; k < K; k++) {
-        const uint32_t j0 = k * B, nb = std::min(B, n - j0);
-        ZraDecodeArgs x = a;
-        x.nFrames = nb;
-        x.frameOff = a.frameOff + (size_t)j0 * a.offStride; x.outOff = a.outOff + j0; x.outCap = a.outCap + j0;
-        if (a.limit) x.limit = a.limit + j0;
-        if (a.pieceBase) x.pieceBase = a.pieceBase + j0;
-        x.frames = a.frames + j0; x.tables = a.tables + (size_t)j0 * ZRA_DEC_TBL_WORDS;
-        x.status = a.status + j0; x.produced = a.produced + j0; x.frameMeta = a.frameMeta + 2 * (size_t)j0;
-        x.pending = a.pending + j0; x.hufJobs = a.hufJobs + j0;
-        x.counters = a.counters + (size_t)(k + 1) * ZRA_DC_WORDS;
-        const uint64_t litShare = (a.litCap / K) & ~255ull;
-        x.lits = a.lits + litShare * k; x.litCap = litShare;
-        x.seqs = a.seqs + (a.seqCap / K) * k; x.seqCap = a.seqCap / K;
-        x.active = nullptr; x.nActive = nb; x.round = 0; x.nextActive = listA + j0;
-        sub[k] = x;
-        hipEvent_t eP = stage_event(), eH = stage_event(), eC = stage_event(); eX = stage_event();
-        if (!eP || !eH || !eC || !eX) return zerr(1);
-        hipLaunchKernelGGL(zra_dec_parse_kernel, dim3((uint32_t)std::min<uint64_t>(nb, (uint64_t)numCUs_ * wP)), dim3(64), 0, sP, x);
-        HIPCHK(hipEventRecord(eP, sP));
-        HIPCHK(hipStreamWaitEvent(sH, eP, 0));
-        hipLaunchKernelGGL(zra_dec_huf_kernel, dim3((uint32_t)std::min<uint64_t>((nb + ZRA_HUF_FRAMES - 1) / ZRA_HUF_FRAMES, (uint64_t)numCUs_ * wH)), dim3(64), 0, sH, x);
-        HIPCHK(hipEventRecord(eH, sH));
-        HIPCHK(hipStreamWaitEvent(sC, eP, 0));
-        hipLaunchKernelGGL(zra_dec_chain_kernel, dim3((uint32_t)std::min<uint64_t>((nb + 63) / 64, chainGrid ? chainGrid : (uint64_t)numCUs_ * chainWaves)), dim3(64), 0, sC, x);
-        HIPCHK(hipEventRecord(eC, sC));
-        HIPCHK(hipStreamWaitEvent(sX, eH, 0)); HIPCHK(hipStreamWaitEvent(sX, eC, 0));
-        hipLaunchKernelGGL(zra_dec_exec_kernel, dim3((uint32_t)std::min<uint64_t>(nb, (uint64_t)numCUs_ * wX)), dim3(64), 0, sX, x);
-        HIPCHK(hipEventRecord(eX, sX));
-      }
-      // everything of the first round is behind the last execute kernel (stream order + its waits); the engine's stream takes over
-      HIPCHK(hipStreamWaitEvent(stream_, eX, 0));
-      std::vector<uint32_t> hc((size_t)(K + 1) * ZRA_DC_WORDS);
-      HIPCHK(hipMemcpyAsync(hc.data(), a.counters, hc.size() * 4, hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipStreamSynchronize(stream_));
-      HIPCHK(hipGetLastError());
-      dstats_[4] += 1; dstats_[7] += 1;
-      stageEvNext_ = 0;
-      // frames that go on (more blocks, or no scratch in their slice's share): slice by slice, the classic rounds
-      for (uint32_t k = 0; k < K; k++) {
-        const uint32_t next = hc[(size_t)(k + 1) * ZRA_DC_WORDS + ZRA_DC_NNEXT];
-        if (!next) continue;
-        const uint32_t j0 = k * B;
-        Status st = run_rounds(sub[k], next, listA + j0, 1, listA + j0, listB + j0, 1);
-        if (st.zra) return st;
-      }
-    }
-  }
   // ---- Block-parallel pass (round 6) for frames of several blocks. The rounds below take one block of every frame per round, and their
   // chain stage runs one LANE per frame: at 256 KiB frames a pass of 8 GiB has 32 Ki lanes walking a 128 KiB block each, twice in a row (47 of
   // 76 ms), at 2 MiB frames 4 Ki lanes, sixteen times (168 of 208 ms). Here every compressed block of every frame is a job of the Huffman
@@ -579,10 +501,10 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
   // A frame that is not a clean frame of zstd's own making (an error anywhere, a compressed block that regenerates something else than
   // 128 KiB, the long-offset mode) comes back on a list and takes the rounds below, where every status of the reference is reproduced.
   // ZRA_DEC_FMB=0 turns the pass off.
-  static const int fmbEnv = std::getenv("ZRA_DEC_FMB") ? std::atoi(std::getenv("ZRA_DEC_FMB")) : 1;
-  static const uint32_t fmbMin = std::getenv("ZRA_DEC_FMB_MIN") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_FMB_MIN")) : 64u;
+  static const int fmbEnv = zra_env::env_int("ZRA_DEC_FMB", 1);
+  static const uint32_t fmbMin = (uint32_t)zra_env::env_int("ZRA_DEC_FMB_MIN", 64);
   const uint32_t bpf = (uint32_t)(((uint64_t)maxFrameBytes + ZRA_FMB_BLOCK - 1) / ZRA_FMB_BLOCK);
-  bool fmb = fmbEnv != 0 && !piped && bpf >= 2 && maxFrameBytes <= (64u << 20) && n >= fmbMin && (uint64_t)n * bpf < (1ull << 30);
+  bool fmb = fmbEnv != 0 && bpf >= 2 && maxFrameBytes <= (64u << 20) && n >= fmbMin && (uint64_t)n * bpf < (1ull << 30);
   uint32_t nRest = n;
   if (fmb) {
     const uint64_t nb = (uint64_t)n * bpf;
@@ -611,7 +533,7 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
       ZraDecodeArgs y = x; y.frames = x.blkRecs; y.tables = x.blkTables;      // the Huffman and chain stages: jobs are blocks
       hipLaunchKernelGGL(zra_dec_huf_kernel, dim3((uint32_t)std::min<uint64_t>((nb + ZRA_HUF_FRAMES - 1) / ZRA_HUF_FRAMES, (uint64_t)numCUs_ * decOccHuf_)), dim3(64), 0, stream_, y);
       HIPCHK(hipEventRecord(se[2], stream_));
-      const uint32_t gridChain = (uint32_t)std::min<uint64_t>((nb + 63) / 64, chainGrid ? chainGrid : (uint64_t)numCUs_ * chainWaves);
+      const uint32_t gridChain = (uint32_t)std::min<uint64_t>((nb + 63) / 64, (uint64_t)numCUs_ * chainWaves);
       bool forked = false;
       if (chainLdsOn && nb >= chainLdsMin) {
         if (!pipeStreams_[1]) { if (hipStreamCreateWithFlags(&pipeStreams_[1], hipStreamNonBlocking) != hipSuccess) { pipeStreams_[1] = nullptr; (void)hipGetLastError(); } }
@@ -644,11 +566,9 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
       nRest = back;
     }
   }
-  if (!piped) {
-    Status st = fmb ? run_rounds(a, nRest, listA, 0, listA, listB, 1)
-                    : run_rounds(a, n, nullptr, 0, listA, listB, (maxFrameBytes + (128u << 10) - 1) / (128u << 10));
-    if (st.zra) return st;
-  }
+  Status st = fmb ? run_rounds(a, nRest, listA, 0, listA, listB, 1)
+                  : run_rounds(a, n, nullptr, 0, listA, listB, (maxFrameBytes + (128u << 10) - 1) / (128u << 10));
+  if (st.zra) return st;
   HIPCHK(hipEventRecord(ev1_, stream_));
   const uint32_t tb = 256;
   hipLaunchKernelGGL(zra_xxh64_verify_kernel, dim3((n * 4 + tb - 1) / tb), dim3(tb), 0, stream_, a.out, a.outOff, dExpect,
@@ -682,7 +602,7 @@ Status Engine::decode_jobs(const uint8_t* dBody, uint64_t bodySize, const uint64
   // passes: the chain kernel runs one LANE per frame, so a pass wants hundreds of thousands of frames; its per-round scratch
   // (literals + sequences of one block per frame, ~1.25 bytes per output byte) is what bounds it — 16 GiB of output per pass
   const uint64_t perFrame = std::min<uint64_t>((uint64_t)maxFrameBytes + 16, (128u << 10) + 16);
-  static const uint64_t passBytes = std::getenv("ZRA_DEC_PASS_MIB") ? (uint64_t)std::atoll(std::getenv("ZRA_DEC_PASS_MIB")) << 20 : 16ull << 30;
+  constexpr uint64_t passBytes = 16ull << 30;
   // equal passes (a remainder pass of a few frames would cost a whole latency-bound round)
   const uint64_t inFlight = std::max<uint64_t>(1, passBytes / perFrame);
   const uint32_t nPass = (uint32_t)((nFrames + inFlight - 1) / inFlight);
@@ -697,7 +617,7 @@ Status Engine::decode_jobs(const uint8_t* dBody, uint64_t bodySize, const uint64
     if (ra) { if (ra->limit) b.limit = ra->limit + p0; if (ra->pieceBase) b.pieceBase = ra->pieceBase + p0; }
     // few jobs: the one-launch kernel (latency path); a job it hands back (damaged / unusual frame) sends the pass through the
     // four-kernel pipeline, where every status of the reference is reproduced
-    static const uint32_t smallMax = std::getenv("ZRA_DEC_SMALL_MAX") ? (uint32_t)std::atoi(std::getenv("ZRA_DEC_SMALL_MAX")) : 1024u;
+    static const uint32_t smallMax = (uint32_t)zra_env::env_int("ZRA_DEC_SMALL_MAX", 1024);
     bool done = false;
     if (b.nFrames <= smallMax) {
       uint32_t bailed = 0;
@@ -921,8 +841,7 @@ Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, co
 // the batch behind a header that has been read and checked (ra_header): the archive handle without slots comes here directly
 Status Engine::ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
                              const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
-  // bring-up: ZRA_RA_TRACE=1 prints the host microseconds between the marks of a call
-  static const bool trace = std::getenv("ZRA_RA_TRACE") != nullptr;
+  const bool trace = ra_trace();
   auto t_last = std::chrono::steady_clock::now();
   auto mark = [&](const char* what) {
     if (!trace) return;

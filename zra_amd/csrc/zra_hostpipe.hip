@@ -10,6 +10,7 @@
 // Frames are independent (zra.cpp:216-225), so the chunked result is byte-identical to the one-piece result.
 #include "zra_engine.h"
 #include "zra_format.h"
+#include "zra_env.h"
 #include <algorithm>
 #include <condition_variable>
 #include <cstdlib>
@@ -43,8 +44,7 @@ struct Pipe {
 }  // namespace
 
 size_t host_chunk_bytes() {
-  const char* e = std::getenv("ZRA_HOST_CHUNK_MIB");              // read per call: tests shrink it to reach the chunked path with small inputs
-  const size_t mib = e ? (size_t)std::atoll(e) : 1024;
+  const size_t mib = (size_t)zra_env::env_i64("ZRA_HOST_CHUNK_MIB", 1024);   // read per call: tests shrink it to reach the chunked path with small inputs
   return std::max<size_t>(1, mib) << 20;
 }
 

@@ -94,7 +94,7 @@ struct ZraDecodeArgs {
   uint32_t* status;          // [nFrames] zstd error code per frame (0 = ok)
   uint32_t* produced;        // [nFrames] bytes regenerated
   uint32_t* frameMeta;       // [2*nFrames] {1 = has checksum / 2 = stopped early (no frame-end checks), stored checksum}
-  uint32_t debugSkip;        // bring-up timing knob (ZRA_DEC_SKIP): execute kernel stage ablation; 0 in production
+  uint32_t debugSkip;        // unused
   // block-parallel pass (round 6, frames of several blocks): the Huffman and chain stages take BLOCKS as jobs — job = frame * bpf + the
   // compressed block's ordinal, its record in `frames`, its tables in `tables` (the host points both at the block arrays for those two
   // launches) —, zra_dec_parse_all_kernel writes them from the frame records, zra_dec_exec_all_kernel walks a frame's blocks in order
@@ -208,37 +208,34 @@ struct ZraEncArgs {
   uint64_t litStride;
   uint8_t* entWork;        // per entropy-stage workgroup: the sequence section's codes [3][seqStride] u8 + chain output [3][seqStride] u16
   uint64_t entWorkStride;
-  uint8_t* slots;          // slotRing * slotStride: the encoded frames, frame f in slot f % slotRing
+  uint8_t* slots;          // slotRing * slotStride: the encoded frames, frame f of the launch in slot f % slotRing
   uint64_t slotStride;
   ZraEncFrameState* state; // [nFrames]
   ZraEncBlockOut* blockOut;// [nFrames]
   uint32_t* contentCk;     // [nFrames] XXH64 low 32 bits of each frame's input
   uint64_t* sizes;         // [nFrames] final frame sizes (written with the last block)
-  // persistent pipeline (single-block dfast frames): TWO persistent kernels and nothing else. The match finder's waves pull frame indices
-  // from `mfQueue`, use the hash-table slot of their workgroup (tables = nSlots * tableStride) and publish a finished frame by writing
-  // `readyStamp` into its block record (ZraEncBlockOut::ready). The entropy stage's workgroups (zra_entropy_kernel) pull frame indices
-  // from `entQueue`, wait for the frame's stamp, encode it into slot (frame % slotRing) and count it in entDone[frame / entSubFrames];
-  // the workgroup that completes a sub-batch scans its frame sizes (offsets[], *running; sub-batches in order: scanDone), and every
-  // workgroup, between two frames, copies encoded frames of scanned sub-batches to their place in the archive (gQueue / gCopied per
-  // sub-batch, gatherJ = the sub-batch being handed out, gatherDone = sub-batches whose slots are free again).
-  // mfQueue == nullptr: one workgroup per frame, tables per frame (batch path; its entropy launches use entQueue alone, readyStamp 0).
+  // persistent pipeline (single-block dfast frames): the match finder's waves pull frame indices from `mfQueue`, use the hash-table slot
+  // of their workgroup (tables = nSlots * tableStride), write `readyStamp` into a finished frame's block record (ZraEncBlockOut::ready) and
+  // count it in mfDone[frame / entSubFrames]; the host releases each sub-batch's entropy launch by a stream wait on that count.
+  // mfQueue == nullptr: one workgroup per frame, tables per frame (batch path).
+  // The entropy stage's workgroups pull frame indices from `entQueue` (both paths) and encode frame f into slot (f % slotRing).
   uint32_t* mfQueue;
   uint32_t* mfStarted;     // counts the match finder's waves as they start (the entropy stage is launched once all of them are resident)
-  uint32_t* mfDone;        // [sub-batches] frames the match finder has finished (pipeMode 1: the host releases a sub-batch's entropy launch by a stream wait on it); may be nullptr
+  uint32_t* mfDone;        // [sub-batches] frames the match finder has finished; may be nullptr
   uint32_t* entQueue;
-  uint32_t* entDone;       // [sub-batches]
-  uint32_t* scanDone;
-  uint32_t* gatherJ;
-  uint32_t* gQueue;        // [sub-batches]
-  uint32_t* gCopied;       // [sub-batches]
-  uint32_t* gatherDone;
-  uint32_t* pipeAbort;     // non-zero: give up waiting (error exit of the host, or a wait that ran out of patience)
-  uint64_t* offsets;       // [nFrames] offset of each frame inside the body (written by the scans)
-  uint64_t* running;       // body bytes so far (carried from launch to launch)
-  uint8_t* gBody;          // the archive's body
-  uint8_t* gEntries;       // seek-table entries (5 bytes per frame of the call) or nullptr
-  uint64_t* gSizesOut;     // u64 size per frame of the call, or nullptr
-  uint32_t entSubFrames;
+  uint32_t* entDone;       // unused
+  uint32_t* scanDone;      // unused
+  uint32_t* gatherJ;       // unused
+  uint32_t* gQueue;        // unused
+  uint32_t* gCopied;       // unused
+  uint32_t* gatherDone;    // unused
+  uint32_t* pipeAbort;     // unused
+  uint64_t* offsets;       // unused
+  uint64_t* running;       // unused
+  uint8_t* gBody;          // unused
+  uint8_t* gEntries;       // unused
+  uint64_t* gSizesOut;     // unused
+  uint32_t entSubFrames;   // frames per sub-batch (mfDone)
   uint32_t slotRing;       // frames the slot buffer holds
   uint32_t readyStamp;
   uint32_t entPrio;        // issue priority of the entropy stage's waves (s_setprio 0..3)
@@ -253,7 +250,7 @@ struct ZraEncArgs {
 #define ZRA_TELE_CUKEYS 2048u
 #define ZRA_TELE_HEAD (32u + ZRA_TELE_CUKEYS)
 #define ZRA_TELE_WAVES 8192u                               /* then per wave (workgroup index): start cycles, start ticks, XCD, frames taken */
-#define ZRA_TELE_ENT (ZRA_TELE_HEAD + 4u * ZRA_TELE_WAVES)   /* then the entropy stage's persistent workgroups: [0] workgroups that took a frame, [1] their resident ticks, [2] ticks spent waiting for a frame or a slot, [3] frames, [8 + k] workgroups on CU key k */
+#define ZRA_TELE_ENT (ZRA_TELE_HEAD + 4u * ZRA_TELE_WAVES)   /* then the entropy stage's persistent workgroups: [0] workgroups that took a frame, [1] their resident ticks, [2] 0 (unused), [3] frames, [8 + k] workgroups on CU key k */
 #define ZRA_TELE_WORDS (ZRA_TELE_ENT + 8u + ZRA_TELE_CUKEYS)
 // bucket flags of the dfast match finder (round 5): every wave computes its frame's flags itself (df_later_flags) into
 // flags + workgroup * flagStride, over ldsWords words of its LDS, ahead of the parse
