@@ -114,6 +114,56 @@ ZRA_EXPORT ZraStatus ZraHipArchiveDropCache(ZraHipArchive* archive);
  *  uncompressed size, frame size}; counters 2-5 are cumulative since the handle was opened. */
 ZRA_EXPORT void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8);
 
+/* ---- update: a new archive from an old one, on the device ----
+ * The reference's Compressor only ever starts from nothing. Frames are independent zstd frames tied together by the seek table alone,
+ * so a change re-encodes the frames it lands in and carries every other frame over byte for byte. */
+
+/** dOut receives an archive whose content is that of the archive at dArchive with
+ *    - bytes [hOffsets[i], hOffsets[i] + hSizes[i]) replaced by dData + hDataOffsets[i], for every write i (host arrays of nWrites
+ *      entries, as ZraHipDecompressRABatch; dArchive, dData, dAppend and dOut are device pointers), and
+ *    - appendSize bytes from dAppend added at the end.
+ *  The frame size is the archive's own: U' = U + appendSize, F' = ceil(U' / frameSize). Synchronous; stream ordering as the other
+ *  compute calls (ZraHipWaitStream).
+ *  - A frame is TOUCHED if a non-empty write intersects it or an appended byte lands in it (the old last frame when U is not a multiple
+ *    of frameSize and appendSize > 0; every new frame). Each touched frame is encoded from its new content with compressionLevel and
+ *    checksum, exactly as ZraHipCompressBuffer encodes a frame of that content: at the level and checksum flag the archive was written
+ *    with, the result is byte-identical (header, table and CRC-32 included) to ZraHipCompressBuffer of the patched content.
+ *  - Every other frame's compressed bytes are CARRIED OVER unchanged. They are neither decoded nor verified: damage in an untouched
+ *    frame survives the update, exactly as it was.
+ *  - A touched frame that keeps some of its old bytes is first decoded whole and its content checksum verified (an update does not
+ *    launder damage); a touched frame whose every byte is replaced is not decoded at all.
+ *  - Header: the 38 fixed bytes are rewritten (U', the new table size), the meta section of a streaming-Compressor archive is copied
+ *    verbatim, the new seek table and the CRC-32 follow. The table and the CRC pass through the host (5 bytes per frame); the body
+ *    never leaves the device.
+ *  Statuses, checked in this order; on every status other than Success no byte of dOut is written:
+ *   1. engine, outSize or dOut NULL; dArchive NULL with archiveSize != 0; an h* array NULL with nWrites != 0; dData NULL while a write is
+ *      non-empty; dAppend NULL with appendSize != 0 -> {ZStdError, 42}, the refusal of the archive and comm calls.
+ *   2. [dOut, dOut + outCapacity) overlaps [dArchive, dArchive + archiveSize) -> {ZStdError, 42}.
+ *   3. Header problems: the statuses of ZraHipArchiveOpen (a frame size of 0, or a table that does not cover the content: HeaderInvalid).
+ *   4. A non-empty write with offset + size > U (or a sum that overflows) -> OutOfBoundsAccess. The bound is inclusive on purpose: the
+ *      reference's ">=" (zra.cpp:260) is a quirk of its reads, and a write must be able to reach the last byte. Two non-empty writes that
+ *      share a byte -> {ZStdError, 42}: there is no "last one wins" between copies that run side by side. Empty writes are ignored
+ *      wherever they point.
+ *   5. An old seek table that runs backwards over a frame that is carried over, or ends beyond the body -> {ZStdError, 20}.
+ *   6. A touched frame that has to be decoded and fails: the status ZraHipDecompressRABatch gives under ZRA_HIP_OPT_RA_WHOLE_FRAMES for
+ *      a query inside that frame; of several failing frames, the one with the lowest index.
+ *   7. header + body >= 2^40 -> CompressedSizeTooLarge (ZraHipCompressBuffer's rule).
+ *   8. outCapacity smaller than the result -> OutputBufferTooSmall, and *outSize holds the size needed. (ZraGetCompressedOutputBufferSize(U',
+ *      frameSize) + the meta size is always enough for the touched frames; carried frames keep the size they have.)
+ *   9. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's: plaintext staging of at most 65,536 frames or 4 GiB
+ *      (more touched frames go through several decode / encode passes), the newly encoded frames, 29 bytes per frame of tables;
+ *      ZraHipReleaseScratch returns it.
+ *  An open ZraHipArchive handle requires unchanged archive bytes: update into a new buffer and open a new handle on it. */
+ZRA_EXPORT ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* dData, const uint64_t* hOffsets, const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites,
+    const void* dAppend, size_t appendSize,
+    void* dOut, size_t outCapacity, size_t* outSize,
+    int8_t compressionLevel, bool checksum);
+/** What the last ZraHipUpdateArchive on the engine did (all zero after any outcome other than Success; engine NULL: all zero):
+ *  out8 = {frames in the result, frames touched, frames decoded, frames compressed, compressed bytes carried over, compressed bytes
+ *  newly encoded, content bytes replaced or appended, decode / encode passes}. Counters, not timings. */
+ZRA_EXPORT void ZraHipGetUpdateStats(ZraHipEngine* engine, uint64_t* out8);
+
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody
  *  (capacity nFrames*ZSTD_compressBound(frameSize)); writes the nFrames local frame sizes (u64, device) to dSizes and the

@@ -124,6 +124,9 @@ def load():
         "ZraHipArchiveRead": (S, [vp, vp, u64p, u64p, u64p, sz]),
         "ZraHipArchiveDropCache": (S, [vp]),
         "ZraHipArchiveGetStats": (None, [vp, u64p]),
+        # update
+        "ZraHipUpdateArchive": (S, [vp, vp, sz, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
+        "ZraHipGetUpdateStats": (None, [vp, u64p]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -167,7 +170,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipShardRange", "ZraHipOwnerOfFrame", "ZraHipRouteQueries", "ZraHipCommGetUniqueId", "ZraHipCommCreateRccl", "ZraHipCommCreateHost", "ZraHipCommLoopback", "ZraHipCommDestroy",
                    "ZraHipCommCompress", "ZraHipCommStitchSizes", "ZraHipShardDestroy", "ZraHipShardHeaderSize", "ZraHipShardGetHeader", "ZraHipShardArchiveSize", "ZraHipShardGetBody",
                    "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe",
-                   "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats"]
+                   "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
+                   "ZraHipUpdateArchive", "ZraHipGetUpdateStats"]
 
 
 def _chk(st, what=""):
@@ -331,8 +335,36 @@ class Engine:
         _chk(self.L.ZraHipCompressFrames(self.h, d_in, in_size, d_body, d_sizes, ctypes.byref(bsz), level, frame_size, checksum))
         return bsz.value
 
+    def update(self, d_archive, size, d_out, out_cap, *, writes=None, d_data=0, d_append=0, append_size=0, level=3, checksum=True):
+        """ZraHipUpdateArchive: the archive at d_archive (size bytes) with `writes` = (offsets, sizes, data_offsets) applied (bytes of the
+        content replaced by d_data + data_offset) and append_size bytes from d_append added, written to d_out. Returns the new size.
+        OutputBufferTooSmall carries the size needed in ZraError.needed."""
+        import numpy as np
+        o, s, do = (np.ascontiguousarray(a, dtype=np.uint64) for a in (writes if writes is not None else ((), (), ())))
+        if not (len(o) == len(s) == len(do)):
+            raise ValueError("writes: offsets, sizes and data_offsets differ in length")
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if len(a) else None
+        osz = ctypes.c_size_t(0)
+        self._order()
+        st = self.L.ZraHipUpdateArchive(self.h, d_archive or None, size, d_data or None, p(o), p(s), p(do), len(o), d_append or None, append_size,
+                                        d_out or None, out_cap, ctypes.byref(osz), level, checksum)
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipUpdateArchive")
+            e.needed = osz.value
+            raise e
+        return osz.value
+
+    def update_stats(self):
+        """Counters of the last update() on this engine (all zero unless it succeeded), keyed by UPDATE_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetUpdateStats(self.h, a)
+        return dict(zip(UPDATE_STATS, (int(v) for v in a)))
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
+
+
+UPDATE_STATS = ("frames", "touched", "decoded", "compressed", "carried_bytes", "encoded_bytes", "content_bytes", "passes")
 
 
 class Archive:

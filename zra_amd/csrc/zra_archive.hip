@@ -27,17 +27,6 @@ constexpr u32 kEmpty = 0xFFFFFFFFu;   // frameOf: the slot holds no frame
 constexpr u8 kClaimed = 2;            // ref: the slot is being decoded into by the running read (neither a victim again nor skipped)
 constexpr u32 kMaxPass = 1u << 16;    // frames of one decode pass: well inside one internal pass of Engine::decode_jobs (>= 128 Ki frames)
 
-// one wave copies one slice: 16-byte moves when source and destination share their alignment modulo 16, copy_bytes' 8-byte ones otherwise
-__device__ __forceinline__ void copy_slice(u8* dst, const u8* src, u32 n, int lane) {
-  if ((((uintptr_t)dst ^ (uintptr_t)src) & 15u) || n < 64) { copy_bytes(dst, src, n, lane, 64); return; }
-  const u32 head = (u32)((16u - ((uintptr_t)dst & 15u)) & 15u);
-  if ((u32)lane < head) dst[lane] = src[lane];
-  const u32 n16 = (n - head) >> 4;
-  const uint4* s4 = (const uint4*)(src + head);
-  uint4* d4 = (uint4*)(dst + head);
-  for (u32 i = lane; i < n16; i += 64) d4[i] = s4[i];
-  for (u32 i = head + (n16 << 4) + lane; i < n; i += 64) dst[i] = src[i];
-}
 }  // namespace
 
 // Wave per slice (slice = the part of a query inside one frame; q[4i + 3] = the first slice of query i, as the batch's direct kernel

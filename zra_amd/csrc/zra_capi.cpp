@@ -733,6 +733,17 @@ void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8) {
   if (!out8) return;
   if (archive) archive->c->stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
+ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* dData, const uint64_t* hOffsets,
+                              const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites, const void* dAppend, size_t appendSize, void* dOut,
+                              size_t outCapacity, size_t* outSize, int8_t level, bool checksum) {
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->update_archive((const uint8_t*)dArchive, archiveSize, (const uint8_t*)dData, hOffsets, hSizes, hDataOffsets, nWrites,
+                                      (const uint8_t*)dAppend, appendSize, (uint8_t*)dOut, outCapacity, outSize, level, checksum));
+}
+void ZraHipGetUpdateStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->update_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

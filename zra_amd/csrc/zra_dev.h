@@ -56,6 +56,18 @@ __device__ __forceinline__ void copy_bytes(u8* dst, const u8* src, u32 n, int t,
   for (u32 i = t; i < n8; i += nthreads) st64(dst + 8 * i, ld64(src + 8 * i));
   for (u32 i = (n8 << 3) + t; i < n; i += nthreads) dst[i] = src[i];
 }
+// one wave copies one slice (the archive handle's cache hits, the update's new bytes): 16-byte moves when source and destination
+// share their alignment modulo 16, copy_bytes' 8-byte ones otherwise
+__device__ __forceinline__ void copy_slice(u8* dst, const u8* src, u32 n, int lane) {
+  if ((((uintptr_t)dst ^ (uintptr_t)src) & 15u) || n < 64) { copy_bytes(dst, src, n, lane, 64); return; }
+  const u32 head = (u32)((16u - ((uintptr_t)dst & 15u)) & 15u);
+  if ((u32)lane < head) dst[lane] = src[lane];
+  const u32 n16 = (n - head) >> 4;
+  const uint4* s4 = (const uint4*)(src + head);
+  uint4* d4 = (uint4*)(dst + head);
+  for (u32 i = lane; i < n16; i += 64) d4[i] = s4[i];
+  for (u32 i = head + (n16 << 4) + lane; i < n; i += 64) dst[i] = src[i];
+}
 struct __attribute__((packed, aligned(1))) u128_u { u32 a, b, c, d; };
 __device__ __forceinline__ void st128(u8* p, u32 a, u32 b, u32 c, u32 d) { u128_u v; v.a = a; v.b = b; v.c = c; v.d = d; *(u128_u*)p = v; }
 

@@ -112,6 +112,16 @@ class Engine {
   // Full archive (header + table + body) on the device.
   Status compress_device(const uint8_t* dIn, size_t inSize, uint8_t* dOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
 
+  // ---- update (zra_update.hip): a new archive at dOut = the one at dArc with nw byte ranges of its content overwritten and appendSize
+  // bytes added. Only the frames whose content changes are decoded (when partly replaced) and encoded again; every other frame's
+  // compressed bytes are carried over as they are. Statuses and their order: zra_hip.h, ZraHipUpdateArchive.
+  Status update_archive(const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
+                        const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
+                        size_t* outSize, int level, bool checksum);
+  // what the last update_archive did: {frames, touched, decoded, compressed, bytes carried, bytes encoded, content bytes written, passes};
+  // all zero unless it succeeded
+  void update_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = ustats_[i]; }
+
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
@@ -169,7 +179,13 @@ class Engine {
   uint64_t lastProducedTotal_ = ~0ull;     // whole-archive decode that fell back to the sequential tail: bytes actually regenerated
   void* encCounters_ = nullptr; size_t encCountersBytes_ = 0;   // sub-batch counters stream B may be waiting on (drain_after_error)
   int waitValueOk_ = 0;                    // 0 unknown, 1 hipStreamWaitValue32 works on device memory, -1 it does not (batch path)
+  // update scratch (zra_update.hip): per-frame plan words, plaintext staging of one pass, the packed newly encoded frames, their sizes,
+  // the per-frame sizes / offsets / source displacements, the new seek table
+  struct UpdScratch { DevBuf plan, stage, packed, encSizes, frames, table; };
+  UpdScratch upd_;
+  uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   friend struct EncodeImpl;
+  friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

@@ -294,6 +294,7 @@ Status Engine::release_scratch() {
     b->release();
   mfTeleDev_ = nullptr;                                // (lived inside encScan_)
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
+  for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table}) b->release();
   decCountersClean_ = false;
   return ok();
 }
@@ -305,6 +306,7 @@ Engine::~Engine() {
                     &encScan_, &hostIn_, &hostOut_, &seqScratch_, &mfFlags_, &decBlkRecs_, &decBlkTables_, &decBlkLists_})
     b->release();
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
+  for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table}) b->release();
   for (auto ev : evPool_) (void)hipEventDestroy(ev);
   for (auto ev : stageEv_) (void)hipEventDestroy(ev);
   if (stream2_) { (void)hipStreamSynchronize(stream2_); (void)hipStreamDestroy(stream2_); }

@@ -1,0 +1,435 @@
+// zra_amd — update of a device-resident archive (zra_hip.h: ZraHipUpdateArchive): byte ranges of the content overwritten, bytes
+// appended, without decoding or encoding the frames that do not change.
+//
+// Every frame is an independent zstd frame and the seek table alone ties them together, so an update
+//   1. plans, per frame, whether new bytes land in it (touched), how many, and its staging slot        zra_upd_mark / zra_upd_plan
+//   2. decodes the touched frames that keep some old bytes, whole and with their checksum              Engine::decode_jobs
+//   3. copies the new bytes over them in the staging buffer                                            zra_upd_patch
+//   4. encodes the staged frames like ZraHipCompressBuffer encodes frames of that content              Engine::compress_frames
+//   5. sizes every frame (new size if touched, old table difference if not), scans, writes the table   zra_upd_sizes / _scan / _offsets
+//   6. copies every frame to its new place: the bandwidth step                                         zra_upd_gather
+// Steps 2-4 run in passes over at most kPassFrames staging slots; the encoded frames stay packed in scratch until step 6.
+//
+// Ordering conditions (all launches on the engine's stream, decode_jobs and compress_frames return synchronised):
+//  (a) slots are ranks among the touched frames in frame order: only the archive's last frame can be short and it is the last slot of
+//      the last pass (what compress_frames expects of its input), decode jobs are in frame order (the first failing job is the
+//      lowest failing frame), and the packed encoded frames are in frame order (one scan gives their places).
+//  (b) the patch kernel of a pass runs behind the pass's decode and before its encode: new bytes win over decoded ones.
+//  (c) nothing is written to dOut before every size is known and every check has passed: a refused update leaves dOut alone.
+#include "zra_engine.h"
+#include "zra_dev.h"
+#include "zra_format.h"
+#include <algorithm>
+#include <vector>
+
+using namespace zra_dev;
+
+namespace {
+constexpr u32 kNone = 0xFFFFFFFFu;        // slotOf: the frame is not touched
+constexpr u32 kPassFrames = 1u << 16;     // frames of one decode -> patch -> encode pass (one internal pass of Engine::decode_jobs)
+// plaintext staging of one pass: 65,536 frames of 64 KiB (the headline frame size) fill it exactly; larger frames get fewer slots
+constexpr u64 kStageBytes = 4ull << 30;
+constexpr u32 kGatherChunk = 32u << 10;   // output bytes one wave of the gather copies per step
+constexpr u32 kGatherGrid = 2048;         // workgroups of the gather at most (4 waves each; 8 per CU on 256 CUs)
+
+__device__ __forceinline__ u64 entry40(const u8* table, u64 f) { const u8* e = table + (size_t)f * 5; return (u64)ld32(e) | ((u64)e[4] << 32); }
+
+// slice s of the tuples q (4 words each: content offset, size, source offset, first slice; sorted by offset, none empty): the frame it
+// lies in, where it starts inside the frame, its length, and where its bytes are in the tuple's source
+struct Slice { u32 tuple; u64 frame; u32 inFrame; u32 len; u64 src; };
+__device__ __forceinline__ Slice slice_of(const u64* q, u32 nq, u64 s, u64 fs) {
+  u32 lo = 0, hi = nq - 1;
+  while (lo < hi) {
+    const u32 mid = lo + (hi - lo + 1) / 2;
+    if (q[4 * (size_t)mid + 3] <= s) lo = mid; else hi = mid - 1;
+  }
+  const u64 off = q[4 * (size_t)lo], size = q[4 * (size_t)lo + 1], k = s - q[4 * (size_t)lo + 3];
+  const u64 f0 = off / fs, head = off - f0 * fs;
+  Slice r;
+  r.tuple = lo; r.frame = f0 + k;
+  r.inFrame = k ? 0u : (u32)head;
+  const u64 done = k ? (fs - head) + (k - 1) * fs : 0;
+  r.len = (u32)min<u64>(fs - r.inFrame, size - done);
+  r.src = q[4 * (size_t)lo + 2] + done;
+  return r;
+}
+
+__device__ __forceinline__ u64 wave_incl_scan64(u64 v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
+  return v;
+}
+}  // namespace
+
+// Thread per slice: the bytes the slice replaces are counted into its frame. Writes do not overlap and the append lies behind all
+// of them, so cover[f] is exactly the number of bytes of frame f that the update supplies.
+extern "C" __global__ void __launch_bounds__(256) zra_upd_mark_kernel(const u64* q, u32 nq, u64 nSlices, u64 fs, u32* cover) {
+  const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (s >= nSlices) return;
+  const Slice c = slice_of(q, nq, s, fs);
+  atomicAdd(&cover[c.frame], c.len);
+}
+
+// One workgroup walks the frames of the result, 1024 at a time. A frame is touched when cover != 0; its staging slot is its rank among
+// the touched frames (ballot + prefix counts over the chunk, a running base across chunks). A touched frame that keeps old bytes
+// (cover < its new length) gets a decode job, ranked the same way: compressed span from the old seek table, destination = its slot of
+// the pass, expected size = its old length. passJob[p] = jobs in front of pass p (slots [p * passSlots, ...)), passJob[passes] = all.
+// An untouched frame is carried over by its table entries: they must not run backwards nor end beyond the body (flag).
+// totals = {touched, jobs, flag}.
+extern "C" __global__ void __launch_bounds__(1024) zra_upd_plan_kernel(const u32* cover, u32 nNew, u32 nOld, const u8* table, u64 bodyBytes, u64 fs,
+                                                                    u64 oldTotal, u64 newTotal, u32 passSlots, u32* slotOf, u64* frameOff,
+                                                                    u64* outOff, u32* expect, u32* passJob, u32* totals) {
+  __shared__ u32 sT[16], sJ[16], sFlag;
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) sFlag = 0;
+  u32 slotBase = 0, jobBase = 0;
+  for (u32 base = 0; base < nNew; base += 1024) {
+    const u32 f = base + tid;
+    const bool in = f < nNew;
+    const u32 c = in ? cover[f] : 0u;
+    const u64 o = (u64)f * fs;
+    const u32 newLen = in ? (u32)min<u64>(fs, newTotal - o) : 0u;
+    const bool touched = c != 0, dec = touched && c != newLen;
+    const u64 mT = __ballot(touched), mJ = __ballot(dec);
+    const u64 below = (1ull << lane) - 1;
+    if (lane == 0) { sT[wave] = (u32)__popcll(mT); sJ[wave] = (u32)__popcll(mJ); }
+    __syncthreads();
+    u32 beforeT = 0, beforeJ = 0, totalT = 0, totalJ = 0;
+    for (u32 w = 0; w < 16; w++) { const u32 t = sT[w], j = sJ[w]; beforeT += w < wave ? t : 0u; beforeJ += w < wave ? j : 0u; totalT += t; totalJ += j; }
+    const u32 slot = slotBase + beforeT + (u32)__popcll(mT & below), job = jobBase + beforeJ + (u32)__popcll(mJ & below);
+    if (in) slotOf[f] = touched ? slot : kNone;
+    if (touched && slot % passSlots == 0) passJob[slot / passSlots] = job;
+    if (dec) {
+      // (dec implies f < nOld: a frame behind the old content is supplied whole by the append)
+      frameOff[2 * (size_t)job] = entry40(table, f); frameOff[2 * (size_t)job + 1] = entry40(table, (u64)f + 1);
+      outOff[job] = (u64)(slot % passSlots) * fs;
+      expect[job] = (u32)min<u64>(fs, oldTotal - o);
+    }
+    if (in && !touched && f < nOld) {
+      const u64 a = entry40(table, f), b = entry40(table, (u64)f + 1);
+      if (b < a || b > bodyBytes) atomicOr(&sFlag, 1u);
+    }
+    slotBase += totalT; jobBase += totalJ;
+    __syncthreads();                                                  // (sT, sJ of the next chunk; sFlag)
+  }
+  if (tid == 0) {
+    passJob[(slotBase + passSlots - 1) / passSlots] = jobBase;
+    totals[0] = slotBase; totals[1] = jobBase; totals[2] = sFlag;
+  }
+}
+
+// Wave per slice, for the slices whose frame has a slot in the pass [s0, s0 + n): the new bytes go over the staged frame. Tuples below
+// nData take their bytes from data, the one behind them (the append) from app.
+extern "C" __global__ void __launch_bounds__(256) zra_upd_patch_kernel(const u64* q, u32 nq, u32 nData, u64 nSlices, u64 fs, const u32* slotOf, u32 s0, u32 n,
+                                                                     const u8* data, const u8* app, u8* stage) {
+  const int lane = (int)(threadIdx.x & 63);
+  for (u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); s < nSlices; s += (u64)gridDim.x * 4) {
+    const Slice c = slice_of(q, nq, s, fs);
+    const u32 slot = slotOf[c.frame];
+    if (slot < s0 || slot - s0 >= n) continue;
+    copy_slice(stage + (u64)(slot - s0) * fs + c.inFrame, (c.tuple < nData ? data : app) + c.src, c.len, lane);
+  }
+}
+
+namespace {
+// compressed size of frame f in the result, and that size again if it was newly encoded (0 if carried over); f == nNew: the end entry
+__device__ __forceinline__ void upd_frame_size(u32 f, u32 nNew, const u32* slotOf, const u64* encSizes, const u8* table, u64* sz, u64* tsz) {
+  *sz = 0; *tsz = 0;
+  if (f >= nNew) return;
+  const u32 slot = slotOf[f];
+  if (slot != kNone) { *sz = *tsz = encSizes[slot]; return; }
+  *sz = entry40(table, (u64)f + 1) - entry40(table, f);               // (not backwards: the plan kernel has checked the untouched frames)
+}
+// exclusive scan of (a, b) over the 1024 threads of a workgroup; *ta, *tb = the sums
+__device__ __forceinline__ void block_excl_scan2(u64& a, u64& b, u64* ta, u64* tb, u64* sA, u64* sB) {
+  const u32 tid = threadIdx.x, wave = tid >> 6; const int lane = (int)(tid & 63);
+  const u64 ia = wave_incl_scan64(a, lane), ib = wave_incl_scan64(b, lane);
+  if (lane == 63) { sA[wave] = ia; sB[wave] = ib; }
+  __syncthreads();
+  u64 ba = 0, bb = 0, sa = 0, sb = 0;
+  for (u32 w = 0; w < 16; w++) { const u64 x = sA[w], y = sB[w]; ba += w < wave ? x : 0; bb += w < wave ? y : 0; sa += x; sb += y; }
+  a = ba + ia - a; b = bb + ib - b; *ta = sa; *tb = sb;
+  __syncthreads();
+}
+}  // namespace
+
+// Workgroup b sums the sizes of frames [1024 b, 1024 b + 1024): sums[2b] all, sums[2b + 1] the newly encoded ones.
+extern "C" __global__ void __launch_bounds__(1024) zra_upd_sizes_kernel(u32 nNew, const u32* slotOf, const u64* encSizes, const u8* table, u64* sums) {
+  __shared__ u64 sA[16], sB[16];
+  u64 a, b, ta, tb;
+  upd_frame_size(blockIdx.x * 1024 + threadIdx.x, nNew, slotOf, encSizes, table, &a, &b);
+  block_excl_scan2(a, b, &ta, &tb, sA, sB);
+  if (threadIdx.x == 0) { sums[2 * (size_t)blockIdx.x] = ta; sums[2 * (size_t)blockIdx.x + 1] = tb; }
+}
+
+// One workgroup: the workgroup sums become exclusive prefixes in place; sums[2 nBlocks], [2 nBlocks + 1] = the totals.
+extern "C" __global__ void __launch_bounds__(1024) zra_upd_scan_kernel(u64* sums, u32 nBlocks) {
+  __shared__ u64 sA[16], sB[16];
+  u64 ca = 0, cb = 0;
+  for (u32 base = 0; base < nBlocks; base += 1024) {
+    const u32 i = base + threadIdx.x;
+    u64 a = i < nBlocks ? sums[2 * (size_t)i] : 0, b = i < nBlocks ? sums[2 * (size_t)i + 1] : 0, ta, tb;
+    block_excl_scan2(a, b, &ta, &tb, sA, sB);
+    if (i < nBlocks) { sums[2 * (size_t)i] = ca + a; sums[2 * (size_t)i + 1] = cb + b; }
+    ca += ta; cb += tb;
+  }
+  if (threadIdx.x == 0) { sums[2 * (size_t)nBlocks] = ca; sums[2 * (size_t)nBlocks + 1] = cb; }
+}
+
+// Thread per frame (and one for the end entry): newOff[f] = where the frame starts in the new body, its 5-byte entry of the new seek
+// table, and disp[f] = the address of its compressed bytes minus newOff[f] — in the old body for a frame carried over, in the packed
+// buffer for a newly encoded one. Neighbours that stay neighbours have the same displacement: the gather copies them as one span.
+extern "C" __global__ void __launch_bounds__(1024) zra_upd_offsets_kernel(u32 nNew, const u32* slotOf, const u64* encSizes, const u8* table, const u64* sums,
+                                                                       const u8* oldBody, const u8* packed, u64* newOff, u64* disp, u8* entries) {
+  __shared__ u64 sA[16], sB[16];
+  const u32 f = blockIdx.x * 1024 + threadIdx.x;
+  u64 a, b, ta, tb;
+  upd_frame_size(f, nNew, slotOf, encSizes, table, &a, &b);
+  const bool enc = b != 0 || (f < nNew && slotOf[f] != kNone);
+  block_excl_scan2(a, b, &ta, &tb, sA, sB);
+  if (f > nNew) return;
+  const u64 off = sums[2 * (size_t)blockIdx.x] + a, toff = sums[2 * (size_t)blockIdx.x + 1] + b;
+  newOff[f] = off;
+  u8* e = entries + (size_t)f * 5;
+  e[0] = (u8)off; e[1] = (u8)(off >> 8); e[2] = (u8)(off >> 16); e[3] = (u8)(off >> 24); e[4] = (u8)(off >> 32);
+  if (f == nNew) disp[f] = ~0ull;
+  else disp[f] = (enc ? (u64)(uintptr_t)packed + toff : (u64)(uintptr_t)oldBody + entry40(table, f)) - off;
+}
+
+// The bandwidth kernel. The new body is cut into chunks of kGatherChunk bytes, a capped grid strides over them, one wave per chunk.
+// The wave finds the frame its chunk starts in by binary search over newOff, then copies span after span: a span ends where the
+// displacement changes (ballot over the next 64 frames at a time) or the chunk does. 16-byte loads aligned on the source, the stores
+// fall as they may (zra_gather_frames_kernel's choice).
+extern "C" __global__ void __launch_bounds__(256) zra_upd_gather_kernel(const u64* newOff, const u64* disp, u32 nNew, u64 total, u8* body) {
+  const u32 lane = threadIdx.x & 63;
+  const u64 nChunks = (total + kGatherChunk - 1) / kGatherChunk;
+  for (u64 c = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); c < nChunks; c += (u64)gridDim.x * 4) {
+    u64 x = c * kGatherChunk;
+    const u64 x1 = min<u64>(x + kGatherChunk, total);
+    u32 lo = 0, hi = nNew - 1;                                        // the last frame that starts at or before x
+    while (lo < hi) {
+      const u32 mid = lo + (hi - lo + 1) / 2;
+      if (newOff[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    u32 f = lo;
+    while (x < x1 && f < nNew) {
+      const u64 d = disp[f];
+      u32 g = f + 1;
+      for (;;) {                                                      // (ends: disp[nNew] is no frame's displacement)
+        const u32 i = g + lane;
+        const bool brk = i > nNew || newOff[min(i, nNew)] >= x1 || disp[min(i, nNew)] != d;
+        const u64 m = __ballot(brk);
+        if (m) { g += (u32)__builtin_ctzll(m); break; }
+        g += 64;
+      }
+      g = min(g, nNew);
+      const u64 end = min<u64>(x1, newOff[g]);
+      if (end > x) {
+        const u8* src = (const u8*)(uintptr_t)(d + x);
+        u8* dst = body + x;
+        const u64 n = end - x;
+        const u32 head = (u32)min<u64>((16u - ((uintptr_t)src & 15u)) & 15u, n);
+        if (lane < head) dst[lane] = src[lane];
+        const u32 n16 = (u32)((n - head) >> 4);
+        const uint4* s4 = (const uint4*)(src + head);
+        u8* d16 = dst + head;
+        u32 i = lane;
+        for (; i + 192 < n16; i += 256) {                             // four loads in flight per lane
+          const uint4 v0 = s4[i], v1 = s4[i + 64], v2 = s4[i + 128], v3 = s4[i + 192];
+          st128(d16 + 16 * (size_t)i, v0.x, v0.y, v0.z, v0.w); st128(d16 + 16 * (size_t)(i + 64), v1.x, v1.y, v1.z, v1.w);
+          st128(d16 + 16 * (size_t)(i + 128), v2.x, v2.y, v2.z, v2.w); st128(d16 + 16 * (size_t)(i + 192), v3.x, v3.y, v3.z, v3.w);
+        }
+        for (; i < n16; i += 64) { const uint4 v = s4[i]; st128(d16 + 16 * (size_t)i, v.x, v.y, v.z, v.w); }
+        for (u64 k = head + ((u64)n16 << 4) + lane; k < n; k += 64) dst[k] = src[k];
+        x = end;
+      }
+      f = g;
+    }
+  }
+}
+
+// =================================================================================================
+namespace zra_eng {
+
+#define UCHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return zerr(1); } } while (0)
+
+struct UpdateImpl {
+  static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
+                    const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
+                    size_t* outSize, int level, bool checksum);
+};
+
+Status Engine::update_archive(const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
+                              const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
+                              size_t* outSize, int level, bool checksum) {
+  for (auto& v : ustats_) v = 0;
+  return UpdateImpl::run(*this, dArc, arcSize, dData, hOff, hSize, hDataOff, nw, dAppend, appendSize, dOut, outCap, outSize, level, checksum);
+}
+
+Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
+                       const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
+                       size_t* outSize, int level, bool checksum) {
+  // ---- 1. arguments, 2. overlap
+  if (!outSize || !dOut || (!dArc && arcSize) || (nw && (!hOff || !hSize || !hDataOff)) || (!dAppend && appendSize)) return zerr(42);
+  if (!dData) for (size_t i = 0; i < nw; i++) if (hSize[i]) return zerr(42);
+  if (outCap && arcSize && (uintptr_t)dOut < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dOut + outCap) return zerr(42);
+  UCHK(hipSetDevice(E.device_));
+  hipStream_t s = E.stream_;
+  // ---- 3. header: the statuses of ZraHipArchiveOpen; beyond them a frame size of 0 and a table that does not cover the content
+  // (an open handle refuses every read of such an archive; here there is no frame to put a byte in)
+  HeaderInfo h;
+  { Status st = E.ra_header(dArc, arcSize, &h); if (st.zra) return st; }
+  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  const uint32_t F = h.frames();
+  if (fs == 0 || (U + fs - 1) / fs != F) return {kHeaderInvalid, 0};
+  // ---- 4. writes. The bound is inclusive: offset + size == uncompressedSize is the write that reaches the last byte. (The reference's
+  // ">=" (zra.cpp:260) is a quirk of its reads, kept there for compatibility; a write that could never touch the last byte of the
+  // content would be a defect.) Empty writes are ignored wherever they point.
+  std::vector<size_t> idx;
+  uint64_t written = appendSize, maxEnd = 0;
+  for (size_t i = 0; i < nw; i++) {
+    const uint64_t o = hOff[i], z = hSize[i];
+    if (!z) continue;
+    if (o > U || z > U - o) return {kOutOfBounds, 0};
+    idx.push_back(i); written += z; maxEnd = std::max(maxEnd, o + z);
+  }
+  // two writes that share a byte: refused — no "last one wins" between slices that are copied side by side
+  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return hOff[a] < hOff[b]; });
+  for (size_t k = 1; k < idx.size(); k++) if (hOff[idx[k - 1]] + hSize[idx[k - 1]] > hOff[idx[k]]) return zerr(42);
+  if (appendSize > ~0ull - U) return {kCompressedTooLarge, 0};
+  const uint64_t U2 = U + appendSize, F2wide = U2 / fs + (U2 % fs ? 1 : 0);
+  if (F2wide > 0xFFFFFFF0ull) return {kCompressedTooLarge, 0};
+  const uint32_t F2 = (uint32_t)F2wide;
+  const size_t nData = idx.size(), nT = nData + (appendSize ? 1 : 0);
+  if (nT > 0xFFFFFFF0ull) return zerr(64);
+  // the tuples, sorted by offset, in page-locked memory and from there to the device in chunks (ra_walk_queries' idiom)
+  uint64_t nSlices = 0;
+  if (nT) {
+    if (E.pinQCap_ < 4 * nT) {
+      if (E.pinQ_) (void)hipHostFree(E.pinQ_);
+      E.pinQ_ = nullptr; E.pinQCap_ = 0;
+      void* pq = nullptr;
+      const size_t cap = std::max<size_t>(4 * nT, 4096);
+      if (hipHostMalloc(&pq, cap * 8 + 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return zerr(64); }
+      E.pinQ_ = (uint64_t*)pq; E.pinQCap_ = cap;
+    }
+    if (!E.qmeta_.reserve(4 * nT * 8 + 64)) return zerr(64);
+    uint64_t* const hq = E.pinQ_;
+    constexpr size_t kChunk = 1u << 17;
+    for (size_t q0 = 0; q0 < nT; q0 += kChunk) {
+      const size_t q1 = std::min(nT, q0 + kChunk);
+      for (size_t q = q0; q < q1; q++) {
+        const uint64_t o = q < nData ? hOff[idx[q]] : U, z = q < nData ? hSize[idx[q]] : appendSize;
+        hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = q < nData ? hDataOff[idx[q]] : 0; hq[4 * q + 3] = nSlices;
+        nSlices += (o + z - 1) / fs - o / fs + 1;
+      }
+      UCHK(hipMemcpyAsync(E.qmeta_.as<uint64_t>() + 4 * q0, hq + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, s));
+    }
+  }
+  const uint64_t* dq = E.qmeta_.as<uint64_t>();
+  // ---- plan
+  const uint32_t passSlots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kPassFrames, kStageBytes / fs));
+  const uint64_t touchedMax = std::min<uint64_t>(F2, nSlices), jobsMax = std::min<uint64_t>(F, nSlices);
+  const size_t passesMax = (size_t)((touchedMax + passSlots - 1) / passSlots);
+  const size_t planWords = 2 * (size_t)F2 + 16 + passesMax + 1;            // cover[F2] | slotOf[F2] | totals[16] | passJob[passes + 1]
+  const uint32_t nBlocks = F2 / 1024 + 1;                                  // (F2 + 1 entries: the frames and the end)
+  if (!E.upd_.plan.reserve(planWords * 4 + 64) || !E.upd_.frames.reserve((2 * ((size_t)F2 + 1) + 2 * ((size_t)nBlocks + 1)) * 8 + 64) ||
+      !E.upd_.table.reserve(((size_t)F2 + 1) * 5 + 64) || !E.frameOff_.reserve((jobsMax + 1) * 16) || !E.outOff_.reserve((jobsMax + 1) * 8) ||
+      !E.expect_.reserve((jobsMax + 1) * 4))
+    return zerr(64);
+  uint32_t* cover = E.upd_.plan.as<uint32_t>(), *slotOf = cover + F2, *totals = slotOf + F2, *passJob = totals + 16;
+  uint64_t* newOff = E.upd_.frames.as<uint64_t>(), *disp = newOff + F2 + 1, *sums = disp + F2 + 1;
+  const uint8_t* oldTable = dArc + h.seekTableOffset;
+  const uint8_t* oldBody = dArc + h.size;
+  const uint64_t bodyBytes = arcSize - h.size;
+  UCHK(hipMemsetAsync(cover, 0, planWords * 4, s));
+  if (nSlices)
+    hipLaunchKernelGGL(zra_upd_mark_kernel, dim3((uint32_t)((nSlices + 255) / 256)), dim3(256), 0, s, dq, (u32)nT, (u64)nSlices, (u64)fs, cover);
+  uint32_t hTotals[3] = {0, 0, 0};
+  if (F2) {
+    hipLaunchKernelGGL(zra_upd_plan_kernel, dim3(1), dim3(1024), 0, s, cover, F2, F, oldTable, (u64)bodyBytes, (u64)fs, (u64)U, (u64)U2, passSlots, slotOf,
+                       E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), passJob, totals);
+    UCHK(hipMemcpyAsync(hTotals, totals, 12, hipMemcpyDeviceToHost, s));
+  }
+  UCHK(hipStreamSynchronize(s));
+  UCHK(hipGetLastError());
+  // ---- 5. the old seek table over the frames carried over
+  if (hTotals[2]) return zerr(20);
+  const uint32_t touched = hTotals[0], jobs = hTotals[1];
+  const uint32_t passes = (touched + passSlots - 1) / passSlots;
+  // ---- 6. passes: decode the frames that keep old bytes, lay the new bytes over them, encode
+  uint64_t encoded = 0;
+  if (touched) {
+    std::vector<uint32_t> hPassJob(passes + 1);
+    UCHK(hipMemcpyAsync(hPassJob.data(), passJob, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
+    UCHK(hipStreamSynchronize(s));
+    const uint64_t bound = zra_fmt::compress_bound(fs);
+    if (!E.upd_.stage.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64) || !E.upd_.packed.reserve((size_t)touched * bound + 64) ||
+        !E.upd_.encSizes.reserve((size_t)touched * 8 + 64))
+      return zerr(64);
+    uint8_t* stage = E.upd_.stage.as<uint8_t>();
+    // only the last frame of the result can be short, and only if new bytes reach it is it staged (then as the last slot of all)
+    const bool lastStaged = F2 && (appendSize || maxEnd > (uint64_t)(F2 - 1) * fs);
+    const uint64_t lastLen = F2 ? U2 - (uint64_t)(F2 - 1) * fs : 0;
+    const uint32_t patchGrid = (uint32_t)std::min<uint64_t>((nSlices + 3) / 4, 1u << 20);
+    for (uint32_t p = 0; p < passes; p++) {
+      const uint32_t s0 = p * passSlots, n = std::min(passSlots, touched - s0);
+      const uint32_t j0 = hPassJob[p], j1 = hPassJob[p + 1];
+      if (j1 > j0) {
+        Status st = E.decode_jobs(oldBody, bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)j0, stage, E.outOff_.as<uint64_t>() + j0,
+                                  E.expect_.as<uint32_t>() + j0, j1 - j0, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2);
+        if (st.zra) return st;
+      }
+      hipLaunchKernelGGL(zra_upd_patch_kernel, dim3(patchGrid), dim3(256), 0, s, dq, (u32)nT, (u32)nData, (u64)nSlices, (u64)fs, slotOf, s0, n,
+                         dData, dAppend, stage);
+      const size_t inSize = (size_t)(n - 1) * fs + (size_t)(p + 1 == passes && lastStaged ? lastLen : fs);
+      size_t bsz = 0;
+      Status st = E.compress_frames(stage, inSize, E.upd_.packed.as<uint8_t>() + encoded, E.upd_.encSizes.as<uint64_t>() + s0, &bsz, level, (uint32_t)fs, checksum);
+      if (st.zra) return st;
+      encoded += bsz;
+    }
+  }
+  // ---- sizes, offsets, table
+  uint64_t hTot[2] = {0, 0};
+  hipLaunchKernelGGL(zra_upd_sizes_kernel, dim3(nBlocks), dim3(1024), 0, s, F2, slotOf, E.upd_.encSizes.as<uint64_t>(), oldTable, sums);
+  hipLaunchKernelGGL(zra_upd_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nBlocks);
+  hipLaunchKernelGGL(zra_upd_offsets_kernel, dim3(nBlocks), dim3(1024), 0, s, F2, slotOf, E.upd_.encSizes.as<uint64_t>(), oldTable, sums, oldBody,
+                     E.upd_.packed.as<uint8_t>(), newOff, disp, E.upd_.table.as<uint8_t>());
+  // the header on the host (5 bytes per frame, as compress_device does): fixed part rewritten, meta section copied, new table, CRC-32
+  const size_t metaSize = h.metaSize, tableBytes = ((size_t)F2 + 1) * 5;
+  const uint64_t headerSize = zra_fmt::kFixedSize + (uint64_t)metaSize + tableBytes;
+  if (headerSize > 0xFFFFFFFFull) return {kCompressedTooLarge, 0};
+  std::vector<uint8_t> hdr((size_t)headerSize);
+  UCHK(hipMemcpyAsync(hTot, sums + 2 * (size_t)nBlocks, 16, hipMemcpyDeviceToHost, s));
+  if (metaSize) UCHK(hipMemcpyAsync(hdr.data() + zra_fmt::kFixedSize, dArc + zra_fmt::kFixedSize, metaSize, hipMemcpyDeviceToHost, s));
+  UCHK(hipMemcpyAsync(hdr.data() + zra_fmt::kFixedSize + metaSize, E.upd_.table.p, tableBytes, hipMemcpyDeviceToHost, s));
+  UCHK(hipStreamSynchronize(s));
+  UCHK(hipGetLastError());
+  const uint64_t body = hTot[0];
+  // ---- 7. size limit (compress_device's rule, zra.cpp:227), 8. capacity
+  if (headerSize + body >= zra_fmt::kMaxCompressedSize) return {kCompressedTooLarge, 0};
+  *outSize = (size_t)(headerSize + body);
+  if (outCap < headerSize + body) return {kOutputTooSmall, 0};
+  zra_fmt::write_fixed(hdr.data(), U2, F2 + 1, (uint32_t)fs, (uint32_t)metaSize);
+  zra_fmt::wr32(hdr.data() + 14, zra_fmt::header_hash(hdr.data(), hdr.data() + zra_fmt::kFixedSize));
+  // ---- gather
+  UCHK(hipMemcpyAsync(dOut, hdr.data(), (size_t)headerSize, hipMemcpyHostToDevice, s));
+  // (ZraHipLastKernelMs after an update: the gather, the call's bandwidth kernel)
+  E.lastKernelMs_ = 0;
+  const bool gather = body && F2;
+  if (gather) {
+    const uint64_t nChunks = (body + kGatherChunk - 1) / kGatherChunk;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nChunks + 3) / 4, kGatherGrid);
+    UCHK(hipEventRecord(E.ev0_, s));
+    hipLaunchKernelGGL(zra_upd_gather_kernel, dim3(grid), dim3(256), 0, s, newOff, disp, F2, (u64)body, dOut + headerSize);
+    UCHK(hipEventRecord(E.ev1_, s));
+  }
+  UCHK(hipStreamSynchronize(s));
+  UCHK(hipGetLastError());
+  if (gather) { float ms = 0; if (hipEventElapsedTime(&ms, E.ev0_, E.ev1_) == hipSuccess) E.lastKernelMs_ = ms; else (void)hipGetLastError(); }
+  const uint64_t st8[8] = {F2, touched, jobs, touched, body - encoded, encoded, written, passes};
+  for (int i = 0; i < 8; i++) E.ustats_[i] = st8[i];
+  return ok();
+}
+
+}  // namespace zra_eng
