@@ -291,3 +291,45 @@ def test_multi_block_frames_in_two_half_batches(zra, gpu_engine):
     d_back = torch.empty(len(data), dtype=torch.uint8, device=dev)
     gpu_engine.decompress(d_arc.data_ptr(), n, d_back.data_ptr(), len(data))
     assert torch.equal(d_back, d_in)
+
+
+def test_the_same_calls_give_the_same_bytes_after_release_scratch(zra):
+    """On a fresh engine one compress, one whole-archive decompress, one batched random-access read and one update reserve buffers of
+    every group (decoder, planner, encoder contexts, update); after release_scratch() the same four calls have to allocate all of them
+    again and give the same bytes. (What this cannot see is a buffer that release_scratch() forgets: the process-wide scratch counter
+    behind the engine pool's cap is not exposed by the C ABI.)"""
+    import torch
+    dev = torch.device("cuda", 0)
+    fs, n = 65536, 1 << 20
+    data = C.gen_E(n)
+    patch = bytes(range(256)) * 4                                           # 1 KiB across the boundary of frames 2 and 3
+    poff = 3 * fs - 500
+    want = bytearray(data); want[poff:poff + len(patch)] = patch
+    d_in = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(dev)
+    d_new = torch.from_numpy(np.frombuffer(patch, dtype=np.uint8).copy()).to(dev)
+    offs = np.array([0, fs - 10, 5 * fs + 123, n - 4097], dtype=np.uint64)
+    sizes = np.array([100, 20, 70000, 4096], dtype=np.uint64)
+    oo = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
+    cap = zra.GetOutputBufferSize(n + len(patch), fs) + 64
+    eng = zra.Engine(0)
+
+    def four_calls():
+        d_arc = torch.zeros(cap, dtype=torch.uint8, device=dev)
+        asz = eng.compress(d_in.data_ptr(), n, d_arc.data_ptr(), 3, fs, True)
+        d_out = torch.zeros(n, dtype=torch.uint8, device=dev)
+        eng.decompress(d_arc.data_ptr(), asz, d_out.data_ptr(), n)
+        d_ra = torch.zeros(int(sizes.sum()), dtype=torch.uint8, device=dev)
+        eng.decompress_ra_batch(d_arc.data_ptr(), asz, d_ra.data_ptr(), offs, sizes, oo)
+        d_upd = torch.zeros(cap, dtype=torch.uint8, device=dev)
+        usz = eng.update(d_arc.data_ptr(), asz, d_upd.data_ptr(), cap, writes=([poff], [len(patch)], [0]), d_data=d_new.data_ptr())
+        return [t.cpu().numpy().tobytes() for t in (d_arc[:asz], d_out, d_ra, d_upd[:usz])]
+
+    try:
+        first = four_calls()
+        assert first[1] == data
+        assert first[2] == b"".join(data[int(o):int(o) + int(s)] for o, s in zip(offs, sizes))
+        assert zra.DecompressBuffer(first[3]) == bytes(want)
+        eng.release_scratch()
+        assert four_calls() == first
+    finally:
+        eng.close()

@@ -13,6 +13,7 @@
 //      overwritten.
 //  (c) a frame is mapped (slotOf / frameOf) only by the commit kernel, after its decode pass: no lookup can find a half-decoded slot.
 #include "zra_archive.h"
+#include "zra_host.h"
 #include "zra_dev.h"
 #include "zra_kernels.h"
 #include <algorithm>
@@ -122,8 +123,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_cache_commit_kernel(const 
     const u32 st = jobOf[t];
     if (st >= s0 && st - s0 < n) {
       const u32 j = st - s0, v = victim[j];
-      const u64 o = (u64)t * fs;
-      const u32 expect = o >= total ? 0u : (u32)min<u64>(fs, total - o);
+      const u32 expect = (u32)frame_expect(t, fs, total);
       if (passOk && status[j] == 0 && produced[j] == expect) { slotOf[t] = v; frameOf[v] = t; atomicAdd(&ctr[1], 1ull); }
       ref[v] = 0;
     }
@@ -134,10 +134,8 @@ extern "C" __global__ void __launch_bounds__(256) zra_cache_commit_kernel(const 
 // =================================================================================================
 namespace zra_eng {
 
-#define ACHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return zerr(1); } } while (0)
-
 Status ArchiveCache::open(Engine* e, const uint8_t* dArc, size_t arcSize, size_t cacheBytes, ArchiveCache** out) {
-  ACHK(hipSetDevice(e->device_));
+  HIPCHK_CLR(hipSetDevice(e->device_));
   HeaderInfo h;
   { Status st = e->ra_header(dArc, arcSize, &h); if (st.zra) return st; }
   ArchiveCache* c = new ArchiveCache();
@@ -180,19 +178,19 @@ void ArchiveCache::stats(uint64_t out[8]) const {
 }
 
 Status ArchiveCache::drop() {
-  ACHK(hipSetDevice(e_->device_));
+  HIPCHK_CLR(hipSetDevice(e_->device_));
   if (!slots_) return ok();
-  ACHK(hipMemsetAsync(slotOf_, 0xFF, ((size_t)nFrames_ + slots_) * 4, e_->stream_));
-  ACHK(hipMemsetAsync(ref_, 0, slots_, e_->stream_));
-  ACHK(hipMemsetAsync(dctr_ + 1, 0, 8, e_->stream_));
-  ACHK(hipStreamSynchronize(e_->stream_));
+  HIPCHK_CLR(hipMemsetAsync(slotOf_, 0xFF, ((size_t)nFrames_ + slots_) * 4, e_->stream_));
+  HIPCHK_CLR(hipMemsetAsync(ref_, 0, slots_, e_->stream_));
+  HIPCHK_CLR(hipMemsetAsync(dctr_ + 1, 0, 8, e_->stream_));
+  HIPCHK_CLR(hipStreamSynchronize(e_->stream_));
   resident_ = 0;
   return ok();
 }
 
 Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt) {
   Engine& E = *e_;
-  ACHK(hipSetDevice(E.device_));
+  HIPCHK_CLR(hipSetDevice(E.device_));
   if (!slots_) {
     // no cache: the batch call itself, header read and checked at open
     E.set_ra_verify_whole_frames(wholeFramesOpt);
@@ -225,20 +223,20 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
   uint64_t nSlices = 0;
   { Status st = E.ra_walk_queries(h_, hOff, hSize, hOutOff, nq, &nSlices); if (st.zra) return st; }
   reads_++;
-  if (nSlices == 0) { ACHK(hipStreamSynchronize(s)); return ok(); }
-  // the batch's planner arrays (RaPlan: cnt, need, slot, cursor, then its totals in 16 words), the lookup's two result words inside those
-  // 16, then seen[nFrames]: one memset
-  const size_t planWords = 4 * (size_t)nF + 16;
+  if (nSlices == 0) { HIPCHK_CLR(hipStreamSynchronize(s)); return ok(); }
+  // the batch's planner scratch (the lookup's two result words inside its totals), then seen[nFrames]: one memset
+  const size_t planWords = RaPlan::words(nF);
   if (!E.raPlan_.reserve((planWords + nF) * 4)) return zerr(64);
   uint32_t* plan = E.raPlan_.as<uint32_t>();
-  uint32_t* words = plan + 4 * (size_t)nF + 8;
-  ACHK(hipMemsetAsync(plan, 0, (planWords + nF) * 4, s));
+  const RaPlan P = RaPlan::over(plan, nF);
+  uint32_t* const seen = plan + planWords, * const words = P.lookup_words();
+  HIPCHK_CLR(hipMemsetAsync(plan, 0, (planWords + nF) * 4, s));
   const uint32_t grid = (uint32_t)std::min<uint64_t>((nSlices + 3) / 4, 1u << 20);
   hipLaunchKernelGGL(zra_cache_lookup_kernel, dim3(grid), dim3(256), 0, s, E.qmeta_.as<uint64_t>(), (u32)nq, (u64)nSlices, (u64)fs, slotOf_, ref_,
-                     arena_, dOut, plan, plan + planWords, words);
-  ACHK(hipMemcpyAsync(pin_, words, 8, hipMemcpyDeviceToHost, s));
-  ACHK(hipStreamSynchronize(s));
-  ACHK(hipGetLastError());
+                     arena_, dOut, P.cnt, seen, words);
+  HIPCHK_CLR(hipMemcpyAsync(pin_, words, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
   const uint32_t missed = ((const uint32_t*)pin_)[0], hit = ((const uint32_t*)pin_)[1];
   hits_ += hit; misses_ += missed;
   if (!missed) return ok();
@@ -263,15 +261,15 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
     ra.limit = E.raLimit_.as<uint32_t>() + s0; ra.pieceBase = E.raPieceBase_.as<uint32_t>() + s0;
     fail = E.decode_jobs(dBody, bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)s0, arena_, E.outOff_.as<uint64_t>() + s0,
                          E.expect_.as<uint32_t>() + s0, n, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2, 0, &ra);
-    hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, plan, plan + 2 * (size_t)nF, nF, s0, n, victim_, V,
+    hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, P.cnt, P.slot, nF, s0, n, victim_, V,
                        E.status_.as<uint32_t>(), E.produced_.as<uint32_t>(), fail.zra ? 0u : 1u, (u64)fs, (u64)U, slotOf_, frameOf_, ref_, dctr_);
   }
   if (!jobs)   // (the planner failed: the claimed slots are released all the same)
-    hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, plan, plan + 2 * (size_t)nF, 0u, 0u, 0u, victim_, V,
+    hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, P.cnt, P.slot, 0u, 0u, 0u, victim_, V,
                        E.status_.as<uint32_t>(), E.produced_.as<uint32_t>(), 0u, (u64)fs, (u64)U, slotOf_, frameOf_, ref_, dctr_);
-  ACHK(hipMemcpyAsync(pin_ + 2, dctr_, 16, hipMemcpyDeviceToHost, s));
-  ACHK(hipStreamSynchronize(s));
-  ACHK(hipGetLastError());
+  HIPCHK_CLR(hipMemcpyAsync(pin_ + 2, dctr_, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
   evictions_ = pin_[2]; resident_ = pin_[3];
   if (fail.zra == kZStdError) {
     // Damage: the status is the batch call's under ZRA_HIP_OPT_RA_WHOLE_FRAMES. Which of several failing frames that call reports

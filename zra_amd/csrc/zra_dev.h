@@ -21,6 +21,13 @@ enum : u32 {
 
 constexpr int WAVE = 64;
 
+// bytes frame i of `total` bytes in frames of `frameSize` regenerates: the remainder in the last frame, nothing in a frame whose slot
+// starts at or beyond the declared size (a crafted header). Fits 32 bits whenever frameSize does.
+__host__ __device__ __forceinline__ u64 frame_expect(u64 i, u64 frameSize, u64 total) {
+  const u64 o = i * frameSize;
+  return o >= total ? 0 : (total - o < frameSize ? total - o : frameSize);
+}
+
 __device__ __forceinline__ u32 hb32(u32 x) { return 31u - (u32)__builtin_clz(x); }  // x != 0
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 

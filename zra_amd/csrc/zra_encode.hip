@@ -3,13 +3,12 @@
 // Replaces the loop body of the reference's CompressBuffer / Compressor::Compress (zra.cpp:216-225, 329-338).
 #include <cstdio>
 #include <unistd.h>
-#include "zra_engine.h"
+#include "zra_host.h"
 #include "zra_dev.h"
 #include "zra_format.h"
 #include "zra_env.h"
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 extern "C" __global__ void zra_mf_kernel(ZraEncArgs a, uint32_t block, uint32_t only, uint32_t onlySlot, uint32_t perWave);
@@ -128,8 +127,6 @@ bool get_params(int level, size_t S, ZraEncParams* p) {
 }  // namespace
 
 namespace zra_eng {
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return zerr(1); } while (0)
 
 Status Engine::compress_frames(const uint8_t* dIn, size_t inSize, uint8_t* dBody, uint64_t* dSizes, size_t* bodySize,
                                int level, uint32_t frameSize, bool checksum) {
@@ -714,7 +711,7 @@ Status Engine::compress_device(const uint8_t* dIn, size_t inSize, uint8_t* dOut,
 }
 
 // ------------------------------------------------------------------ host-pointer helpers used by the C/C++ API
-// compress_host: zra_hostpipe.hip
+// compress_host, decode_host: zra_hostpipe.hip
 Status Engine::compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
                                     int level, uint32_t frameSize, bool checksum) {
   HIPCHK(hipSetDevice(device_));
@@ -730,82 +727,6 @@ Status Engine::compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody
   sizes.resize(nFrames);
   HIPCHK(hipMemcpyAsync(hBody, hostOut_.p, *bodySize, hipMemcpyDeviceToHost, stream_));
   HIPCHK(hipMemcpyAsync(sizes.data(), dSizes, nFrames * 8, hipMemcpyDeviceToHost, stream_));
-  HIPCHK(hipStreamSynchronize(stream_));
-  return ok();
-}
-
-Status Engine::decode_host(const uint8_t* hSpan, size_t spanSize, const std::vector<uint64_t>& starts, const std::vector<uint64_t>& ends,
-                           uint32_t frameSize, uint64_t total, uint8_t* hOut, size_t skip, size_t size, bool wholeArchive) {
-  HIPCHK(hipSetDevice(device_));
-  const uint32_t nFrames = (uint32_t)starts.size();
-  if (nFrames == 0) return ok();
-  std::vector<uint64_t> se((size_t)nFrames * 2), oo(nFrames);
-  std::vector<uint32_t> ex(nFrames);
-  for (uint32_t i = 0; i < nFrames; i++) {
-    se[2 * (size_t)i] = starts[i]; se[2 * (size_t)i + 1] = ends[i];
-    const uint64_t o = (uint64_t)i * frameSize;
-    oo[i] = wholeArchive ? std::min<uint64_t>(o, total) : o;        // a slot past the declared size has no room and no address of its own
-    ex[i] = o >= total ? 0 : (uint32_t)std::min<uint64_t>(frameSize, total - o);
-  }
-  if (wholeArchive && skip == 0 && frameSize && (size_t)nFrames >= 2 * std::max<size_t>(1, host_chunk_bytes() / frameSize) && size == std::min<uint64_t>(total, (uint64_t)nFrames * frameSize)) {
-    bool fallBack = false;
-    Status s = decode_host_pipelined(hSpan, starts, ends, frameSize, total, hOut, &fallBack);
-    if (!fallBack) return s;
-  }
-  // ---- small calls (round 6; the reference's own calling convention, one query of a few KiB through ZraDecompressRA): the four pageable
-  // host-to-device copies (each staged and waited for by the runtime), the synchronisation behind them and the pageable copy back were
-  // ~40 % of such a call. Here the job arrays and the compressed span travel in ONE copy from page-locked memory, the kernel is queued
-  // straight behind it, and the answer comes back through page-locked memory: one copy in, one launch, one copy out, one wait.
-  constexpr size_t kSmallSpan = 768u << 10, kSmallOut = 1u << 20, kSmallJobs = 16;
-  if (!wholeArchive && nFrames <= kSmallJobs && spanSize <= kSmallSpan && size <= kSmallOut && (uint64_t)nFrames * frameSize <= (64ull << 20)) {
-    const size_t metaBytes = (size_t)kSmallJobs * (16 + 8 + 4 + 4);                   // frameOff pairs, outOff, expect (padded)
-    const size_t inBytes = metaBytes + ((spanSize + 63) & ~(size_t)63);
-    if (!pinSmall_) {
-      void* pq = nullptr;
-      if (hipHostMalloc(&pq, metaBytes + kSmallSpan + 64 + kSmallOut + 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); pq = nullptr; }
-      pinSmall_ = (uint8_t*)pq;
-    }
-    if (pinSmall_ && hostIn_.reserve(metaBytes + kSmallSpan + 128) && hostOut_.reserve((size_t)nFrames * frameSize + 64)) {
-      uint8_t* const hp = pinSmall_;
-      std::memcpy(hp, se.data(), se.size() * 8);
-      std::memcpy(hp + kSmallJobs * 16, oo.data(), (size_t)nFrames * 8);
-      std::memcpy(hp + kSmallJobs * 24, ex.data(), (size_t)nFrames * 4);
-      std::memcpy(hp + metaBytes, hSpan, spanSize);
-      uint8_t* const dIn = hostIn_.as<uint8_t>();
-      HIPCHK(hipMemcpyAsync(dIn, hp, inBytes, hipMemcpyHostToDevice, stream_));
-      Status s = decode_jobs(dIn + metaBytes, spanSize, (const uint64_t*)dIn, hostOut_.as<uint8_t>(), (const uint64_t*)(dIn + kSmallJobs * 16),
-                             (const uint32_t*)(dIn + kSmallJobs * 24), nFrames, frameSize, 2, 0);
-      if (s.zra) return s;
-      if (skip + size > (uint64_t)nFrames * frameSize) return {kOutOfBounds, 0};
-      if (size) {
-        uint8_t* const ho = pinSmall_ + metaBytes + kSmallSpan + 64;
-        HIPCHK(hipMemcpyAsync(ho, hostOut_.as<uint8_t>() + skip, size, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        std::memcpy(hOut, ho, size);
-      }
-      return ok();
-    }
-  }
-  // whole-archive mode never writes at or beyond `total` (slots past it have no room), whatever the header's frameSize claims
-  if (!hostIn_.reserve(spanSize + 64) || !hostOut_.reserve((wholeArchive ? (size_t)total : (size_t)nFrames * frameSize) + 64) || !frameOff_.reserve(se.size() * 8) ||
-      !outOff_.reserve((size_t)nFrames * 8) || !expect_.reserve((size_t)nFrames * 4))
-    return zerr(64);
-  HIPCHK(hipMemcpyAsync(hostIn_.p, hSpan, spanSize, hipMemcpyHostToDevice, stream_));
-  HIPCHK(hipMemcpyAsync(frameOff_.p, se.data(), se.size() * 8, hipMemcpyHostToDevice, stream_));
-  HIPCHK(hipMemcpyAsync(outOff_.p, oo.data(), (size_t)nFrames * 8, hipMemcpyHostToDevice, stream_));
-  HIPCHK(hipMemcpyAsync(expect_.p, ex.data(), (size_t)nFrames * 4, hipMemcpyHostToDevice, stream_));
-  HIPCHK(hipStreamSynchronize(stream_));
-  Status s = decode_jobs(hostIn_.as<uint8_t>(), spanSize, frameOff_.as<uint64_t>(), hostOut_.as<uint8_t>(), outOff_.as<uint64_t>(),
-                         expect_.as<uint32_t>(), nFrames, frameSize, 2, wholeArchive ? total : 0);
-  if (s.zra) return s;
-  if (wholeArchive && lastProducedTotal_ != ~0ull) {
-    // frames that regenerated another size than the header's frameSize (corrupted or foreign archive): the sequential tail has packed
-    // them back to back like the reference's one multi-frame call (zra.cpp:249) — what it wrote, less or MORE than the nominal slots
-    // add up to (a frameSize field damaged downwards), is what reaches the caller; never more than the declared size
-    const uint64_t have = std::min<uint64_t>(total, lastProducedTotal_);
-    size = have > skip ? (size_t)(have - skip) : 0;
-  } else if (skip + size > (uint64_t)nFrames * frameSize) return {kOutOfBounds, 0};
-  if (size) HIPCHK(hipMemcpyAsync(hOut, hostOut_.as<uint8_t>() + skip, size, hipMemcpyDeviceToHost, stream_));
   HIPCHK(hipStreamSynchronize(stream_));
   return ok();
 }

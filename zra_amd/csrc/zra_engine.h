@@ -79,9 +79,10 @@ class Engine {
   Status decode_scratch(struct ZraDecodeArgs& a, uint32_t maxFrameBytes);
   // Whole archive resident on the device (header + body), output on the device.
   Status decompress_device(const uint8_t* dArc, size_t arcSize, uint8_t* dOut, size_t outCap);
-  // Batched random access, archive + output on the device, query arrays on the host.
-  Status decompress_ra_batch(const uint8_t* dArc, size_t arcSize, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize,
-                             const uint64_t* hOutOff, size_t nq);
+  // Batched random access (zra_ra.hip), archive + output on the device, query arrays on the host.
+  Status decompress_ra_batch(const uint8_t* dArc, size_t arcSize, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+    return decompress_ra_batch_shard(dArc, arcSize, nullptr, 0, 0, dOut, hOff, hSize, hOutOff, nq);
+  }
   Status decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
                                    const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
   // pieces of the batch, shared with the archive handle (zra_archive.hip): the header read + checks, the walk over the host query
@@ -122,7 +123,7 @@ class Engine {
   // all zero unless it succeeded
   void update_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = ustats_[i]; }
 
-  // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API
+  // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
                               int level, uint32_t frameSize, bool checksum);
@@ -153,6 +154,17 @@ class Engine {
   double dstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<hipEvent_t> stageEv_; size_t stageEvNext_ = 0;
   hipEvent_t stage_event();
+  // one parse -> Huffman -> chain -> execute sequence on stream_ between the stage events it hands back in se[]: nJobs sizes the grids
+  // of the two middle stages and `mid` is their argument block, nFrames and `a` those of parse and execute (blockPass: the _all kernels)
+  Status launch_stages(uint64_t nJobs, const struct ZraDecodeArgs& a, const struct ZraDecodeArgs& mid, uint32_t nFrames, bool blockPass, hipEvent_t se[5]);
+  Status launch_chain(uint64_t nJobs, const struct ZraDecodeArgs& mid, hipEvent_t after);
+  Status decode_sequential_tail(const struct ZraDecodeArgs& a, const uint64_t* dFrameOff, uint32_t offStride, const uint64_t* dOutOff, uint32_t first,
+                                uint32_t nFrames, uint32_t maxFrameBytes, uint64_t seqTotal);
+  // job arrays built on the host -> frameOff_ / outOff_ / expect_; synchronises (the host arrays may go out of scope)
+  Status upload_jobs(const std::vector<uint64_t>& frameOff, const std::vector<uint64_t>& outOff, const std::vector<uint32_t>& expect);
+  Status read_fixed_header(const uint8_t* dArc, size_t arcSize, HeaderInfo* h);   // copy-back + parse_fixed_header + the two size checks
+  uint64_t* pinned_tuples(size_t nTuples);   // pinQ_ grown to 4 words per tuple; nullptr: no memory
+  void free_scratch();                       // every DevBuf of the engine handed back: release_scratch() and the destructor
   hipEvent_t evR_[17] = {nullptr};   // per-round events of one encode batch: e[2r] before mf, e[2r+1] between, e[2r+2] after entropy
   // decode scratch
   DevBuf decFrames_, decTables_, decLists_, decCounters_, decLits_, decSeqs_, roundN_;

@@ -64,6 +64,20 @@ struct ZraDecFrame {
 // one random-access slice: `len` bytes at `srcOff` inside decoded frame job `job` go to raOut + dstOff
 struct ZraRaPiece { uint64_t dstOff; uint32_t srcOff, len; };
 
+// planner scratch of one random-access batch (zra_ra.hip; the archive handle counts its misses into it): four arrays of one word per
+// frame of the archive, then kTotalsWords words of totals — one zeroed allocation of words(nFrames) words
+struct RaPlan {
+  uint32_t* cnt;             // [nFrames] slices that touch the frame
+  uint32_t* need;            // [nFrames] bytes of the frame the batch needs (max over its slices of the slice end)
+  uint32_t* slot;            // [nFrames] dense number of the frame among the touched ones
+  uint32_t* cursor;          // [nFrames] fill cursor of the frame's slice list
+  uint32_t* totals;          // {touched frames, slices}
+  static constexpr size_t kTotalsWords = 16;
+  static size_t words(uint32_t nFrames) { return 4 * (size_t)nFrames + kTotalsWords; }
+  static RaPlan over(uint32_t* p, uint32_t n) { return RaPlan{p, p + n, p + 2 * (size_t)n, p + 3 * (size_t)n, p + 4 * (size_t)n}; }
+  uint32_t* lookup_words() const { return totals + 8; }   // free for the archive handle: {distinct missed frames, distinct hit frames}
+};
+
 struct ZraDecodeArgs {
   const uint8_t* body;       // compressed bytes (all frames)
   uint64_t bodySize;         // readable bytes at body

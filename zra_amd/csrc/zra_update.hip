@@ -16,7 +16,7 @@
 //      lowest failing frame), and the packed encoded frames are in frame order (one scan gives their places).
 //  (b) the patch kernel of a pass runs behind the pass's decode and before its encode: new bytes win over decoded ones.
 //  (c) nothing is written to dOut before every size is known and every check has passed: a refused update leaves dOut alone.
-#include "zra_engine.h"
+#include "zra_host.h"
 #include "zra_dev.h"
 #include "zra_format.h"
 #include <algorithm>
@@ -251,8 +251,6 @@ extern "C" __global__ void __launch_bounds__(256) zra_upd_gather_kernel(const u6
 // =================================================================================================
 namespace zra_eng {
 
-#define UCHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return zerr(1); } } while (0)
-
 struct UpdateImpl {
   static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
                     const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
@@ -273,7 +271,7 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   if (!outSize || !dOut || (!dArc && arcSize) || (nw && (!hOff || !hSize || !hDataOff)) || (!dAppend && appendSize)) return zerr(42);
   if (!dData) for (size_t i = 0; i < nw; i++) if (hSize[i]) return zerr(42);
   if (outCap && arcSize && (uintptr_t)dOut < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dOut + outCap) return zerr(42);
-  UCHK(hipSetDevice(E.device_));
+  HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   // ---- 3. header: the statuses of ZraHipArchiveOpen; beyond them a frame size of 0 and a table that does not cover the content
   // (an open handle refuses every read of such an archive; here there is no frame to put a byte in)
@@ -305,16 +303,8 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   // the tuples, sorted by offset, in page-locked memory and from there to the device in chunks (ra_walk_queries' idiom)
   uint64_t nSlices = 0;
   if (nT) {
-    if (E.pinQCap_ < 4 * nT) {
-      if (E.pinQ_) (void)hipHostFree(E.pinQ_);
-      E.pinQ_ = nullptr; E.pinQCap_ = 0;
-      void* pq = nullptr;
-      const size_t cap = std::max<size_t>(4 * nT, 4096);
-      if (hipHostMalloc(&pq, cap * 8 + 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return zerr(64); }
-      E.pinQ_ = (uint64_t*)pq; E.pinQCap_ = cap;
-    }
-    if (!E.qmeta_.reserve(4 * nT * 8 + 64)) return zerr(64);
-    uint64_t* const hq = E.pinQ_;
+    uint64_t* const hq = E.pinned_tuples(nT);
+    if (!hq || !E.qmeta_.reserve(4 * nT * 8 + 64)) return zerr(64);
     constexpr size_t kChunk = 1u << 17;
     for (size_t q0 = 0; q0 < nT; q0 += kChunk) {
       const size_t q1 = std::min(nT, q0 + kChunk);
@@ -323,7 +313,7 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
         hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = q < nData ? hDataOff[idx[q]] : 0; hq[4 * q + 3] = nSlices;
         nSlices += (o + z - 1) / fs - o / fs + 1;
       }
-      UCHK(hipMemcpyAsync(E.qmeta_.as<uint64_t>() + 4 * q0, hq + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, s));
+      HIPCHK_CLR(hipMemcpyAsync(E.qmeta_.as<uint64_t>() + 4 * q0, hq + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, s));
     }
   }
   const uint64_t* dq = E.qmeta_.as<uint64_t>();
@@ -342,17 +332,17 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   const uint8_t* oldTable = dArc + h.seekTableOffset;
   const uint8_t* oldBody = dArc + h.size;
   const uint64_t bodyBytes = arcSize - h.size;
-  UCHK(hipMemsetAsync(cover, 0, planWords * 4, s));
+  HIPCHK_CLR(hipMemsetAsync(cover, 0, planWords * 4, s));
   if (nSlices)
     hipLaunchKernelGGL(zra_upd_mark_kernel, dim3((uint32_t)((nSlices + 255) / 256)), dim3(256), 0, s, dq, (u32)nT, (u64)nSlices, (u64)fs, cover);
   uint32_t hTotals[3] = {0, 0, 0};
   if (F2) {
     hipLaunchKernelGGL(zra_upd_plan_kernel, dim3(1), dim3(1024), 0, s, cover, F2, F, oldTable, (u64)bodyBytes, (u64)fs, (u64)U, (u64)U2, passSlots, slotOf,
                        E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), passJob, totals);
-    UCHK(hipMemcpyAsync(hTotals, totals, 12, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipMemcpyAsync(hTotals, totals, 12, hipMemcpyDeviceToHost, s));
   }
-  UCHK(hipStreamSynchronize(s));
-  UCHK(hipGetLastError());
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
   // ---- 5. the old seek table over the frames carried over
   if (hTotals[2]) return zerr(20);
   const uint32_t touched = hTotals[0], jobs = hTotals[1];
@@ -361,8 +351,8 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   uint64_t encoded = 0;
   if (touched) {
     std::vector<uint32_t> hPassJob(passes + 1);
-    UCHK(hipMemcpyAsync(hPassJob.data(), passJob, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
-    UCHK(hipStreamSynchronize(s));
+    HIPCHK_CLR(hipMemcpyAsync(hPassJob.data(), passJob, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
     const uint64_t bound = zra_fmt::compress_bound(fs);
     if (!E.upd_.stage.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64) || !E.upd_.packed.reserve((size_t)touched * bound + 64) ||
         !E.upd_.encSizes.reserve((size_t)touched * 8 + 64))
@@ -400,11 +390,11 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   const uint64_t headerSize = zra_fmt::kFixedSize + (uint64_t)metaSize + tableBytes;
   if (headerSize > 0xFFFFFFFFull) return {kCompressedTooLarge, 0};
   std::vector<uint8_t> hdr((size_t)headerSize);
-  UCHK(hipMemcpyAsync(hTot, sums + 2 * (size_t)nBlocks, 16, hipMemcpyDeviceToHost, s));
-  if (metaSize) UCHK(hipMemcpyAsync(hdr.data() + zra_fmt::kFixedSize, dArc + zra_fmt::kFixedSize, metaSize, hipMemcpyDeviceToHost, s));
-  UCHK(hipMemcpyAsync(hdr.data() + zra_fmt::kFixedSize + metaSize, E.upd_.table.p, tableBytes, hipMemcpyDeviceToHost, s));
-  UCHK(hipStreamSynchronize(s));
-  UCHK(hipGetLastError());
+  HIPCHK_CLR(hipMemcpyAsync(hTot, sums + 2 * (size_t)nBlocks, 16, hipMemcpyDeviceToHost, s));
+  if (metaSize) HIPCHK_CLR(hipMemcpyAsync(hdr.data() + zra_fmt::kFixedSize, dArc + zra_fmt::kFixedSize, metaSize, hipMemcpyDeviceToHost, s));
+  HIPCHK_CLR(hipMemcpyAsync(hdr.data() + zra_fmt::kFixedSize + metaSize, E.upd_.table.p, tableBytes, hipMemcpyDeviceToHost, s));
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
   const uint64_t body = hTot[0];
   // ---- 7. size limit (compress_device's rule, zra.cpp:227), 8. capacity
   if (headerSize + body >= zra_fmt::kMaxCompressedSize) return {kCompressedTooLarge, 0};
@@ -413,19 +403,19 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   zra_fmt::write_fixed(hdr.data(), U2, F2 + 1, (uint32_t)fs, (uint32_t)metaSize);
   zra_fmt::wr32(hdr.data() + 14, zra_fmt::header_hash(hdr.data(), hdr.data() + zra_fmt::kFixedSize));
   // ---- gather
-  UCHK(hipMemcpyAsync(dOut, hdr.data(), (size_t)headerSize, hipMemcpyHostToDevice, s));
+  HIPCHK_CLR(hipMemcpyAsync(dOut, hdr.data(), (size_t)headerSize, hipMemcpyHostToDevice, s));
   // (ZraHipLastKernelMs after an update: the gather, the call's bandwidth kernel)
   E.lastKernelMs_ = 0;
   const bool gather = body && F2;
   if (gather) {
     const uint64_t nChunks = (body + kGatherChunk - 1) / kGatherChunk;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((nChunks + 3) / 4, kGatherGrid);
-    UCHK(hipEventRecord(E.ev0_, s));
+    HIPCHK_CLR(hipEventRecord(E.ev0_, s));
     hipLaunchKernelGGL(zra_upd_gather_kernel, dim3(grid), dim3(256), 0, s, newOff, disp, F2, (u64)body, dOut + headerSize);
-    UCHK(hipEventRecord(E.ev1_, s));
+    HIPCHK_CLR(hipEventRecord(E.ev1_, s));
   }
-  UCHK(hipStreamSynchronize(s));
-  UCHK(hipGetLastError());
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
   if (gather) { float ms = 0; if (hipEventElapsedTime(&ms, E.ev0_, E.ev1_) == hipSuccess) E.lastKernelMs_ = ms; else (void)hipGetLastError(); }
   const uint64_t st8[8] = {F2, touched, jobs, touched, body - encoded, encoded, written, passes};
   for (int i = 0; i < 8; i++) E.ustats_[i] = st8[i];
