@@ -129,7 +129,7 @@ ZRA_EXPORT void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* ou
  *    checksum, exactly as ZraHipCompressBuffer encodes a frame of that content: at the level and checksum flag the archive was written
  *    with, the result is byte-identical (header, table and CRC-32 included) to ZraHipCompressBuffer of the patched content.
  *  - Every other frame's compressed bytes are CARRIED OVER unchanged. They are neither decoded nor verified: damage in an untouched
- *    frame survives the update, exactly as it was.
+ *    frame survives the update, exactly as it was (ZraHipVerifyArchive below finds it).
  *  - A touched frame that keeps some of its old bytes is first decoded whole and its content checksum verified (an update does not
  *    launder damage); a touched frame whose every byte is replaced is not decoded at all.
  *  - Header: the 38 fixed bytes are rewritten (U', the new table size), the meta section of a streaming-Compressor archive is copied
@@ -163,6 +163,66 @@ ZRA_EXPORT ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArch
  *  out8 = {frames in the result, frames touched, frames decoded, frames compressed, compressed bytes carried over, compressed bytes
  *  newly encoded, content bytes replaced or appended, decode / encode passes}. Counters, not timings. */
 ZRA_EXPORT void ZraHipGetUpdateStats(ZraHipEngine* engine, uint64_t* out8);
+
+/* ---- verify: every faulty frame of a device-resident archive, without an output buffer ----
+ * The counterpart of `zstd -t` for an archive that lives in HBM through many updates. ZraHipDecompressBuffer needs room for the whole
+ * content and stops at the first failing frame; this call needs a bounded staging window and reports every bad frame. */
+#define ZRA_HIP_VERIFY_STRUCTURE 1u   /* header, CRC-32, seek table, every frame's zstd frame header and block-header walk; nothing decoded */
+#define ZRA_HIP_VERIFY_CONTENT   2u   /* the above, then every structurally sound frame decoded whole, content checksum verified */
+
+/** One faulty frame. code: zstd error code; stage: the ZRA_HIP_VERIFY_* bit that found it. */
+typedef struct ZraHipFrameFault { uint64_t frame; uint32_t code; uint32_t stage; } ZraHipFrameFault;
+
+/** Checks frames [firstFrame, firstFrame + frameCount) of the archive at dArchive (archiveSize bytes, device memory); frameCount =
+ *  UINT64_MAX: to the last frame. Synchronous; stream ordering as the other compute calls (ZraHipWaitStream). The archive is only read.
+ *  Result:
+ *  - Success whenever the verification ran, however many frames are bad: bad frames are data, not a failure of the call.
+ *  - *nFaults = the faulty frames of the range; it may exceed faultCapacity. The first min(*nFaults, faultCapacity) of them are written
+ *    to hFaults (a HOST array) in ascending frame order, at most one entry per frame. hFaults may be NULL when faultCapacity is 0.
+ *  - On any status other than Success nothing is written to hFaults and *nFaults is 0.
+ *  Statuses, checked in this order:
+ *   1. engine or nFaults NULL; dArchive NULL with archiveSize != 0; hFaults NULL with faultCapacity != 0; mode 0 or with bits other than
+ *      the two above -> {ZStdError, 42}.
+ *   2. Header problems: the statuses of ZraHipArchiveOpen.
+ *   3. The stored header CRC-32 differs from the one computed over the header as it lies on the device (fixed part, meta section, seek
+ *      table) -> HeaderInvalid, the status of the host-pointer option ZRA_HIP_OPT_VERIFY_HEADER_CRC. The header travels to the host
+ *      once for this, 5 bytes per frame; no other byte of the archive leaves the device.
+ *   4. firstFrame > frames, or frameCount != UINT64_MAX and firstFrame + frameCount > frames -> OutOfBoundsAccess. An empty range is
+ *      Success with 0 faults.
+ *   5. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's (ZraHipReleaseScratch returns it): 28 bytes of
+ *      tables per frame of the RANGE, 16 bytes per listed fault, the staging window, the decoder's own scratch for one pass.
+ *  STRUCTURE stage (always): one lane per frame, nothing decoded; it reads the frame's two table entries, its frame header and three
+ *  bytes per block. With [a, b) = the frame's seek-table span and n = b - a, the first rule of this table that holds gives the code:
+ *      b < a, or b > body size                                                              72  (the span convention of the decoder)
+ *      the archive's last frame: b != body size                                             72
+ *      n < 9, n >= 4 GiB, or n < frame header size + 3                                      72
+ *      magic != 0xFD2FB528                                                                  10
+ *      reserved bit of the frame header descriptor set                                      14
+ *      window descriptor with a window log above 31 (frames without Single_Segment)         16
+ *      a dictionary id other than 0                                                         32
+ *      a declared Frame_Content_Size != min(frameSize, uncompressedSize - frame * frameSize): larger 70, smaller 20
+ *      block walk from the end of the frame header, a 3-byte block header at a time (raw and compressed blocks advance by
+ *      Block_Size, RLE blocks by 1), up to and including the block with Last_Block set:
+ *        fewer than 3 bytes left for a block header                                         72
+ *        reserved block type 3                                                              20
+ *        a block body running past the span                                                 72
+ *      the end of the last block, plus 4 when the checksum flag is set, != n                72
+ *  These are the decoder's own rules, restated (a frame flagged here also fails when it is decoded); the decoder may name another
+ *  code for the same frame where it meets a second problem first.
+ *  CONTENT stage (only with ZRA_HIP_VERIFY_CONTENT): the frames of the range that passed the structure stage — the others are not
+ *  decoded — are decoded whole, in frame order, into a staging window of stagingBytes (0: min(65,536 frames, 4 GiB), the update's
+ *  bound) in passes of max(1, min(65,536, stagingBytes / frameSize)) frames, and their content checksums are verified. A frame's code is
+ *  the one ZraHipDecompressRABatch gives under ZRA_HIP_OPT_RA_WHOLE_FRAMES for a query inside it (a frame that regenerates another size
+ *  than its slot: 20). A failing frame does not disturb another frame of its pass. After each pass the per-frame statuses are compacted
+ *  into the fault list on the device, in order; the list comes to the host once, at the end.
+ *  Not covered: the shards of a distributed archive (ZraHipShard), repair, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipVerifyArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t mode,
+                                         uint64_t firstFrame, uint64_t frameCount, size_t stagingBytes,
+                                         ZraHipFrameFault* hFaults, size_t faultCapacity, size_t* nFaults);
+/** The last ZraHipVerifyArchive on the engine (all zero after any outcome other than Success; engine NULL: all zero):
+ *  out8 = {frames in the archive, frames checked, structure faults, content faults, frames decoded, content bytes regenerated, decode
+ *  passes, 0}. Counters, not timings. */
+ZRA_EXPORT void ZraHipGetVerifyStats(ZraHipEngine* engine, uint64_t* out8);
 
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody

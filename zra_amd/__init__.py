@@ -40,6 +40,13 @@ class ZraHipSlice(ctypes.Structure):
     _fields_ = [("owner", ctypes.c_uint32), ("query", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("size", ctypes.c_uint64), ("within", ctypes.c_uint64)]
 
 
+class ZraHipFrameFault(ctypes.Structure):
+    """include/zra_hip.h: one faulty frame of ZraHipVerifyArchive"""
+    _fields_ = [("frame", ctypes.c_uint64), ("code", ctypes.c_uint32), ("stage", ctypes.c_uint32)]
+
+
+VERIFY_STRUCTURE, VERIFY_CONTENT = 1, 2      # ZRA_HIP_VERIFY_*
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t))
@@ -127,6 +134,9 @@ def load():
         # update
         "ZraHipUpdateArchive": (S, [vp, vp, sz, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
         "ZraHipGetUpdateStats": (None, [vp, u64p]),
+        # verify
+        "ZraHipVerifyArchive": (S, [vp, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipFrameFault), sz, szp]),
+        "ZraHipGetVerifyStats": (None, [vp, u64p]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -171,7 +181,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCommCompress", "ZraHipCommStitchSizes", "ZraHipShardDestroy", "ZraHipShardHeaderSize", "ZraHipShardGetHeader", "ZraHipShardArchiveSize", "ZraHipShardGetBody",
                    "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe",
                    "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
-                   "ZraHipUpdateArchive", "ZraHipGetUpdateStats"]
+                   "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats"]
 
 
 def _chk(st, what=""):
@@ -360,11 +370,32 @@ class Engine:
         self.L.ZraHipGetUpdateStats(self.h, a)
         return dict(zip(UPDATE_STATS, (int(v) for v in a)))
 
+    def verify(self, d_archive, size, *, content=True, first_frame=0, frame_count=None, staging_bytes=0, max_faults=1 << 16):
+        """ZraHipVerifyArchive over frames [first_frame, first_frame + frame_count) (None: to the end) of the archive at d_archive:
+        header CRC-32, seek table and block walk of every frame, and with `content` every sound frame decoded and its checksum verified.
+        Returns (n_faults, [(frame, code, stage), ...]): every faulty frame is counted, the first max_faults are listed, in frame order.
+        Faulty frames are data; ZraError is a call that could not verify (bad header, range outside the archive, no memory)."""
+        arr = (ZraHipFrameFault * max_faults)() if max_faults else None
+        n = ctypes.c_size_t(0)
+        self._order()
+        _chk(self.L.ZraHipVerifyArchive(self.h, d_archive or None, size, VERIFY_CONTENT if content else VERIFY_STRUCTURE, first_frame,
+                                        (1 << 64) - 1 if frame_count is None else frame_count, staging_bytes, arr, max_faults, ctypes.byref(n)),
+             "ZraHipVerifyArchive")
+        return n.value, [(int(arr[i].frame), int(arr[i].code), int(arr[i].stage)) for i in range(min(n.value, max_faults))]
+
+    def verify_stats(self):
+        """Counters of the last verify() on this engine (all zero unless it succeeded), keyed by VERIFY_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetVerifyStats(self.h, a)
+        return dict(zip(VERIFY_STATS, (int(v) for v in a[:7])))
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
 
 UPDATE_STATS = ("frames", "touched", "decoded", "compressed", "carried_bytes", "encoded_bytes", "content_bytes", "passes")
+
+VERIFY_STATS = ("frames", "checked", "structure_faults", "content_faults", "decoded", "content_bytes", "passes")
 
 
 class Archive:

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzra_amd.so")
 RESOURCES = os.path.join(HERE, "build", "kernel_resources.json")     # per kernel: VGPRs, scratch, spills, occupancy (from the compiler's remarks)
-SOURCES = ["zra_decode.hip", "zra_encode_mf.hip", "zra_encode_ent.hip", "zra_encode.hip", "zra_engine.hip", "zra_ra.hip", "zra_archive.hip", "zra_update.hip", "zra_hostpipe.hip", "zra_comm.hip", "zra_capi.cpp"]
+SOURCES = ["zra_decode.hip", "zra_encode_mf.hip", "zra_encode_ent.hip", "zra_encode.hip", "zra_engine.hip", "zra_ra.hip", "zra_archive.hip", "zra_update.hip", "zra_verify.hip", "zra_hostpipe.hip", "zra_comm.hip", "zra_capi.cpp"]
 
 
 def needs_build():
@@ -67,8 +67,10 @@ def build(force=False, verbose=False):
     subprocess.check_call(link)
     # command-line counterpart of the reference's zratool (C++ API consumer)
     tool = os.path.join(HERE, "tools", "zratool_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I" + os.path.join(HERE, "..", "include"), os.path.join(HERE, "tools", "zratool_amd.cpp"),
-                           "-o", tool, "-L" + HERE, "-lzra_amd", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"])
+    # (its mode `t` holds the archive in device memory: the HIP runtime's C API, no device code)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(HERE, "..", "include"), "-I/opt/rocm/include",
+                           os.path.join(HERE, "tools", "zratool_amd.cpp"), "-o", tool, "-L" + HERE, "-lzra_amd", "-L/opt/rocm/lib", "-lamdhip64",
+                           "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"])
     return LIB
 
 

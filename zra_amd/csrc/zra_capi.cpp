@@ -744,6 +744,16 @@ void ZraHipGetUpdateStats(ZraHipEngine* engine, uint64_t* out8) {
   if (!out8) return;
   if (engine) engine->e->update_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
+ZraStatus ZraHipVerifyArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t mode, uint64_t firstFrame, uint64_t frameCount,
+                              size_t stagingBytes, ZraHipFrameFault* hFaults, size_t faultCapacity, size_t* nFaults) {
+  if (nFaults) *nFaults = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->verify_archive((const uint8_t*)dArchive, archiveSize, mode, firstFrame, frameCount, stagingBytes, hFaults, faultCapacity, nFaults));
+}
+void ZraHipGetVerifyStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->verify_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

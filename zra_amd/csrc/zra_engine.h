@@ -76,6 +76,10 @@ class Engine {
   Status decode_launch(const struct ZraDecodeArgs& a, const uint32_t* dExpect, uint32_t maxFrameBytes, uint32_t jobBase, unsigned long long* hResult);
   // the same for few jobs: one launch (zra_ra_small_kernel), one synchronisation; *bailed = jobs that need decode_launch after all
   Status decode_small(const struct ZraDecodeArgs& a, const uint32_t* dExpect, uint32_t maxFrameBytes, uint32_t jobBase, unsigned long long* hResult, uint32_t* bailed);
+  // one pass of decode_jobs over the jobs of `b` (at most one pass's worth): decode_small when they are few, decode_launch when they are
+  // many or the small kernel handed one back. result_ must hold ~0 words (decode_jobs' memset). Afterwards status_ / produced_ hold every
+  // job's own status and regenerated size, whatever *res says: what the verifier collects (zra_verify.hip).
+  Status decode_pass(const struct ZraDecodeArgs& b, const uint32_t* dExpect, uint32_t maxFrameBytes, uint32_t jobBase, unsigned long long* res);
   Status decode_scratch(struct ZraDecodeArgs& a, uint32_t maxFrameBytes);
   // Whole archive resident on the device (header + body), output on the device.
   Status decompress_device(const uint8_t* dArc, size_t arcSize, uint8_t* dOut, size_t outCap);
@@ -122,6 +126,15 @@ class Engine {
   // what the last update_archive did: {frames, touched, decoded, compressed, bytes carried, bytes encoded, content bytes written, passes};
   // all zero unless it succeeded
   void update_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = ustats_[i]; }
+
+  // ---- verify (zra_verify.hip): header CRC-32, seek table and every frame's block walk of frames [first, first + count) of the archive
+  // at dArc, then (content) every structurally sound frame decoded whole into a staging window, checksum verified. Every faulty frame is
+  // reported, in frame order. Statuses, codes and their order: zra_hip.h, ZraHipVerifyArchive. hFaults: ZraHipFrameFault's layout.
+  Status verify_archive(const uint8_t* dArc, size_t arcSize, uint32_t mode, uint64_t first, uint64_t count, size_t stagingBytes,
+                        void* hFaults, size_t faultCap, size_t* nFaults);
+  // the last verify_archive: {frames, checked, structure faults, content faults, decoded, content bytes regenerated, passes, 0}; all zero
+  // unless it succeeded
+  void verify_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = vstats_[i]; }
 
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
@@ -196,8 +209,13 @@ class Engine {
   struct UpdScratch { DevBuf plan, stage, packed, encSizes, frames, table; };
   UpdScratch upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the staging window of one decode pass, the fault list
+  struct VerifyScratch { DevBuf plan, stage, faults; };
+  VerifyScratch vfy_;
+  uint64_t vstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
+  friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

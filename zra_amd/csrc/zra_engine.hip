@@ -161,6 +161,7 @@ void Engine::free_scratch() {
     b->release();
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
   for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table}) b->release();
+  for (DevBuf* b : {&vfy_.plan, &vfy_.stage, &vfy_.faults}) b->release();
 }
 
 Status Engine::release_scratch() {
@@ -426,6 +427,22 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
   return ok();
 }
 
+// One pass of decode_jobs. Few jobs: the one-launch kernel (latency path); a job it hands back (damaged / unusual frame) sends the pass
+// through the four-kernel pipeline, where every status of the reference is reproduced.
+Status Engine::decode_pass(const ZraDecodeArgs& b, const uint32_t* dExpect, uint32_t maxFrameBytes, uint32_t jobBase, unsigned long long* res) {
+  static const uint32_t smallMax = (uint32_t)zra_env::env_int("ZRA_DEC_SMALL_MAX", 1024);
+  if (b.nFrames <= smallMax) {
+    uint32_t bailed = 0;
+    unsigned long long r2 = *res;
+    Status st = decode_small(b, dExpect, maxFrameBytes, jobBase, &r2, &bailed);
+    if (st.zra) return st;
+    if (!bailed) { *res = r2; return ok(); }
+    if (*res == ~0ull) HIPCHK(hipMemsetAsync(result_.p, 0xFF, 64, stream_));   // (what the handed-back pass left in the result word)
+    else { unsigned long long keep = *res; HIPCHK(hipMemsetAsync(result_.p, 0xFF, 64, stream_)); HIPCHK(hipMemcpyAsync(result_.p, &keep, 8, hipMemcpyHostToDevice, stream_)); HIPCHK(hipStreamSynchronize(stream_)); }
+  }
+  return decode_launch(b, dExpect, maxFrameBytes, jobBase, res);
+}
+
 // seqTotal == 0: every frame owns its slot (random access: the reference decodes the touched frames into frameSize buffers).
 // seqTotal != 0: whole-archive semantics of ONE multi-frame zstd call over `seqTotal` bytes of destination (zra.cpp:249): frames are
 // decoded side by side into their nominal slots; if one regenerates another size than its slot (only possible for a corrupted or
@@ -458,23 +475,8 @@ Status Engine::decode_jobs(const uint8_t* dBody, uint64_t bodySize, const uint64
     b.nFrames = std::min(passFrames, nFrames - p0);
     b.frameOff = dFrameOff + (size_t)p0 * offStride; b.outOff = dOutOff + p0; b.outCap = dExpect + p0;
     if (ra) { if (ra->limit) b.limit = ra->limit + p0; if (ra->pieceBase) b.pieceBase = ra->pieceBase + p0; }
-    // few jobs: the one-launch kernel (latency path); a job it hands back (damaged / unusual frame) sends the pass through the
-    // four-kernel pipeline, where every status of the reference is reproduced
-    static const uint32_t smallMax = (uint32_t)zra_env::env_int("ZRA_DEC_SMALL_MAX", 1024);
-    bool done = false;
-    if (b.nFrames <= smallMax) {
-      uint32_t bailed = 0;
-      unsigned long long r2 = res;
-      Status st = decode_small(b, dExpect + p0, maxFrameBytes, p0, &r2, &bailed);
-      if (st.zra) return st;
-      if (!bailed) { res = r2; done = true; }
-      else if (res == ~0ull) HIPCHK(hipMemsetAsync(result_.p, 0xFF, 64, stream_));   // (what the handed-back pass left in the result word)
-      else { unsigned long long keep = res; HIPCHK(hipMemsetAsync(result_.p, 0xFF, 64, stream_)); HIPCHK(hipMemcpyAsync(result_.p, &keep, 8, hipMemcpyHostToDevice, stream_)); HIPCHK(hipStreamSynchronize(stream_)); }
-    }
-    if (!done) {
-      Status st = decode_launch(b, dExpect + p0, maxFrameBytes, p0, &res);
-      if (st.zra) return st;
-    }
+    Status st = decode_pass(b, dExpect + p0, maxFrameBytes, p0, &res);
+    if (st.zra) return st;
   }
   if (res == ~0ull) return ok();
   const uint32_t code = (uint32_t)(res & 0xFF), first = (uint32_t)(res >> 8);

@@ -8,6 +8,11 @@ using namespace zra_dev;
 
 namespace {
 
+// whole-frame jobs carry no limit. A limit of `expect` would stop the decoder as soon as that many bytes exist: before the frame end of
+// a frame whose last block does not say it is the last, and before the frame-end checks (a stopped frame has none). The frame's room
+// is its capacity, outCap.
+constexpr u32 kNoLimit = 0xFFFFFFFFu;
+
 // the jobs are built from the query arrays and the archive's own seek table (zra.cpp:265-269 per query: first frame, frames touched, head skip, tail length)
 // pass 1: every query marks the frames it touches
 __global__ void zra_ra_count_kernel(const u64* q, u32 nq, u64 fs, RaPlan P) {
@@ -59,7 +64,7 @@ __global__ void __launch_bounds__(1024) zra_ra_plan_kernel(RaPlan P, u32 nFrames
     // (victim: the archive handle's arena slots, zra_archive.hip — job st of a pass decodes into slot victim[st % passSlots])
     outOff[st] = (u64)(victim ? victim[st % passSlots] : st % passSlots) * fs;
     outCap[st] = expect;
-    limit[st] = fullFrames ? expect : min(P.need[f], expect);
+    limit[st] = fullFrames ? kNoLimit : min(P.need[f], expect);
     pieceBase[st] = sp;
     st++; sp += c;
   }
@@ -106,7 +111,7 @@ __global__ void zra_ra_direct_kernel(const u64* q, u32 nq, u32 nPieces, u64 fs, 
     const u64 len = min<u64>(fs - srcOff, size - done);
     outOff[st] = (u64)st * fs;
     outCap[st] = expect;
-    limit[st] = fullFrames ? expect : min((u32)(srcOff + len), expect);
+    limit[st] = fullFrames ? kNoLimit : min((u32)(srcOff + len), expect);
     pieceBase[st] = st;
     ZraRaPiece pc; pc.dstOff = dst + done; pc.srcOff = srcOff; pc.len = (u32)len;
     pieces[st] = pc;

@@ -5,8 +5,13 @@
 //   d   : streaming decompress (FullDecompressor)
 //   imc : in-memory CompressBuffer          imd : in-memory DecompressBuffer
 //   b   : benchmark of all four + one random-access query with a memcmp check
+// and one mode of its own, against include/zra_hip.h:
+//   t   : test an archive like `zstd -t` (ZraHipVerifyArchive, content verification on the device); one line per faulty frame and a
+//         summary; exit status 0 clean, 1 faults, 2 the call failed
 #include <zra.hpp>
 #include <zra.h>
+#include <zra_hip.h>
+#include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <chrono>
@@ -86,6 +91,35 @@ std::string remove_extension(std::string name) {
   if (pos != std::string::npos && name.substr(pos) == ".zra") return name.substr(0, pos);
   return name;
 }
+
+// mode t: the file goes to device memory as it is, the verification runs there
+int test_archive(const char* path) {
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!arc.empty() && (hipMalloc(&dArc, arc.size()) != hipSuccess || hipMemcpy(dArc, arc.data(), arc.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+    std::fprintf(stderr, "%s: no device memory for %zu bytes\n", path, arc.size());
+    if (dArc) (void)hipFree(dArc);
+    ZraHipDestroyEngine(eng);
+    return 2;
+  }
+  std::vector<ZraHipFrameFault> faults(1u << 16);
+  size_t n = 0;
+  st = ZraHipVerifyArchive(eng, dArc, arc.size(), ZRA_HIP_VERIFY_CONTENT, 0, UINT64_MAX, 0, faults.data(), faults.size(), &n);
+  uint64_t s8[8] = {0};
+  ZraHipGetVerifyStats(eng, s8);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot verify: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min(n, faults.size()); i++)
+    std::printf("frame %llu: zstd error %u (%s)\n", (unsigned long long)faults[i].frame, faults[i].code,
+                faults[i].stage == ZRA_HIP_VERIFY_STRUCTURE ? "structure" : "content");
+  if (n > faults.size()) std::printf("... and %zu more\n", n - faults.size());
+  std::printf("%s: %llu frames, %llu decoded, %zu faulty: %s\n", path, (unsigned long long)s8[1], (unsigned long long)s8[4], n, n ? "DAMAGED" : "ok");
+  return n ? 1 : 0;
+}
 }  // namespace
 
 // argv of the reference tool, position by position (zratool.cpp:98-125,213-221):
@@ -94,6 +128,7 @@ std::string remove_extension(std::string name) {
 //   d   {file} {stream buffer MB = 10}                                       -> {file} without ".zra"
 //   imd {file}                                                               -> {file} without ".zra"
 //   b   {file} {level} {frameSize} {stream buffer MB} {offset = 0x1000} {size = 0x10000}
+// ours: t {file}
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::printf("%s {mode} {file} ...\n"
@@ -101,11 +136,13 @@ int main(int argc, char** argv) {
                 "imc  {file} {compression level = 3} {frame size = 16384} - In-memory Compression\n"
                 "d {file} {stream buffer size = 10MB} - Streaming Decompression\n"
                 "imd  {file} - In-memory Decompression\n"
-                "b  {file} {compression level = 3} {frame size = 16384} {stream buffer size = 10MB} {offset = 0x1000} {size = 0x10000} - Benchmark (Memory Intensive)\n",
+                "b  {file} {compression level = 3} {frame size = 16384} {stream buffer size = 10MB} {offset = 0x1000} {size = 0x10000} - Benchmark (Memory Intensive)\n"
+                "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n",
                 argv[0]);
     return 0;
   }
   const std::string mode = argv[1];
+  if (mode == "t") return test_archive(argv[2]);
   const bool comp = mode == "c" || mode == "imc" || mode == "b";
   const zra::i8 level = comp && argc > 3 ? (zra::i8)std::atoi(argv[3]) : 0;
   const zra::u32 frameSize = comp && argc > 4 ? (zra::u32)std::strtoul(argv[4], nullptr, 10) : 16384;
