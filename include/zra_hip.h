@@ -113,6 +113,39 @@ ZRA_EXPORT ZraStatus ZraHipArchiveDropCache(ZraHipArchive* archive);
 /** out8 = {cache slots, frames resident now, reads accepted, frame hits, frame misses (= frames decoded), evictions,
  *  uncompressed size, frame size}; counters 2-5 are cumulative since the handle was opened. */
 ZRA_EXPORT void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8);
+/** ZraHipUpdateArchive (below) through the handle: the archive the handle is bound to is updated into dOut, the handle is bound to the
+ *  result, and its cache stays coherent and warm. Synchronous; stream ordering as the other compute calls (ZraHipWaitStream).
+ *  - Result: dOut and *outSize are byte for byte what ZraHipUpdateArchive(the handle's engine, the bytes the handle is bound to, the same
+ *    arguments) writes, with its statuses 1-9 in its order. Two checks come in front: archive NULL -> {ZStdError, 42}; and, joined to
+ *    check 2, [dOut, dOut + outCapacity) overlapping the handle's arena -> {ZStdError, 42}. Header problems cannot occur beyond those
+ *    a handle can be opened with (a frame size of 0: HeaderInvalid): the handle holds a checked header, which is not read again.
+ *  - Re-binding: on Success the handle serves the archive at dOut (*outSize bytes, U' and F'). The buffer it was bound to before is no
+ *    longer referenced: the caller may free it, or pass it as dOut of the next update (ping-pong). The new bytes must stay valid and
+ *    unchanged until close, the rule of ZraHipArchiveOpen. The header the handle keeps is built from the host copy the update wrote.
+ *  - Failure: on every refusal (statuses 1-9 of ZraHipUpdateArchive and the two checks above) nothing has changed: dOut is untouched,
+ *    the handle is bound as before, and every resident frame, reference bit, the hand and all counters are as before. When F' exceeds
+ *    what the frame table of the cache holds, a larger one (with headroom for further appends) is allocated behind check 4 and swapped
+ *    in on Success; if it cannot be had -> {ZStdError, 64}. The one exception is a HIP runtime error ({ZStdError, 1}) behind check 8,
+ *    while the result is being written: dOut and the touched resident frames are then undefined and the handle is still bound to the
+ *    old archive; close it, or ZraHipArchiveDropCache before reading on.
+ *  - Cache (at least 1 slot; TOUCHED as in ZraHipUpdateArchive): an untouched resident frame stays resident in its slot. A touched frame
+ *    that keeps some old bytes and is resident is not decoded: its old plaintext is copied from the arena into the update's staging
+ *    (this launders no damage: a frame is resident only after a whole decode with status 0, checksum verified, exact size); one that
+ *    is not resident is decoded exactly as by ZraHipUpdateArchive. Every touched resident frame, one replaced whole included, stays
+ *    resident and its slot holds the new plaintext after the call; the old last frame grown by an append stays resident with its new
+ *    length. A touched frame that was not resident and every appended frame are not inserted. The update inserts and evicts nothing,
+ *    moves no hand and sets no reference bit: it is not a read. Slots and arena stay as opened. hits, misses, reads and evictions of
+ *    ZraHipArchiveGetStats do not change; uncompressed size becomes U'.
+ *  - 0 slots: ZraHipUpdateArchive plus the re-binding.
+ *  - ZraHipGetUpdateStats(engine) describes the call; "frames decoded" counts decode jobs, so not the frames staged from the cache. */
+ZRA_EXPORT ZraStatus ZraHipArchiveUpdate(ZraHipArchive* archive,
+    const void* dData, const uint64_t* hOffsets, const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites,
+    const void* dAppend, size_t appendSize,
+    void* dOut, size_t outCapacity, size_t* outSize, int8_t compressionLevel, bool checksum);
+/** out8 = {updates accepted, frames now, archive size now, frames staged from the cache in the last accepted update, resident frames
+ *  refreshed (holding new bytes) in it, frames staged (cumulative), frames refreshed (cumulative), 0}. Refreshed >= staged: a resident
+ *  frame replaced whole is refreshed, not staged. archive NULL: all zero; out8 NULL: no-op. */
+ZRA_EXPORT void ZraHipArchiveGetUpdateStats(const ZraHipArchive* archive, uint64_t* out8);
 
 /* ---- update: a new archive from an old one, on the device ----
  * The reference's Compressor only ever starts from nothing. Frames are independent zstd frames tied together by the seek table alone,
@@ -153,7 +186,8 @@ ZRA_EXPORT void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* ou
  *   9. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's: plaintext staging of at most 65,536 frames or 4 GiB
  *      (more touched frames go through several decode / encode passes), the newly encoded frames, 29 bytes per frame of tables;
  *      ZraHipReleaseScratch returns it.
- *  An open ZraHipArchive handle requires unchanged archive bytes: update into a new buffer and open a new handle on it. */
+ *  An open ZraHipArchive handle requires unchanged archive bytes: update into a new buffer and open a new handle on it, or update
+ *  through the handle (ZraHipArchiveUpdate), which keeps its cache. */
 ZRA_EXPORT ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* dData, const uint64_t* hOffsets, const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites,
     const void* dAppend, size_t appendSize,
@@ -352,6 +386,10 @@ ZRA_EXPORT uint32_t ZraHipGetOptions(void);
 /** Bring-up aid (not a product entry point): the match finder's sequences {litLength | matchLength<<20 | offsetValue<<40} left in
  *  scratch for frame `frame` of the last compress call's last batch (last block of the frame); meta3 = {nbSeq, lastLL, skip}. */
 ZRA_EXPORT uint32_t ZraHipDebugReadSeqs(ZraHipEngine* engine, uint32_t frame, uint64_t* out, uint32_t cap, uint32_t* meta3);
+
+/** Bring-up aid (not a product entry point): HIP-event time (ms, on the engine's stream) of the stage-from-cache kernel launches of the
+ *  last ZraHipArchiveUpdate on this engine, summed over its passes; 0 when none ran. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugUpdateStageMs(ZraHipEngine* engine);
 
 #ifdef __cplusplus
 }

@@ -131,9 +131,12 @@ def load():
         "ZraHipArchiveRead": (S, [vp, vp, u64p, u64p, u64p, sz]),
         "ZraHipArchiveDropCache": (S, [vp]),
         "ZraHipArchiveGetStats": (None, [vp, u64p]),
+        "ZraHipArchiveUpdate": (S, [vp, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
+        "ZraHipArchiveGetUpdateStats": (None, [vp, u64p]),
         # update
         "ZraHipUpdateArchive": (S, [vp, vp, sz, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
         "ZraHipGetUpdateStats": (None, [vp, u64p]),
+        "ZraHipDebugUpdateStageMs": (ctypes.c_double, [vp]),
         # verify
         "ZraHipVerifyArchive": (S, [vp, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipFrameFault), sz, szp]),
         "ZraHipGetVerifyStats": (None, [vp, u64p]),
@@ -181,6 +184,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCommCompress", "ZraHipCommStitchSizes", "ZraHipShardDestroy", "ZraHipShardHeaderSize", "ZraHipShardGetHeader", "ZraHipShardArchiveSize", "ZraHipShardGetBody",
                    "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe",
                    "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
+                   "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats"]
 
 
@@ -392,6 +396,8 @@ class Engine:
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
+ARCHIVE_UPDATE_STATS = ("updates", "frames", "archive_bytes", "staged", "refreshed", "staged_total", "refreshed_total")
+
 
 UPDATE_STATS = ("frames", "touched", "decoded", "compressed", "carried_bytes", "encoded_bytes", "content_bytes", "passes")
 
@@ -401,7 +407,8 @@ VERIFY_STATS = ("frames", "checked", "structure_faults", "content_faults", "deco
 class Archive:
     """Archive handle (include/zra_hip.h: ZraHipArchive*): a device-resident archive opened once on `engine`, with a cache of whole
     decoded frames in an HBM arena of `cache_bytes` (0: no cache, reads are ZraHipDecompressRABatch). The archive's bytes must stay
-    valid and unchanged until close(). Keeps its Engine alive: the engine is not destroyed before the handle."""
+    valid and unchanged until close() or until update() binds the handle to its result. d_archive and size are the archive the handle
+    serves now. Keeps its Engine alive: the engine is not destroyed before the handle."""
 
     def __init__(self, engine, d_archive_ptr, size, cache_bytes=0):
         self.engine = engine
@@ -411,6 +418,7 @@ class Archive:
         engine._order()
         _chk(self.L.ZraHipArchiveOpen(engine.h, d_archive_ptr, size, cache_bytes, ctypes.byref(h)), "ZraHipArchiveOpen")
         self.h = h
+        self.d_archive, self.size = d_archive_ptr, size
 
     def read(self, d_out, offsets, sizes, out_offsets):
         import numpy as np
@@ -425,6 +433,32 @@ class Archive:
         a = (ctypes.c_uint64 * 8)()
         self.L.ZraHipArchiveGetStats(self.h, a)
         return dict(zip(ARCHIVE_STATS, (int(v) for v in a)))
+
+    def update(self, d_out, out_cap, *, writes=None, d_data=0, d_append=0, append_size=0, level=3, checksum=True):
+        """ZraHipArchiveUpdate: Engine.update of the archive the handle serves, written to d_out; old plaintext comes from the cache where
+        it is resident, the handle serves the result afterwards and its resident frames hold the new bytes. Returns the new size.
+        OutputBufferTooSmall carries the size needed in ZraError.needed; after any error the handle is as it was."""
+        import numpy as np
+        o, s, do = (np.ascontiguousarray(a, dtype=np.uint64) for a in (writes if writes is not None else ((), (), ())))
+        if not (len(o) == len(s) == len(do)):
+            raise ValueError("writes: offsets, sizes and data_offsets differ in length")
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if len(a) else None
+        osz = ctypes.c_size_t(0)
+        self.engine._order()
+        st = self.L.ZraHipArchiveUpdate(self.h, d_data or None, p(o), p(s), p(do), len(o), d_append or None, append_size, d_out or None, out_cap,
+                                        ctypes.byref(osz), level, checksum)
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipArchiveUpdate")
+            e.needed = osz.value
+            raise e
+        self.d_archive, self.size = d_out, osz.value
+        return osz.value
+
+    def update_stats(self):
+        """Counters of the updates through this handle, keyed by ARCHIVE_UPDATE_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipArchiveGetUpdateStats(self.h, a)
+        return dict(zip(ARCHIVE_UPDATE_STATS, (int(v) for v in a[:7])))
 
     def drop_cache(self):
         _chk(self.L.ZraHipArchiveDropCache(self.h), "ZraHipArchiveDropCache")

@@ -18,19 +18,33 @@ class ArchiveCache {
   Status drop();
   // {slots, resident, reads, hits, misses, evictions, uncompressed size, frame size}
   void stats(uint64_t out[8]) const;
+  // Engine::update_archive of the archive the handle is bound to, old plaintext taken from the arena where it is resident; on Success
+  // the handle serves the archive at dOut and every resident frame holds its new content (zra_hip.h: ZraHipArchiveUpdate). On any other
+  // status nothing has changed.
+  Status update(const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend,
+                size_t appendSize, uint8_t* dOut, size_t outCap, size_t* outSize, int level, bool checksum);
+  // {updates accepted, frames now, archive size now, staged from the cache (last update), resident frames refreshed (last), staged
+  // (cumulative), refreshed (cumulative), 0}
+  void update_stats(uint64_t out[8]) const;
 
  private:
   ArchiveCache() = default;
+  static const uint32_t* update_table(void* ctx, uint32_t frames);   // UpdCacheView::table
   Status read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
   Engine* e_ = nullptr;
   const uint8_t* dArc_ = nullptr;
   size_t arcSize_ = 0;
   HeaderInfo h_{};
   uint32_t nFrames_ = 0, slots_ = 0, maxPass_ = 0;
-  // device state, one allocation: slotOf[nFrames] | frameOf[slots] | victim[maxPass] (u32) | ref[slots] (u8) | hand (u32) + counters (u64)
+  // device state, one allocation: frameOf[slots] | victim[maxPass] (u32) | ref[slots] (u8) | hand (u32) + counters (u64)
   void* state_ = nullptr;
   uint8_t* arena_ = nullptr;            // slots x frameSize
-  uint32_t* slotOf_ = nullptr;          // frame -> slot, kNone when not resident
+  // frame -> slot, kNone when not resident. An allocation of its own: it grows with the archive (update), slotCap_ entries, those
+  // behind nFrames_ always kNone
+  uint32_t* slotOf_ = nullptr;
+  size_t slotCap_ = 0;
+  uint32_t* grown_ = nullptr;           // a larger table made for the running update, not yet swapped in
+  size_t grownCap_ = 0;
   uint32_t* frameOf_ = nullptr;         // slot -> frame, kEmpty when free
   uint32_t* victim_ = nullptr;          // the slots the current read decodes into
   uint8_t* ref_ = nullptr;              // CLOCK reference bit (2: claimed by the running read)
@@ -38,6 +52,7 @@ class ArchiveCache {
   unsigned long long* dctr_ = nullptr;  // {evictions, resident}
   uint64_t* pin_ = nullptr;             // page-locked read-back words
   uint64_t reads_ = 0, hits_ = 0, misses_ = 0, evictions_ = 0, resident_ = 0;
+  uint64_t updates_ = 0, stagedLast_ = 0, refreshedLast_ = 0, stagedTotal_ = 0, refreshedTotal_ = 0;
 };
 
 }  // namespace zra_eng

@@ -145,18 +145,20 @@ Status ArchiveCache::open(Engine* e, const uint8_t* dArc, size_t arcSize, size_t
   c->slots_ = fs ? (uint32_t)std::min<uint64_t>(cacheBytes / fs, c->nFrames_) : 0u;
   c->maxPass_ = std::min(c->slots_, kMaxPass);
   const size_t S = c->slots_, F = c->nFrames_;
-  const size_t u32Bytes = (F + S + c->maxPass_) * 4, stateBytes = ((u32Bytes + S + 7) & ~(size_t)7) + 8 + 16;
+  const size_t u32Bytes = (S + c->maxPass_) * 4, stateBytes = ((u32Bytes + S + 7) & ~(size_t)7) + 8 + 16;
   auto fail = [&]() { (void)hipGetLastError(); delete c; return zerr(64); };
   if (hipHostMalloc((void**)&c->pin_, 64, hipHostMallocDefault) != hipSuccess) { c->pin_ = nullptr; return fail(); }
   if (S) {
     if (hipMalloc((void**)&c->arena_, S * fs) != hipSuccess) { c->arena_ = nullptr; return fail(); }
     if (hipMalloc(&c->state_, stateBytes) != hipSuccess) { c->state_ = nullptr; return fail(); }
+    if (hipMalloc((void**)&c->slotOf_, F * 4) != hipSuccess) { c->slotOf_ = nullptr; return fail(); }
+    c->slotCap_ = F;
     uint8_t* b = (uint8_t*)c->state_;
-    c->slotOf_ = (uint32_t*)b; c->frameOf_ = c->slotOf_ + F; c->victim_ = c->frameOf_ + S;
+    c->frameOf_ = (uint32_t*)b; c->victim_ = c->frameOf_ + S;
     c->ref_ = b + u32Bytes;
     c->hand_ = (uint32_t*)(b + ((u32Bytes + S + 7) & ~(size_t)7));
     c->dctr_ = (unsigned long long*)((uint8_t*)c->hand_ + 8);
-    if (hipMemsetAsync(b, 0xFF, u32Bytes, e->stream_) != hipSuccess ||
+    if (hipMemsetAsync(c->slotOf_, 0xFF, F * 4, e->stream_) != hipSuccess || hipMemsetAsync(b, 0xFF, u32Bytes, e->stream_) != hipSuccess ||
         hipMemsetAsync(c->ref_, 0, stateBytes - u32Bytes, e->stream_) != hipSuccess || hipStreamSynchronize(e->stream_) != hipSuccess) {
       (void)hipGetLastError(); delete c; return zerr(1);
     }
@@ -169,6 +171,7 @@ ArchiveCache::~ArchiveCache() {
   if (e_) { (void)hipSetDevice(e_->device_); (void)hipStreamSynchronize(e_->stream_); }
   if (arena_) (void)hipFree(arena_);
   if (state_) (void)hipFree(state_);
+  if (slotOf_) (void)hipFree(slotOf_);
   if (pin_) (void)hipHostFree(pin_);
 }
 
@@ -180,11 +183,54 @@ void ArchiveCache::stats(uint64_t out[8]) const {
 Status ArchiveCache::drop() {
   HIPCHK_CLR(hipSetDevice(e_->device_));
   if (!slots_) return ok();
-  HIPCHK_CLR(hipMemsetAsync(slotOf_, 0xFF, ((size_t)nFrames_ + slots_) * 4, e_->stream_));
+  HIPCHK_CLR(hipMemsetAsync(slotOf_, 0xFF, (size_t)nFrames_ * 4, e_->stream_));
+  HIPCHK_CLR(hipMemsetAsync(frameOf_, 0xFF, (size_t)slots_ * 4, e_->stream_));
   HIPCHK_CLR(hipMemsetAsync(ref_, 0, slots_, e_->stream_));
   HIPCHK_CLR(hipMemsetAsync(dctr_ + 1, 0, 8, e_->stream_));
   HIPCHK_CLR(hipStreamSynchronize(e_->stream_));
   resident_ = 0;
+  return ok();
+}
+
+void ArchiveCache::update_stats(uint64_t out[8]) const {
+  const uint64_t v[8] = {updates_, nFrames_, arcSize_, stagedLast_, refreshedLast_, stagedTotal_, refreshedTotal_, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+
+// The update is not a read: it maps and unmaps no frame, sets no reference bit and leaves the hand where it is. What it changes of the
+// cache are the BYTES of the touched resident frames (Engine::update_archive lays the new bytes over their slots, behind its last
+// check) and the length of slotOf, which must cover the frames of the result before the update's planner reads it. The update asks
+// for that table behind its host-side checks (UpdCacheView::table): a grown one is a copy with the new entries kNone, swapped in
+// after the update's last synchronisation, or freed again.
+const uint32_t* ArchiveCache::update_table(void* ctx, uint32_t frames) {
+  ArchiveCache* c = (ArchiveCache*)ctx;
+  if (frames <= c->slotCap_) return c->slotOf_;
+  // headroom of a quarter and 1,024 frames: a stream of appends does not allocate each time
+  const size_t cap = (size_t)std::min<uint64_t>((uint64_t)frames + frames / 4 + 1024, 0xFFFFFFF0ull);
+  hipStream_t s = c->e_->stream_;
+  if (hipMalloc((void**)&c->grown_, cap * 4) != hipSuccess) { (void)hipGetLastError(); c->grown_ = nullptr; return nullptr; }
+  if (hipMemsetAsync(c->grown_, 0xFF, cap * 4, s) != hipSuccess ||
+      hipMemcpyAsync(c->grown_, c->slotOf_, (size_t)c->nFrames_ * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    (void)hipGetLastError(); (void)hipStreamSynchronize(s); (void)hipFree(c->grown_); c->grown_ = nullptr; return nullptr;
+  }
+  c->grownCap_ = cap;
+  return c->grown_;
+}
+
+Status ArchiveCache::update(const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hDataOff, size_t nw,
+                            const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap, size_t* outSize, int level, bool checksum) {
+  Engine& E = *e_;
+  UpdCacheView v;
+  v.h = h_; v.arena = arena_; v.slots = slots_; v.table = &ArchiveCache::update_table; v.ctx = this;
+  const Status st = E.update_archive(dArc_, arcSize_, dData, hOff, hSize, hDataOff, nw, dAppend, appendSize, dOut, outCap, outSize, level, checksum, &v);
+  if (st.zra) {
+    if (grown_) { (void)hipStreamSynchronize(E.stream_); (void)hipFree(grown_); grown_ = nullptr; }
+    return st;
+  }
+  if (grown_) { (void)hipFree(slotOf_); slotOf_ = grown_; slotCap_ = grownCap_; grown_ = nullptr; }
+  dArc_ = dOut; arcSize_ = *outSize; h_ = v.newHeader; nFrames_ = h_.frames();
+  updates_++;
+  stagedLast_ = v.staged; refreshedLast_ = v.refreshed; stagedTotal_ += v.staged; refreshedTotal_ += v.refreshed;
   return ok();
 }
 

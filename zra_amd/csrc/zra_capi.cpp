@@ -733,6 +733,17 @@ void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8) {
   if (!out8) return;
   if (archive) archive->c->stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
+ZraStatus ZraHipArchiveUpdate(ZraHipArchive* archive, const void* dData, const uint64_t* hOffsets, const uint64_t* hSizes, const uint64_t* hDataOffsets,
+                              size_t nWrites, const void* dAppend, size_t appendSize, void* dOut, size_t outCapacity, size_t* outSize, int8_t level,
+                              bool checksum) {
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->update((const uint8_t*)dData, hOffsets, hSizes, hDataOffsets, nWrites, (const uint8_t*)dAppend, appendSize, (uint8_t*)dOut,
+                               outCapacity, outSize, level, checksum));
+}
+void ZraHipArchiveGetUpdateStats(const ZraHipArchive* archive, uint64_t* out8) {
+  if (!out8) return;
+  if (archive) archive->c->update_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
 ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* dData, const uint64_t* hOffsets,
                               const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites, const void* dAppend, size_t appendSize, void* dOut,
                               size_t outCapacity, size_t* outSize, int8_t level, bool checksum) {
@@ -740,6 +751,7 @@ ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t
   return mk(engine->e->update_archive((const uint8_t*)dArchive, archiveSize, (const uint8_t*)dData, hOffsets, hSizes, hDataOffsets, nWrites,
                                       (const uint8_t*)dAppend, appendSize, (uint8_t*)dOut, outCapacity, outSize, level, checksum));
 }
+double ZraHipDebugUpdateStageMs(ZraHipEngine* engine) { return engine ? engine->e->update_stage_ms() : 0.0; }
 void ZraHipGetUpdateStats(ZraHipEngine* engine, uint64_t* out8) {
   if (!out8) return;
   if (engine) engine->e->update_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;

@@ -33,6 +33,22 @@ struct HeaderInfo {
 };
 // parse the 38 fixed bytes; returns a ZRA status code (0 ok)
 int parse_fixed_header(const uint8_t* fixed38, HeaderInfo* h);
+// An update through an archive handle (zra_archive.hip, ZraHipArchiveUpdate): what the handle lends to Engine::update_archive and what
+// comes back.
+struct UpdCacheView {
+  HeaderInfo h{};                    // the handle's checked header, taken in place of a read from the device
+  uint8_t* arena = nullptr;          // slots x frameSize: old plaintext is read from it, and new bytes are laid over it after the last check
+  uint32_t slots = 0;                // 0: a handle without a cache (table is not called)
+  // frame -> arena slot (0xFFFFFFFF: not resident), readable for `frames` frames, those behind the old frames not resident. Called once,
+  // behind the host-side checks of the update (statuses 1-4), with the frames of the RESULT: the handle grows its table here, on the
+  // engine's stream. nullptr: no memory ({ZStdError, 64})
+  const uint32_t* (*table)(void* ctx, uint32_t frames) = nullptr;
+  void* ctx = nullptr;
+  // on Success: the header of the archive at dOut (from the host copy the update wrote), frames staged from the arena in place of a
+  // decode, resident frames that hold new bytes
+  HeaderInfo newHeader{};
+  uint32_t staged = 0, refreshed = 0;
+};
 // chunk length of the pipelined host-pointer calls (zra_hostpipe.hip); ZRA_HOST_CHUNK_MIB, default 1024
 size_t host_chunk_bytes();
 
@@ -122,10 +138,12 @@ class Engine {
   // compressed bytes are carried over as they are. Statuses and their order: zra_hip.h, ZraHipUpdateArchive.
   Status update_archive(const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
                         const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
-                        size_t* outSize, int level, bool checksum);
+                        size_t* outSize, int level, bool checksum, UpdCacheView* cache = nullptr);
   // what the last update_archive did: {frames, touched, decoded, compressed, bytes carried, bytes encoded, content bytes written, passes};
-  // all zero unless it succeeded
+  // all zero unless it succeeded. decoded counts decode jobs: frames staged from a handle's cache are not among them
   void update_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = ustats_[i]; }
+  // bring-up: HIP-event time of the last update's zra_upd_stage_cached_kernel launches, summed over its passes (0: none ran)
+  double update_stage_ms() const { return updStageMs_; }
 
   // ---- verify (zra_verify.hip): header CRC-32, seek table and every frame's block walk of frames [first, first + count) of the archive
   // at dArc, then (content) every structurally sound frame decoded whole into a staging window, checksum verified. Every faulty frame is
@@ -205,10 +223,12 @@ class Engine {
   void* encCounters_ = nullptr; size_t encCountersBytes_ = 0;   // sub-batch counters stream B may be waiting on (drain_after_error)
   int waitValueOk_ = 0;                    // 0 unknown, 1 hipStreamWaitValue32 works on device memory, -1 it does not (batch path)
   // update scratch (zra_update.hip): per-frame plan words, plaintext staging of one pass, the packed newly encoded frames, their sizes,
-  // the per-frame sizes / offsets / source displacements, the new seek table
-  struct UpdScratch { DevBuf plan, stage, packed, encSizes, frames, table; };
+  // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
+  struct UpdScratch { DevBuf plan, stage, packed, encSizes, frames, table, copies; };
   UpdScratch upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipEvent_t evUpd_[2] = {nullptr, nullptr};   // around a pass's stage-from-cache kernel (created by the first update through a handle)
+  double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the staging window of one decode pass, the fault list
   struct VerifyScratch { DevBuf plan, stage, faults; };
   VerifyScratch vfy_;

@@ -160,7 +160,7 @@ void Engine::free_scratch() {
                     &produced_, &frameMeta_, &frameOff_, &outOff_, &expect_, &result_, &temp_, &qmeta_, &encScan_, &hostIn_, &hostOut_, &seqScratch_, &mfFlags_, &decBlkRecs_, &decBlkTables_, &decBlkLists_})
     b->release();
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
-  for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table}) b->release();
+  for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table, &upd_.copies}) b->release();
   for (DevBuf* b : {&vfy_.plan, &vfy_.stage, &vfy_.faults}) b->release();
 }
 
@@ -185,6 +185,7 @@ Engine::~Engine() {
   if (pinQ_) (void)hipHostFree(pinQ_);
   if (pinSmall_) (void)hipHostFree(pinSmall_);
   for (auto& ev : evR_) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : evUpd_) if (ev) (void)hipEventDestroy(ev);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
   if (evWait_) (void)hipEventDestroy(evWait_);

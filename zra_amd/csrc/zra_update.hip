@@ -4,6 +4,7 @@
 // Every frame is an independent zstd frame and the seek table alone ties them together, so an update
 //   1. plans, per frame, whether new bytes land in it (touched), how many, and its staging slot        zra_upd_mark / zra_upd_plan
 //   2. decodes the touched frames that keep some old bytes, whole and with their checksum              Engine::decode_jobs
+//      (through an archive handle: those of them that are resident are copied out of its arena instead   zra_upd_stage_cached)
 //   3. copies the new bytes over them in the staging buffer                                            zra_upd_patch
 //   4. encodes the staged frames like ZraHipCompressBuffer encodes frames of that content              Engine::compress_frames
 //   5. sizes every frame (new size if touched, old table difference if not), scans, writes the table   zra_upd_sizes / _scan / _offsets
@@ -16,6 +17,11 @@
 //      lowest failing frame), and the packed encoded frames are in frame order (one scan gives their places).
 //  (b) the patch kernel of a pass runs behind the pass's decode and before its encode: new bytes win over decoded ones.
 //  (c) nothing is written to dOut before every size is known and every check has passed: a refused update leaves dOut alone.
+// Through an archive handle (UpdCacheView) two more:
+//  (d) a pass's copies out of the arena write other staging slots than its decode jobs and run before its patch kernel; copies and
+//      jobs are each ranked in frame order, so (a) holds for the jobs: the first failing job is the lowest failing DECODED frame.
+//  (e) the arena is only read before the last check; the new bytes are laid over the resident frames beside the gather: a REFUSED
+//      update changes nothing (a HIP runtime error behind that point leaves dOut and those frames undefined).
 #include "zra_host.h"
 #include "zra_dev.h"
 #include "zra_format.h"
@@ -54,6 +60,24 @@ __device__ __forceinline__ Slice slice_of(const u64* q, u32 nq, u64 s, u64 fs) {
   return r;
 }
 
+// one wave copies n bytes: 16-byte loads aligned on the source, four in flight per lane; the stores fall as they may
+// (zra_gather_frames_kernel's choice)
+__device__ __forceinline__ void copy_span(u8* dst, const u8* src, u64 n, u32 lane) {
+  const u32 head = (u32)min<u64>((16u - ((uintptr_t)src & 15u)) & 15u, n);
+  if (lane < head) dst[lane] = src[lane];
+  const u32 n16 = (u32)((n - head) >> 4);
+  const uint4* s4 = (const uint4*)(src + head);
+  u8* d16 = dst + head;
+  u32 i = lane;
+  for (; i + 192 < n16; i += 256) {
+    const uint4 v0 = s4[i], v1 = s4[i + 64], v2 = s4[i + 128], v3 = s4[i + 192];
+    st128(d16 + 16 * (size_t)i, v0.x, v0.y, v0.z, v0.w); st128(d16 + 16 * (size_t)(i + 64), v1.x, v1.y, v1.z, v1.w);
+    st128(d16 + 16 * (size_t)(i + 128), v2.x, v2.y, v2.z, v2.w); st128(d16 + 16 * (size_t)(i + 192), v3.x, v3.y, v3.z, v3.w);
+  }
+  for (; i < n16; i += 64) { const uint4 v = s4[i]; st128(d16 + 16 * (size_t)i, v.x, v.y, v.z, v.w); }
+  for (u64 k = head + ((u64)n16 << 4) + lane; k < n; k += 64) dst[k] = src[k];
+}
+
 __device__ __forceinline__ u64 wave_incl_scan64(u64 v, int lane) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
@@ -75,30 +99,45 @@ extern "C" __global__ void __launch_bounds__(256) zra_upd_mark_kernel(const u64*
 // (cover < its new length) gets a decode job, ranked the same way: compressed span from the old seek table, destination = its slot of
 // the pass, expected size = its old length. passJob[p] = jobs in front of pass p (slots [p * passSlots, ...)), passJob[passes] = all.
 // An untouched frame is carried over by its table entries: they must not run backwards nor end beyond the body (flag).
-// totals = {touched, jobs, flag}.
+// With a handle's cache (cacheSlotOf != nullptr, readable for nNew frames) a frame that keeps old bytes and is resident gets no job but
+// a copy entry {staging slot, arena slot, old length, frame}, ranked in frame order like the jobs, passCopy[] like passJob[]; and
+// every touched resident frame is counted: its arena slot is to hold the new content.
+// totals = {touched, jobs, flag, copies, touched resident frames}.
 extern "C" __global__ void __launch_bounds__(1024) zra_upd_plan_kernel(const u32* cover, u32 nNew, u32 nOld, const u8* table, u64 bodyBytes, u64 fs,
-                                                                    u64 oldTotal, u64 newTotal, u32 passSlots, u32* slotOf, u64* frameOff,
-                                                                    u64* outOff, u32* expect, u32* passJob, u32* totals) {
-  __shared__ u32 sT[16], sJ[16], sFlag;
+                                                                    u64 oldTotal, u64 newTotal, u32 passSlots, const u32* cacheSlotOf, u32* slotOf,
+                                                                    u64* frameOff, u64* outOff, u32* expect, u32* passJob, u32* copies,
+                                                                    u32* passCopy, u32* totals) {
+  __shared__ u32 sT[16], sJ[16], sC[16], sF[16], sFlag;
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) sFlag = 0;
-  u32 slotBase = 0, jobBase = 0;
+  u32 slotBase = 0, jobBase = 0, copyBase = 0, fresh = 0;
   for (u32 base = 0; base < nNew; base += 1024) {
     const u32 f = base + tid;
     const bool in = f < nNew;
     const u32 c = in ? cover[f] : 0u;
     const u64 o = (u64)f * fs;
     const u32 newLen = in ? (u32)min<u64>(fs, newTotal - o) : 0u;
-    const bool touched = c != 0, dec = touched && c != newLen;
-    const u64 mT = __ballot(touched), mJ = __ballot(dec);
+    const bool touched = c != 0;
+    const u32 cs = touched && cacheSlotOf ? cacheSlotOf[f] : kNone;
+    const bool keeps = touched && c != newLen, cpy = keeps && cs != kNone, dec = keeps && !cpy;
+    const u64 mT = __ballot(touched), mJ = __ballot(dec), mC = __ballot(cpy), mF = __ballot(cs != kNone);
     const u64 below = (1ull << lane) - 1;
-    if (lane == 0) { sT[wave] = (u32)__popcll(mT); sJ[wave] = (u32)__popcll(mJ); }
+    if (lane == 0) { sT[wave] = (u32)__popcll(mT); sJ[wave] = (u32)__popcll(mJ); sC[wave] = (u32)__popcll(mC); sF[wave] = (u32)__popcll(mF); }
     __syncthreads();
-    u32 beforeT = 0, beforeJ = 0, totalT = 0, totalJ = 0;
-    for (u32 w = 0; w < 16; w++) { const u32 t = sT[w], j = sJ[w]; beforeT += w < wave ? t : 0u; beforeJ += w < wave ? j : 0u; totalT += t; totalJ += j; }
+    u32 beforeT = 0, beforeJ = 0, beforeC = 0, totalT = 0, totalJ = 0, totalC = 0;
+    for (u32 w = 0; w < 16; w++) {
+      const u32 t = sT[w], j = sJ[w], k = sC[w];
+      beforeT += w < wave ? t : 0u; beforeJ += w < wave ? j : 0u; beforeC += w < wave ? k : 0u; totalT += t; totalJ += j; totalC += k;
+      fresh += sF[w];
+    }
     const u32 slot = slotBase + beforeT + (u32)__popcll(mT & below), job = jobBase + beforeJ + (u32)__popcll(mJ & below);
+    const u32 copy = copyBase + beforeC + (u32)__popcll(mC & below);
     if (in) slotOf[f] = touched ? slot : kNone;
-    if (touched && slot % passSlots == 0) passJob[slot / passSlots] = job;
+    if (touched && slot % passSlots == 0) { passJob[slot / passSlots] = job; passCopy[slot / passSlots] = copy; }
+    if (cpy) {
+      u32* e = copies + 4 * (size_t)copy;
+      e[0] = slot; e[1] = cs; e[2] = (u32)min<u64>(fs, oldTotal - o); e[3] = f;
+    }
     if (dec) {
       // (dec implies f < nOld: a frame behind the old content is supplied whole by the append)
       frameOff[2 * (size_t)job] = entry40(table, f); frameOff[2 * (size_t)job + 1] = entry40(table, (u64)f + 1);
@@ -109,12 +148,30 @@ extern "C" __global__ void __launch_bounds__(1024) zra_upd_plan_kernel(const u32
       const u64 a = entry40(table, f), b = entry40(table, (u64)f + 1);
       if (b < a || b > bodyBytes) atomicOr(&sFlag, 1u);
     }
-    slotBase += totalT; jobBase += totalJ;
-    __syncthreads();                                                  // (sT, sJ of the next chunk; sFlag)
+    slotBase += totalT; jobBase += totalJ; copyBase += totalC;
+    __syncthreads();                                                  // (sT, sJ, sC, sF of the next chunk; sFlag)
   }
   if (tid == 0) {
-    passJob[(slotBase + passSlots - 1) / passSlots] = jobBase;
-    totals[0] = slotBase; totals[1] = jobBase; totals[2] = sFlag;
+    passJob[(slotBase + passSlots - 1) / passSlots] = jobBase; passCopy[(slotBase + passSlots - 1) / passSlots] = copyBase;
+    totals[0] = slotBase; totals[1] = jobBase; totals[2] = sFlag; totals[3] = copyBase; totals[4] = fresh;
+  }
+}
+
+// The cache's bandwidth kernel: copy entries [0, n) of a pass (zra_upd_plan_kernel), a wave per kGatherChunk bytes of a frame (one wave
+// for a frame of up to 32 KiB, 64 for one of 2 MiB), a capped grid striding over them. The frame's old length goes from its arena slot
+// to its staging slot of the pass that starts at slot s0; both sides are fs-strided, so with a frame size that is no multiple of 16
+// they are not co-aligned (copy_span: loads aligned, stores as they fall).
+extern "C" __global__ void __launch_bounds__(256) zra_upd_stage_cached_kernel(const u32* copies, u32 n, u32 s0, u64 fs, const u8* arena, u8* stage) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 perFrame = (u32)((fs + kGatherChunk - 1) / kGatherChunk);
+  const u64 nWork = (u64)n * perFrame;
+  for (u64 w = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); w < nWork; w += (u64)gridDim.x * 4) {
+    const u32 k = (u32)(w / perFrame);
+    const u64 x = (w - (u64)k * perFrame) * kGatherChunk;
+    const u32* e = copies + 4 * (size_t)k;
+    const u32 slot = e[0], cs = e[1], len = e[2];
+    if (x >= len) continue;
+    copy_span(stage + (u64)(slot - s0) * fs + x, arena + (u64)cs * fs + x, min<u64>(kGatherChunk, len - x), lane);
   }
 }
 
@@ -198,8 +255,7 @@ extern "C" __global__ void __launch_bounds__(1024) zra_upd_offsets_kernel(u32 nN
 
 // The bandwidth kernel. The new body is cut into chunks of kGatherChunk bytes, a capped grid strides over them, one wave per chunk.
 // The wave finds the frame its chunk starts in by binary search over newOff, then copies span after span: a span ends where the
-// displacement changes (ballot over the next 64 frames at a time) or the chunk does. 16-byte loads aligned on the source, the stores
-// fall as they may (zra_gather_frames_kernel's choice).
+// displacement changes (ballot over the next 64 frames at a time) or the chunk does (copy_span).
 extern "C" __global__ void __launch_bounds__(256) zra_upd_gather_kernel(const u64* newOff, const u64* disp, u32 nNew, u64 total, u8* body) {
   const u32 lane = threadIdx.x & 63;
   const u64 nChunks = (total + kGatherChunk - 1) / kGatherChunk;
@@ -225,22 +281,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_upd_gather_kernel(const u6
       g = min(g, nNew);
       const u64 end = min<u64>(x1, newOff[g]);
       if (end > x) {
-        const u8* src = (const u8*)(uintptr_t)(d + x);
-        u8* dst = body + x;
-        const u64 n = end - x;
-        const u32 head = (u32)min<u64>((16u - ((uintptr_t)src & 15u)) & 15u, n);
-        if (lane < head) dst[lane] = src[lane];
-        const u32 n16 = (u32)((n - head) >> 4);
-        const uint4* s4 = (const uint4*)(src + head);
-        u8* d16 = dst + head;
-        u32 i = lane;
-        for (; i + 192 < n16; i += 256) {                             // four loads in flight per lane
-          const uint4 v0 = s4[i], v1 = s4[i + 64], v2 = s4[i + 128], v3 = s4[i + 192];
-          st128(d16 + 16 * (size_t)i, v0.x, v0.y, v0.z, v0.w); st128(d16 + 16 * (size_t)(i + 64), v1.x, v1.y, v1.z, v1.w);
-          st128(d16 + 16 * (size_t)(i + 128), v2.x, v2.y, v2.z, v2.w); st128(d16 + 16 * (size_t)(i + 192), v3.x, v3.y, v3.z, v3.w);
-        }
-        for (; i < n16; i += 64) { const uint4 v = s4[i]; st128(d16 + 16 * (size_t)i, v.x, v.y, v.z, v.w); }
-        for (u64 k = head + ((u64)n16 << 4) + lane; k < n; k += 64) dst[k] = src[k];
+        copy_span(body + x, (const u8*)(uintptr_t)(d + x), end - x, lane);
         x = end;
       }
       f = g;
@@ -254,29 +295,35 @@ namespace zra_eng {
 struct UpdateImpl {
   static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
                     const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
-                    size_t* outSize, int level, bool checksum);
+                    size_t* outSize, int level, bool checksum, UpdCacheView* cache);
 };
 
 Status Engine::update_archive(const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
                               const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
-                              size_t* outSize, int level, bool checksum) {
+                              size_t* outSize, int level, bool checksum, UpdCacheView* cache) {
   for (auto& v : ustats_) v = 0;
-  return UpdateImpl::run(*this, dArc, arcSize, dData, hOff, hSize, hDataOff, nw, dAppend, appendSize, dOut, outCap, outSize, level, checksum);
+  return UpdateImpl::run(*this, dArc, arcSize, dData, hOff, hSize, hDataOff, nw, dAppend, appendSize, dOut, outCap, outSize, level, checksum, cache);
 }
 
 Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
                        const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
-                       size_t* outSize, int level, bool checksum) {
-  // ---- 1. arguments, 2. overlap
+                       size_t* outSize, int level, bool checksum, UpdCacheView* cache) {
+  // ---- 1. arguments, 2. overlap (with the archive, and with the arena of the handle the update goes through)
   if (!outSize || !dOut || (!dArc && arcSize) || (nw && (!hOff || !hSize || !hDataOff)) || (!dAppend && appendSize)) return zerr(42);
   if (!dData) for (size_t i = 0; i < nw; i++) if (hSize[i]) return zerr(42);
   if (outCap && arcSize && (uintptr_t)dOut < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dOut + outCap) return zerr(42);
+  const bool cached = cache && cache->slots;
+  if (cached && outCap && (uintptr_t)dOut < (uintptr_t)cache->arena + (size_t)cache->slots * cache->h.frameSize &&
+      (uintptr_t)cache->arena < (uintptr_t)dOut + outCap)
+    return zerr(42);
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   // ---- 3. header: the statuses of ZraHipArchiveOpen; beyond them a frame size of 0 and a table that does not cover the content
   // (an open handle refuses every read of such an archive; here there is no frame to put a byte in)
+  // (a handle holds a checked header: it is not read from the device again)
   HeaderInfo h;
-  { Status st = E.ra_header(dArc, arcSize, &h); if (st.zra) return st; }
+  if (cache) h = cache->h;
+  else { Status st = E.ra_header(dArc, arcSize, &h); if (st.zra) return st; }
   const uint64_t fs = h.frameSize, U = h.uncompressedSize;
   const uint32_t F = h.frames();
   if (fs == 0 || (U + fs - 1) / fs != F) return {kHeaderInvalid, 0};
@@ -300,6 +347,11 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   const uint32_t F2 = (uint32_t)F2wide;
   const size_t nData = idx.size(), nT = nData + (appendSize ? 1 : 0);
   if (nT > 0xFFFFFFF0ull) return zerr(64);
+  // the handle's frame table over the frames of the result (behind the host-side checks: a refused call allocates nothing)
+  const uint32_t* const cacheSlotOf = cached ? cache->table(cache->ctx, F2) : nullptr;
+  if (cached && !cacheSlotOf) return zerr(64);
+  E.updStageMs_ = 0;
+  if (cached && !E.evUpd_[0]) for (auto& ev : E.evUpd_) if (hipEventCreate(&ev) != hipSuccess) { ev = nullptr; (void)hipGetLastError(); return zerr(1); }
   // the tuples, sorted by offset, in page-locked memory and from there to the device in chunks (ra_walk_queries' idiom)
   uint64_t nSlices = 0;
   if (nT) {
@@ -321,13 +373,15 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   const uint32_t passSlots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kPassFrames, kStageBytes / fs));
   const uint64_t touchedMax = std::min<uint64_t>(F2, nSlices), jobsMax = std::min<uint64_t>(F, nSlices);
   const size_t passesMax = (size_t)((touchedMax + passSlots - 1) / passSlots);
-  const size_t planWords = 2 * (size_t)F2 + 16 + passesMax + 1;            // cover[F2] | slotOf[F2] | totals[16] | passJob[passes + 1]
+  // cover[F2] | slotOf[F2] | totals[16] | passJob[passes + 1] | passCopy[passes + 1]
+  const size_t planWords = 2 * (size_t)F2 + 16 + 2 * (passesMax + 1);
   const uint32_t nBlocks = F2 / 1024 + 1;                                  // (F2 + 1 entries: the frames and the end)
   if (!E.upd_.plan.reserve(planWords * 4 + 64) || !E.upd_.frames.reserve((2 * ((size_t)F2 + 1) + 2 * ((size_t)nBlocks + 1)) * 8 + 64) ||
       !E.upd_.table.reserve(((size_t)F2 + 1) * 5 + 64) || !E.frameOff_.reserve((jobsMax + 1) * 16) || !E.outOff_.reserve((jobsMax + 1) * 8) ||
-      !E.expect_.reserve((jobsMax + 1) * 4))
+      !E.expect_.reserve((jobsMax + 1) * 4) || (cacheSlotOf && !E.upd_.copies.reserve((jobsMax + 1) * 16)))
     return zerr(64);
   uint32_t* cover = E.upd_.plan.as<uint32_t>(), *slotOf = cover + F2, *totals = slotOf + F2, *passJob = totals + 16;
+  uint32_t* const passCopy = passJob + passesMax + 1, * const copies = cacheSlotOf ? E.upd_.copies.as<uint32_t>() : nullptr;
   uint64_t* newOff = E.upd_.frames.as<uint64_t>(), *disp = newOff + F2 + 1, *sums = disp + F2 + 1;
   const uint8_t* oldTable = dArc + h.seekTableOffset;
   const uint8_t* oldBody = dArc + h.size;
@@ -335,23 +389,25 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   HIPCHK_CLR(hipMemsetAsync(cover, 0, planWords * 4, s));
   if (nSlices)
     hipLaunchKernelGGL(zra_upd_mark_kernel, dim3((uint32_t)((nSlices + 255) / 256)), dim3(256), 0, s, dq, (u32)nT, (u64)nSlices, (u64)fs, cover);
-  uint32_t hTotals[3] = {0, 0, 0};
+  uint32_t hTotals[5] = {0, 0, 0, 0, 0};
   if (F2) {
-    hipLaunchKernelGGL(zra_upd_plan_kernel, dim3(1), dim3(1024), 0, s, cover, F2, F, oldTable, (u64)bodyBytes, (u64)fs, (u64)U, (u64)U2, passSlots, slotOf,
-                       E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), passJob, totals);
-    HIPCHK_CLR(hipMemcpyAsync(hTotals, totals, 12, hipMemcpyDeviceToHost, s));
+    hipLaunchKernelGGL(zra_upd_plan_kernel, dim3(1), dim3(1024), 0, s, cover, F2, F, oldTable, (u64)bodyBytes, (u64)fs, (u64)U, (u64)U2, passSlots,
+                       cacheSlotOf, slotOf, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), passJob, copies, passCopy,
+                       totals);
+    HIPCHK_CLR(hipMemcpyAsync(hTotals, totals, sizeof(hTotals), hipMemcpyDeviceToHost, s));
   }
   HIPCHK_CLR(hipStreamSynchronize(s));
   HIPCHK_CLR(hipGetLastError());
   // ---- 5. the old seek table over the frames carried over
   if (hTotals[2]) return zerr(20);
-  const uint32_t touched = hTotals[0], jobs = hTotals[1];
+  const uint32_t touched = hTotals[0], jobs = hTotals[1], staged = hTotals[3], refreshed = hTotals[4];
   const uint32_t passes = (touched + passSlots - 1) / passSlots;
   // ---- 6. passes: decode the frames that keep old bytes, lay the new bytes over them, encode
   uint64_t encoded = 0;
   if (touched) {
-    std::vector<uint32_t> hPassJob(passes + 1);
+    std::vector<uint32_t> hPassJob(passes + 1), hPassCopy(passes + 1, 0u);
     HIPCHK_CLR(hipMemcpyAsync(hPassJob.data(), passJob, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (staged) HIPCHK_CLR(hipMemcpyAsync(hPassCopy.data(), passCopy, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
     const uint64_t bound = zra_fmt::compress_bound(fs);
     if (!E.upd_.stage.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64) || !E.upd_.packed.reserve((size_t)touched * bound + 64) ||
@@ -364,7 +420,14 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
     const uint32_t patchGrid = (uint32_t)std::min<uint64_t>((nSlices + 3) / 4, 1u << 20);
     for (uint32_t p = 0; p < passes; p++) {
       const uint32_t s0 = p * passSlots, n = std::min(passSlots, touched - s0);
-      const uint32_t j0 = hPassJob[p], j1 = hPassJob[p + 1];
+      const uint32_t j0 = hPassJob[p], j1 = hPassJob[p + 1], c0 = hPassCopy[p], c1 = hPassCopy[p + 1];
+      if (c1 > c0) {                                                  // (other staging slots than the decode jobs': no order between the two)
+        const uint64_t nWork = (uint64_t)(c1 - c0) * ((fs + kGatherChunk - 1) / kGatherChunk);
+        HIPCHK_CLR(hipEventRecord(E.evUpd_[0], s));
+        hipLaunchKernelGGL(zra_upd_stage_cached_kernel, dim3((uint32_t)std::min<uint64_t>((nWork + 3) / 4, kGatherGrid)), dim3(256), 0, s,
+                           copies + 4 * (size_t)c0, c1 - c0, s0, (u64)fs, cache->arena, stage);
+        HIPCHK_CLR(hipEventRecord(E.evUpd_[1], s));
+      }
       if (j1 > j0) {
         Status st = E.decode_jobs(oldBody, bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)j0, stage, E.outOff_.as<uint64_t>() + j0,
                                   E.expect_.as<uint32_t>() + j0, j1 - j0, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2);
@@ -377,6 +440,8 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
       Status st = E.compress_frames(stage, inSize, E.upd_.packed.as<uint8_t>() + encoded, E.upd_.encSizes.as<uint64_t>() + s0, &bsz, level, (uint32_t)fs, checksum);
       if (st.zra) return st;
       encoded += bsz;
+      // (compress_frames returned synchronised: the pass's events have completed)
+      if (c1 > c0) { float ms = 0; if (hipEventElapsedTime(&ms, E.evUpd_[0], E.evUpd_[1]) == hipSuccess) E.updStageMs_ += ms; else (void)hipGetLastError(); }
     }
   }
   // ---- sizes, offsets, table
@@ -402,6 +467,12 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   if (outCap < headerSize + body) return {kOutputTooSmall, 0};
   zra_fmt::write_fixed(hdr.data(), U2, F2 + 1, (uint32_t)fs, (uint32_t)metaSize);
   zra_fmt::wr32(hdr.data() + 14, zra_fmt::header_hash(hdr.data(), hdr.data() + zra_fmt::kFixedSize));
+  // ---- the handle's resident frames: the same slices over their arena slots (the patch is idempotent, and a staging window of an
+  // earlier pass is long overwritten). A wholly replaced frame and the old last frame grown by the append are among them. Launched
+  // whenever there is a cache and a slice: coherence does not hang on the counter.
+  if (cached && nSlices)
+    hipLaunchKernelGGL(zra_upd_patch_kernel, dim3((uint32_t)std::min<uint64_t>((nSlices + 3) / 4, 1u << 20)), dim3(256), 0, s, dq, (u32)nT, (u32)nData,
+                       (u64)nSlices, (u64)fs, cacheSlotOf, 0u, cache->slots, dData, dAppend, cache->arena);
   // ---- gather
   HIPCHK_CLR(hipMemcpyAsync(dOut, hdr.data(), (size_t)headerSize, hipMemcpyHostToDevice, s));
   // (ZraHipLastKernelMs after an update: the gather, the call's bandwidth kernel)
@@ -419,6 +490,10 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   if (gather) { float ms = 0; if (hipEventElapsedTime(&ms, E.ev0_, E.ev1_) == hipSuccess) E.lastKernelMs_ = ms; else (void)hipGetLastError(); }
   const uint64_t st8[8] = {F2, touched, jobs, touched, body - encoded, encoded, written, passes};
   for (int i = 0; i < 8; i++) E.ustats_[i] = st8[i];
+  if (cache) {
+    if (parse_fixed_header(hdr.data(), &cache->newHeader)) return zerr(1);   // (cannot happen: the fixed part was written above)
+    cache->staged = staged; cache->refreshed = refreshed;
+  }
   return ok();
 }
 
