@@ -258,6 +258,60 @@ ZRA_EXPORT ZraStatus ZraHipVerifyArchive(ZraHipEngine* engine, const void* dArch
  *  passes, 0}. Counters, not timings. */
 ZRA_EXPORT void ZraHipGetVerifyStats(ZraHipEngine* engine, uint64_t* out8);
 
+/* ---- search: where a byte pattern occurs in the content of a device-resident archive, without an output buffer ----
+ * The counterpart of `zstdgrep`. Random access answers "give me bytes [a, b)"; a caller who does not know the offset yet would have to
+ * ZraHipDecompressBuffer the whole content into a second buffer and scan it with code of their own. This call decodes the frames of a
+ * content range into a bounded staging window, a pass at a time, and scans the plaintext where it lies. */
+#define ZRA_HIP_SEARCH_MAX_PATTERN 256u
+
+/** Finds the patternSize bytes at hPattern (HOST memory, 1 .. ZRA_HIP_SEARCH_MAX_PATTERN bytes, taken literally) in the content range
+ *  [offset, offset + size) of the archive at dArchive (archiveSize bytes, device memory); size = UINT64_MAX: to the end of the content.
+ *  Synchronous; stream ordering as the other compute calls (ZraHipWaitStream). The archive is only read.
+ *  Result, with m = patternSize and [lo, hi) = the range:
+ *  - A match is a content offset p with lo <= p, p + m <= hi and content[p, p + m) == pattern: the whole occurrence lies inside the
+ *    range. Overlapping occurrences are all matches (00 00 00 in 1,000 zero bytes has 998).
+ *  - *nMatches = the number of matches; it may exceed matchCapacity. The first min(*nMatches, matchCapacity) offsets are written to
+ *    hMatches (a HOST array) in ascending order, each exactly once; nothing is written behind them. hMatches may be NULL when
+ *    matchCapacity is 0: a count-only search.
+ *  - On any status other than Success nothing is written to hMatches and *nMatches is 0. No offset reaches the host before the last
+ *    pass is done: a search never reports matches from an archive it could not decode.
+ *  Statuses, checked in this order:
+ *   1. engine, nMatches or hPattern NULL; dArchive NULL with archiveSize != 0; hMatches NULL with matchCapacity != 0; patternSize 0 or
+ *      above ZRA_HIP_SEARCH_MAX_PATTERN -> {ZStdError, 42}.
+ *   2. Header problems: the statuses of ZraHipArchiveOpen (content without frames, i.e. a frame size of 0: HeaderInvalid). The stored
+ *      header CRC-32 is NOT checked here: that is ZraHipVerifyArchive's job.
+ *   3. offset > U, or size != UINT64_MAX and offset + size > U (or a sum that overflows) -> OutOfBoundsAccess. The bound is inclusive, as
+ *      the update's rule 4: a search must be able to reach the last byte. A range shorter than the pattern, the empty range included, is
+ *      Success with 0 matches, and nothing is decoded.
+ *   4. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's (ZraHipReleaseScratch returns it): the staging
+ *      window, a carry area of ZRA_HIP_SEARCH_MAX_PATTERN bytes in front of it, 8 bytes per listed match, 12 bytes per 8 KiB of window
+ *      for the tile tables, the decoder's own scratch for one pass.
+ *   5. A decoded frame that fails: the status ZraHipDecompressRABatch gives under ZRA_HIP_OPT_RA_WHOLE_FRAMES for a query inside that
+ *      frame; of several failing frames, the one with the lowest index (passes run in frame order and the call stops behind the first
+ *      pass with a failing frame).
+ *  Only the frames that intersect [lo, hi) are decoded, each whole, its content checksum verified, in frame order, into a staging
+ *  window of stagingBytes (0: min(65,536 frames, 4 GiB)) in passes of max(1, min(65,536, stagingBytes / frameSize)) frames: the rules
+ *  of ZraHipVerifyArchive. Frames outside the range are not touched; damage there does not disturb the search. Occurrences that
+ *  straddle frames or passes are found: the last m - 1 bytes of a pass are carried in front of the next one, and an occurrence is
+ *  reported by the pass that holds its last byte.
+ *  Cost: the scan reads every decoded byte once from HBM and a few times from LDS; a position whose first min(m, 4) bytes differ from
+ *  the pattern's costs one word compare. The worst case is a pattern that matches everywhere (zeros in zeros): every position then runs
+ *  the full m-byte compare, and every listed match is compared twice. That is accepted; there is no machinery for it.
+ *  Not covered: a handle variant that scans resident frames from the cache of a ZraHipArchive, several patterns per call, regular
+ *  expressions, the shards of a distributed archive (ZraHipShard), the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipSearchArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPattern, size_t patternSize,
+    uint64_t offset, uint64_t size,
+    size_t stagingBytes,
+    uint64_t* hMatches, size_t matchCapacity, uint64_t* nMatches);
+/** The last ZraHipSearchArchive on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, frames decoded, content bytes regenerated, matches, matches listed, decode passes, 0, 0}. Counters,
+ *  not timings. */
+ZRA_EXPORT void ZraHipGetSearchStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugUpdateStageMs: HIP-event time of the last search's scan launches (count, prefix scan, fill, carry),
+ *  summed over its passes; the decode of the same call is in ZraHipGetKernelStats. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugSearchScanMs(ZraHipEngine* engine);
+
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody
  *  (capacity nFrames*ZSTD_compressBound(frameSize)); writes the nFrames local frame sizes (u64, device) to dSizes and the

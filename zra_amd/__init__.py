@@ -140,6 +140,10 @@ def load():
         # verify
         "ZraHipVerifyArchive": (S, [vp, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipFrameFault), sz, szp]),
         "ZraHipGetVerifyStats": (None, [vp, u64p]),
+        # search
+        "ZraHipSearchArchive": (S, [vp, vp, sz, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipGetSearchStats": (None, [vp, u64p]),
+        "ZraHipDebugSearchScanMs": (ctypes.c_double, [vp]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -185,7 +189,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe",
                    "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
                    "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
-                   "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats"]
+                   "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
+                   "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs"]
 
 
 def _chk(st, what=""):
@@ -393,6 +398,30 @@ class Engine:
         self.L.ZraHipGetVerifyStats(self.h, a)
         return dict(zip(VERIFY_STATS, (int(v) for v in a[:7])))
 
+    def search(self, d_archive, size, pattern, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20):
+        """ZraHipSearchArchive: the content offsets at which `pattern` (1 .. SEARCH_MAX_PATTERN bytes, literal) occurs whole inside
+        [offset, offset + length) (None: to the end) of the content of the archive at d_archive. Returns (n_matches, [offsets]): every
+        match is counted, overlapping ones included, and the first max_matches are listed in ascending order. ZraError is a call that
+        could not search (bad header, range outside the content, a frame of the range that does not decode, no memory)."""
+        pattern = bytes(pattern)
+        arr = (ctypes.c_uint64 * max_matches)() if max_matches else None
+        n = ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipSearchArchive(self.h, d_archive or None, size, _cbuf(pattern), len(pattern), offset,
+                                        (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_matches, ctypes.byref(n)),
+             "ZraHipSearchArchive")
+        return n.value, [int(v) for v in arr[:min(n.value, max_matches)]] if arr is not None else []
+
+    def search_stats(self):
+        """Counters of the last search() on this engine (all zero unless it succeeded), keyed by SEARCH_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetSearchStats(self.h, a)
+        return dict(zip(SEARCH_STATS, (int(v) for v in a[:6])))
+
+    def search_scan_ms(self):
+        """bring-up: HIP-event time of the last search()'s scan launches, summed over its passes (its decode: kernel_stats()['dec_ms'])."""
+        return self.L.ZraHipDebugSearchScanMs(self.h)
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
@@ -402,6 +431,9 @@ ARCHIVE_UPDATE_STATS = ("updates", "frames", "archive_bytes", "staged", "refresh
 UPDATE_STATS = ("frames", "touched", "decoded", "compressed", "carried_bytes", "encoded_bytes", "content_bytes", "passes")
 
 VERIFY_STATS = ("frames", "checked", "structure_faults", "content_faults", "decoded", "content_bytes", "passes")
+
+SEARCH_MAX_PATTERN = 256                     # ZRA_HIP_SEARCH_MAX_PATTERN
+SEARCH_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes")
 
 
 class Archive:

@@ -766,6 +766,18 @@ void ZraHipGetVerifyStats(ZraHipEngine* engine, uint64_t* out8) {
   if (!out8) return;
   if (engine) engine->e->verify_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
+ZraStatus ZraHipSearchArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPattern, size_t patternSize, uint64_t offset,
+                              uint64_t size, size_t stagingBytes, uint64_t* hMatches, size_t matchCapacity, uint64_t* nMatches) {
+  if (nMatches) *nMatches = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->search_archive((const uint8_t*)dArchive, archiveSize, hPattern, patternSize, offset, size, stagingBytes, hMatches, matchCapacity,
+                                      nMatches));
+}
+void ZraHipGetSearchStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->search_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugSearchScanMs(ZraHipEngine* engine) { return engine ? engine->e->search_scan_ms() : 0.0; }
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

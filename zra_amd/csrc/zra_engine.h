@@ -154,6 +154,16 @@ class Engine {
   // unless it succeeded
   void verify_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = vstats_[i]; }
 
+  // ---- search (zra_search.hip): every content offset p of [offset, offset + size) (size ~0: to the end) at which the patternSize host
+  // bytes at hPattern occur whole inside the range, ascending. Only the frames of the range are decoded, whole, a staging window at a
+  // time; the window's plaintext is scanned on the device. Statuses and their order: zra_hip.h, ZraHipSearchArchive.
+  Status search_archive(const uint8_t* dArc, size_t arcSize, const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size,
+                        size_t stagingBytes, uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
+  // the last search_archive: {frames, decoded, content bytes regenerated, matches, matches listed, passes, 0, 0}; all zero unless it succeeded
+  void search_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = sstats_[i]; }
+  // bring-up: HIP-event time of the last search's scan launches (count, scan, fill, carry), summed over its passes
+  double search_scan_ms() const { return searchScanMs_; }
+
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
@@ -233,9 +243,17 @@ class Engine {
   struct VerifyScratch { DevBuf plan, stage, faults; };
   VerifyScratch vfy_;
   uint64_t vstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // search scratch (zra_search.hip): the carry area + staging window of one decode pass, the pattern + match count + per-tile tables,
+  // the match list
+  struct SearchScratch { DevBuf stage, tables, list; };
+  SearchScratch srch_;
+  uint64_t sstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipEvent_t evSearch_[2] = {nullptr, nullptr};   // around a pass's scan launches (created by the first search)
+  double searchScanMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
+  friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

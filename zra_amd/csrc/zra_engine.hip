@@ -162,6 +162,7 @@ void Engine::free_scratch() {
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
   for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table, &upd_.copies}) b->release();
   for (DevBuf* b : {&vfy_.plan, &vfy_.stage, &vfy_.faults}) b->release();
+  for (DevBuf* b : {&srch_.stage, &srch_.tables, &srch_.list}) b->release();
 }
 
 Status Engine::release_scratch() {
@@ -186,6 +187,7 @@ Engine::~Engine() {
   if (pinSmall_) (void)hipHostFree(pinSmall_);
   for (auto& ev : evR_) if (ev) (void)hipEventDestroy(ev);
   for (auto ev : evUpd_) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : evSearch_) if (ev) (void)hipEventDestroy(ev);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
   if (evWait_) (void)hipEventDestroy(evWait_);

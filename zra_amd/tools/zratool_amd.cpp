@@ -5,9 +5,11 @@
 //   d   : streaming decompress (FullDecompressor)
 //   imc : in-memory CompressBuffer          imd : in-memory DecompressBuffer
 //   b   : benchmark of all four + one random-access query with a memcmp check
-// and one mode of its own, against include/zra_hip.h:
+// and two modes of its own, against include/zra_hip.h:
 //   t   : test an archive like `zstd -t` (ZraHipVerifyArchive, content verification on the device); one line per faulty frame and a
 //         summary; exit status 0 clean, 1 faults, 2 the call failed
+//   g   : search an archive like `zstdgrep -F -b -o` (ZraHipSearchArchive, decode and scan on the device); one content offset per line
+//         and a summary; exit status as grep: 0 matches, 1 none, 2 trouble
 #include <zra.hpp>
 #include <zra.h>
 #include <zra_hip.h>
@@ -120,6 +122,51 @@ int test_archive(const char* path) {
   std::printf("%s: %llu frames, %llu decoded, %zu faulty: %s\n", path, (unsigned long long)s8[1], (unsigned long long)s8[4], n, n ? "DAMAGED" : "ok");
   return n ? 1 : 0;
 }
+
+// mode g's archive: file -> device memory. false: message printed, nothing held
+bool to_device(const char* path, const zra::Buffer& arc, void** dArc) {
+  *dArc = nullptr;
+  if (arc.empty()) return true;
+  if (hipMalloc(dArc, arc.size()) == hipSuccess && hipMemcpy(*dArc, arc.data(), arc.size(), hipMemcpyHostToDevice) == hipSuccess) return true;
+  std::fprintf(stderr, "%s: no device memory for %zu bytes\n", path, arc.size());
+  if (*dArc) (void)hipFree(*dArc);
+  *dArc = nullptr;
+  return false;
+}
+
+// mode g. The pattern is taken literally; behind a leading "hex:" it is pairs of hex digits.
+int search_archive(const char* path, const char* text) {
+  std::string pat = text;
+  if (pat.rfind("hex:", 0) == 0) {
+    const std::string digits = pat.substr(4);
+    pat.clear();
+    if (digits.size() % 2 || digits.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
+      std::fprintf(stderr, "%s: not pairs of hex digits\n", text);
+      return 2;
+    }
+    for (size_t i = 0; i < digits.size(); i += 2) pat.push_back((char)std::stoul(digits.substr(i, 2), nullptr, 16));
+  }
+  if (pat.empty() || pat.size() > ZRA_HIP_SEARCH_MAX_PATTERN) {
+    std::fprintf(stderr, "a pattern has 1 to %u bytes\n", ZRA_HIP_SEARCH_MAX_PATTERN);
+    return 2;
+  }
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  std::vector<uint64_t> at(1u << 20);
+  uint64_t n = 0;
+  st = ZraHipSearchArchive(eng, dArc, arc.size(), pat.data(), pat.size(), 0, UINT64_MAX, 0, at.data(), at.size(), &n);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot search: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(n, at.size()); i++) std::printf("%llu\n", (unsigned long long)at[i]);
+  if (n > at.size()) std::printf("... and %llu more\n", (unsigned long long)(n - at.size()));
+  std::printf("%llu matches\n", (unsigned long long)n);
+  return n ? 0 : 1;
+}
 }  // namespace
 
 // argv of the reference tool, position by position (zratool.cpp:98-125,213-221):
@@ -129,6 +176,7 @@ int test_archive(const char* path) {
 //   imd {file}                                                               -> {file} without ".zra"
 //   b   {file} {level} {frameSize} {stream buffer MB} {offset = 0x1000} {size = 0x10000}
 // ours: t {file}
+//       g {file} {pattern | hex:digits}
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::printf("%s {mode} {file} ...\n"
@@ -137,12 +185,17 @@ int main(int argc, char** argv) {
                 "d {file} {stream buffer size = 10MB} - Streaming Decompression\n"
                 "imd  {file} - In-memory Decompression\n"
                 "b  {file} {compression level = 3} {frame size = 16384} {stream buffer size = 10MB} {offset = 0x1000} {size = 0x10000} - Benchmark (Memory Intensive)\n"
-                "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n",
+                "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n"
+                "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n",
                 argv[0]);
     return 0;
   }
   const std::string mode = argv[1];
   if (mode == "t") return test_archive(argv[2]);
+  if (mode == "g") {
+    if (argc < 4) { std::fprintf(stderr, "g {file} {pattern | hex:digits}\n"); return 2; }
+    return search_archive(argv[2], argv[3]);
+  }
   const bool comp = mode == "c" || mode == "imc" || mode == "b";
   const zra::i8 level = comp && argc > 3 ? (zra::i8)std::atoi(argv[3]) : 0;
   const zra::u32 frameSize = comp && argc > 4 ? (zra::u32)std::strtoul(argv[4], nullptr, 10) : 16384;
