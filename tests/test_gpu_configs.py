@@ -333,3 +333,77 @@ def test_the_same_calls_give_the_same_bytes_after_release_scratch(zra):
         assert four_calls() == first
     finally:
         eng.close()
+
+
+def test_archive_calls_interleaved_on_one_engine_share_the_staging_window(zra):
+    """Search, verify, update and batched random access keep their staged plaintext in ONE window of the engine, sliced at the frame size
+    of the archive at hand. On one engine the calls alternate between an archive of 4,096-byte frames and one of 1,000-byte frames (70
+    frames each, the last one short, checksums on), so every call finds the window as another call, at another stride, left it; then the
+    scratch is handed back and the sequence runs again in reverse. Yardsticks: the plaintext (search_model, slices), DecompressBuffer of
+    an update's result, and for verify the one frame of a third copy whose payload the test damaged."""
+    import search_model as SM
+    import verify_model as VM
+    from test_gpu_update import _compress, _dev, _patched, _touched, _update
+    from test_gpu_verify import _flip_mid, _verify
+    eng = zra.Engine(0)
+    rng = np.random.RandomState(19)
+    arcs = []
+    for fs, U in ((4096, 69 * 4096 + 1234), (1000, 69 * 1000 + 321)):
+        data = rng.randint(0, 4, size=U).astype(np.uint8).tobytes()            # 64 possible 3-byte strings: hundreds of occurrences
+        arc = _compress(eng, zra, data, 3, fs, True)
+        a = dict(fs=fs, U=U, data=data, arc=arc, d=_dev(arc), short=data[fs - 1:fs + 2], big=data[3 * fs - 100:3 * fs + 156])
+        assert VM.fields(arc)[2] == 70 and any(p % fs > fs - 3 for p in SM.matches(data, a["short"]))   # 70 frames; a match across a seam
+        arcs.append(a)
+    bad_frame = 41
+    bad = _flip_mid(arcs[1]["arc"], [bad_frame])
+    d_bad = _dev(bad)
+
+    def search(a, pat, staging, passes):
+        want = SM.matches(a["data"], pat)
+        assert eng.search(a["d"].data_ptr(), len(a["arc"]), pat, staging_bytes=staging) == (len(want), want) and want, (a["fs"], staging)
+        s = eng.search_stats()
+        assert s == dict(frames=70, decoded=70, content_bytes=a["U"], matches=len(want), listed=len(want), passes=passes), (a["fs"], staging, s)
+
+    def verify(a, staging, passes):
+        assert _verify(eng, a["arc"], a["d"], content=True, staging_bytes=staging) == ((0, 0), 0, []), (a["fs"], staging)
+        s = eng.verify_stats()
+        assert s == dict(frames=70, checked=70, structure_faults=0, content_faults=0, decoded=70, content_bytes=a["U"], passes=passes), (a["fs"], staging, s)
+        if a["fs"] == 1000:
+            st, n, faults = _verify(eng, bad, d_bad, content=True, staging_bytes=staging)
+            assert (st, n) == ((0, 0), 1) and [(f, stage) for f, _, stage in faults] == [(bad_frame, VM.CONTENT)] and faults[0][1] != 0, (staging, st, faults)
+            s = eng.verify_stats()
+            assert (s["frames"], s["checked"], s["structure_faults"], s["content_faults"], s["decoded"], s["passes"]) == (70, 70, 0, 1, 70, passes), s
+
+    def update(a):
+        fs, U = a["fs"], a["U"]
+        writes, append = [(5 * fs - 7, b"\x07" * 20)], bytes(range(200, 250)) * (fs // 50 + 1)     # across frames 4 | 5; a frame and a bit more
+        st, out, size = _update(eng, zra, a["arc"], writes, append, d_arc=a["d"])
+        assert st == (0, 0) and zra.DecompressBuffer(out[:size]) == _patched(a["data"], writes, append), (fs, st)
+        s = eng.update_stats()
+        touched = _touched(writes, append, U, fs)
+        assert touched == {4, 5, 69, 70}
+        # frames 4, 5 and the old last frame keep old bytes: decoded; frame 70 is all new
+        assert (s["frames"], s["touched"], s["decoded"], s["compressed"], s["content_bytes"], s["passes"]) == (71, 4, 3, 4, 20 + len(append), 1), (fs, s)
+
+    def read(a):
+        import torch
+        fs, U = a["fs"], a["U"]
+        offs, sizes = [3 * fs - 10, U - 101], [30, 100]                         # across frames 2 | 3; up to the last byte but one
+        d_out = torch.zeros(130, dtype=torch.uint8, device="cuda:0")
+        eng.decompress_ra_batch(a["d"].data_ptr(), len(a["arc"]), d_out.data_ptr(), offs, sizes, [0, 30])
+        assert d_out.cpu().numpy().tobytes() == a["data"][offs[0]:offs[0] + 30] + a["data"][U - 101:U - 1], fs
+        assert eng.kernel_stats()["dec_launches"] >= 1
+
+    steps = [lambda a: search(a, a["short"], 1, 70), lambda a: verify(a, 1, 70), update, read,
+             lambda a: search(a, a["short"], 0, 1), lambda a: verify(a, 0, 1),
+             lambda a: search(a, a["big"], 3 * a["fs"], 24)]                    # 256 bytes: the carry area in front of slot 0 is full
+    try:
+        for step in steps:
+            for a in arcs:
+                step(a)
+        eng.release_scratch()
+        for step in reversed(steps):
+            for a in reversed(arcs):
+                step(a)
+    finally:
+        eng.close()

@@ -30,6 +30,7 @@ class ArchiveCache {
  private:
   ArchiveCache() = default;
   static const uint32_t* update_table(void* ctx, uint32_t frames);   // UpdCacheView::table
+  ArchiveView view() const { return ArchiveView::over(h_, dArc_, arcSize_); }   // the archive the handle serves now, its header checked at open / by the update
   Status read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
   Engine* e_ = nullptr;
   const uint8_t* dArc_ = nullptr;

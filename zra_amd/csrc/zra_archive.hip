@@ -38,20 +38,11 @@ extern "C" __global__ void __launch_bounds__(256) zra_cache_lookup_kernel(const 
                                                                         const u8* arena, u8* out, u32* cnt, u32* seen, u32* words) {
   const int lane = (int)(threadIdx.x & 63);
   for (u64 s = (u64)blockIdx.x * 4 + (threadIdx.x >> 6); s < nSlices; s += (u64)gridDim.x * 4) {
-    // the query that holds slice s: the last one whose first slice is <= s (a query of size 0 owns no slice)
-    u32 lo = 0, hi = nq - 1;
-    while (lo < hi) {
-      const u32 mid = lo + (hi - lo + 1) / 2;
-      if (q[4 * (size_t)mid + 3] <= s) lo = mid; else hi = mid - 1;
-    }
-    const u64 off = q[4 * (size_t)lo], size = q[4 * (size_t)lo + 1], dst = q[4 * (size_t)lo + 2], k = s - q[4 * (size_t)lo + 3];
-    const u64 f0 = off / fs, f = f0 + k, head = off - f0 * fs;
-    const u32 srcOff = k ? 0u : (u32)head;
-    const u64 done = k ? (fs - head) + (k - 1) * fs : 0;
-    const u32 len = (u32)min<u64>(fs - srcOff, size - done);
+    const Slice c = slice_of(q, nq, s, fs);
+    const u64 f = c.frame;
     const u32 v = slotOf[f];
     if (v != kNone) {
-      copy_slice(out + dst + done, arena + (u64)v * fs + srcOff, len, lane);
+      copy_slice(out + c.user, arena + (u64)v * fs + c.inFrame, c.len, lane);
       if (lane == 0) {
         if (!ref[v]) ref[v] = 1;
         if (atomicExch(&seen[f], 1u) == 0) atomicAdd(&words[1], 1u);
@@ -240,7 +231,7 @@ Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* h
   if (!slots_) {
     // no cache: the batch call itself, header read and checked at open
     E.set_ra_verify_whole_frames(wholeFramesOpt);
-    Status st = E.ra_batch_body(dArc_, h_, dArc_ + h_.size, arcSize_ - h_.size, 0, dOut, hOff, hSize, hOutOff, nq);
+    Status st = E.ra_batch_body(view(), dOut, hOff, hSize, hOutOff, nq);
     if (st.zra == kOutOfBounds) return st;
     reads_++;
     const uint64_t fs = h_.frameSize;
@@ -256,18 +247,19 @@ Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* h
     }
     return st;
   }
-  E.kstats_[4] = E.kstats_[5] = 0; for (auto& d : E.dstats_) d = 0;
+  E.reset_decode_stats();
   return read_cached(dOut, hOff, hSize, hOutOff, nq);
 }
 
 Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
   Engine& E = *e_;
   hipStream_t s = E.stream_;
-  const uint64_t fs = h_.frameSize, U = h_.uncompressedSize;
-  const uint32_t nF = nFrames_;
+  const ArchiveView a = view();
+  const uint64_t fs = a.fs, U = a.U;
+  const uint32_t nF = a.frames;
   if (nq == 0) { reads_++; return ok(); }
   uint64_t nSlices = 0;
-  { Status st = E.ra_walk_queries(h_, hOff, hSize, hOutOff, nq, &nSlices); if (st.zra) return st; }
+  { Status st = E.ra_walk_queries(a, hOff, hSize, hOutOff, nq, &nSlices); if (st.zra) return st; }
   reads_++;
   if (nSlices == 0) { HIPCHK_CLR(hipStreamSynchronize(s)); return ok(); }
   // the batch's planner scratch (the lookup's two result words inside its totals), then seen[nFrames]: one memset
@@ -294,10 +286,8 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
   const uint32_t V = std::min(missed, maxPass_);
   hipLaunchKernelGGL(zra_cache_victims_kernel, dim3(1), dim3(1024), 0, s, slotOf_, frameOf_, ref_, hand_, dctr_, slots_, V, victim_, 0u);
   uint32_t totals[2];
-  Status fail = E.ra_plan_fill(plan, nq, nF, dArc_ + h_.seekTableOffset, 0, fs, U, V, true, victim_, totals);
+  Status fail = E.ra_plan_fill(plan, nq, a, V, true, victim_, totals);
   const uint32_t jobs = fail.zra ? 0u : totals[0];
-  const uint8_t* dBody = dArc_ + h_.size;
-  const uint64_t bodyBytes = arcSize_ - h_.size;
   ZraDecodeArgs ra{};
   ra.pieces = E.raPieces_.as<ZraRaPiece>(); ra.raOut = dOut;
   const uint32_t commitGrid = (std::max(nF, V) + 255) / 256;
@@ -305,7 +295,7 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
     const uint32_t n = std::min(V, jobs - s0);
     if (s0) hipLaunchKernelGGL(zra_cache_victims_kernel, dim3(1), dim3(1024), 0, s, slotOf_, frameOf_, ref_, hand_, dctr_, slots_, V, victim_, 1u);
     ra.limit = E.raLimit_.as<uint32_t>() + s0; ra.pieceBase = E.raPieceBase_.as<uint32_t>() + s0;
-    fail = E.decode_jobs(dBody, bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)s0, arena_, E.outOff_.as<uint64_t>() + s0,
+    fail = E.decode_jobs(a.body, a.bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)s0, arena_, E.outOff_.as<uint64_t>() + s0,
                          E.expect_.as<uint32_t>() + s0, n, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2, 0, &ra);
     hipLaunchKernelGGL(zra_cache_commit_kernel, dim3(commitGrid), dim3(256), 0, s, P.cnt, P.slot, nF, s0, n, victim_, V,
                        E.status_.as<uint32_t>(), E.produced_.as<uint32_t>(), fail.zra ? 0u : 1u, (u64)fs, (u64)U, slotOf_, frameOf_, ref_, dctr_);
@@ -323,7 +313,7 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
     // itself is asked; the frames it decodes are the same, whole.
     const bool was = E.ra_verify_whole_frames();
     E.set_ra_verify_whole_frames(true);
-    const Status st2 = E.ra_batch_body(dArc_, h_, dBody, bodyBytes, 0, dOut, hOff, hSize, hOutOff, nq);
+    const Status st2 = E.ra_batch_body(a, dOut, hOff, hSize, hOutOff, nq);
     E.set_ra_verify_whole_frames(was);
     if (st2.zra) return st2;
   }

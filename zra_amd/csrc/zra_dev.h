@@ -75,6 +75,27 @@ __device__ __forceinline__ void copy_slice(u8* dst, const u8* src, u32 n, int la
   for (u32 i = lane; i < n16; i += 64) d4[i] = s4[i];
   for (u32 i = head + (n16 << 4) + lane; i < n; i += 64) dst[i] = src[i];
 }
+// entry f of a seek table: 5 bytes, the 40-bit offset of frame f in the archive's body (entry `frames` = the body's length)
+__device__ __forceinline__ u64 seek_entry(const u8* table, u64 f) { const u8* e = table + (size_t)f * 5; return (u64)ld32(e) | ((u64)e[4] << 32); }
+// slice s (the part of a tuple's range inside one frame) of the tuples q, 4 words each: content offset, size, offset in the caller's buffer,
+// first slice. Its tuple, frame, start inside the frame, length, and place in the caller's buffer (a read's destination, a write's source)
+struct Slice { u32 tuple; u64 frame; u32 inFrame; u32 len; u64 user; };
+__device__ __forceinline__ Slice slice_of(const u64* q, u32 nq, u64 s, u64 fs) {
+  u32 lo = 0, hi = nq - 1;                                            // the last tuple whose first slice is <= s
+  while (lo < hi) {
+    const u32 mid = lo + (hi - lo + 1) / 2;
+    if (q[4 * (size_t)mid + 3] <= s) lo = mid; else hi = mid - 1;
+  }
+  const u64 off = q[4 * (size_t)lo], size = q[4 * (size_t)lo + 1], k = s - q[4 * (size_t)lo + 3];
+  const u64 f0 = off / fs, head = off - f0 * fs;
+  Slice r;
+  r.tuple = lo; r.frame = f0 + k;
+  r.inFrame = k ? 0u : (u32)head;
+  const u64 done = k ? (fs - head) + (k - 1) * fs : 0;
+  r.len = (u32)min<u64>(fs - r.inFrame, size - done);
+  r.user = q[4 * (size_t)lo + 2] + done;
+  return r;
+}
 struct __attribute__((packed, aligned(1))) u128_u { u32 a, b, c, d; };
 __device__ __forceinline__ void st128(u8* p, u32 a, u32 b, u32 c, u32 d) { u128_u v; v.a = a; v.b = b; v.c = c; v.d = d; *(u128_u*)p = v; }
 

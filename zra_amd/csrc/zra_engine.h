@@ -33,6 +33,31 @@ struct HeaderInfo {
 };
 // parse the 38 fixed bytes; returns a ZRA status code (0 ok)
 int parse_fixed_header(const uint8_t* fixed38, HeaderInfo* h);
+// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search): the checked header and
+// where its parts lie. Built once per call, by Engine::archive_view or, from a header checked before (a handle's), by `over`. A shard of
+// a distributed archive (zra_comm.hip) overrides body / bodyBytes with the bytes [bodyBase, bodyBase + bodyBytes) of the body it holds.
+struct ArchiveView {
+  HeaderInfo h{};
+  const uint8_t* table = nullptr, * body = nullptr;   // seek table (frames + 1 entries of 5 bytes), compressed frames
+  uint64_t bodyBytes = 0, bodyBase = 0;
+  uint32_t frames = 0;
+  uint64_t fs = 0, U = 0;            // frame size, uncompressed size
+  static ArchiveView over(const HeaderInfo& h, const uint8_t* dArc, size_t arcSize) {
+    ArchiveView a;
+    a.h = h; a.table = dArc + h.seekTableOffset; a.body = dArc + h.size; a.bodyBytes = arcSize - h.size; a.frames = h.frames(); a.fs = h.frameSize; a.U = h.uncompressedSize;
+    return a;
+  }
+};
+// Slots of one staged pass (whole frames, slot s at s * frameSize of the staging window): at most kPassFrames (one internal pass of
+// Engine::decode_jobs) and what fits stagingBytes (0: kStageBytes, which 65,536 frames of the headline 64 KiB fill exactly), at least one.
+constexpr uint32_t kPassFrames = 1u << 16;
+constexpr uint64_t kStageBytes = 4ull << 30;
+inline uint32_t pass_slots(uint64_t fs, uint64_t stagingBytes = 0, uint64_t maxFrames = kPassFrames) {
+  const uint64_t fit = (stagingBytes ? stagingBytes : kStageBytes) / (fs ? fs : 1);
+  return (uint32_t)(fit < 1 ? 1 : fit < maxFrames ? fit : maxFrames);
+}
+// the code a failing frame is reported with: 255 (the decoder's own "regenerated another size than its slot") is corruption_detected
+__host__ __device__ inline int reported_code(unsigned long long firstError) { const int c = (int)(firstError & 0xFF); return c == 255 ? 20 : c; }
 // An update through an archive handle (zra_archive.hip, ZraHipArchiveUpdate): what the handle lends to Engine::update_archive and what
 // comes back.
 struct UpdCacheView {
@@ -105,14 +130,24 @@ class Engine {
   }
   Status decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
                                    const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
-  // pieces of the batch, shared with the archive handle (zra_archive.hip): the header read + checks, the walk over the host query
-  // arrays (bounds, tuples uploaded to the device), the planner of the decode jobs, and the batch behind an already checked header
+  // pieces of the batch, shared with the other device-archive calls: the header read + checks and the view they give, the walk over the
+  // host query arrays (bounds, tuples uploaded to the device), the planner of the decode jobs, the batch behind an already checked header
   Status ra_header(const uint8_t* dArc, size_t arcSize, HeaderInfo* h);
-  Status ra_walk_queries(const HeaderInfo& h, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces);
-  Status ra_plan_fill(uint32_t* plan, size_t nq, uint32_t nFrames, const uint8_t* table, uint64_t bodyBase, uint64_t fs, uint64_t U,
-                      uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]);
-  Status ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
-                       const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
+  Status archive_view(const uint8_t* dArc, size_t arcSize, ArchiveView* a) {
+    HeaderInfo h; const Status st = ra_header(dArc, arcSize, &h); if (!st.zra) *a = ArchiveView::over(h, dArc, arcSize); return st;
+  }
+  Status ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces);
+  Status ra_plan_fill(uint32_t* plan, size_t nq, const ArchiveView& a, uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]);
+  Status ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
+  // tuples [q0, q1) of pinQ_ (pinned_tuples) -> qmeta_, queued on the stream; the caller writes and sends them kTupleChunk at a time
+  static constexpr size_t kTupleChunk = 1u << 17;
+  Status upload_tuples(size_t q0, size_t q1) {
+    if (hipMemcpyAsync(qmeta_.as<uint64_t>() + 4 * q0, pinQ_ + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, stream_) == hipSuccess) return ok();
+    (void)hipGetLastError(); return zerr(1);
+  }
+  // One staged pass (verify, search): jobs [j0, j0 + n) of frameOff_ / expect_ decoded whole, checksums verified, into `window`, job j0 + k at
+  // outOff_[k] (the same slots every pass). *firstError = decode_pass' word (~0: none failed); status_ / produced_: every job's own. Synchronised.
+  Status staged_pass(const ArchiveView& a, uint32_t j0, uint32_t n, uint8_t* window, unsigned long long* firstError);
   // Host-walked frame list (reference semantics of DecompressBuffer: seek table not consulted). hFrameOff has nFrames+1 entries
   // relative to dBody; frames are assumed to regenerate frameSize bytes each (last: the remainder of total).
   Status decompress_frames_host_list(const uint8_t* dBody, uint64_t bodySize, const std::vector<uint64_t>& hFrameOff,
@@ -205,6 +240,13 @@ class Engine {
   Status upload_jobs(const std::vector<uint64_t>& frameOff, const std::vector<uint64_t>& outOff, const std::vector<uint32_t>& expect);
   Status read_fixed_header(const uint8_t* dArc, size_t arcSize, HeaderInfo* h);   // copy-back + parse_fixed_header + the two size checks
   uint64_t* pinned_tuples(size_t nTuples);   // pinQ_ grown to 4 words per tuple; nullptr: no memory
+  void reset_decode_stats() { kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0; }
+  // milliseconds between two recorded and completed events; 0 (and the runtime's error cleared) when they cannot be had
+  static float elapsed_ms(hipEvent_t e0, hipEvent_t e1) { float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { ms = 0; (void)hipGetLastError(); } return ms; }
+  bool call_events() {                       // evCall_ created on first use; false: the runtime refused (error cleared)
+    for (auto& ev : evCall_) if (!ev && hipEventCreate(&ev) != hipSuccess) { ev = nullptr; (void)hipGetLastError(); return false; }
+    return true;
+  }
   void free_scratch();                       // every DevBuf of the engine handed back: release_scratch() and the destructor
   hipEvent_t evR_[17] = {nullptr};   // per-round events of one encode batch: e[2r] before mf, e[2r+1] between, e[2r+2] after entropy
   // decode scratch
@@ -215,7 +257,13 @@ class Engine {
   uint64_t* pinQ_ = nullptr; size_t pinQCap_ = 0;   // page-locked query tuples of the running batch (host side of an asynchronous copy)
   int decOccParse_ = 0, decOccExec_ = 0, decOccHuf_ = 0; // resident workgroups per CU of the parse / execute kernels
   bool raVerifyWholeFrames_ = false;     // batched random access decodes every touched frame in full and checks its checksum
-  DevBuf status_, produced_, frameMeta_, frameOff_, outOff_, expect_, result_, temp_, qmeta_;
+  DevBuf status_, produced_, frameMeta_, frameOff_, outOff_, expect_, result_, qmeta_;
+  // THE plaintext staging window of the device-archive calls (batch, update, verify, search): whole frames of one decode pass, slot s at
+  // s * frameSize; the search keeps its carry area in front of slot 0. Every engine call runs on stream_ and returns synchronised, so one
+  // window is live at a time. THE RULE: a call reserves the window once, before it takes a pointer into it (reserve may move the buffer),
+  // and from there to its last use calls nothing that reserves it. decode_jobs / decode_pass / staged_pass and compress_frames do not
+  // (decoder and encoder scratch). The handle's read and update call ra_batch_body / update_archive, which do, but hold no window then.
+  DevBuf stage_;
   // encode scratch (see zra_encode.hip)
   struct EncCtx { DevBuf tables, seqs, lits, work, slots, misc, ck, sizes, rec; };   // rec: the split entropy stage's per-frame records (ZraEntRec)
   EncCtx encCtx_[2];
@@ -232,23 +280,19 @@ class Engine {
   uint64_t lastProducedTotal_ = ~0ull;     // whole-archive decode that fell back to the sequential tail: bytes actually regenerated
   void* encCounters_ = nullptr; size_t encCountersBytes_ = 0;   // sub-batch counters stream B may be waiting on (drain_after_error)
   int waitValueOk_ = 0;                    // 0 unknown, 1 hipStreamWaitValue32 works on device memory, -1 it does not (batch path)
-  // update scratch (zra_update.hip): per-frame plan words, plaintext staging of one pass, the packed newly encoded frames, their sizes,
+  // update scratch (zra_update.hip): per-frame plan words, the packed newly encoded frames, their sizes,
   // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
-  struct UpdScratch { DevBuf plan, stage, packed, encSizes, frames, table, copies; };
-  UpdScratch upd_;
+  struct UpdScratch { DevBuf plan, packed, encSizes, frames, table, copies; } upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipEvent_t evUpd_[2] = {nullptr, nullptr};   // around a pass's stage-from-cache kernel (created by the first update through a handle)
+  // around a pass's stage-from-cache kernel (update through a handle) or scan launches (search); the two never run inside each other
+  hipEvent_t evCall_[2] = {nullptr, nullptr};
   double updStageMs_ = 0;
-  // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the staging window of one decode pass, the fault list
-  struct VerifyScratch { DevBuf plan, stage, faults; };
-  VerifyScratch vfy_;
+  // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list
+  struct VerifyScratch { DevBuf plan, faults; } vfy_;
   uint64_t vstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // search scratch (zra_search.hip): the carry area + staging window of one decode pass, the pattern + match count + per-tile tables,
-  // the match list
-  struct SearchScratch { DevBuf stage, tables, list; };
-  SearchScratch srch_;
+  // search scratch (zra_search.hip): the pattern + match count + per-tile tables, the match list
+  struct SearchScratch { DevBuf tables, list; } srch_;
   uint64_t sstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hipEvent_t evSearch_[2] = {nullptr, nullptr};   // around a pass's scan launches (created by the first search)
   double searchScanMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)

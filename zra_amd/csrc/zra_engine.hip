@@ -50,10 +50,7 @@ namespace {
 __global__ void zra_jobs_from_seektable_kernel(const u8* table, u32 nFrames, u32 frameSize, u64 total,
                                                u64* frameOff, u64* outOff, u32* expect) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= nFrames) {
-    const u8* e = table + (size_t)i * 5;
-    frameOff[i] = (u64)ld32(e) | ((u64)e[4] << 32);
-  }
+  if (i <= nFrames) frameOff[i] = seek_entry(table, i);
   if (i < nFrames) {
     // a frame whose slot starts at or beyond the declared size gets no room at all (an inflated tableSize or a shrunk
     // uncompressedSize in a crafted header): the decoder then reports dstSize_tooSmall for it, like the reference's single
@@ -157,12 +154,11 @@ Status Engine::create(Engine** out, int device) {
 
 void Engine::free_scratch() {
   for (DevBuf* b : {&raPlan_, &raLimit_, &raPieceBase_, &raPieces_, &decFrames_, &decTables_, &decLists_, &decCounters_, &decLits_, &decSeqs_, &roundN_, &status_,
-                    &produced_, &frameMeta_, &frameOff_, &outOff_, &expect_, &result_, &temp_, &qmeta_, &encScan_, &hostIn_, &hostOut_, &seqScratch_, &mfFlags_, &decBlkRecs_, &decBlkTables_, &decBlkLists_})
+                    &produced_, &frameMeta_, &frameOff_, &outOff_, &expect_, &result_, &stage_, &qmeta_, &encScan_, &hostIn_, &hostOut_, &seqScratch_, &mfFlags_, &decBlkRecs_, &decBlkTables_, &decBlkLists_})
     b->release();
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
-  for (DevBuf* b : {&upd_.plan, &upd_.stage, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table, &upd_.copies}) b->release();
-  for (DevBuf* b : {&vfy_.plan, &vfy_.stage, &vfy_.faults}) b->release();
-  for (DevBuf* b : {&srch_.stage, &srch_.tables, &srch_.list}) b->release();
+  for (DevBuf* b : {&upd_.plan, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table, &upd_.copies}) b->release();
+  for (DevBuf* b : {&vfy_.plan, &vfy_.faults, &srch_.tables, &srch_.list}) b->release();
 }
 
 Status Engine::release_scratch() {
@@ -186,8 +182,7 @@ Engine::~Engine() {
   if (pinQ_) (void)hipHostFree(pinQ_);
   if (pinSmall_) (void)hipHostFree(pinSmall_);
   for (auto& ev : evR_) if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : evUpd_) if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : evSearch_) if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : evCall_) if (ev) (void)hipEventDestroy(ev);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
   if (evWait_) (void)hipEventDestroy(evWait_);
@@ -446,6 +441,17 @@ Status Engine::decode_pass(const ZraDecodeArgs& b, const uint32_t* dExpect, uint
   return decode_launch(b, dExpect, maxFrameBytes, jobBase, res);
 }
 
+Status Engine::staged_pass(const ArchiveView& a, uint32_t j0, uint32_t n, uint8_t* window, unsigned long long* firstError) {
+  lastProducedTotal_ = ~0ull;
+  if (!result_.reserve(64)) return zerr(64);
+  HIPCHK_CLR(hipMemsetAsync(result_.p, 0xFF, 64, stream_));
+  ZraDecodeArgs b{};
+  b.body = a.body; b.bodySize = a.bodyBytes; b.out = window; b.offStride = 2; b.nFrames = n;
+  b.frameOff = frameOff_.as<uint64_t>() + 2 * (size_t)j0; b.outOff = outOff_.as<uint64_t>(); b.outCap = expect_.as<uint32_t>() + j0;
+  *firstError = ~0ull;
+  return decode_pass(b, b.outCap, (uint32_t)std::min<uint64_t>(a.fs, 0xFFFFFFFFu), 0, firstError);
+}
+
 // seqTotal == 0: every frame owns its slot (random access: the reference decodes the touched frames into frameSize buffers).
 // seqTotal != 0: whole-archive semantics of ONE multi-frame zstd call over `seqTotal` bytes of destination (zra.cpp:249): frames are
 // decoded side by side into their nominal slots; if one regenerates another size than its slot (only possible for a corrupted or
@@ -484,7 +490,7 @@ Status Engine::decode_jobs(const uint8_t* dBody, uint64_t bodySize, const uint64
   if (res == ~0ull) return ok();
   const uint32_t code = (uint32_t)(res & 0xFF), first = (uint32_t)(res >> 8);
   const bool resize = code == 255 /* ZE_SIZE_MISMATCH */ || code == 70;
-  if (!seqTotal || !resize) return zerr(code == 255 ? 20 : (int)code);
+  if (!seqTotal || !resize) return zerr(reported_code(res));
   return decode_sequential_tail(a, dFrameOff, offStride, dOutOff, first, nFrames, maxFrameBytes, seqTotal);
 }
 
@@ -567,7 +573,7 @@ Status Engine::read_fixed_header(const uint8_t* dArc, size_t arcSize, HeaderInfo
 
 Status Engine::decompress_device(const uint8_t* dArc, size_t arcSize, uint8_t* dOut, size_t outCap) {
   HIPCHK(hipSetDevice(device_));
-  kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0;
+  reset_decode_stats();
   HeaderInfo h;
   { Status st = read_fixed_header(dArc, arcSize, &h); if (st.zra) return st; }
   if (outCap < h.uncompressedSize) return {kOutputTooSmall, 0};            // zra.cpp:245-246

@@ -33,8 +33,7 @@ __global__ void zra_ra_count_kernel(const u64* q, u32 nq, u64 fs, RaPlan P) {
 // body: a shard of a distributed archive holds its own frames only); a span that starts before them comes out inverted (refused as
 // srcSize_wrong by the decoder, like any span outside the buffer)
 __device__ __forceinline__ void ra_frame_span(const u8* table, u64 f, u64 bodyBase, u64* so, u64* se) {
-  const u8* e = table + (size_t)f * 5;
-  const u64 a = (u64)ld32(e) | ((u64)e[4] << 32), b = (u64)ld32(e + 5) | ((u64)e[9] << 32);
+  const u64 a = seek_entry(table, f), b = seek_entry(table, f + 1);
   if (a < bodyBase || b < bodyBase) { *so = 1; *se = 0; }
   else { *so = a - bodyBase; *se = b - bodyBase; }
 }
@@ -151,9 +150,9 @@ uint64_t* Engine::pinned_tuples(size_t nTuples) {
 // overflow-safe), the slices (one per frame a query touches) and the (offset, size, destination, first slice) tuples the device
 // kernels read — written straight into page-locked memory, so that their copy (into qmeta_) runs at bus speed beside the launches that
 // follow. *maxPieces = the slices; 0 when there is nothing to decode (the copies may still be in flight: the caller synchronises).
-Status Engine::ra_walk_queries(const HeaderInfo& h, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces) {
-  const uint32_t nFrames = h.frames();
-  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+Status Engine::ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces) {
+  const uint32_t nFrames = a.frames;
+  const uint64_t fs = a.fs, U = a.U;
   *maxPieces = 0;
   if (nq > 0xFFFFFFF0ull) return zerr(64);
   uint64_t* const hq = pinned_tuples(nq);
@@ -166,16 +165,15 @@ Status Engine::ra_walk_queries(const HeaderInfo& h, const uint64_t* hOff, const 
     return ok();
   }
   if (!qmeta_.reserve(4 * nq * 8 + 64)) return zerr(64);
-  constexpr size_t kChunk = 1u << 17;                   // tuples go to the device while the next ones are being written
-  for (size_t q0 = 0; q0 < nq; q0 += kChunk) {
-    const size_t q1 = std::min(nq, q0 + kChunk);
+  for (size_t q0 = 0; q0 < nq; q0 += kTupleChunk) {     // tuples go to the device while the next ones are being written
+    const size_t q1 = std::min(nq, q0 + kTupleChunk);
     for (size_t q = q0; q < q1; q++) {
       const uint64_t o = hOff[q], z = hSize[q];
       if (z >= U || o >= U - z) { (void)hipStreamSynchronize(stream_); return {kOutOfBounds, 0}; }
       hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = hOutOff[q]; hq[4 * q + 3] = pieces;
       if (z) pieces += pow2 ? ((o + z - 1) >> fsLog) - (o >> fsLog) + 1 : (o + z - 1) / fs - o / fs + 1;
     }
-    HIPCHK(hipMemcpyAsync(qmeta_.as<uint64_t>() + 4 * q0, hq + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, stream_));
+    { Status st = upload_tuples(q0, q1); if (st.zra) return st; }
   }
   *maxPieces = pieces;
   return ok();
@@ -183,13 +181,12 @@ Status Engine::ra_walk_queries(const HeaderInfo& h, const uint64_t* hOff, const 
 
 // dense job numbers, decode jobs and piece lists of the frames counted in plan (a RaPlan's scratch) from the query tuples in qmeta_;
 // totals = {jobs, pieces}. victim: see zra_ra_plan_kernel (nullptr: scratch window).
-Status Engine::ra_plan_fill(uint32_t* plan, size_t nq, uint32_t nFrames, const uint8_t* table, uint64_t bodyBase, uint64_t fs, uint64_t U,
-                            uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]) {
-  const RaPlan P = RaPlan::over(plan, nFrames);
-  hipLaunchKernelGGL(zra_ra_plan_kernel, dim3(1), dim3(1024), 0, stream_, P, nFrames, table, (u64)bodyBase, (u64)fs, (u64)U, passSlots,
+Status Engine::ra_plan_fill(uint32_t* plan, size_t nq, const ArchiveView& a, uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]) {
+  const RaPlan P = RaPlan::over(plan, a.frames);
+  hipLaunchKernelGGL(zra_ra_plan_kernel, dim3(1), dim3(1024), 0, stream_, P, a.frames, a.table, (u64)a.bodyBase, (u64)a.fs, (u64)a.U, passSlots,
                      fullFrames ? 1u : 0u, frameOff_.as<uint64_t>(), outOff_.as<uint64_t>(), expect_.as<uint32_t>(), raLimit_.as<uint32_t>(),
                      raPieceBase_.as<uint32_t>(), victim);
-  hipLaunchKernelGGL(zra_ra_fill_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, qmeta_.as<uint64_t>(), (u32)nq, (u64)fs, P,
+  hipLaunchKernelGGL(zra_ra_fill_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, qmeta_.as<uint64_t>(), (u32)nq, (u64)a.fs, P,
                      raPieceBase_.as<uint32_t>(), raPieces_.as<ZraRaPiece>());
   totals[0] = totals[1] = 0;
   HIPCHK(hipMemcpyAsync(totals, P.totals, 8, hipMemcpyDeviceToHost, stream_));
@@ -203,30 +200,28 @@ Status Engine::ra_plan_fill(uint32_t* plan, size_t nq, uint32_t nFrames, const u
 Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
                                          const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
   HIPCHK(hipSetDevice(device_));
-  kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0;
-  HeaderInfo h;
-  { Status st = ra_header(dArc, arcSize, &h); if (st.zra) return st; }
-  if (!dBody) { dBody = dArc + h.size; bodyBytes = arcSize - h.size; bodyBase = 0; }
-  return ra_batch_body(dArc, h, dBody, bodyBytes, bodyBase, dOut, hOff, hSize, hOutOff, nq);
+  reset_decode_stats();
+  ArchiveView a;
+  { Status st = archive_view(dArc, arcSize, &a); if (st.zra) return st; }
+  if (dBody) { a.body = dBody; a.bodyBytes = bodyBytes; a.bodyBase = bodyBase; }
+  return ra_batch_body(a, dOut, hOff, hSize, hOutOff, nq);
 }
 
 // the batch behind a header that has been read and checked (ra_header): the archive handle without slots comes here directly
-Status Engine::ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uint8_t* dBody, uint64_t bodyBytes, uint64_t bodyBase, uint8_t* dOut,
-                             const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+Status Engine::ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
   RaTrace trace{"  ra", 14};
   HIPCHK(hipSetDevice(device_));
-  kstats_[4] = kstats_[5] = 0; for (auto& d : dstats_) d = 0;
+  reset_decode_stats();
   trace.mark("header read");
-  const uint32_t nFrames = h.frames();
-  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  const uint32_t nFrames = a.frames;
+  const uint64_t fs = a.fs, U = a.U;
   if (nq == 0) return ok();
   uint64_t maxPieces = 0;
-  { Status st = ra_walk_queries(h, hOff, hSize, hOutOff, nq, &maxPieces); if (st.zra) return st; }
+  { Status st = ra_walk_queries(a, hOff, hSize, hOutOff, nq, &maxPieces); if (st.zra) return st; }
   if (fs == 0 || nFrames == 0) return ok();
   if (maxPieces == 0) { HIPCHK(hipStreamSynchronize(stream_)); return ok(); }
   trace.mark("queries");
-  const uint64_t tempBudget = 16ull << 30;
-  const uint32_t passSlots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nFrames, tempBudget / fs));
+  const uint32_t passSlots = pass_slots(fs, 16ull << 30, nFrames);    // (the batch's own bounds: 16 GiB, every frame of the archive)
   const bool direct = maxPieces * 8 <= nFrames && maxPieces <= passSlots;
   const size_t nJobsMax = direct ? (size_t)maxPieces : (size_t)nFrames;
   if (!frameOff_.reserve((nJobsMax + 1) * 16) || !outOff_.reserve(nJobsMax * 8) || !expect_.reserve(nJobsMax * 4) ||
@@ -235,7 +230,7 @@ Status Engine::ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uin
   uint32_t touched = 0;
   if (direct) {
     hipLaunchKernelGGL(zra_ra_direct_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, qmeta_.as<uint64_t>(), (u32)nq, (u32)maxPieces, (u64)fs,
-                       (u64)U, dArc + h.seekTableOffset, (u64)bodyBase, raVerifyWholeFrames_ ? 1u : 0u, frameOff_.as<uint64_t>(), outOff_.as<uint64_t>(),
+                       (u64)U, a.table, (u64)a.bodyBase, raVerifyWholeFrames_ ? 1u : 0u, frameOff_.as<uint64_t>(), outOff_.as<uint64_t>(),
                        expect_.as<uint32_t>(), raLimit_.as<uint32_t>(), raPieceBase_.as<uint32_t>(), raPieces_.as<ZraRaPiece>());
     touched = (uint32_t)maxPieces;
     trace.mark("jobs queued");
@@ -245,7 +240,7 @@ Status Engine::ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uin
     hipLaunchKernelGGL(zra_ra_count_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream_, qmeta_.as<uint64_t>(), (u32)nq, (u64)fs,
                        RaPlan::over(raPlan_.as<uint32_t>(), nFrames));
     uint32_t totals[2];
-    Status st = ra_plan_fill(raPlan_.as<uint32_t>(), nq, nFrames, dArc + h.seekTableOffset, bodyBase, fs, U, passSlots, raVerifyWholeFrames_, nullptr, totals);
+    Status st = ra_plan_fill(raPlan_.as<uint32_t>(), nq, a, passSlots, raVerifyWholeFrames_, nullptr, totals);
     if (st.zra) return st;
     touched = totals[0];
     trace.mark("plan");
@@ -253,13 +248,13 @@ Status Engine::ra_batch_body(const uint8_t* dArc, const HeaderInfo& h, const uin
   if (!touched) return ok();
   // decode the touched frames, a scratch window of passSlots frames at a time (only frames that are decoded in full — or larger
   // than what the decoder needs as its match window — actually write there); slices leave for dOut as each frame finishes
-  if (!temp_.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64)) return zerr(64);
+  if (!stage_.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64)) return zerr(64);
   ZraDecodeArgs ra{};
   ra.pieces = raPieces_.as<ZraRaPiece>(); ra.raOut = dOut;
   for (uint32_t s0 = 0; s0 < touched; s0 += passSlots) {
     const uint32_t n = std::min(passSlots, touched - s0);
     ra.limit = raLimit_.as<uint32_t>() + s0; ra.pieceBase = raPieceBase_.as<uint32_t>() + s0;
-    Status st = decode_jobs(dBody, bodyBytes, frameOff_.as<uint64_t>() + 2 * (size_t)s0, temp_.as<uint8_t>(), outOff_.as<uint64_t>() + s0,
+    Status st = decode_jobs(a.body, a.bodyBytes, frameOff_.as<uint64_t>() + 2 * (size_t)s0, stage_.as<uint8_t>(), outOff_.as<uint64_t>() + s0,
                             expect_.as<uint32_t>() + s0, n, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2, 0, &ra);
     if (st.zra) return st;
   }

@@ -1,17 +1,17 @@
 // zra_amd — search of a device-resident archive (zra_hip.h: ZraHipSearchArchive): every content offset at which a byte pattern
 // occurs inside a content range, in ascending order, without an output buffer for the content.
 //
-//   1. the fixed header comes to the host (Engine::ra_header); the range becomes frames [f0, f1]
+//   1. the fixed header comes to the host (Engine::archive_view); the range becomes frames [f0, f1]
 //   2. per pass of at most passSlots consecutive frames: the frames become decode jobs                   zra_search_jobs_kernel
-//   3. the pass is decoded whole, checksums verified, into the staging window                            Engine::decode_pass
+//   3. the pass is decoded whole, checksums verified, into the staging window                            Engine::staged_pass
 //   4. the window's plaintext is scanned a tile per workgroup: matches per tile                          zra_search_count_kernel
 //   5. the tile counts become list positions behind the matches of the earlier passes                    zra_search_scan_kernel
 //   6. tiles that hold a listed match redo their compare and write the offsets                           zra_search_fill_kernel
 //   7. the last m - 1 bytes seen so far move in front of slot 0 for the next pass                         zra_search_carry_kernel
 //   8. the match count and the first matchCapacity offsets come to the host, once
-// The staging buffer is  [ carry area, kMaxPattern bytes | slot 0 | slot 1 | ... ]: slot s lies at s * frameSize behind the carry area.
+// The staging window (Engine::stage_, reserved kMaxPattern bytes larger) is  [ carry area | slot 0 | slot 1 | ... ]: slot s lies at s * frameSize behind the carry area.
 //
-// Ordering conditions (all launches on the engine's stream, decode_pass returns synchronised):
+// Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
 //  (contiguity) the frames of a pass are consecutive and all but the archive's last regenerate frameSize bytes (anything else is a
 //      failing frame and ends the call), so the slots hold the content [passBase, passEnd) as one run, passEnd = min(U, (last frame of
 //      the pass + 1) * frameSize). The scan's bounds come from that arithmetic alone: what lies behind a short last frame, and in slots a
@@ -33,8 +33,6 @@ using namespace zra_dev;
 
 namespace {
 constexpr u32 kMaxPattern = 256;          // ZRA_HIP_SEARCH_MAX_PATTERN
-constexpr u32 kPassFrames = 1u << 16;     // frames of one decode pass at most: verify's bound (zra_verify.hip)
-constexpr u64 kStageBytes = 4ull << 30;   // default staging window: verify's bound
 // Start positions of one workgroup. 8 KiB: the halo of up to 255 bytes a tile stages beyond its own positions is then 3 % of its global
 // reads, tile + halo take 8.5 KiB of LDS (a CU holds its 8 workgroups of 256 lanes with room to spare), 1 GiB of plaintext is 131,072
 // workgroups, and the per-tile tables (4-byte count, 8-byte base) cost 0.15 % of the window.
@@ -44,8 +42,6 @@ constexpr u32 kWaveIters = kWavePos / 64;
 // staged bytes: up to 15 in front (the 16-byte alignment of the first global load), the tile, m - 1 halo bytes, rounded up to 16; the
 // compare reads whole words and may look up to 7 bytes beyond its pattern's end (masked off)
 constexpr u32 kLdsWords = (kTile + kMaxPattern + 64) / 4;
-
-__device__ __forceinline__ u64 entry40(const u8* table, u64 f) { const u8* e = table + (size_t)f * 5; return (u64)ld32(e) | ((u64)e[4] << 32); }
 
 // the four bytes at byte index i of an LDS word array
 __device__ __forceinline__ u32 lds_word(const u32* s, u32 i) {
@@ -97,7 +93,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_search_jobs_kernel(const u
   const u32 j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   const u64 f = first + j;
-  frameOff[2 * (size_t)j] = entry40(table, f); frameOff[2 * (size_t)j + 1] = entry40(table, f + 1);
+  frameOff[2 * (size_t)j] = seek_entry(table, f); frameOff[2 * (size_t)j + 1] = seek_entry(table, f + 1);
   outOff[j] = (u64)j * fs;
   expect[j] = (u32)frame_expect(f, fs, total);
 }
@@ -193,12 +189,12 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   if (!nMatches || !hPat || (!dArc && arcSize) || (!hMatches && matchCap) || m == 0 || m > kMaxPattern) return zerr(42);
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
-  E.kstats_[4] = E.kstats_[5] = 0; for (auto& d : E.dstats_) d = 0;
+  E.reset_decode_stats();
   // ---- 2. header: the statuses of ZraHipArchiveOpen. (The header's CRC-32 is not looked at: that is the verifier's job.)
-  HeaderInfo h;
-  { Status st = E.ra_header(dArc, arcSize, &h); if (st.zra) return st; }
-  const uint32_t F = h.frames();
-  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  ArchiveView arc;
+  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  const uint32_t F = arc.frames;
+  const uint64_t fs = arc.fs, U = arc.U;
   // ---- 3. the range [lo, hi), inclusive bound: a search reaches the last byte
   if (offset > U || (size != ~0ull && (offset + size < offset || offset + size > U))) return {kOutOfBounds, 0};
   const uint64_t lo = offset, hi = size == ~0ull ? U : offset + size;
@@ -206,19 +202,19 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   if (fs == 0 || F == 0) return {kHeaderInvalid, 0};                       // (content without frames: ra_header lets a frame size of 0 through)
   const uint64_t f0 = lo / fs, f1 = (hi - 1) / fs, n = f1 - f0 + 1;
   // ---- 4. scratch
-  const uint32_t passSlots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kPassFrames, (stagingBytes ? stagingBytes : kStageBytes) / fs));
+  const uint32_t passSlots = pass_slots(fs, stagingBytes);
   const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
   const uint64_t passes = (n + passSlots - 1) / passSlots;
   const uint64_t window = (uint64_t)nSlots * fs;
   const size_t tilesMax = (size_t)((window + kTile - 1) / kTile);
   const size_t listCap = (size_t)std::min<uint64_t>(matchCap, hi - lo - m + 1);
   // tables: pattern (kMaxPattern bytes) | the ping-pong match count (2 words of 8 bytes, padded to 64) | bases[tiles] | counts[tiles]
-  if (!E.srch_.stage.reserve(kMaxPattern + (size_t)window + 64) || !E.srch_.tables.reserve(kMaxPattern + 64 + tilesMax * 12 + 64) ||
+  if (!E.stage_.reserve(kMaxPattern + (size_t)window + 64) || !E.srch_.tables.reserve(kMaxPattern + 64 + tilesMax * 12 + 64) ||
       !E.srch_.list.reserve(listCap * 8 + 64) || !E.frameOff_.reserve(((size_t)nSlots + 1) * 16) || !E.outOff_.reserve(((size_t)nSlots + 1) * 8) ||
-      !E.expect_.reserve(((size_t)nSlots + 1) * 4) || !E.result_.reserve(64))
+      !E.expect_.reserve(((size_t)nSlots + 1) * 4))
     return zerr(64);
-  if (!E.evSearch_[0]) for (auto& ev : E.evSearch_) if (hipEventCreate(&ev) != hipSuccess) { ev = nullptr; (void)hipGetLastError(); return zerr(1); }
-  uint8_t* const win = E.srch_.stage.as<uint8_t>() + kMaxPattern;           // slot 0; the carry area lies in front of it
+  if (!E.call_events()) return zerr(1);
+  uint8_t* const win = E.stage_.as<uint8_t>() + kMaxPattern;                // slot 0; the carry area lies in front of it
   uint8_t* const tb = E.srch_.tables.as<uint8_t>();
   const uint32_t* const pat = (const uint32_t*)tb;
   uint64_t* const cnt = (uint64_t*)(tb + kMaxPattern);
@@ -231,42 +227,29 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
     HIPCHK_CLR(hipMemcpyAsync(tb, padded, sizeof(padded), hipMemcpyHostToDevice, s));
     HIPCHK_CLR(hipStreamSynchronize(s));                                    // (`padded` goes out of scope)
   }
-  const uint8_t* table = dArc + h.seekTableOffset;
-  const uint8_t* body = dArc + h.size;
-  const uint64_t bodyBytes = arcSize - h.size;
   // ---- passes
   uint32_t launches = 0, carry = 0;
   bool timed = false;
-  auto take_time = [&]() {                                                  // (behind a synchronisation of the stream)
-    if (!timed) return;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, E.evSearch_[0], E.evSearch_[1]) == hipSuccess) E.searchScanMs_ += ms; else (void)hipGetLastError();
-    timed = false;
-  };
-  E.lastProducedTotal_ = ~0ull;
+  // (behind a synchronisation of the stream)
+  auto take_time = [&]() { if (timed) E.searchScanMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); timed = false; };
   for (uint64_t p = 0; p < passes; p++) {
     const uint64_t first = f0 + p * passSlots;
     const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    hipLaunchKernelGGL(zra_search_jobs_kernel, dim3((nj + 255) / 256), dim3(256), 0, s, table, (u64)fs, (u64)U, (u64)first, nj, E.frameOff_.as<uint64_t>(),
+    hipLaunchKernelGGL(zra_search_jobs_kernel, dim3((nj + 255) / 256), dim3(256), 0, s, arc.table, (u64)fs, (u64)U, (u64)first, nj, E.frameOff_.as<uint64_t>(),
                        E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    HIPCHK_CLR(hipMemsetAsync(E.result_.p, 0xFF, 64, s));
-    ZraDecodeArgs b{};
-    b.body = body; b.bodySize = bodyBytes; b.out = win; b.offStride = 2; b.nFrames = nj;
-    b.frameOff = E.frameOff_.as<uint64_t>(); b.outOff = E.outOff_.as<uint64_t>(); b.outCap = E.expect_.as<uint32_t>();
-    unsigned long long firstError = ~0ull;
-    Status st = E.decode_pass(b, E.expect_.as<uint32_t>(), (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 0, &firstError);
+    unsigned long long firstError;
+    Status st = E.staged_pass(arc, 0, nj, win, &firstError);
     take_time();
     if (st.zra) { E.searchScanMs_ = 0; return st; }
     if (firstError != ~0ull) {                                              // the lowest failing frame of the first failing pass
-      const uint32_t code = (uint32_t)(firstError & 0xFF);
       E.searchScanMs_ = 0;
-      return zerr(code == 255 ? 20 : (int)code);                            // (ZE_SIZE_MISMATCH, reported as everywhere else)
+      return zerr(reported_code(firstError));
     }
     // (contiguity) the run of this pass, and (ownership) the start positions it owns, relative to slot 0
     const uint64_t passBase = first * fs, passEnd = std::min<uint64_t>(U, (first + nj) * fs), L = passEnd - passBase;
     const long long xLo = lo > passBase ? (long long)(lo - passBase) : -(long long)std::min<uint64_t>(m - 1, passBase - lo);
     const long long xEnd = (long long)(std::min<uint64_t>(passEnd, hi) - passBase) - (long long)m + 1;
-    HIPCHK_CLR(hipEventRecord(E.evSearch_[0], s));
+    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
     if (xEnd > xLo) {
       const uint64_t nPos = (uint64_t)(xEnd - xLo);
       const uint32_t tiles = (uint32_t)((nPos + kTile - 1) / kTile);
@@ -281,7 +264,7 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
       carry = (uint32_t)std::min<uint64_t>(m - 1, carry + L);
       hipLaunchKernelGGL(zra_search_carry_kernel, dim3(1), dim3(256), 0, s, win, (u64)L, carry);
     }
-    HIPCHK_CLR(hipEventRecord(E.evSearch_[1], s));
+    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
     timed = true;
   }
   // ---- the count, then the list, once

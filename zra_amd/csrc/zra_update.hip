@@ -9,7 +9,7 @@
 //   4. encodes the staged frames like ZraHipCompressBuffer encodes frames of that content              Engine::compress_frames
 //   5. sizes every frame (new size if touched, old table difference if not), scans, writes the table   zra_upd_sizes / _scan / _offsets
 //   6. copies every frame to its new place: the bandwidth step                                         zra_upd_gather
-// Steps 2-4 run in passes over at most kPassFrames staging slots; the encoded frames stay packed in scratch until step 6.
+// Steps 2-4 run in passes over the slots of the engine's staging window (pass_slots); the encoded frames stay packed in scratch until step 6.
 //
 // Ordering conditions (all launches on the engine's stream, decode_jobs and compress_frames return synchronised):
 //  (a) slots are ranks among the touched frames in frame order: only the archive's last frame can be short and it is the last slot of
@@ -32,33 +32,8 @@ using namespace zra_dev;
 
 namespace {
 constexpr u32 kNone = 0xFFFFFFFFu;        // slotOf: the frame is not touched
-constexpr u32 kPassFrames = 1u << 16;     // frames of one decode -> patch -> encode pass (one internal pass of Engine::decode_jobs)
-// plaintext staging of one pass: 65,536 frames of 64 KiB (the headline frame size) fill it exactly; larger frames get fewer slots
-constexpr u64 kStageBytes = 4ull << 30;
 constexpr u32 kGatherChunk = 32u << 10;   // output bytes one wave of the gather copies per step
 constexpr u32 kGatherGrid = 2048;         // workgroups of the gather at most (4 waves each; 8 per CU on 256 CUs)
-
-__device__ __forceinline__ u64 entry40(const u8* table, u64 f) { const u8* e = table + (size_t)f * 5; return (u64)ld32(e) | ((u64)e[4] << 32); }
-
-// slice s of the tuples q (4 words each: content offset, size, source offset, first slice; sorted by offset, none empty): the frame it
-// lies in, where it starts inside the frame, its length, and where its bytes are in the tuple's source
-struct Slice { u32 tuple; u64 frame; u32 inFrame; u32 len; u64 src; };
-__device__ __forceinline__ Slice slice_of(const u64* q, u32 nq, u64 s, u64 fs) {
-  u32 lo = 0, hi = nq - 1;
-  while (lo < hi) {
-    const u32 mid = lo + (hi - lo + 1) / 2;
-    if (q[4 * (size_t)mid + 3] <= s) lo = mid; else hi = mid - 1;
-  }
-  const u64 off = q[4 * (size_t)lo], size = q[4 * (size_t)lo + 1], k = s - q[4 * (size_t)lo + 3];
-  const u64 f0 = off / fs, head = off - f0 * fs;
-  Slice r;
-  r.tuple = lo; r.frame = f0 + k;
-  r.inFrame = k ? 0u : (u32)head;
-  const u64 done = k ? (fs - head) + (k - 1) * fs : 0;
-  r.len = (u32)min<u64>(fs - r.inFrame, size - done);
-  r.src = q[4 * (size_t)lo + 2] + done;
-  return r;
-}
 
 // one wave copies n bytes: 16-byte loads aligned on the source, four in flight per lane; the stores fall as they may
 // (zra_gather_frames_kernel's choice)
@@ -140,12 +115,12 @@ extern "C" __global__ void __launch_bounds__(1024) zra_upd_plan_kernel(const u32
     }
     if (dec) {
       // (dec implies f < nOld: a frame behind the old content is supplied whole by the append)
-      frameOff[2 * (size_t)job] = entry40(table, f); frameOff[2 * (size_t)job + 1] = entry40(table, (u64)f + 1);
+      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, (u64)f + 1);
       outOff[job] = (u64)(slot % passSlots) * fs;
       expect[job] = (u32)min<u64>(fs, oldTotal - o);
     }
     if (in && !touched && f < nOld) {
-      const u64 a = entry40(table, f), b = entry40(table, (u64)f + 1);
+      const u64 a = seek_entry(table, f), b = seek_entry(table, (u64)f + 1);
       if (b < a || b > bodyBytes) atomicOr(&sFlag, 1u);
     }
     slotBase += totalT; jobBase += totalJ; copyBase += totalC;
@@ -184,7 +159,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_upd_patch_kernel(const u64
     const Slice c = slice_of(q, nq, s, fs);
     const u32 slot = slotOf[c.frame];
     if (slot < s0 || slot - s0 >= n) continue;
-    copy_slice(stage + (u64)(slot - s0) * fs + c.inFrame, (c.tuple < nData ? data : app) + c.src, c.len, lane);
+    copy_slice(stage + (u64)(slot - s0) * fs + c.inFrame, (c.tuple < nData ? data : app) + c.user, c.len, lane);
   }
 }
 
@@ -195,7 +170,7 @@ __device__ __forceinline__ void upd_frame_size(u32 f, u32 nNew, const u32* slotO
   if (f >= nNew) return;
   const u32 slot = slotOf[f];
   if (slot != kNone) { *sz = *tsz = encSizes[slot]; return; }
-  *sz = entry40(table, (u64)f + 1) - entry40(table, f);               // (not backwards: the plan kernel has checked the untouched frames)
+  *sz = seek_entry(table, (u64)f + 1) - seek_entry(table, f);               // (not backwards: the plan kernel has checked the untouched frames)
 }
 // exclusive scan of (a, b) over the 1024 threads of a workgroup; *ta, *tb = the sums
 __device__ __forceinline__ void block_excl_scan2(u64& a, u64& b, u64* ta, u64* tb, u64* sA, u64* sB) {
@@ -250,7 +225,7 @@ extern "C" __global__ void __launch_bounds__(1024) zra_upd_offsets_kernel(u32 nN
   u8* e = entries + (size_t)f * 5;
   e[0] = (u8)off; e[1] = (u8)(off >> 8); e[2] = (u8)(off >> 16); e[3] = (u8)(off >> 24); e[4] = (u8)(off >> 32);
   if (f == nNew) disp[f] = ~0ull;
-  else disp[f] = (enc ? (u64)(uintptr_t)packed + toff : (u64)(uintptr_t)oldBody + entry40(table, f)) - off;
+  else disp[f] = (enc ? (u64)(uintptr_t)packed + toff : (u64)(uintptr_t)oldBody + seek_entry(table, f)) - off;
 }
 
 // The bandwidth kernel. The new body is cut into chunks of kGatherChunk bytes, a capped grid strides over them, one wave per chunk.
@@ -321,11 +296,11 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   // ---- 3. header: the statuses of ZraHipArchiveOpen; beyond them a frame size of 0 and a table that does not cover the content
   // (an open handle refuses every read of such an archive; here there is no frame to put a byte in)
   // (a handle holds a checked header: it is not read from the device again)
-  HeaderInfo h;
-  if (cache) h = cache->h;
-  else { Status st = E.ra_header(dArc, arcSize, &h); if (st.zra) return st; }
-  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
-  const uint32_t F = h.frames();
+  ArchiveView arc;
+  if (cache) arc = ArchiveView::over(cache->h, dArc, arcSize);
+  else { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  const uint64_t fs = arc.fs, U = arc.U;
+  const uint32_t F = arc.frames;
   if (fs == 0 || (U + fs - 1) / fs != F) return {kHeaderInvalid, 0};
   // ---- 4. writes. The bound is inclusive: offset + size == uncompressedSize is the write that reaches the last byte. (The reference's
   // ">=" (zra.cpp:260) is a quirk of its reads, kept there for compatibility; a write that could never touch the last byte of the
@@ -351,26 +326,25 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   const uint32_t* const cacheSlotOf = cached ? cache->table(cache->ctx, F2) : nullptr;
   if (cached && !cacheSlotOf) return zerr(64);
   E.updStageMs_ = 0;
-  if (cached && !E.evUpd_[0]) for (auto& ev : E.evUpd_) if (hipEventCreate(&ev) != hipSuccess) { ev = nullptr; (void)hipGetLastError(); return zerr(1); }
-  // the tuples, sorted by offset, in page-locked memory and from there to the device in chunks (ra_walk_queries' idiom)
+  if (cached && !E.call_events()) return zerr(1);
+  // the tuples, sorted by offset, in page-locked memory and from there to the device in chunks
   uint64_t nSlices = 0;
   if (nT) {
     uint64_t* const hq = E.pinned_tuples(nT);
     if (!hq || !E.qmeta_.reserve(4 * nT * 8 + 64)) return zerr(64);
-    constexpr size_t kChunk = 1u << 17;
-    for (size_t q0 = 0; q0 < nT; q0 += kChunk) {
-      const size_t q1 = std::min(nT, q0 + kChunk);
+    for (size_t q0 = 0; q0 < nT; q0 += Engine::kTupleChunk) {
+      const size_t q1 = std::min(nT, q0 + Engine::kTupleChunk);
       for (size_t q = q0; q < q1; q++) {
         const uint64_t o = q < nData ? hOff[idx[q]] : U, z = q < nData ? hSize[idx[q]] : appendSize;
         hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = q < nData ? hDataOff[idx[q]] : 0; hq[4 * q + 3] = nSlices;
         nSlices += (o + z - 1) / fs - o / fs + 1;
       }
-      HIPCHK_CLR(hipMemcpyAsync(E.qmeta_.as<uint64_t>() + 4 * q0, hq + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, s));
+      { Status st = E.upload_tuples(q0, q1); if (st.zra) return st; }
     }
   }
   const uint64_t* dq = E.qmeta_.as<uint64_t>();
   // ---- plan
-  const uint32_t passSlots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kPassFrames, kStageBytes / fs));
+  const uint32_t passSlots = pass_slots(fs);
   const uint64_t touchedMax = std::min<uint64_t>(F2, nSlices), jobsMax = std::min<uint64_t>(F, nSlices);
   const size_t passesMax = (size_t)((touchedMax + passSlots - 1) / passSlots);
   // cover[F2] | slotOf[F2] | totals[16] | passJob[passes + 1] | passCopy[passes + 1]
@@ -383,15 +357,12 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   uint32_t* cover = E.upd_.plan.as<uint32_t>(), *slotOf = cover + F2, *totals = slotOf + F2, *passJob = totals + 16;
   uint32_t* const passCopy = passJob + passesMax + 1, * const copies = cacheSlotOf ? E.upd_.copies.as<uint32_t>() : nullptr;
   uint64_t* newOff = E.upd_.frames.as<uint64_t>(), *disp = newOff + F2 + 1, *sums = disp + F2 + 1;
-  const uint8_t* oldTable = dArc + h.seekTableOffset;
-  const uint8_t* oldBody = dArc + h.size;
-  const uint64_t bodyBytes = arcSize - h.size;
   HIPCHK_CLR(hipMemsetAsync(cover, 0, planWords * 4, s));
   if (nSlices)
     hipLaunchKernelGGL(zra_upd_mark_kernel, dim3((uint32_t)((nSlices + 255) / 256)), dim3(256), 0, s, dq, (u32)nT, (u64)nSlices, (u64)fs, cover);
   uint32_t hTotals[5] = {0, 0, 0, 0, 0};
   if (F2) {
-    hipLaunchKernelGGL(zra_upd_plan_kernel, dim3(1), dim3(1024), 0, s, cover, F2, F, oldTable, (u64)bodyBytes, (u64)fs, (u64)U, (u64)U2, passSlots,
+    hipLaunchKernelGGL(zra_upd_plan_kernel, dim3(1), dim3(1024), 0, s, cover, F2, F, arc.table, (u64)arc.bodyBytes, (u64)fs, (u64)U, (u64)U2, passSlots,
                        cacheSlotOf, slotOf, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), passJob, copies, passCopy,
                        totals);
     HIPCHK_CLR(hipMemcpyAsync(hTotals, totals, sizeof(hTotals), hipMemcpyDeviceToHost, s));
@@ -410,10 +381,10 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
     if (staged) HIPCHK_CLR(hipMemcpyAsync(hPassCopy.data(), passCopy, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
     const uint64_t bound = zra_fmt::compress_bound(fs);
-    if (!E.upd_.stage.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64) || !E.upd_.packed.reserve((size_t)touched * bound + 64) ||
+    if (!E.stage_.reserve((size_t)std::min<uint64_t>(touched, passSlots) * fs + 64) || !E.upd_.packed.reserve((size_t)touched * bound + 64) ||
         !E.upd_.encSizes.reserve((size_t)touched * 8 + 64))
       return zerr(64);
-    uint8_t* stage = E.upd_.stage.as<uint8_t>();
+    uint8_t* const stage = E.stage_.as<uint8_t>();
     // only the last frame of the result can be short, and only if new bytes reach it is it staged (then as the last slot of all)
     const bool lastStaged = F2 && (appendSize || maxEnd > (uint64_t)(F2 - 1) * fs);
     const uint64_t lastLen = F2 ? U2 - (uint64_t)(F2 - 1) * fs : 0;
@@ -423,13 +394,13 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
       const uint32_t j0 = hPassJob[p], j1 = hPassJob[p + 1], c0 = hPassCopy[p], c1 = hPassCopy[p + 1];
       if (c1 > c0) {                                                  // (other staging slots than the decode jobs': no order between the two)
         const uint64_t nWork = (uint64_t)(c1 - c0) * ((fs + kGatherChunk - 1) / kGatherChunk);
-        HIPCHK_CLR(hipEventRecord(E.evUpd_[0], s));
+        HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
         hipLaunchKernelGGL(zra_upd_stage_cached_kernel, dim3((uint32_t)std::min<uint64_t>((nWork + 3) / 4, kGatherGrid)), dim3(256), 0, s,
                            copies + 4 * (size_t)c0, c1 - c0, s0, (u64)fs, cache->arena, stage);
-        HIPCHK_CLR(hipEventRecord(E.evUpd_[1], s));
+        HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
       }
       if (j1 > j0) {
-        Status st = E.decode_jobs(oldBody, bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)j0, stage, E.outOff_.as<uint64_t>() + j0,
+        Status st = E.decode_jobs(arc.body, arc.bodyBytes, E.frameOff_.as<uint64_t>() + 2 * (size_t)j0, stage, E.outOff_.as<uint64_t>() + j0,
                                   E.expect_.as<uint32_t>() + j0, j1 - j0, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 2);
         if (st.zra) return st;
       }
@@ -441,17 +412,17 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
       if (st.zra) return st;
       encoded += bsz;
       // (compress_frames returned synchronised: the pass's events have completed)
-      if (c1 > c0) { float ms = 0; if (hipEventElapsedTime(&ms, E.evUpd_[0], E.evUpd_[1]) == hipSuccess) E.updStageMs_ += ms; else (void)hipGetLastError(); }
+      if (c1 > c0) E.updStageMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]);
     }
   }
   // ---- sizes, offsets, table
   uint64_t hTot[2] = {0, 0};
-  hipLaunchKernelGGL(zra_upd_sizes_kernel, dim3(nBlocks), dim3(1024), 0, s, F2, slotOf, E.upd_.encSizes.as<uint64_t>(), oldTable, sums);
+  hipLaunchKernelGGL(zra_upd_sizes_kernel, dim3(nBlocks), dim3(1024), 0, s, F2, slotOf, E.upd_.encSizes.as<uint64_t>(), arc.table, sums);
   hipLaunchKernelGGL(zra_upd_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nBlocks);
-  hipLaunchKernelGGL(zra_upd_offsets_kernel, dim3(nBlocks), dim3(1024), 0, s, F2, slotOf, E.upd_.encSizes.as<uint64_t>(), oldTable, sums, oldBody,
+  hipLaunchKernelGGL(zra_upd_offsets_kernel, dim3(nBlocks), dim3(1024), 0, s, F2, slotOf, E.upd_.encSizes.as<uint64_t>(), arc.table, sums, arc.body,
                      E.upd_.packed.as<uint8_t>(), newOff, disp, E.upd_.table.as<uint8_t>());
   // the header on the host (5 bytes per frame, as compress_device does): fixed part rewritten, meta section copied, new table, CRC-32
-  const size_t metaSize = h.metaSize, tableBytes = ((size_t)F2 + 1) * 5;
+  const size_t metaSize = arc.h.metaSize, tableBytes = ((size_t)F2 + 1) * 5;
   const uint64_t headerSize = zra_fmt::kFixedSize + (uint64_t)metaSize + tableBytes;
   if (headerSize > 0xFFFFFFFFull) return {kCompressedTooLarge, 0};
   std::vector<uint8_t> hdr((size_t)headerSize);
@@ -487,7 +458,7 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   }
   HIPCHK_CLR(hipStreamSynchronize(s));
   HIPCHK_CLR(hipGetLastError());
-  if (gather) { float ms = 0; if (hipEventElapsedTime(&ms, E.ev0_, E.ev1_) == hipSuccess) E.lastKernelMs_ = ms; else (void)hipGetLastError(); }
+  if (gather) E.lastKernelMs_ = Engine::elapsed_ms(E.ev0_, E.ev1_);
   const uint64_t st8[8] = {F2, touched, jobs, touched, body - encoded, encoded, written, passes};
   for (int i = 0; i < 8; i++) E.ustats_[i] = st8[i];
   if (cache) {

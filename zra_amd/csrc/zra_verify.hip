@@ -4,12 +4,12 @@
 //   1. the header comes to the host once (5 bytes per frame) and its CRC-32 is checked                  zra_fmt::header_hash
 //   2. structure: a lane per frame walks the frame's table entries, frame header and block headers       zra_vfy_structure_kernel
 //   3. content only: the structurally sound frames become decode jobs, in frame order                    zra_vfy_jobs_kernel
-//   4. content only: passes of at most passSlots jobs are decoded whole into the staging window          Engine::decode_pass
+//   4. content only: passes of at most passSlots jobs are decoded whole into the staging window          Engine::staged_pass
 //   5. the faults of the frames a pass covers are appended to the device fault list, in frame order      zra_vfy_collect_kernel
 //   6. the fault count and the first faultCapacity entries come to the host, once
 // Everything is indexed by i = frame - firstFrame: the tables cost 28 bytes per frame of the RANGE, not of the archive.
 //
-// Ordering conditions (all launches on the engine's stream, decode_pass returns synchronised):
+// Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
 //  (a) jobs are ranks among the sound frames in frame order, so pass p decodes the sound frames of the index span
 //      [passFirst[p], passFirst[p + 1]) and no others; the collection behind pass p covers exactly that span (the first one starts at 0,
 //      the last one ends at the range's end), so the spans tile the range and the fault list is ascending across passes.
@@ -27,20 +27,16 @@ using namespace zra_dev;
 
 namespace {
 constexpr u32 kNoJob = 0xFFFFFFFFu;       // jobOf: the frame is structurally faulty, nothing decodes it
-constexpr u32 kPassFrames = 1u << 16;     // jobs of one decode pass at most (one internal pass of Engine::decode_jobs)
-constexpr u64 kStageBytes = 4ull << 30;   // default staging window: the update's bound (zra_update.hip)
 constexpr u32 kCollectSpan = 1u << 16;    // frames of one collection launch: 256 workgroups of 256 lanes
 constexpr u32 kStageStructure = 1u, kStageContent = 2u;   // ZRA_HIP_VERIFY_*
 
 // ZraHipFrameFault (zra_hip.h), restated: the device list is copied to the caller's array as it is
 struct Fault { u64 frame; u32 code; u32 stage; };
 
-__device__ __forceinline__ u64 entry40(const u8* table, u64 f) { const u8* e = table + (size_t)f * 5; return (u64)ld32(e) | ((u64)e[4] << 32); }
-
 // The structure rules of one frame (the table in zra_hip.h, in its order); 0 = sound. Reads the frame's two table entries, its header
 // and three bytes per block; every read lies inside [body + a, body + b), which the first rule puts inside the body.
 __device__ __forceinline__ u32 structure_code(const u8* table, u32 nFrames, const u8* body, u64 bodyBytes, u64 fs, u64 total, u32 f) {
-  const u64 a = entry40(table, f), b = entry40(table, (u64)f + 1);
+  const u64 a = seek_entry(table, f), b = seek_entry(table, (u64)f + 1);
   if (b < a || b > bodyBytes) return ZE_SRCSIZE_WRONG;
   if (f + 1 == nFrames && b != bodyBytes) return ZE_SRCSIZE_WRONG;
   const u64 n = b - a;
@@ -86,7 +82,7 @@ __device__ __forceinline__ u32 fault_word(const u32* sstat, const u32* jobOf, co
   const u32 j = jobOf[i] - jobBase;                                   // (condition (a): inside the pass; anything else reads nothing)
   if (j >= nJobs) return 0;
   u32 c = status[j] & 0xFF;
-  if (c == 255) c = ZE_CORRUPTION;                                    // ZE_SIZE_MISMATCH (zra_engine.hip), reported as everywhere else
+  c = (u32)zra_eng::reported_code(c);
   return c ? c | (kStageContent << 8) : 0u;
 }
 }  // namespace
@@ -121,7 +117,7 @@ extern "C" __global__ void __launch_bounds__(1024) zra_vfy_jobs_kernel(const u32
     if (in) jobOf[i] = sound ? job : kNoJob;
     if (sound) {
       const u64 f = (u64)first + i;
-      frameOff[2 * (size_t)job] = entry40(table, f); frameOff[2 * (size_t)job + 1] = entry40(table, f + 1);
+      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, f + 1);
       expect[job] = (u32)frame_expect(f, fs, total);
       if (job % passSlots == 0) passFirst[job / passSlots] = i;
     }
@@ -186,26 +182,26 @@ Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t 
   if (!nFaults || (!dArc && arcSize) || (!hFaults && faultCap) || !mode || (mode & ~(kStageStructure | kStageContent))) return zerr(42);
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
-  E.kstats_[4] = E.kstats_[5] = 0; for (auto& d : E.dstats_) d = 0;
+  E.reset_decode_stats();
   // ---- 2. header: the statuses of ZraHipArchiveOpen
-  HeaderInfo h;
-  { Status st = E.ra_header(dArc, arcSize, &h); if (st.zra) return st; }
-  // ---- 3. the CRC-32 over the header as it lies on the device (ra_header: 38 <= h.size <= arcSize)
+  ArchiveView arc;
+  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  // ---- 3. the CRC-32 over the header as it lies on the device (ra_header: 38 <= arc.h.size <= arcSize)
   {
-    std::vector<uint8_t> hdr(h.size);
-    HIPCHK_CLR(hipMemcpyAsync(hdr.data(), dArc, h.size, hipMemcpyDeviceToHost, s));
+    std::vector<uint8_t> hdr(arc.h.size);
+    HIPCHK_CLR(hipMemcpyAsync(hdr.data(), dArc, arc.h.size, hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
     if (zra_fmt::header_hash(hdr.data(), hdr.data() + zra_fmt::kFixedSize) != zra_fmt::rd32(hdr.data() + 14)) return {kHeaderInvalid, 0};
   }
   // ---- 4. the range
-  const uint32_t F = h.frames();
-  const uint64_t fs = h.frameSize, U = h.uncompressedSize;
+  const uint32_t F = arc.frames;
+  const uint64_t fs = arc.fs, U = arc.U;
   if (first > F || (count != ~0ull && count > F - first)) return {kOutOfBounds, 0};
   const uint32_t f0 = (uint32_t)first, n = count == ~0ull ? F - f0 : (uint32_t)count;
   if (!n) { E.vstats_[0] = F; return ok(); }
   // ---- 5. scratch
   const bool content = (mode & kStageContent) != 0;
-  const uint32_t passSlots = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kPassFrames, (stagingBytes ? stagingBytes : kStageBytes) / std::max<uint64_t>(fs, 1)));
+  const uint32_t passSlots = pass_slots(fs, stagingBytes);
   const uint32_t nSlots = std::min(passSlots, n);
   const size_t passesMax = (size_t)n / passSlots + 2;
   const size_t listCap = (size_t)std::min<uint64_t>(faultCap, n);
@@ -217,12 +213,9 @@ Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t 
   uint32_t* cnt = totals + 4;                                              // the ping-pong fault count (condition (c))
   unsigned long long* bytes = (unsigned long long*)(totals + 8);
   Fault* faults = (Fault*)E.vfy_.faults.p;
-  const uint8_t* table = dArc + h.seekTableOffset;
-  const uint8_t* body = dArc + h.size;
-  const uint64_t bodyBytes = arcSize - h.size;
   HIPCHK_CLR(hipMemsetAsync(totals, 0, 64, s));
   // ---- structure
-  hipLaunchKernelGGL(zra_vfy_structure_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, F, body, (u64)bodyBytes, (u64)fs, (u64)U, f0, n, sstat);
+  hipLaunchKernelGGL(zra_vfy_structure_kernel, dim3((n + 255) / 256), dim3(256), 0, s, arc.table, F, arc.body, (u64)arc.bodyBytes, (u64)fs, (u64)U, f0, n, sstat);
   uint32_t launches = 0;
   // faults of range indices [i0, i1) -> the list; status: the status words of the pass that decoded the sound frames among them
   auto collect = [&](uint32_t i0, uint32_t i1, const uint32_t* status, const uint32_t* produced, uint32_t jobBase, uint32_t nJobs) {
@@ -237,7 +230,7 @@ Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t 
   if (!content) collect(0, n, nullptr, nullptr, 0, 0);
   else {
     // ---- content: jobs, then passes of decode + collection
-    hipLaunchKernelGGL(zra_vfy_jobs_kernel, dim3(1), dim3(1024), 0, s, sstat, f0, n, table, (u64)fs, (u64)U, passSlots, nSlots, jobOf, E.frameOff_.as<uint64_t>(),
+    hipLaunchKernelGGL(zra_vfy_jobs_kernel, dim3(1), dim3(1024), 0, s, sstat, f0, n, arc.table, (u64)fs, (u64)U, passSlots, nSlots, jobOf, E.frameOff_.as<uint64_t>(),
                        E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), passFirst, totals);
     HIPCHK_CLR(hipMemcpyAsync(&jobs, totals, 4, hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
@@ -249,16 +242,11 @@ Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t 
       HIPCHK_CLR(hipMemcpyAsync(pf.data(), passFirst, ((size_t)passes + 1) * 4, hipMemcpyDeviceToHost, s));
       HIPCHK_CLR(hipStreamSynchronize(s));
       pf[0] = 0;                                                           // (faulty frames in front of the first sound one)
-      if (!E.vfy_.stage.reserve((size_t)std::min(jobs, passSlots) * fs + 64) || !E.result_.reserve(64)) return zerr(64);
-      E.lastProducedTotal_ = ~0ull;
+      if (!E.stage_.reserve((size_t)std::min(jobs, passSlots) * fs + 64)) return zerr(64);
       for (uint32_t p = 0; p < passes; p++) {
         const uint32_t j0 = p * passSlots, nj = std::min(passSlots, jobs - j0);
-        HIPCHK_CLR(hipMemsetAsync(E.result_.p, 0xFF, 64, s));
-        ZraDecodeArgs b{};
-        b.body = body; b.bodySize = bodyBytes; b.out = E.vfy_.stage.as<uint8_t>(); b.offStride = 2; b.nFrames = nj;
-        b.frameOff = E.frameOff_.as<uint64_t>() + 2 * (size_t)j0; b.outOff = E.outOff_.as<uint64_t>(); b.outCap = E.expect_.as<uint32_t>() + j0;
-        unsigned long long first_error = ~0ull;                            // (the pass's reduction: not what a scrubber wants)
-        Status st = E.decode_pass(b, E.expect_.as<uint32_t>() + j0, (uint32_t)std::min<uint64_t>(fs, 0xFFFFFFFFu), 0, &first_error);
+        unsigned long long firstError;                                     // (the pass's reduction: not what a scrubber wants)
+        Status st = E.staged_pass(arc, j0, nj, E.stage_.as<uint8_t>(), &firstError);
         if (st.zra) return st;
         collect(pf[p], pf[p + 1], E.status_.as<uint32_t>(), E.produced_.as<uint32_t>(), j0, nj);
       }
