@@ -312,6 +312,70 @@ ZRA_EXPORT void ZraHipGetSearchStats(ZraHipEngine* engine, uint64_t* out8);
  *  summed over its passes; the decode of the same call is in ZraHipGetKernelStats. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugSearchScanMs(ZraHipEngine* engine);
 
+/* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
+ * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte
+ * ranges; the same content written at two levels raises the same question. A caller would have to ZraHipDecompressBuffer both contents
+ * into two buffers and compare them with code of their own. This call uses what the container has and a plain zstd stream lacks,
+ * independent frames: identical compressed bytes of a frame mean identical content, decided at the bandwidth of the compressed data. */
+#define ZRA_HIP_COMPARE_DECODE_ALL 1u   /* no compressed-bytes shortcut: every frame of the range is decoded on both sides */
+
+typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipContentRange;
+
+/** Compares the content of the archive at dA (sizeA bytes, device memory) with that of the archive at dB (sizeB bytes, device memory)
+ *  inside the content range [offset, offset + size); size = UINT64_MAX: to C = min(UA, UB), the end of the shorter content.
+ *  Synchronous; stream ordering as the other compute calls (ZraHipWaitStream). Both archives are only read.
+ *  Result, with [lo, hi) = the range:
+ *  - A differing range is a MAXIMAL run [s, e) inside [lo, hi) with A[p] != B[p] for every p in it: a run that continues from one frame
+ *    into the next, or from one pass into the next, is one range; a run that the range cuts is reported clipped.
+ *  - *nRanges = the number of differing ranges; it may exceed rangeCapacity. The first min(*nRanges, rangeCapacity) ranges are written
+ *    to hRanges (a HOST array) in ascending order, each exactly once; nothing is written behind them. hRanges may be NULL when
+ *    rangeCapacity is 0: a count-only compare.
+ *  - *differingBytes = the sum of the sizes of all ranges, listed or not. differingBytes may be NULL.
+ *  - Content behind C, where the archives have different lengths, is not a range: UA and UB are in ZraHipGetCompareSizes, and the
+ *    caller compares them.
+ *  - On any status other than Success nothing is written to hRanges, *nRanges and *differingBytes are 0 and all stats are zero. No
+ *    range reaches the host before the last pass is done.
+ *  Statuses, checked in this order:
+ *   1. engine or nRanges NULL; dA or dB NULL with a size other than 0; hRanges NULL with rangeCapacity != 0; mode with bits other than
+ *      ZRA_HIP_COMPARE_DECODE_ALL -> {ZStdError, 42}.
+ *   2. Header problems of A, then of B: the statuses of ZraHipArchiveOpen (a frame size of 0 on either side: HeaderInvalid). The stored
+ *      header CRC-32 is NOT checked here: that is ZraHipVerifyArchive's job.
+ *   3. Different frame sizes -> {ZStdError, 40} (parameter_unsupported).
+ *   4. offset > C, or size != UINT64_MAX and offset + size > C (or a sum that overflows) -> OutOfBoundsAccess. The bound is inclusive,
+ *      as the search's rule 3. The empty range is Success with 0 ranges, and nothing is read.
+ *   5. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's (ZraHipReleaseScratch returns it): the staging
+ *      window, 1 byte per slot of a pass, the decoder's job arrays for two archives, 16 bytes per 8 KiB tile of the decoded frames of
+ *      a pass, 16 bytes per listed range, the decoder's own scratch for one pass.
+ *   6. A frame that has to be decoded and fails: the status ZraHipDecompressRABatch gives under ZRA_HIP_OPT_RA_WHOLE_FRAMES for a query
+ *      inside that frame; of several failing frames the one with the lowest index, A before B at the same index (passes run in frame
+ *      order and the call stops behind the first pass with a failing frame).
+ *  THE SHORTCUT, and what it does not promise. Without ZRA_HIP_COMPARE_DECODE_ALL a frame of the range is EQUAL without being decoded
+ *  when its two seek-table spans are well formed (the decoder's convention: a <= b <= body size), equally long and hold the same
+ *  bytes. Anything else is decoded on both sides, whole, checksums verified: an odd span, another length, one differing byte; the
+ *  decoder's own refusal is then the status. Identical damaged frames are therefore equal and go unnoticed, exactly as the update
+ *  carries them over: COMPARE IS NOT VERIFY (ZraHipVerifyArchive is). On archives whose frames all decode, both modes give the same
+ *  ranges.
+ *  The frames are taken in passes of max(1, min(65,536, stagingBytes / (2 * frameSize))) consecutive frames (stagingBytes 0: 4 GiB in
+ *  all): the staging window holds one half per archive. Frames outside the range are not touched.
+ *  Cost: every compressed byte of the range is read once (less for a frame that differs early); a frame pair that is decoded is read
+ *  once more as plaintext, twice when it holds a listed range boundary.
+ *  Not covered: archives of different frame sizes beyond the refusal, a variant on ZraHipArchive handles that uses resident frames,
+ *  the shards of a distributed archive (ZraHipShard), the host-pointer API, a patch that ZraHipUpdateArchive could apply. */
+ZRA_EXPORT ZraStatus ZraHipCompareArchives(ZraHipEngine* engine,
+    const void* dA, size_t sizeA, const void* dB, size_t sizeB,
+    uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes);
+/** The last ZraHipCompareArchives on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames of the range, frames equal by their compressed bytes, frame pairs decoded, content bytes of the range compared
+ *  after a decode, ranges, ranges listed, passes, 0}. Counters, not timings. */
+ZRA_EXPORT void ZraHipGetCompareStats(ZraHipEngine* engine, uint64_t* out8);
+/** The content sizes of the last ZraHipCompareArchives on the engine: out2 = {UA, UB}, set on every Success, the empty range included
+ *  (whose stats are all zero); {0, 0} after any other outcome. engine NULL: {0, 0}; out2 NULL: no-op. */
+ZRA_EXPORT void ZraHipGetCompareSizes(ZraHipEngine* engine, uint64_t* out2);
+/** Bring-up aid, like ZraHipDebugSearchScanMs: HIP-event time of the last compare's own launches (span compare, job build, count,
+ *  prefix scan, fill), summed over its passes; the decode of the same call is in ZraHipGetKernelStats. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugCompareMs(ZraHipEngine* engine);
+
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody
  *  (capacity nFrames*ZSTD_compressBound(frameSize)); writes the nFrames local frame sizes (u64, device) to dSizes and the

@@ -144,6 +144,11 @@ def load():
         "ZraHipSearchArchive": (S, [vp, vp, sz, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipGetSearchStats": (None, [vp, u64p]),
         "ZraHipDebugSearchScanMs": (ctypes.c_double, [vp]),
+        # compare
+        "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
+        "ZraHipGetCompareStats": (None, [vp, u64p]),
+        "ZraHipGetCompareSizes": (None, [vp, u64p]),
+        "ZraHipDebugCompareMs": (ctypes.c_double, [vp]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -190,7 +195,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
                    "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
-                   "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs"]
+                   "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
+                   "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs"]
 
 
 def _chk(st, what=""):
@@ -422,6 +428,37 @@ class Engine:
         """bring-up: HIP-event time of the last search()'s scan launches, summed over its passes (its decode: kernel_stats()['dec_ms'])."""
         return self.L.ZraHipDebugSearchScanMs(self.h)
 
+    def compare(self, d_a, size_a, d_b, size_b, *, decode_all=False, offset=0, length=None, staging_bytes=0, max_ranges=1 << 16):
+        """ZraHipCompareArchives: the maximal runs of content positions inside [offset, offset + length) (None: to the end of the
+        shorter content) at which the archives at d_a and d_b differ. Returns (n_ranges, differing_bytes, [(offset, size)]): every
+        range is counted, and the first max_ranges are listed in ascending order. Frames whose compressed bytes agree are equal
+        without a decode unless decode_all. The two content sizes: compare_sizes(). ZraError is a call that could not compare (bad
+        header, different frame sizes, range outside the common content, a frame that had to be decoded and does not, no memory)."""
+        arr = (ctypes.c_uint64 * (2 * max_ranges))() if max_ranges else None
+        n, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipCompareArchives(self.h, d_a or None, size_a, d_b or None, size_b, COMPARE_DECODE_ALL if decode_all else 0, offset,
+                                          (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_ranges, ctypes.byref(n),
+                                          ctypes.byref(nb)), "ZraHipCompareArchives")
+        k = min(n.value, max_ranges)
+        return n.value, nb.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def compare_stats(self):
+        """Counters of the last compare() on this engine (all zero unless it succeeded), keyed by COMPARE_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetCompareStats(self.h, a)
+        return dict(zip(COMPARE_STATS, (int(v) for v in a[:7])))
+
+    def compare_sizes(self):
+        """(UA, UB): the content sizes of the two archives of the last compare() (zero unless it succeeded)."""
+        a = (ctypes.c_uint64 * 2)()
+        self.L.ZraHipGetCompareSizes(self.h, a)
+        return int(a[0]), int(a[1])
+
+    def compare_ms(self):
+        """bring-up: HIP-event time of the last compare()'s own launches, summed over its passes (its decode: kernel_stats()['dec_ms'])."""
+        return self.L.ZraHipDebugCompareMs(self.h)
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
@@ -434,6 +471,9 @@ VERIFY_STATS = ("frames", "checked", "structure_faults", "content_faults", "deco
 
 SEARCH_MAX_PATTERN = 256                     # ZRA_HIP_SEARCH_MAX_PATTERN
 SEARCH_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes")
+
+COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
+COMPARE_STATS = ("frames", "equal_compressed", "decoded", "content_bytes", "ranges", "listed", "passes")
 
 
 class Archive:

@@ -778,6 +778,24 @@ void ZraHipGetSearchStats(ZraHipEngine* engine, uint64_t* out8) {
   if (engine) engine->e->search_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugSearchScanMs(ZraHipEngine* engine) { return engine ? engine->e->search_scan_ms() : 0.0; }
+ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
+                                size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {
+  static_assert(sizeof(ZraHipContentRange) == 16, "two 64-bit words per range");
+  if (nRanges) *nRanges = 0;
+  if (differingBytes) *differingBytes = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->compare_archives((const uint8_t*)dA, sizeA, (const uint8_t*)dB, sizeB, mode, offset, size, stagingBytes, (uint64_t*)hRanges,
+                                        rangeCapacity, nRanges, differingBytes));
+}
+void ZraHipGetCompareStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->compare_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+void ZraHipGetCompareSizes(ZraHipEngine* engine, uint64_t* out2) {
+  if (!out2) return;
+  if (engine) engine->e->compare_sizes(out2); else out2[0] = out2[1] = 0;
+}
+double ZraHipDebugCompareMs(ZraHipEngine* engine) { return engine ? engine->e->compare_ms() : 0.0; }
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

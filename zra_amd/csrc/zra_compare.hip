@@ -1,0 +1,432 @@
+// zra_amd — compare of two device-resident archives (zra_hip.h: ZraHipCompareArchives): the maximal runs of content positions inside a
+// content range at which the two archives differ, in ascending order, without an output buffer for either content.
+//
+//   1. both fixed headers come to the host (Engine::archive_view, A then B); the range becomes frames [f0, f1] of both archives
+//   2. per pass of at most passSlots consecutive frames: the two seek-table spans of every frame are compared as they
+//      lie, a wave per frame: one flag per slot, equal or decode                                          zra_cmp_spans_kernel
+//   3. the decode-flagged frames of the pass, in frame order, become decode jobs of both archives          zra_cmp_jobs_kernel
+//   4. the jobs are decoded whole, checksums verified, A into the first half of the window, B into the
+//      second; none flagged: the decoder is not launched                                                   Engine::staged_pass, twice
+//   5. the two halves are compared a tile per workgroup: run starts and run ends per tile                  zra_cmp_count_kernel
+//   6. the tile counts become list positions behind the starts and ends of the earlier passes             zra_cmp_scan_kernel
+//   7. tiles that hold a listed start or end redo their compare and write the positions                    zra_cmp_fill_kernel
+//   8. the counts and the first rangeCapacity starts and ends come to the host, once; the host writes {start, end - start}
+// The staging window (Engine::stage_) is [ half A | half B ], a half = the pass's slots rounded up to 16 bytes: slot s of either half
+// lies at s * frameSize of it, so the two plaintexts of a frame share their alignment modulo 16.
+//
+// Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
+//  (slots) slot = frame - first frame of the pass, on both sides, whether the frame is decoded or not. A decoded frame that is not the
+//      last of the range regenerates frameSize bytes on both sides (anything else is a failing frame and ends the call), so the byte in
+//      front of a decoded frame's first byte is the last byte of the slot in front: the window is addressed by arithmetic alone. The
+//      slot of an equal-flagged frame, and what lies behind a short last frame, is plaintext of earlier passes and is never read: a
+//      tile's positions are clipped to [lo, hi) and hi <= min(UA, UB), the bytes both sides regenerate.
+//  (look-behind) with d(p) = "A and B differ at p", a start is d(p) && !(p > lo && d(p - 1)), an end (exclusive) is
+//      !d(p) && p > lo && d(p - 1), found by the tile that holds p. Three ends lie at positions no tile holds, and belong to the tile
+//      that holds p - 1 (they are the last end of that tile): the end at hi; the end at the first byte of an equal-flagged frame behind
+//      a decoded one of the same pass (the flags of a pass are complete before its tiles run); and, when the decoded frame was the last
+//      of its pass, the carry: the count launch leaves d(p - 1) in a word, and the next pass reads it: as d(p - 1) of its first tile if
+//      its first frame is decoded, else in its item 0, which owns the end at the pass's first byte.
+//  (order) the items of a pass are item 0, then the tiles of the decoded frames in content order; starts and ends are counted per item,
+//      scanned, and filled independently. Every run has one start and one end, so start i and end i belong together, and a range cut by
+//      the capacity never appears. The scan launches are chained by two 64-bit totals that ping-pong between two word pairs, the carry
+//      between two words (pass k reads word k & 1 and writes word (k + 1) & 1, which the host zeroed in front of the count launch). A
+//      list position is a sum of counts and lane prefixes, never the result of an atomic, and no workgroup waits for another one.
+//  (d) nothing goes to the caller's array before the last pass is done: a call that fails midway writes nothing.
+#include "zra_host.h"
+#include "zra_dev.h"
+#include <algorithm>
+
+using namespace zra_dev;
+
+namespace {
+constexpr u32 kTile = 8192;                  // content positions of one workgroup: the search's tile (zra_search.hip)
+constexpr u32 kChunks = kTile / 16 + 1;      // 16-byte loads of a tile that starts behind a 16-byte boundary
+constexpr u32 kOwn = 3;                      // consecutive chunks a lane owns when the boundaries are taken: 171 lanes x 3 = 513
+constexpr u32 kOwners = kChunks / kOwn;
+static_assert(kOwners * kOwn == kChunks && kOwners <= 256, "every chunk has one owner");
+// the table words in front of the per-item entries (bytes): totals {starts, ends} x 2 | differing bytes | content bytes compared |
+// carry x 2 (u32) | decode jobs of the pass (u32)
+constexpr u32 kHdrBytes = 64, kOffDiff = 32, kOffBytes = 40, kOffCarry = 48, kOffJobs = 56;
+
+// bit j = byte j of the 16 is not zero
+__device__ __forceinline__ u32 nonzero_bytes(uint4 x) {
+  auto four = [](u32 w) {
+    const u32 b = ((((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u) >> 7;
+    return (b | (b >> 7) | (b >> 14) | (b >> 21)) & 0xFu;
+  };
+  return four(x.x) | (four(x.y) << 4) | (four(x.z) << 8) | (four(x.w) << 12);
+}
+// bits j of a chunk whose byte 0 is tile position r0 with a <= r0 + j < b
+__device__ __forceinline__ u32 valid_bits(int r0, int a, int b) {
+  const int l = min(16, max(0, a - r0)), h = min(16, max(0, b - r0));
+  return h > l ? ((1u << h) - 1u) & ~((1u << l) - 1u) : 0u;
+}
+
+struct TileArgs {
+  const u8* winA; const u8* winB;            // slot 0 of the two halves
+  const u64* outOff; const u8* flags;        // job -> slot * frameSize; slot -> 1 decode, 0 equal
+  u64 fs, first, lo, hi;
+  u32 nj, tpf;                               // slots of the pass, tiles per frame
+  const u32* carryIn;
+};
+// What one tile found: the run starts and ends among the positions its lane owns (st / en: bit j of word q = byte j of chunk
+// kOwn * tid + q), their counts over the workgroup (per wave: sRed[w] starts, sRed[4 + w] ends), the differing bytes, the end no
+// position of the tile holds (look-behind), the carry.
+struct TileOut {
+  u32 st[kOwn], en[kOwn];
+  u32 nS, nE;                                // this lane's
+  u32 totS, totE, totDiff;                   // the workgroup's
+  bool extraEnd, carryOut;
+  u64 extraAt, pos0;                         // content position of the extra end; of byte 0 of chunk 0
+};
+
+// Item `item` (>= 0: job item / tpf, tile item % tpf of its frame) of a pass. The tile's positions are [a, b) of its frame, clipped to
+// [lo, hi) and the frame size by arithmetic. Both halves are loaded with 16-byte loads from the aligned address at or below the tile's
+// first byte (the halves share their alignment), only chunks that hold a position of [a, b): at most 15 bytes in front of it (inside
+// the window: slot 0 is aligned) and 15 behind (inside the window's slack). sM: kChunks + 3 words.
+__device__ __forceinline__ void diff_tile(const TileArgs& T, u32 item, u32* sM, u32* sRed, TileOut& o) {
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const u32 k = item / T.tpf, t = item % T.tpf;
+  const u64 off = T.outOff[k];
+  const u32 s = (u32)(off / T.fs);
+  const u64 fBase = (T.first + s) * T.fs, t0 = (u64)t * kTile;
+  const u64 iLo = T.lo > fBase ? T.lo - fBase : 0, iHi = min(T.fs, T.hi - fBase);
+  const u64 a64 = max(t0, iLo), b64 = min(t0 + kTile, iHi);
+  for (u32 q = 0; q < kOwn; q++) o.st[q] = o.en[q] = 0;
+  o.nS = o.nE = o.totS = o.totE = o.totDiff = 0; o.extraEnd = o.carryOut = false; o.extraAt = 0; o.pos0 = 0;
+  if (a64 >= b64) return;                                                     // (uniform in the workgroup)
+  const int a = (int)(a64 - t0), b = (int)(b64 - t0);
+  const u8* const pA = T.winA + off + t0; const u8* const pB = T.winB + off + t0;
+  const u32 d = (u32)((size_t)pA & 15);
+  const uint4* const gA = (const uint4*)(pA - d); const uint4* const gB = (const uint4*)(pB - d);
+  o.pos0 = fBase + t0 - d;
+  // d(p - 1) of the tile's first position (look-behind)
+  bool prev = false;
+  if (tid == 0 && fBase + a64 != T.lo) {
+    if (a64 > 0) prev = pA[a - 1] != pB[a - 1];                               // the same frame, or the tile in front
+    else if (s > 0) prev = T.flags[s - 1] && pA[-1] != pB[-1];                // the frame in front: decoded in this pass, or equal
+    else prev = *T.carryIn != 0;                                              // the last frame of the pass in front
+  }
+  for (u32 c = tid; c < kChunks + 2; c += 256) {
+    const int r0 = (int)(16 * c) - (int)d;
+    u32 m = 0;
+    if (c < kChunks && r0 < b && r0 + 16 > a) {
+      const uint4 x = gA[c], y = gB[c];
+      m = nonzero_bytes(make_uint4(x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w)) & valid_bits(r0, a, b);
+    }
+    sM[c + 1] = m;                                                            // bit j of word c + 1 = position 16 (c + 1) + j - 16 - d of the tile
+  }
+  if (tid == 0) sM[0] = 0;
+  __syncthreads();
+  if (tid == 0 && prev) { const u32 e = (u32)a + d + 15; sM[e >> 4] |= 1u << (e & 15); }   // position a - 1: outside the valid bits, seen as a predecessor
+  __syncthreads();
+  u32 diff = 0;
+  if (tid < kOwners) {
+#pragma unroll
+    for (u32 q = 0; q < kOwn; q++) {
+      const u32 c = kOwn * tid + q;
+      const u32 m = sM[c + 1], before = ((m << 1) | (sM[c] >> 15)) & 0xFFFFu, v = valid_bits((int)(16 * c) - (int)d, a, b);
+      o.st[q] = m & ~before & v;
+      o.en[q] = ~m & before & v;
+      o.nS += (u32)__popc(o.st[q]); o.nE += (u32)__popc(o.en[q]); diff += (u32)__popc(m & v);
+    }
+  }
+  const u32 wS = wave_sum(o.nS), wE = wave_sum(o.nE), wD = wave_sum(diff);
+  if (lane == 0) { sRed[wave] = wS; sRed[4 + wave] = wE; sRed[8 + wave] = wD; }
+  __syncthreads();
+  for (u32 w = 0; w < 4; w++) { o.totS += sRed[w]; o.totE += sRed[4 + w]; o.totDiff += sRed[8 + w]; }
+  // the end behind the frame's last position of the range, when no tile holds it
+  const u32 eL = (u32)b - 1 + d + 16;
+  if (b64 == iHi && ((sM[eL >> 4] >> (eL & 15)) & 1)) {
+    o.extraAt = fBase + b64;
+    if (o.extraAt == T.hi) o.extraEnd = true;
+    else if (s + 1 < T.nj) o.extraEnd = T.flags[s + 1] == 0;
+    else o.carryOut = true;
+  }
+}
+}  // namespace
+
+// Wave per frame of a pass: flags[j] = 0 when the two seek-table spans of frame first + j are well formed (the decoder's convention:
+// a <= b <= body size), equally long and hold the same bytes; 1 otherwise: the frame is decoded. Only bytes of the two spans are read.
+// The spans start at unrelated alignments: up to 15 head bytes bring side A to a 16-byte boundary, then 16-byte vectors (A aligned,
+// B as it lies), four per lane and trip, then up to 15 tail bytes. The wave leaves on the first trip with a differing vector.
+// The compare is exact for every length, 0 included: two identical spans too short to be a frame (fewer than 9 bytes) are equal on
+// purpose, like any other pair of identical damaged frames (zra_hip.h: compare is not verify).
+extern "C" __global__ void __launch_bounds__(256) zra_cmp_spans_kernel(const u8* tableA, const u8* bodyA, u64 bodyBytesA, const u8* tableB, const u8* bodyB,
+                                                                       u64 bodyBytesB, u64 first, u32 nj, u8* flags) {
+  const u32 j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (j >= nj) return;                                                        // (uniform in the wave)
+  const u64 f = first + j;
+  const u64 a0 = seek_entry(tableA, f), a1 = seek_entry(tableA, f + 1), b0 = seek_entry(tableB, f), b1 = seek_entry(tableB, f + 1);
+  bool decode = !(a0 <= a1 && a1 <= bodyBytesA && b0 <= b1 && b1 <= bodyBytesB && a1 - a0 == b1 - b0);
+  if (!decode) {
+    const u64 n = a1 - a0;
+    const u8* pa = bodyA + a0; const u8* pb = bodyB + b0;
+    const u32 head = (u32)min<u64>(n, (16u - (u32)((size_t)pa & 15)) & 15u);
+    bool differ = lane < head && pa[lane] != pb[lane];
+    pa += head; pb += head;
+    const u64 nv = (n - head) >> 4;
+    const u32 tail = (u32)((n - head) & 15);
+    if (lane < tail) differ |= pa[16 * nv + lane] != pb[16 * nv + lane];
+    const uint4* const va = (const uint4*)pa;
+    const u128_u* const vb = (const u128_u*)pb;
+    for (u64 i0 = 0; i0 < nv && !__any(differ); i0 += 256) {
+      uint4 x[4]; u128_u y[4];
+#pragma unroll
+      for (u32 q = 0; q < 4; q++) {
+        const u64 i = i0 + 64 * q + lane;
+        if (i < nv) { x[q] = va[i]; y[q] = vb[i]; } else { x[q] = make_uint4(0, 0, 0, 0); y[q].a = y[q].b = y[q].c = y[q].d = 0; }
+      }
+#pragma unroll
+      for (u32 q = 0; q < 4; q++) differ |= ((x[q].x ^ y[q].a) | (x[q].y ^ y[q].b) | (x[q].z ^ y[q].c) | (x[q].w ^ y[q].d)) != 0;
+    }
+    decode = __any(differ);
+  }
+  if (lane == 0) flags[j] = decode ? 1 : 0;
+}
+
+// One workgroup: the decode-flagged slots of the pass, in order, become jobs 0 .. nDec - 1 of archive A (frameOff / expect at job k)
+// and of archive B (at job jobsB + k); outOff[k] = the slot's place in its half, the same for both. A job decodes its frame's seek-table
+// span, whatever it says (the decoder refuses a span that runs backwards or leaves the body), and has to regenerate that frame's share
+// of its own archive's content. hdr: the job count for the host, and the content bytes of [lo, hi) inside the decoded frames, summed.
+extern "C" __global__ void __launch_bounds__(1024) zra_cmp_jobs_kernel(const u8* flags, u32 nj, const u8* tableA, u64 UA, const u8* tableB, u64 UB, u64 fs,
+                                                                       u64 first, u64 lo, u64 hi, u64* frameOff, u64* outOff, u32* expect, u32 jobsB, u8* hdr) {
+  __shared__ u32 sS[1024];
+  __shared__ u64 sBytes;
+  const u32 tid = threadIdx.x;
+  const u32 per = (nj + 1023) / 1024;
+  const u32 s0 = min(nj, tid * per), s1 = min(nj, s0 + per);
+  u32 own = 0;
+  for (u32 s = s0; s < s1; s++) own += flags[s] != 0;
+  sS[tid] = own;
+  if (tid == 0) sBytes = 0;
+  __syncthreads();
+  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
+    const u32 x = tid >= d ? sS[tid - d] : 0;
+    __syncthreads();
+    sS[tid] += x;
+    __syncthreads();
+  }
+  u32 k = sS[tid] - own;
+  u64 bytes = 0;
+  for (u32 s = s0; s < s1; s++) {
+    if (!flags[s]) continue;
+    const u64 f = first + s;
+    frameOff[2 * (size_t)k] = seek_entry(tableA, f); frameOff[2 * (size_t)k + 1] = seek_entry(tableA, f + 1);
+    frameOff[2 * ((size_t)jobsB + k)] = seek_entry(tableB, f); frameOff[2 * ((size_t)jobsB + k) + 1] = seek_entry(tableB, f + 1);
+    expect[k] = (u32)frame_expect(f, fs, UA); expect[(size_t)jobsB + k] = (u32)frame_expect(f, fs, UB);
+    outOff[k] = (u64)s * fs;
+    bytes += min(hi, (f + 1) * fs) - max(lo, f * fs);
+    k++;
+  }
+  if (bytes) atomicAdd((unsigned long long*)&sBytes, (unsigned long long)bytes);
+  __syncthreads();
+  if (tid == 1023) { *(u32*)(hdr + kOffJobs) = sS[1023]; *(u64*)(hdr + kOffBytes) += sBytes; }
+}
+
+// Workgroup 0 is item 0 of the pass (the end at the pass's first byte, when the pass in front left a run open and the first frame is
+// equal); workgroup i > 0: tile i - 1 of the decoded frames. tab[2 i] = the item's starts, tab[2 i + 1] = its ends. The differing
+// bytes are summed into one word (a sum, not a position); the tile behind which the pass ends leaves the carry.
+extern "C" __global__ void __launch_bounds__(256) zra_cmp_count_kernel(TileArgs T, u64* tab, u64* diffBytes, u32* carryOut) {
+  __shared__ u32 sM[kChunks + 3], sRed[12];
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) { tab[0] = 0; tab[1] = (*T.carryIn != 0 && T.flags[0] == 0) ? 1 : 0; }
+    return;
+  }
+  TileOut o;
+  diff_tile(T, blockIdx.x - 1, sM, sRed, o);
+  if (threadIdx.x == 0) {
+    tab[2 * (size_t)blockIdx.x] = o.totS; tab[2 * (size_t)blockIdx.x + 1] = o.totE + (o.extraEnd ? 1 : 0);
+    if (o.totDiff) atomicAdd((unsigned long long*)diffBytes, (unsigned long long)o.totDiff);
+    if (o.carryOut) *carryOut = 1;
+  }
+}
+
+// One workgroup, in place: tab[2 i] / tab[2 i + 1] = totIn + the starts / ends of the items in front of item i, for i = 0 .. nItems
+// (entry nItems: behind all of them; an item's own counts are the difference to the next entry); totOut = that last entry.
+extern "C" __global__ void __launch_bounds__(1024) zra_cmp_scan_kernel(u64* tab, u32 nItems, const u64* totIn, u64* totOut) {
+  __shared__ u64 sS[1024], sE[1024];
+  const u32 tid = threadIdx.x;
+  const u32 per = (nItems + 1023) / 1024;
+  const u32 i0 = min(nItems, tid * per), i1 = min(nItems, i0 + per);
+  u64 ownS = 0, ownE = 0;
+  for (u32 i = i0; i < i1; i++) { ownS += tab[2 * (size_t)i]; ownE += tab[2 * (size_t)i + 1]; }
+  sS[tid] = ownS; sE[tid] = ownE;
+  __syncthreads();
+  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
+    const u64 x = tid >= d ? sS[tid - d] : 0, y = tid >= d ? sE[tid - d] : 0;
+    __syncthreads();
+    sS[tid] += x; sE[tid] += y;
+    __syncthreads();
+  }
+  u64 atS = totIn[0] + sS[tid] - ownS, atE = totIn[1] + sE[tid] - ownE;
+  for (u32 i = i0; i < i1; i++) {
+    const u64 cS = tab[2 * (size_t)i], cE = tab[2 * (size_t)i + 1];
+    tab[2 * (size_t)i] = atS; tab[2 * (size_t)i + 1] = atE;
+    atS += cS; atE += cE;
+  }
+  if (tid == 1023) {
+    const u64 eS = totIn[0] + sS[1023], eE = totIn[1] + sE[1023];
+    tab[2 * (size_t)nItems] = eS; tab[2 * (size_t)nItems + 1] = eE;
+    totOut[0] = eS; totOut[1] = eE;
+  }
+}
+
+// Workgroup i redoes item i's compare when one of its starts or ends has a place in the lists (an item without any, or behind the
+// capacity, leaves at once). A start's place is the item's base, plus the starts of the waves in front of its own, plus those of the
+// lanes in front of its own (a prefix sum over the wave), plus those in front of it in its lane; an end's likewise.
+extern "C" __global__ void __launch_bounds__(256) zra_cmp_fill_kernel(TileArgs T, const u64* tab, u64* starts, u64* ends, u64 cap) {
+  __shared__ u32 sM[kChunks + 3], sRed[12];
+  const u64 baseS = tab[2 * (size_t)blockIdx.x], baseE = tab[2 * (size_t)blockIdx.x + 1];
+  const u64 cntS = tab[2 * (size_t)blockIdx.x + 2] - baseS, cntE = tab[2 * (size_t)blockIdx.x + 3] - baseE;
+  if ((cntS == 0 || baseS >= cap) && (cntE == 0 || baseE >= cap)) return;   // (uniform in the workgroup)
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) ends[baseE] = T.first * T.fs;                       // (cntE == 1 and baseE < cap)
+    return;
+  }
+  TileOut o;
+  diff_tile(T, blockIdx.x - 1, sM, sRed, o);
+  const u32 tid = threadIdx.x, wave = tid >> 6;
+  u64 atS = baseS + wave_incl_scan(o.nS) - o.nS, atE = baseE + wave_incl_scan(o.nE) - o.nE;
+  for (u32 w = 0; w < wave; w++) { atS += sRed[w]; atE += sRed[4 + w]; }
+#pragma unroll
+  for (u32 q = 0; q < kOwn; q++) {
+    const u64 p = o.pos0 + 16 * (u64)(kOwn * tid + q);
+    for (u32 m = o.st[q]; m; m &= m - 1, atS++) if (atS < cap) starts[atS] = p + (u32)__builtin_ctz(m);
+    for (u32 m = o.en[q]; m; m &= m - 1, atE++) if (atE < cap) ends[atE] = p + (u32)__builtin_ctz(m);
+  }
+  if (tid == 0 && o.extraEnd && baseE + o.totE < cap) ends[baseE + o.totE] = o.extraAt;
+}
+
+// =================================================================================================
+namespace zra_eng {
+
+struct CompareImpl {
+  static Status run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
+                    size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes);
+};
+
+Status Engine::compare_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
+                                size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes) {
+  for (auto& v : cstats_) v = 0;
+  cmpSizes_[0] = cmpSizes_[1] = 0;
+  compareMs_ = 0;
+  if (nRanges) *nRanges = 0;
+  if (differingBytes) *differingBytes = 0;
+  const Status st = CompareImpl::run(*this, dA, sizeA, dB, sizeB, mode, offset, size, stagingBytes, hRanges, rangeCap, nRanges, differingBytes);
+  if (st.zra) compareMs_ = 0;
+  return st;
+}
+
+Status CompareImpl::run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
+                        size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes) {
+  constexpr uint32_t kDecodeAll = 1u;                                         // ZRA_HIP_COMPARE_DECODE_ALL
+  // ---- 1. arguments
+  if (!nRanges || (!dA && sizeA) || (!dB && sizeB) || (!hRanges && rangeCap) || (mode & ~kDecodeAll)) return zerr(42);
+  HIPCHK_CLR(hipSetDevice(E.device_));
+  hipStream_t s = E.stream_;
+  E.reset_decode_stats();
+  // ---- 2. headers, A then B: the statuses of ZraHipArchiveOpen. (The headers' CRC-32 is not looked at: that is the verifier's job.)
+  ArchiveView A, B;
+  { Status st = E.archive_view(dA, sizeA, &A); if (st.zra) return st; }
+  if (A.fs == 0) return {kHeaderInvalid, 0};
+  { Status st = E.archive_view(dB, sizeB, &B); if (st.zra) return st; }
+  if (B.fs == 0) return {kHeaderInvalid, 0};
+  // ---- 3. one frame size
+  if (A.fs != B.fs) return zerr(40);
+  const uint64_t fs = A.fs, C = std::min(A.U, B.U);
+  // ---- 4. the range [lo, hi) of the common content, inclusive bound
+  if (offset > C || (size != ~0ull && (offset + size < offset || offset + size > C))) return {kOutOfBounds, 0};
+  const uint64_t lo = offset, hi = size == ~0ull ? C : offset + size;
+  if (hi == lo) { E.cmpSizes_[0] = A.U; E.cmpSizes_[1] = B.U; return ok(); }
+  const uint64_t f0 = lo / fs, f1 = (hi - 1) / fs, n = f1 - f0 + 1;           // (frames of both archives: hi <= C, and ra_header ties frames to U)
+  // ---- 5. scratch
+  const uint32_t passSlots = pass_slots(2 * fs, stagingBytes);
+  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
+  const uint64_t passes = (n + passSlots - 1) / passSlots;
+  const uint64_t half = ((uint64_t)nSlots * fs + 15) & ~15ull;
+  const uint32_t tpf = (uint32_t)((fs + kTile - 1) / kTile);
+  const size_t itemsMax = 1 + (size_t)nSlots * tpf;
+  const size_t listCap = (size_t)std::min<uint64_t>(rangeCap, (hi - lo + 1) / 2);   // (runs are at least one byte long and one byte apart)
+  if (!E.stage_.reserve((size_t)(2 * half) + 64) || !E.cmp_.flags.reserve((size_t)nSlots + 64) || !E.cmp_.tables.reserve(kHdrBytes + (itemsMax + 1) * 16 + 64) ||
+      !E.cmp_.list.reserve(listCap * 16 + 64) || !E.frameOff_.reserve((2 * (size_t)nSlots + 1) * 16) || !E.outOff_.reserve(((size_t)nSlots + 1) * 8) ||
+      !E.expect_.reserve((2 * (size_t)nSlots + 1) * 4))
+    return zerr(64);
+  if (!E.call_events()) return zerr(1);
+  uint8_t* const winA = E.stage_.as<uint8_t>();
+  uint8_t* const winB = winA + half;
+  uint8_t* const flags = E.cmp_.flags.as<uint8_t>();
+  uint8_t* const hdr = E.cmp_.tables.as<uint8_t>();
+  uint64_t* const tot = (uint64_t*)hdr;
+  uint32_t* const carry = (uint32_t*)(hdr + kOffCarry);
+  uint64_t* const tab = (uint64_t*)(hdr + kHdrBytes);
+  uint64_t* const starts = E.cmp_.list.as<uint64_t>();
+  uint64_t* const ends = starts + listCap;
+  HIPCHK_CLR(hipMemsetAsync(hdr, 0, kHdrBytes, s));
+  // ---- passes
+  uint64_t decoded = 0;
+  // evCall_[0] .. evCall_[1] spans the compare's own launches between two decodes: the tiles of a pass and the spans and jobs of the
+  // next one follow each other on the stream. Taken behind a synchronisation of the stream.
+  auto take_time = [&]() { E.compareMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
+  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
+  for (uint64_t p = 0; p < passes; p++) {
+    const uint64_t first = f0 + p * passSlots;
+    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
+    if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(flags, 1, nj, s));
+    else
+      hipLaunchKernelGGL(zra_cmp_spans_kernel, dim3((nj + 3) / 4), dim3(256), 0, s, A.table, A.body, (u64)A.bodyBytes, B.table, B.body, (u64)B.bodyBytes, (u64)first,
+                         nj, flags);
+    hipLaunchKernelGGL(zra_cmp_jobs_kernel, dim3(1), dim3(1024), 0, s, flags, nj, A.table, (u64)A.U, B.table, (u64)B.U, (u64)fs, (u64)first, (u64)lo, (u64)hi,
+                       E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), nSlots, hdr);
+    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
+    uint32_t nDec = 0;
+    HIPCHK_CLR(hipMemcpyAsync(&nDec, hdr + kOffJobs, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
+    HIPCHK_CLR(hipGetLastError());
+    take_time();
+    if (nDec > nj) return zerr(1);                                            // (cannot happen)
+    if (nDec) {
+      unsigned long long errA, errB;
+      { Status st = E.staged_pass(A, 0, nDec, winA, &errA); if (st.zra) return st; }
+      { Status st = E.staged_pass(B, nSlots, nDec, winB, &errB); if (st.zra) return st; }
+      // the lowest failing frame of the first failing pass (jobs are in frame order, the same on both sides), A before B
+      if (errA != ~0ull || errB != ~0ull) return zerr(reported_code((errB >> 8) < (errA >> 8) ? errB : errA));
+      decoded += nDec;
+    }
+    // (look-behind) item 0 and the tiles of the decoded frames
+    const uint32_t items = 1 + nDec * tpf;
+    TileArgs T;
+    T.winA = winA; T.winB = winB; T.outOff = E.outOff_.as<uint64_t>(); T.flags = flags; T.fs = fs; T.first = first; T.lo = lo; T.hi = hi; T.nj = nj; T.tpf = tpf;
+    T.carryIn = carry + (p & 1);
+    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
+    HIPCHK_CLR(hipMemsetAsync(carry + ((p + 1) & 1), 0, 4, s));
+    hipLaunchKernelGGL(zra_cmp_count_kernel, dim3(items), dim3(256), 0, s, T, tab, (u64*)(hdr + kOffDiff), carry + ((p + 1) & 1));
+    hipLaunchKernelGGL(zra_cmp_scan_kernel, dim3(1), dim3(1024), 0, s, tab, items, tot + 2 * (p & 1), tot + 2 * ((p + 1) & 1));
+    if (listCap) hipLaunchKernelGGL(zra_cmp_fill_kernel, dim3(items), dim3(256), 0, s, T, tab, starts, ends, (u64)listCap);
+  }
+  // ---- the counts, then the lists, once
+  uint64_t h8[8] = {0};
+  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
+  HIPCHK_CLR(hipMemcpyAsync(h8, hdr, kHdrBytes, hipMemcpyDeviceToHost, s));
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
+  take_time();
+  const uint64_t total = h8[2 * (passes & 1)];
+  if (h8[2 * (passes & 1) + 1] != total) return zerr(1);                      // (cannot happen: every run has one start and one end)
+  const size_t nOut = (size_t)std::min<uint64_t>(total, listCap);
+  if (nOut) {
+    std::vector<uint64_t> se(2 * nOut);
+    HIPCHK_CLR(hipMemcpyAsync(se.data(), starts, nOut * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipMemcpyAsync(se.data() + nOut, ends, nOut * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
+    for (size_t i = 0; i < nOut; i++) { hRanges[2 * i] = se[i]; hRanges[2 * i + 1] = se[nOut + i] - se[i]; }
+  }
+  *nRanges = total;
+  if (differingBytes) *differingBytes = h8[kOffDiff / 8];
+  const uint64_t st8[8] = {n, n - decoded, decoded, h8[kOffBytes / 8], total, nOut, passes, 0};
+  for (int i = 0; i < 8; i++) E.cstats_[i] = st8[i];
+  E.cmpSizes_[0] = A.U; E.cmpSizes_[1] = B.U;
+  return ok();
+}
+
+}  // namespace zra_eng

@@ -33,7 +33,7 @@ struct HeaderInfo {
 };
 // parse the 38 fixed bytes; returns a ZRA status code (0 ok)
 int parse_fixed_header(const uint8_t* fixed38, HeaderInfo* h);
-// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search): the checked header and
+// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search, compare): the checked header and
 // where its parts lie. Built once per call, by Engine::archive_view or, from a header checked before (a handle's), by `over`. A shard of
 // a distributed archive (zra_comm.hip) overrides body / bodyBytes with the bytes [bodyBase, bodyBase + bodyBytes) of the body it holds.
 struct ArchiveView {
@@ -145,7 +145,7 @@ class Engine {
     if (hipMemcpyAsync(qmeta_.as<uint64_t>() + 4 * q0, pinQ_ + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, stream_) == hipSuccess) return ok();
     (void)hipGetLastError(); return zerr(1);
   }
-  // One staged pass (verify, search): jobs [j0, j0 + n) of frameOff_ / expect_ decoded whole, checksums verified, into `window`, job j0 + k at
+  // One staged pass (verify, search, compare): jobs [j0, j0 + n) of frameOff_ / expect_ decoded whole, checksums verified, into `window`, job j0 + k at
   // outOff_[k] (the same slots every pass). *firstError = decode_pass' word (~0: none failed); status_ / produced_: every job's own. Synchronised.
   Status staged_pass(const ArchiveView& a, uint32_t j0, uint32_t n, uint8_t* window, unsigned long long* firstError);
   // Host-walked frame list (reference semantics of DecompressBuffer: seek table not consulted). hFrameOff has nFrames+1 entries
@@ -198,6 +198,19 @@ class Engine {
   void search_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = sstats_[i]; }
   // bring-up: HIP-event time of the last search's scan launches (count, scan, fill, carry), summed over its passes
   double search_scan_ms() const { return searchScanMs_; }
+
+  // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
+  // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
+  // the same in both archives is equal without a decode (mode 1: every frame is decoded); the others are decoded whole on both sides, a
+  // staging window of two halves at a time, and compared on the device. Statuses and their order: zra_hip.h, ZraHipCompareArchives.
+  Status compare_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
+                          size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes);
+  // the last compare_archives: {frames of the range, equal by compressed bytes, frame pairs decoded, content bytes compared after decode,
+  // ranges, ranges listed, passes, 0}; all zero unless it succeeded. compare_sizes: the two content sizes, likewise
+  void compare_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = cstats_[i]; }
+  void compare_sizes(uint64_t out[2]) const { out[0] = cmpSizes_[0]; out[1] = cmpSizes_[1]; }
+  // bring-up: HIP-event time of the last compare's own launches (spans, jobs, count, scan, fill), summed over its passes
+  double compare_ms() const { return compareMs_; }
 
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
@@ -258,8 +271,8 @@ class Engine {
   int decOccParse_ = 0, decOccExec_ = 0, decOccHuf_ = 0; // resident workgroups per CU of the parse / execute kernels
   bool raVerifyWholeFrames_ = false;     // batched random access decodes every touched frame in full and checks its checksum
   DevBuf status_, produced_, frameMeta_, frameOff_, outOff_, expect_, result_, qmeta_;
-  // THE plaintext staging window of the device-archive calls (batch, update, verify, search): whole frames of one decode pass, slot s at
-  // s * frameSize; the search keeps its carry area in front of slot 0. Every engine call runs on stream_ and returns synchronised, so one
+  // THE plaintext staging window of the device-archive calls (batch, update, verify, search, compare): whole frames of one decode pass, slot s at
+  // s * frameSize; the search keeps its carry area in front of slot 0, the compare two halves of slots. Every engine call runs on stream_ and returns synchronised, so one
   // window is live at a time. THE RULE: a call reserves the window once, before it takes a pointer into it (reserve may move the buffer),
   // and from there to its last use calls nothing that reserves it. decode_jobs / decode_pass / staged_pass and compress_frames do not
   // (decoder and encoder scratch). The handle's read and update call ra_batch_body / update_archive, which do, but hold no window then.
@@ -284,7 +297,7 @@ class Engine {
   // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
   struct UpdScratch { DevBuf plan, packed, encSizes, frames, table, copies; } upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // around a pass's stage-from-cache kernel (update through a handle) or scan launches (search); the two never run inside each other
+  // around a pass's stage-from-cache kernel (update through a handle), scan launches (search) or own launches (compare); they never run inside each other
   hipEvent_t evCall_[2] = {nullptr, nullptr};
   double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list
@@ -294,10 +307,15 @@ class Engine {
   struct SearchScratch { DevBuf tables, list; } srch_;
   uint64_t sstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double searchScanMs_ = 0;
+  // compare scratch (zra_compare.hip): a flag per slot, the totals + carry + per-item table, the starts and ends of the listed ranges
+  struct CompareScratch { DevBuf flags, tables, list; } cmp_;
+  uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
+  double compareMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
+  friend struct CompareImpl;       // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

@@ -5,11 +5,13 @@
 //   d   : streaming decompress (FullDecompressor)
 //   imc : in-memory CompressBuffer          imd : in-memory DecompressBuffer
 //   b   : benchmark of all four + one random-access query with a memcmp check
-// and two modes of its own, against include/zra_hip.h:
+// and three modes of its own, against include/zra_hip.h:
 //   t   : test an archive like `zstd -t` (ZraHipVerifyArchive, content verification on the device); one line per faulty frame and a
 //         summary; exit status 0 clean, 1 faults, 2 the call failed
 //   g   : search an archive like `zstdgrep -F -b -o` (ZraHipSearchArchive, decode and scan on the device); one content offset per line
 //         and a summary; exit status as grep: 0 matches, 1 none, 2 trouble
+//   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
+//         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 #include <zra.hpp>
 #include <zra.h>
 #include <zra_hip.h>
@@ -167,6 +169,29 @@ int search_archive(const char* path, const char* text) {
   std::printf("%llu matches\n", (unsigned long long)n);
   return n ? 0 : 1;
 }
+
+// mode cmp. Nothing goes to stdout when the call fails.
+int compare_archives(const char* pathA, const char* pathB) {
+  zra::Buffer a = read_file(pathA), b = read_file(pathB);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", pathA, ZraGetErrorString(st)); return 2; }
+  void* dA = nullptr; void* dB = nullptr;
+  if (!to_device(pathA, a, &dA)) { ZraHipDestroyEngine(eng); return 2; }
+  if (!to_device(pathB, b, &dB)) { if (dA) (void)hipFree(dA); ZraHipDestroyEngine(eng); return 2; }
+  std::vector<ZraHipContentRange> at(1u << 20);
+  uint64_t n = 0, bytes = 0, u2[2] = {0, 0};
+  st = ZraHipCompareArchives(eng, dA, a.size(), dB, b.size(), 0, 0, UINT64_MAX, 0, at.data(), at.size(), &n, &bytes);
+  ZraHipGetCompareSizes(eng, u2);
+  if (dA) (void)hipFree(dA);
+  if (dB) (void)hipFree(dB);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s %s: cannot compare: %s\n", pathA, pathB, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(n, at.size()); i++) std::printf("%llu %llu\n", (unsigned long long)at[i].offset, (unsigned long long)at[i].size);
+  std::printf("%llu ranges, %llu bytes differ\n", (unsigned long long)n, (unsigned long long)bytes);
+  if (u2[0] != u2[1]) std::printf("sizes differ: %llu %llu\n", (unsigned long long)u2[0], (unsigned long long)u2[1]);
+  return n || u2[0] != u2[1] ? 1 : 0;
+}
 }  // namespace
 
 // argv of the reference tool, position by position (zratool.cpp:98-125,213-221):
@@ -177,6 +202,7 @@ int search_archive(const char* path, const char* text) {
 //   b   {file} {level} {frameSize} {stream buffer MB} {offset = 0x1000} {size = 0x10000}
 // ours: t {file}
 //       g {file} {pattern | hex:digits}
+//       cmp {file A} {file B}
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::printf("%s {mode} {file} ...\n"
@@ -186,7 +212,8 @@ int main(int argc, char** argv) {
                 "imd  {file} - In-memory Decompression\n"
                 "b  {file} {compression level = 3} {frame size = 16384} {stream buffer size = 10MB} {offset = 0x1000} {size = 0x10000} - Benchmark (Memory Intensive)\n"
                 "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n"
-                "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n",
+                "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n"
+                "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n",
                 argv[0]);
     return 0;
   }
@@ -195,6 +222,10 @@ int main(int argc, char** argv) {
   if (mode == "g") {
     if (argc < 4) { std::fprintf(stderr, "g {file} {pattern | hex:digits}\n"); return 2; }
     return search_archive(argv[2], argv[3]);
+  }
+  if (mode == "cmp") {
+    if (argc < 4) { std::fprintf(stderr, "cmp {file A} {file B}\n"); return 2; }
+    return compare_archives(argv[2], argv[3]);
   }
   const bool comp = mode == "c" || mode == "imc" || mode == "b";
   const zra::i8 level = comp && argc > 3 ? (zra::i8)std::atoi(argv[3]) : 0;
