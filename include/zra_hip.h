@@ -297,7 +297,8 @@ ZRA_EXPORT void ZraHipGetVerifyStats(ZraHipEngine* engine, uint64_t* out8);
  *  Cost: the scan reads every decoded byte once from HBM and a few times from LDS; a position whose first min(m, 4) bytes differ from
  *  the pattern's costs one word compare. The worst case is a pattern that matches everywhere (zeros in zeros): every position then runs
  *  the full m-byte compare, and every listed match is compared twice. That is accepted; there is no machinery for it.
- *  Not covered: a handle variant that scans resident frames from the cache of a ZraHipArchive, several patterns per call, regular
+ *  Several patterns per call: ZraHipSearchArchiveMulti, below.
+ *  Not covered: a handle variant that scans resident frames from the cache of a ZraHipArchive, regular
  *  expressions, the shards of a distributed archive (ZraHipShard), the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipSearchArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPattern, size_t patternSize,
@@ -311,6 +312,57 @@ ZRA_EXPORT void ZraHipGetSearchStats(ZraHipEngine* engine, uint64_t* out8);
 /** Bring-up aid, like ZraHipDebugUpdateStageMs: HIP-event time of the last search's scan launches (count, prefix scan, fill, carry),
  *  summed over its passes; the decode of the same call is in ZraHipGetKernelStats. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugSearchScanMs(ZraHipEngine* engine);
+
+/* ---- search for several patterns in one pass: what `grep -F -f patterns` is to `grep` ----
+ * The cost of a search is the decode of every frame of its range. A caller with K strings (request ids, a keyword list) would pay K
+ * decodes of the same frames with ZraHipSearchArchive and merge K lists on the host; this call decodes once and scans for all K. */
+#define ZRA_HIP_SEARCH_MAX_PATTERNS      64u
+#define ZRA_HIP_SEARCH_MAX_PATTERN_BYTES 4096u   /* sum of all pattern lengths */
+typedef struct ZraHipPatternMatch { uint64_t offset; uint32_t pattern; uint32_t reserved; } ZraHipPatternMatch;  /* reserved = 0 */
+
+/** Finds nPatterns byte patterns in the content range [offset, offset + size) of the archive at dArchive (size = UINT64_MAX: to the end
+ *  of the content). hPatterns (HOST memory) holds the patterns one after the other; pattern i has hPatternSizes[i] bytes, 1 ..
+ *  ZRA_HIP_SEARCH_MAX_PATTERN each, taken literally. Equal patterns are allowed and reported independently. Synchronous; the archive
+ *  is only read.
+ *  Result, with m_i the length of pattern i, M = max m_i and [lo, hi) = the range:
+ *  - A match is a pair (p, i) with lo <= p, p + m_i <= hi and content[p, p + m_i) == pattern i. Overlapping occurrences are all
+ *    matches, and so are several patterns at one p.
+ *  - *nMatches = the number of matches; it may exceed matchCapacity. The first min(*nMatches, matchCapacity) matches are written to
+ *    hMatches (a HOST array) in ascending (offset, pattern index) order, each exactly once, reserved = 0; nothing is written behind
+ *    them. A capacity that ends between two matches at one offset cuts there. hMatches may be NULL when matchCapacity is 0.
+ *  - hPerPattern may be NULL; otherwise a HOST array of nPatterns entries that receives the matches of each pattern, listed or not.
+ *  - On any status other than Success nothing is written to hMatches or hPerPattern, *nMatches is 0 and all stats are zero. No match
+ *    reaches the host before the last pass is done.
+ *  Statuses, checked in this order:
+ *   1. engine, nMatches, hPatterns or hPatternSizes NULL; dArchive NULL with archiveSize != 0; hMatches NULL with matchCapacity != 0;
+ *      nPatterns 0 or above ZRA_HIP_SEARCH_MAX_PATTERNS; a pattern size of 0 or above ZRA_HIP_SEARCH_MAX_PATTERN; a sum of the sizes
+ *      above ZRA_HIP_SEARCH_MAX_PATTERN_BYTES -> {ZStdError, 42}.
+ *   2. Header problems: ZraHipSearchArchive's rule 2.
+ *   3. The range: ZraHipSearchArchive's rule 3, inclusive bound. A range shorter than the shortest pattern is Success with 0 matches:
+ *      nothing is decoded and hPerPattern is all zero.
+ *   4. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's: the staging window with its carry area, 16 bytes
+ *      per listed match, 28 bytes per 8 KiB of window, 14 KiB for the pattern table, the decoder's own scratch for one pass.
+ *   5. A decoded frame that fails: ZraHipSearchArchive's rule 5.
+ *  Passes, staging window, stagingBytes, "only the frames of the range", whole frames and verified checksums: ZraHipSearchArchive.
+ *  The last M - 1 bytes of a pass are carried in front of the next one, and a start position p is tested, for all patterns, by the
+ *  pass that holds content byte min(p + M - 1, hi - 1); the list ascends whatever the pattern lengths are.
+ *  Cost: one decode of the range. The scan tests every position's first two bytes against a 65,536-bit table made of the patterns'
+ *  first two bytes (a 1-byte pattern sets all 256 bits of its byte); only a position whose bit is set, a "filter survivor", is compared
+ *  against the patterns that begin with its first byte. The worst case is patterns that match everywhere (64 patterns of zeros in
+ *  zeros): every position then runs 64 full compares, and every listed match is compared twice. That is accepted.
+ *  Not covered: regular expressions and case folding, patterns in device memory, a handle variant on resident frames, shards, the
+ *  host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipSearchArchiveMulti(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint64_t offset, uint64_t size,
+    size_t stagingBytes,
+    ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern);
+/** The last ZraHipSearchArchiveMulti on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL:
+ *  no-op): out8 = {frames in the archive, frames decoded, content bytes regenerated, matches, matches listed, decode passes, patterns,
+ *  filter survivors}. A multi search does not touch ZraHipGetSearchStats, and the other way round. */
+ZRA_EXPORT void ZraHipGetSearchMultiStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugSearchScanMs: HIP-event time of the scan launches of the last multi search. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugSearchMultiScanMs(ZraHipEngine* engine);
 
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte

@@ -47,6 +47,12 @@ class ZraHipFrameFault(ctypes.Structure):
 
 VERIFY_STRUCTURE, VERIFY_CONTENT = 1, 2      # ZRA_HIP_VERIFY_*
 
+
+class ZraHipPatternMatch(ctypes.Structure):
+    """include/zra_hip.h: one match of ZraHipSearchArchiveMulti"""
+    _fields_ = [("offset", ctypes.c_uint64), ("pattern", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t),
                                ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t))
@@ -144,6 +150,10 @@ def load():
         "ZraHipSearchArchive": (S, [vp, vp, sz, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipGetSearchStats": (None, [vp, u64p]),
         "ZraHipDebugSearchScanMs": (ctypes.c_double, [vp]),
+        "ZraHipSearchArchiveMulti": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipPatternMatch), sz,
+                                         u64p, u64p]),
+        "ZraHipGetSearchMultiStats": (None, [vp, u64p]),
+        "ZraHipDebugSearchMultiScanMs": (ctypes.c_double, [vp]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -196,6 +206,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
+                   "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs"]
 
 
@@ -428,6 +439,34 @@ class Engine:
         """bring-up: HIP-event time of the last search()'s scan launches, summed over its passes (its decode: kernel_stats()['dec_ms'])."""
         return self.L.ZraHipDebugSearchScanMs(self.h)
 
+    def search_multi(self, d_archive, size, patterns, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20):
+        """ZraHipSearchArchiveMulti: where each of `patterns` (1 .. SEARCH_MAX_PATTERNS byte strings of 1 .. SEARCH_MAX_PATTERN bytes,
+        SEARCH_MAX_PATTERN_BYTES in all, literal) occurs whole inside [offset, offset + length) (None: to the end) of the content of
+        the archive at d_archive, in one decode of the range. Returns (n_matches, [(offset, pattern index)], per_pattern): every match
+        is counted, the first max_matches are listed in ascending (offset, pattern index) order, and per_pattern[i] counts the matches
+        of patterns[i], listed or not. ZraError is a call that could not search."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ZraHipPatternMatch * max_matches)() if max_matches else None
+        per = (ctypes.c_uint64 * max(len(patterns), 1))()
+        n = ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipSearchArchiveMulti(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), offset,
+                                             (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_matches, ctypes.byref(n), per),
+             "ZraHipSearchArchiveMulti")
+        listed = [(int(arr[i].offset), int(arr[i].pattern)) for i in range(min(n.value, max_matches))] if arr is not None else []
+        return n.value, listed, [int(v) for v in per[:len(patterns)]]
+
+    def search_multi_stats(self):
+        """Counters of the last search_multi() on this engine (all zero unless it succeeded), keyed by SEARCH_MULTI_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetSearchMultiStats(self.h, a)
+        return dict(zip(SEARCH_MULTI_STATS, (int(v) for v in a)))
+
+    def search_multi_scan_ms(self):
+        """bring-up: HIP-event time of the last search_multi()'s scan launches, summed over its passes."""
+        return self.L.ZraHipDebugSearchMultiScanMs(self.h)
+
     def compare(self, d_a, size_a, d_b, size_b, *, decode_all=False, offset=0, length=None, staging_bytes=0, max_ranges=1 << 16):
         """ZraHipCompareArchives: the maximal runs of content positions inside [offset, offset + length) (None: to the end of the
         shorter content) at which the archives at d_a and d_b differ. Returns (n_ranges, differing_bytes, [(offset, size)]): every
@@ -471,6 +510,9 @@ VERIFY_STATS = ("frames", "checked", "structure_faults", "content_faults", "deco
 
 SEARCH_MAX_PATTERN = 256                     # ZRA_HIP_SEARCH_MAX_PATTERN
 SEARCH_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes")
+SEARCH_MAX_PATTERNS = 64                     # ZRA_HIP_SEARCH_MAX_PATTERNS
+SEARCH_MAX_PATTERN_BYTES = 4096              # ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
+SEARCH_MULTI_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes", "patterns", "survivors")
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
 COMPARE_STATS = ("frames", "equal_compressed", "decoded", "content_bytes", "ranges", "listed", "passes")

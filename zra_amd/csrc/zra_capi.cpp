@@ -778,6 +778,20 @@ void ZraHipGetSearchStats(ZraHipEngine* engine, uint64_t* out8) {
   if (engine) engine->e->search_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugSearchScanMs(ZraHipEngine* engine) { return engine ? engine->e->search_scan_ms() : 0.0; }
+ZraStatus ZraHipSearchArchiveMulti(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes,
+                                   size_t nPatterns, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipPatternMatch* hMatches, size_t matchCapacity,
+                                   uint64_t* nMatches, uint64_t* hPerPattern) {
+  static_assert(sizeof(ZraHipPatternMatch) == 16, "a 64-bit offset and two 32-bit words per match");
+  if (nMatches) *nMatches = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->search_archive_multi((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches,
+                                            matchCapacity, nMatches, hPerPattern));
+}
+void ZraHipGetSearchMultiStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->search_multi_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugSearchMultiScanMs(ZraHipEngine* engine) { return engine ? engine->e->search_multi_scan_ms() : 0.0; }
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {
   static_assert(sizeof(ZraHipContentRange) == 16, "two 64-bit words per range");

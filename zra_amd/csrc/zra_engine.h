@@ -199,6 +199,18 @@ class Engine {
   // bring-up: HIP-event time of the last search's scan launches (count, scan, fill, carry), summed over its passes
   double search_scan_ms() const { return searchScanMs_; }
 
+  // ---- search for several patterns (zra_msearch.hip): every (content offset, pattern index) at which one of the nPatterns host
+  // patterns (laid end to end at hPatterns, pattern i of hPatternSizes[i] bytes) occurs whole inside the range, ascending, in ONE
+  // decode of the range's frames. hMatches: ZraHipPatternMatch's layout; hPerPattern (optional): the matches of each pattern.
+  // Statuses and their order: zra_hip.h, ZraHipSearchArchiveMulti.
+  Status search_archive_multi(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset,
+                              uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
+  // the last search_archive_multi: {frames, decoded, content bytes regenerated, matches, matches listed, passes, patterns, filter
+  // survivors}; all zero unless it succeeded. The single-pattern search and this one leave each other's counters alone
+  void search_multi_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = mstats_[i]; }
+  // bring-up: HIP-event time of the last multi search's scan launches (count, scan, fill, carry), summed over its passes
+  double search_multi_scan_ms() const { return msearchScanMs_; }
+
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
   // the same in both archives is equal without a decode (mode 1: every frame is decoded); the others are decoded whole on both sides, a
@@ -307,6 +319,10 @@ class Engine {
   struct SearchScratch { DevBuf tables, list; } srch_;
   uint64_t sstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double searchScanMs_ = 0;
+  // multi-pattern search scratch (zra_msearch.hip): the pattern table + totals + per-tile tables, the list of (offset, pattern) pairs
+  struct MSearchScratch { DevBuf tables, list; } msrch_;
+  uint64_t mstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double msearchScanMs_ = 0;
   // compare scratch (zra_compare.hip): a flag per slot, the totals + carry + per-item table, the starts and ends of the listed ranges
   struct CompareScratch { DevBuf flags, tables, list; } cmp_;
   uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
@@ -315,8 +331,17 @@ class Engine {
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
+  friend struct MSearchImpl;       // the multi-pattern search does the same (zra_msearch.hip)
   friend struct CompareImpl;       // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
+
+// The search's per-pass steps that do not depend on the pattern, launched on stream s (zra_search.hip; the multi-pattern search
+// shares them): the decode jobs of frames [first, first + n) into slots 0 .. n - 1; bases[t] = *cntIn + the counts in front of item
+// t, *cntOut = *cntIn + all of them; the last n bytes of the run win[.., L) moved to win[-n, 0), n <= 255.
+void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,
+                        uint32_t* expect);
+void search_launch_scan(hipStream_t s, const uint32_t* counts, uint32_t nItems, uint64_t* bases, const uint64_t* cntIn, uint64_t* cntOut);
+void search_launch_carry(hipStream_t s, uint8_t* win, uint64_t L, uint32_t n);
 
 }  // namespace zra_eng

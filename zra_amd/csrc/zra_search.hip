@@ -170,6 +170,18 @@ extern "C" __global__ void __launch_bounds__(256) zra_search_carry_kernel(u8* wi
 // =================================================================================================
 namespace zra_eng {
 
+// the steps ZraHipSearchArchiveMulti shares (zra_engine.h)
+void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,
+                        uint32_t* expect) {
+  hipLaunchKernelGGL(zra_search_jobs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, table, (u64)fs, (u64)total, (u64)first, n, frameOff, outOff, expect);
+}
+void search_launch_scan(hipStream_t s, const uint32_t* counts, uint32_t nItems, uint64_t* bases, const uint64_t* cntIn, uint64_t* cntOut) {
+  hipLaunchKernelGGL(zra_search_scan_kernel, dim3(1), dim3(1024), 0, s, counts, nItems, bases, cntIn, cntOut);
+}
+void search_launch_carry(hipStream_t s, uint8_t* win, uint64_t L, uint32_t n) {
+  hipLaunchKernelGGL(zra_search_carry_kernel, dim3(1), dim3(256), 0, s, win, (u64)L, n);
+}
+
 struct SearchImpl {
   static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, size_t m, uint64_t offset, uint64_t size, size_t stagingBytes,
                     uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
@@ -235,8 +247,7 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
   for (uint64_t p = 0; p < passes; p++) {
     const uint64_t first = f0 + p * passSlots;
     const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    hipLaunchKernelGGL(zra_search_jobs_kernel, dim3((nj + 255) / 256), dim3(256), 0, s, arc.table, (u64)fs, (u64)U, (u64)first, nj, E.frameOff_.as<uint64_t>(),
-                       E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
+    search_launch_jobs(s, arc.table, fs, U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
     unsigned long long firstError;
     Status st = E.staged_pass(arc, 0, nj, win, &firstError);
     take_time();
@@ -254,7 +265,7 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
       const uint64_t nPos = (uint64_t)(xEnd - xLo);
       const uint32_t tiles = (uint32_t)((nPos + kTile - 1) / kTile);
       hipLaunchKernelGGL(zra_search_count_kernel, dim3(tiles), dim3(256), 0, s, win, xLo, (u64)nPos, pat, (u32)m, counts);
-      hipLaunchKernelGGL(zra_search_scan_kernel, dim3(1), dim3(1024), 0, s, counts, tiles, bases, cnt + (launches & 1), cnt + ((launches + 1) & 1));
+      search_launch_scan(s, counts, tiles, bases, cnt + (launches & 1), cnt + ((launches + 1) & 1));
       launches++;
       if (listCap)
         hipLaunchKernelGGL(zra_search_fill_kernel, dim3(tiles), dim3(256), 0, s, win, xLo, (u64)nPos, pat, (u32)m, counts, bases,
@@ -262,7 +273,7 @@ Status SearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
     }
     if (p + 1 < passes && m > 1) {
       carry = (uint32_t)std::min<uint64_t>(m - 1, carry + L);
-      hipLaunchKernelGGL(zra_search_carry_kernel, dim3(1), dim3(256), 0, s, win, (u64)L, carry);
+      search_launch_carry(s, win, L, carry);
     }
     HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
     timed = true;

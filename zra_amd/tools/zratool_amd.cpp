@@ -5,11 +5,13 @@
 //   d   : streaming decompress (FullDecompressor)
 //   imc : in-memory CompressBuffer          imd : in-memory DecompressBuffer
 //   b   : benchmark of all four + one random-access query with a memcmp check
-// and three modes of its own, against include/zra_hip.h:
+// and four modes of its own, against include/zra_hip.h:
 //   t   : test an archive like `zstd -t` (ZraHipVerifyArchive, content verification on the device); one line per faulty frame and a
 //         summary; exit status 0 clean, 1 faults, 2 the call failed
 //   g   : search an archive like `zstdgrep -F -b -o` (ZraHipSearchArchive, decode and scan on the device); one content offset per line
 //         and a summary; exit status as grep: 0 matches, 1 none, 2 trouble
+//   gm  : the same for 1 to 64 patterns in one pass, like `grep -F -f` (ZraHipSearchArchiveMulti); `offset<TAB>pattern index` per line
+//         and a summary; exit status as g
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 #include <zra.hpp>
@@ -136,22 +138,30 @@ bool to_device(const char* path, const zra::Buffer& arc, void** dArc) {
   return false;
 }
 
-// mode g. The pattern is taken literally; behind a leading "hex:" it is pairs of hex digits.
-int search_archive(const char* path, const char* text) {
+// A pattern of modes g and gm is taken literally; behind a leading "hex:" it is pairs of hex digits. false: message printed
+bool parse_pattern(const char* text, std::string* out) {
   std::string pat = text;
   if (pat.rfind("hex:", 0) == 0) {
     const std::string digits = pat.substr(4);
     pat.clear();
     if (digits.size() % 2 || digits.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
       std::fprintf(stderr, "%s: not pairs of hex digits\n", text);
-      return 2;
+      return false;
     }
     for (size_t i = 0; i < digits.size(); i += 2) pat.push_back((char)std::stoul(digits.substr(i, 2), nullptr, 16));
   }
   if (pat.empty() || pat.size() > ZRA_HIP_SEARCH_MAX_PATTERN) {
     std::fprintf(stderr, "a pattern has 1 to %u bytes\n", ZRA_HIP_SEARCH_MAX_PATTERN);
-    return 2;
+    return false;
   }
+  *out = pat;
+  return true;
+}
+
+// mode g
+int search_archive(const char* path, const char* text) {
+  std::string pat;
+  if (!parse_pattern(text, &pat)) return 2;
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -168,6 +178,38 @@ int search_archive(const char* path, const char* text) {
   if (n > at.size()) std::printf("... and %llu more\n", (unsigned long long)(n - at.size()));
   std::printf("%llu matches\n", (unsigned long long)n);
   return n ? 0 : 1;
+}
+
+// mode gm: the patterns texts[0 .. n), their indices in that order
+int search_archive_multi(const char* path, char** texts, int n) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  for (int i = 0; i < n; i++) {
+    std::string pat;
+    if (!parse_pattern(texts[i], &pat)) return 2;
+    all += pat;
+    sizes.push_back((uint32_t)pat.size());
+  }
+  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all.size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
+    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
+    return 2;
+  }
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  std::vector<ZraHipPatternMatch> at(1u << 20);
+  uint64_t total = 0;
+  st = ZraHipSearchArchiveMulti(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), 0, UINT64_MAX, 0, at.data(), at.size(), &total, nullptr);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot search: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(total, at.size()); i++) std::printf("%llu\t%u\n", (unsigned long long)at[i].offset, at[i].pattern);
+  if (total > at.size()) std::printf("... and %llu more\n", (unsigned long long)(total - at.size()));
+  std::printf("%llu matches\n", (unsigned long long)total);
+  return total ? 0 : 1;
 }
 
 // mode cmp. Nothing goes to stdout when the call fails.
@@ -202,6 +244,7 @@ int compare_archives(const char* pathA, const char* pathB) {
 //   b   {file} {level} {frameSize} {stream buffer MB} {offset = 0x1000} {size = 0x10000}
 // ours: t {file}
 //       g {file} {pattern | hex:digits}
+//       gm {file} {pattern | hex:digits}...
 //       cmp {file A} {file B}
 int main(int argc, char** argv) {
   if (argc < 3) {
@@ -213,6 +256,7 @@ int main(int argc, char** argv) {
                 "b  {file} {compression level = 3} {frame size = 16384} {stream buffer size = 10MB} {offset = 0x1000} {size = 0x10000} - Benchmark (Memory Intensive)\n"
                 "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n"
                 "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n"
+                "gm {file} {pattern | hex:digits}... - Search an archive on the device for 1 to 64 patterns in one pass: offset and pattern index of every match (exit status as g)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n",
                 argv[0]);
     return 0;
@@ -222,6 +266,10 @@ int main(int argc, char** argv) {
   if (mode == "g") {
     if (argc < 4) { std::fprintf(stderr, "g {file} {pattern | hex:digits}\n"); return 2; }
     return search_archive(argv[2], argv[3]);
+  }
+  if (mode == "gm") {
+    if (argc < 4) { std::fprintf(stderr, "gm {file} {pattern | hex:digits}...\n"); return 2; }
+    return search_archive_multi(argv[2], argv + 3, argc - 3);
   }
   if (mode == "cmp") {
     if (argc < 4) { std::fprintf(stderr, "cmp {file A} {file B}\n"); return 2; }
