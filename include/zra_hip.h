@@ -412,7 +412,8 @@ typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipCont
  *  Cost: every compressed byte of the range is read once (less for a frame that differs early); a frame pair that is decoded is read
  *  once more as plaintext, twice when it holds a listed range boundary.
  *  Not covered: archives of different frame sizes beyond the refusal, a variant on ZraHipArchive handles that uses resident frames,
- *  the shards of a distributed archive (ZraHipShard), the host-pointer API, a patch that ZraHipUpdateArchive could apply. */
+ *  the shards of a distributed archive (ZraHipShard), the host-pointer API. (The patch that ZraHipUpdateArchive applies:
+ *  ZraHipDiffArchives below.) */
 ZRA_EXPORT ZraStatus ZraHipCompareArchives(ZraHipEngine* engine,
     const void* dA, size_t sizeA, const void* dB, size_t sizeB,
     uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes,
@@ -427,6 +428,74 @@ ZRA_EXPORT void ZraHipGetCompareSizes(ZraHipEngine* engine, uint64_t* out2);
 /** Bring-up aid, like ZraHipDebugSearchScanMs: HIP-event time of the last compare's own launches (span compare, job build, count,
  *  prefix scan, fill), summed over its passes; the decode of the same call is in ZraHipGetKernelStats. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugCompareMs(ZraHipEngine* engine);
+
+/* ---- diff: the patch that turns one device-resident archive's content into another's, in the shape ZraHipUpdateArchive takes ----
+ * The compare says where two archives differ; a replica needs the bytes as well. The compare has the plaintext of every differing
+ * frame pair in its staging window when it finds the ranges: this call keeps B's side of it. One pass over A and B yields the writes
+ * and the packed bytes, without a buffer for either content. */
+#define ZRA_HIP_DIFF_DECODE_ALL 1u      /* as ZRA_HIP_COMPARE_DECODE_ALL: every frame of [0, C) is decoded on both sides */
+#define ZRA_HIP_DIFF_MAX_GRAIN  8192u
+
+/** The writes and the append that give the archive at dA (sizeA bytes, device memory) the content of the archive at dB (sizeB bytes,
+ *  device memory). UA and UB are the content sizes, C = min(UA, UB), fs the common frame size. Synchronous; stream ordering as the
+ *  other compute calls (ZraHipWaitStream). Both archives are only read.
+ *  GRAINS. grain is a power of two from 1 to ZRA_HIP_DIFF_MAX_GRAIN. Frame f is cut into grains of `grain` bytes counted from the
+ *  frame's own first byte, so a grain never straddles a frame. A grain is clipped to its frame and to C: the last grain of a frame
+ *  may be short. A grain is DIRTY if A and B differ at one or more of its positions.
+ *  WRITES. A write is a maximal run of dirty grains that follow each other in content order; the last grain of frame f and the first
+ *  grain of frame f + 1 are neighbours, so a run that continues across frames, or across passes, is one write. Its offset and size are
+ *  the union of its clipped grains. With grain = 1 the writes are exactly the ranges ZraHipCompareArchives gives for [0, C). A larger
+ *  grain trades a few equal bytes in dData for fewer writes (a write costs 24 bytes of host arrays and a tuple in the update;
+ *  rewriting an equal byte is harmless).
+ *  - *nWrites = the number of writes. hOffsets[i], hSizes[i] (HOST arrays of writeCapacity entries) describe write i, ascending; no
+ *    two writes share or touch a byte, so rule 4 of ZraHipUpdateArchive is met.
+ *  - dData (device memory, dataCapacity bytes) receives B's bytes of all dirty grains, in content order, packed: hDataOffsets[i] is
+ *    the sum of the sizes of the writes in front of write i.
+ *  - TAIL. When UB > UA, B's bytes [UA, UB) follow the dirty bytes in dData: *appendOffset is their offset in dData and *appendSize =
+ *    UB - UA. When UB == UA, *appendSize = 0 and *appendOffset is the number of dirty bytes.
+ *  - *dataSize = dirty bytes + *appendSize.
+ *  ZraHipUpdateArchive(engine, dA, sizeA, dData, hOffsets, hSizes, hDataOffsets, *nWrites, (char*)dData + *appendOffset, *appendSize,
+ *  ...) then yields an archive with B's content; at the level and checksum flag B was written with, B's bytes.
+ *  Statuses, checked in this order:
+ *   1. engine, nWrites, dataSize, appendOffset or appendSize NULL; dA or dB NULL with a size other than 0; one of the three host
+ *      arrays NULL with writeCapacity != 0; dData NULL with dataCapacity != 0; mode with bits other than ZRA_HIP_DIFF_DECODE_ALL;
+ *      grain not a power of two in 1 .. 8192 -> {ZStdError, 42}.
+ *   2. [dData, dData + dataCapacity) overlaps either archive -> {ZStdError, 42}.
+ *   3. Header problems of A, then of B, as rule 2 of ZraHipCompareArchives.
+ *   4. Different frame sizes -> {ZStdError, 40}.
+ *   5. UB < UA -> {ZStdError, 40}: an update cannot shorten content, so no patch exists.
+ *   6. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's (ZraHipReleaseScratch returns it): the staging
+ *      window, 1 byte per slot of a pass, the decoder's job arrays for two archives, 24 bytes per 8 KiB tile of the decoded frames of
+ *      a pass, 16 bytes per write up to writeCapacity, the decoder's own scratch for one pass.
+ *   7. A frame that has to be decoded and fails, as rule 6 of ZraHipCompareArchives. The tail frames of B come behind all pair passes.
+ *   8. *nWrites > writeCapacity or *dataSize > dataCapacity -> OutputBufferTooSmall. The four output words hold what the patch needs:
+ *      this is the one outcome other than Success that sets them. A call with capacities 0 / 0 is the sizing call.
+ *  On every status other than Success nothing is written to the three host arrays and the stats are zero; apart from rule 8 the
+ *  output words are 0. dData is written while the passes run: after a status other than Success its first dataCapacity bytes are
+ *  undefined. No byte at or behind dData + dataCapacity is ever written, whatever the outcome. As in the compare, no list entry
+ *  reaches the host before the last pass is done.
+ *  THE SHORTCUT is the compare's, word for word: a frame with equal compressed spans is clean and is not decoded, so DIFF IS NOT
+ *  VERIFY. With ZRA_HIP_DIFF_DECODE_ALL every frame of [0, C) is decoded on both sides. Identical archives give Success with 0 writes,
+ *  *dataSize 0 and no decode launch.
+ *  Passes: the frames of [0, C) in passes of max(1, min(65,536, stagingBytes / (2 * frameSize))) frame pairs, as the compare; then
+ *  B's frames from the one that holds C on, in passes of max(1, min(65,536, stagingBytes / frameSize)) (stagingBytes 0: 4 GiB). When
+ *  UA lies inside a frame, that frame of B is decoded in both.
+ *  Not covered: a content sub-range, shrinking (UB < UA), a variant on ZraHipArchive handles, the shards of a distributed archive, the
+ *  host-pointer API, a gap-merging rule other than grains. */
+ZRA_EXPORT ZraStatus ZraHipDiffArchives(ZraHipEngine* engine,
+    const void* dA, size_t sizeA, const void* dB, size_t sizeB,
+    uint32_t mode, uint32_t grain, size_t stagingBytes,
+    uint64_t* hOffsets, uint64_t* hSizes, uint64_t* hDataOffsets, size_t writeCapacity, uint64_t* nWrites,
+    void* dData, size_t dataCapacity, uint64_t* dataSize,
+    uint64_t* appendOffset, uint64_t* appendSize);
+/** The last ZraHipDiffArchives on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames of [0, C), frames equal by their compressed bytes, frame pairs decoded, tail frames of B decoded, writes, dirty
+ *  bytes, passes (pair + tail), dirty grains}. A diff does not touch ZraHipGetCompareStats, and the other way round. */
+ZRA_EXPORT void ZraHipGetDiffStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugCompareMs: HIP-event time of the last diff's own launches (span compare, job build, count, prefix
+ *  scan, fill with the gather copy, tail jobs and tail copy), summed over its passes; its decodes are in ZraHipGetKernelStats.
+ *  engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugDiffMs(ZraHipEngine* engine);
 
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody

@@ -159,6 +159,10 @@ def load():
         "ZraHipGetCompareStats": (None, [vp, u64p]),
         "ZraHipGetCompareSizes": (None, [vp, u64p]),
         "ZraHipDebugCompareMs": (ctypes.c_double, [vp]),
+        # diff
+        "ZraHipDiffArchives": (S, [vp, vp, sz, vp, sz, u32, u32, sz, u64p, u64p, u64p, sz, u64p, vp, sz, u64p, u64p, u64p]),
+        "ZraHipGetDiffStats": (None, [vp, u64p]),
+        "ZraHipDebugDiffMs": (ctypes.c_double, [vp]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -207,7 +211,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
-                   "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs"]
+                   "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
+                   "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs"]
 
 
 def _chk(st, what=""):
@@ -498,6 +503,39 @@ class Engine:
         """bring-up: HIP-event time of the last compare()'s own launches, summed over its passes (its decode: kernel_stats()['dec_ms'])."""
         return self.L.ZraHipDebugCompareMs(self.h)
 
+    def diff(self, d_a, size_a, d_b, size_b, d_data, data_cap, *, grain=1, decode_all=False, staging_bytes=0, max_writes=1 << 16):
+        """ZraHipDiffArchives: the patch that gives the archive at d_a the content of the archive at d_b. Returns ((offsets, sizes,
+        data_offsets), append_offset, append_size, data_size): three numpy u64 arrays, one entry per write (a maximal run of dirty
+        grains of `grain` bytes), to be passed as `writes=` of update() with d_data=d_data; B's bytes of the writes lie packed at
+        d_data (data_cap bytes, device memory), and B's append_size bytes behind A's content at d_data + append_offset.
+        OutputBufferTooSmall (more than max_writes writes, or more than data_cap bytes) carries what the patch needs in
+        ZraError.needed_writes and ZraError.needed_data. ZraError otherwise is a call that could not diff (bad header, different frame
+        sizes, B shorter than A, a frame that had to be decoded and does not, no memory)."""
+        import numpy as np
+        o, s, do = (np.zeros(max_writes, dtype=np.uint64) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if max_writes else None
+        n, ds, ao, asz = (ctypes.c_uint64(0) for _ in range(4))
+        self._order()
+        st = self.L.ZraHipDiffArchives(self.h, d_a or None, size_a, d_b or None, size_b, DIFF_DECODE_ALL if decode_all else 0, grain, staging_bytes,
+                                       p(o), p(s), p(do), max_writes, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds), ctypes.byref(ao),
+                                       ctypes.byref(asz))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipDiffArchives")
+            e.needed_writes, e.needed_data = n.value, ds.value
+            raise e
+        k = n.value
+        return (o[:k].copy(), s[:k].copy(), do[:k].copy()), ao.value, asz.value, ds.value
+
+    def diff_stats(self):
+        """Counters of the last diff() on this engine (all zero unless it succeeded), keyed by DIFF_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetDiffStats(self.h, a)
+        return dict(zip(DIFF_STATS, (int(v) for v in a)))
+
+    def diff_ms(self):
+        """bring-up: HIP-event time of the last diff()'s own launches, summed over its passes (its decodes: kernel_stats()['dec_ms'])."""
+        return self.L.ZraHipDebugDiffMs(self.h)
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
@@ -516,6 +554,10 @@ SEARCH_MULTI_STATS = ("frames", "decoded", "content_bytes", "matches", "listed",
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
 COMPARE_STATS = ("frames", "equal_compressed", "decoded", "content_bytes", "ranges", "listed", "passes")
+
+DIFF_DECODE_ALL = 1                          # ZRA_HIP_DIFF_DECODE_ALL
+DIFF_MAX_GRAIN = 8192                        # ZRA_HIP_DIFF_MAX_GRAIN
+DIFF_STATS = ("frames", "equal_compressed", "decoded", "tail_decoded", "writes", "dirty_bytes", "passes", "dirty_grains")
 
 
 class Archive:

@@ -810,6 +810,19 @@ void ZraHipGetCompareSizes(ZraHipEngine* engine, uint64_t* out2) {
   if (engine) engine->e->compare_sizes(out2); else out2[0] = out2[1] = 0;
 }
 double ZraHipDebugCompareMs(ZraHipEngine* engine) { return engine ? engine->e->compare_ms() : 0.0; }
+ZraStatus ZraHipDiffArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
+                             uint64_t* hOffsets, uint64_t* hSizes, uint64_t* hDataOffsets, size_t writeCapacity, uint64_t* nWrites, void* dData,
+                             size_t dataCapacity, uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
+  for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->diff_archives((const uint8_t*)dA, sizeA, (const uint8_t*)dB, sizeB, mode, grain, stagingBytes, hOffsets, hSizes, hDataOffsets,
+                                     writeCapacity, nWrites, (uint8_t*)dData, dataCapacity, dataSize, appendOffset, appendSize));
+}
+void ZraHipGetDiffStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->diff_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugDiffMs(ZraHipEngine* engine) { return engine ? engine->e->diff_ms() : 0.0; }
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

@@ -32,6 +32,7 @@
 //      between two words (pass k reads word k & 1 and writes word (k + 1) & 1, which the host zeroed in front of the count launch). A
 //      list position is a sum of counts and lane prefixes, never the result of an atomic, and no workgroup waits for another one.
 //  (d) nothing goes to the caller's array before the last pass is done: a call that fails midway writes nothing.
+// The diff of two archives (zra_hip.h: ZraHipDiffArchives) is the second half of this file: the same passes with the plaintext kept.
 #include "zra_host.h"
 #include "zra_dev.h"
 #include <algorithm>
@@ -84,14 +85,31 @@ struct TileOut {
 // [lo, hi) and the frame size by arithmetic. Both halves are loaded with 16-byte loads from the aligned address at or below the tile's
 // first byte (the halves share their alignment), only chunks that hold a position of [a, b): at most 15 bytes in front of it (inside
 // the window: slot 0 is aligned) and 15 behind (inside the window's slack). sM: kChunks + 3 words.
+// The tile's place (item -> slot s of the pass, tile t0 of its frame, positions [a64, b64) of the frame) ...
+#define ZRA_TILE_GEOMETRY(T, item)                                                                   \
+  const u32 k = (item) / (T).tpf, t = (item) % (T).tpf;                                              \
+  const u64 off = (T).outOff[k];                                                                     \
+  const u32 s = (u32)(off / (T).fs);                                                                 \
+  const u64 fBase = ((T).first + s) * (T).fs, t0 = (u64)t * kTile;                                   \
+  const u64 iLo = (T).lo > fBase ? (T).lo - fBase : 0, iHi = min((T).fs, (T).hi - fBase);            \
+  const u64 a64 = max(t0, iLo), b64 = min(t0 + kTile, iHi)
+// ... and its difference bits in ADDRESS space: bit j of sM[c + 1] = byte j of chunk c of the two halves differs and is position
+// 16 c + j - d of the tile, inside [a, b); chunk c = the 16 bytes at gA + c / gB + c. sM[1 .. kChunks + 2] are written.
+__device__ __forceinline__ void tile_bits(const uint4* gA, const uint4* gB, u32 d, int a, int b, u32* sM) {
+  for (u32 c = threadIdx.x; c < kChunks + 2; c += 256) {
+    const int r0 = (int)(16 * c) - (int)d;
+    u32 m = 0;
+    if (c < kChunks && r0 < b && r0 + 16 > a) {
+      const uint4 x = gA[c], y = gB[c];
+      m = nonzero_bytes(make_uint4(x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w)) & valid_bits(r0, a, b);
+    }
+    sM[c + 1] = m;                                                            // bit j of word c + 1 = position 16 (c + 1) + j - 16 - d of the tile
+  }
+}
+
 __device__ __forceinline__ void diff_tile(const TileArgs& T, u32 item, u32* sM, u32* sRed, TileOut& o) {
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const u32 k = item / T.tpf, t = item % T.tpf;
-  const u64 off = T.outOff[k];
-  const u32 s = (u32)(off / T.fs);
-  const u64 fBase = (T.first + s) * T.fs, t0 = (u64)t * kTile;
-  const u64 iLo = T.lo > fBase ? T.lo - fBase : 0, iHi = min(T.fs, T.hi - fBase);
-  const u64 a64 = max(t0, iLo), b64 = min(t0 + kTile, iHi);
+  ZRA_TILE_GEOMETRY(T, item);
   for (u32 q = 0; q < kOwn; q++) o.st[q] = o.en[q] = 0;
   o.nS = o.nE = o.totS = o.totE = o.totDiff = 0; o.extraEnd = o.carryOut = false; o.extraAt = 0; o.pos0 = 0;
   if (a64 >= b64) return;                                                     // (uniform in the workgroup)
@@ -107,15 +125,7 @@ __device__ __forceinline__ void diff_tile(const TileArgs& T, u32 item, u32* sM, 
     else if (s > 0) prev = T.flags[s - 1] && pA[-1] != pB[-1];                // the frame in front: decoded in this pass, or equal
     else prev = *T.carryIn != 0;                                              // the last frame of the pass in front
   }
-  for (u32 c = tid; c < kChunks + 2; c += 256) {
-    const int r0 = (int)(16 * c) - (int)d;
-    u32 m = 0;
-    if (c < kChunks && r0 < b && r0 + 16 > a) {
-      const uint4 x = gA[c], y = gB[c];
-      m = nonzero_bytes(make_uint4(x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w)) & valid_bits(r0, a, b);
-    }
-    sM[c + 1] = m;                                                            // bit j of word c + 1 = position 16 (c + 1) + j - 16 - d of the tile
-  }
+  tile_bits(gA, gB, d, a, b, sM);
   if (tid == 0) sM[0] = 0;
   __syncthreads();
   if (tid == 0 && prev) { const u32 e = (u32)a + d + 15; sM[e >> 4] |= 1u << (e & 15); }   // position a - 1: outside the valid bits, seen as a predecessor
@@ -299,6 +309,216 @@ extern "C" __global__ void __launch_bounds__(256) zra_cmp_fill_kernel(TileArgs T
 }
 
 // =================================================================================================
+// Diff (zra_hip.h: ZraHipDiffArchives): the compare over [0, C) with the plaintext kept. The passes, the span compare, the job build
+// and the two staged_pass calls are the compare's. A tile's difference bits become a DIRTY-GRAIN mask, the runs of that mask are the
+// writes, and the fill copies B's bytes of the dirty grains, packed, to the caller's buffer; B's content behind C follows in passes
+// of its own. The four ordering conditions above hold with "dirty grain" in place of d(p):
+//  (slots) unchanged. Frame f's grains are counted from the frame's first byte and grain divides kTile, so a grain lies inside one
+//      tile of one decoded frame: its bits come from bytes the pass regenerated, clipped to the frame and to C by arithmetic.
+//  (look-behind) D(p) = "the grain that holds p is dirty". D(p - 1) of a tile's first position is the grain in front: the last one of
+//      the tile in front, or the (possibly short) last one of the frame in front when that frame was decoded in this pass, whose bytes
+//      the workgroup compares itself; 0 in front of position 0 and behind an equal-flagged frame; the carry word behind the last frame
+//      of the pass in front. The three tile-less ends (at C, in front of an equal-flagged frame, the pass carry) are the compare's.
+//  (order) three columns per item: starts, ends, dirty bytes; three 64-bit totals ping-pong between passes. A list position and a
+//      byte's place in the packed data are sums of counts and prefixes, never the result of an atomic.
+//  (d) the lists stay on the device until the last pass is done; dData alone is written while the passes run, never at or behind
+//      dataCapacity.
+namespace {
+constexpr u32 kWords = kTile / 16;           // 16-bit words of a tile's mask in tile-position space: a lane owns words 2 tid and 2 tid + 1
+// the diff's table words in front of the per-item entries (bytes): dirty grains at kOffDiff | kOffBytes, kOffCarry, kOffJobs as above (the
+// job build writes them) | totals {starts, ends, dirty bytes} x 2
+constexpr u32 kDiffHdrBytes = 128, kOffTot3 = 64;
+
+struct GrainOut {
+  u32 st[2], en[2], dm[2];                   // starts, ends and dirty positions of the lane's two words (bit j = tile position 16 w + j)
+  u32 nS, nE, nB;                            // this lane's
+  u32 totS, totE, totB, totG;                // the workgroup's; totG: dirty grains
+  bool extraEnd, carryOut;
+  u64 extraAt, pos0;                         // content position of the extra end; of tile position 0
+  const u8* pB;                              // B's byte at tile position 0
+};
+
+// Item `item` of a pass as diff_tile takes it, lo = 0: the tile's positions are [0, b). sM: kChunks + 3 words, sD: kWords + 1,
+// sRed: 20. The difference bits are built in address space (tile_bits: chunk c starts d bytes in front of the tile when the slot is
+// not 16-byte aligned), re-indexed to tile positions, smeared over their grains (inside a word for grain <= 16, over grain / 16
+// words above), and clipped to [0, b) again: the last grain of a frame, or the one that holds C, is short.
+__device__ __forceinline__ void grain_tile(const TileArgs& T, u32 item, u32 grain, u32* sM, u32* sD, u32* sRed, GrainOut& o) {
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  ZRA_TILE_GEOMETRY(T, item);
+  for (u32 q = 0; q < 2; q++) o.st[q] = o.en[q] = o.dm[q] = 0;
+  o.nS = o.nE = o.nB = o.totS = o.totE = o.totB = o.totG = 0; o.extraEnd = o.carryOut = false; o.extraAt = 0; o.pos0 = fBase + t0; o.pB = nullptr;
+  if (a64 >= b64) return;                                                     // (uniform in the workgroup)
+  const int b = (int)(b64 - t0);                                              // (a64 == t0: lo is 0)
+  const u8* const pA = T.winA + off + t0; const u8* const pB = T.winB + off + t0;
+  const u32 d = (u32)((size_t)pA & 15);
+  o.pB = pB;
+  tile_bits((const uint4*)(pA - d), (const uint4*)(pB - d), d, 0, b, sM);
+  // (look-behind) the grain in front of position 0: n bytes that end at pA / pB, compared by the whole workgroup; or the carry
+  u32 n = 0;
+  if (t0 > 0) n = grain;                                                      // the last grain of the tile in front
+  else if (s > 0) n = T.flags[s - 1] ? (u32)(T.fs - ((T.fs - 1) / grain) * grain) : 0;   // the last grain of the frame in front: decoded in this pass, or equal
+  int behind = tid == 0 && t0 == 0 && s == 0 && fBase != 0 && *T.carryIn != 0;           // the last frame of the pass in front
+  if (n) {
+    const u8* const qA = pA - n;
+    const u32 d0 = (u32)((size_t)qA & 15);                                    // (the halves share their alignment; qA - d0 is inside the window: slot 0 is aligned)
+    const uint4* const hA = (const uint4*)(qA - d0); const uint4* const hB = (const uint4*)(pB - n - d0);
+    for (u32 c = tid; c < (d0 + n + 15) / 16; c += 256) {
+      const uint4 x = hA[c], y = hB[c];
+      behind |= (nonzero_bytes(make_uint4(x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w)) & valid_bits((int)(16 * c) - (int)d0, 0, (int)n)) != 0;
+    }
+  }
+  const bool prev = __syncthreads_or(behind) != 0;                            // (and sM is complete)
+  // address space -> tile positions: position 16 w + i is bit 16 w + i + d of the address-space mask
+  u32 g[2], grains = 0;
+  bool any = false;
+#pragma unroll
+  for (u32 q = 0; q < 2; q++) {
+    const u32 w = 2 * tid + q;
+    g[q] = ((sM[w + 1] >> d) | (sM[w + 2] << (16 - d))) & 0xFFFFu;
+    if (grain <= 16) {                                                        // bit i of x = a difference in positions i .. i + grain - 1; a grain starts at every multiple of `grain`
+      u32 x = g[q];
+      for (u32 sh = 1; sh < grain; sh <<= 1) x |= x >> sh;
+      x &= 0xFFFFu / ((1u << grain) - 1u);                                    // (0x5555 for 2, 0x1111 for 4, 0x0101 for 8, 1 for 16)
+      grains += (u32)__popc(x);
+      g[q] = x * ((1u << grain) - 1u);
+    }
+    any |= g[q] != 0;
+  }
+  // grain > 16: the grain's grain / 16 words belong to H = grain / 32 consecutive lanes (a lane's two words lie in one grain)
+  const unsigned long long lanes = __ballot(any);
+  if (lane == 0) sRed[16 + wave] = lanes != 0;
+  __syncthreads();
+  if (grain > 16) {
+    const u32 H = grain / 32;
+    bool dirty;
+    if (H <= 64) dirty = ((lanes >> (lane & ~(H - 1))) & (H == 64 ? ~0ull : (1ull << H) - 1)) != 0;
+    else { dirty = false; for (u32 w = wave & ~(H / 64 - 1), e = w + H / 64; w < e; w++) dirty |= sRed[16 + w] != 0; }
+    g[0] = g[1] = dirty ? 0xFFFFu : 0u;
+    grains = dirty && (tid & (H - 1)) == 0;
+  }
+#pragma unroll
+  for (u32 q = 0; q < 2; q++) { o.dm[q] = g[q] & valid_bits((int)(16 * (2 * tid + q)), 0, b); sD[2 * tid + q + 1] = o.dm[q]; }
+  if (tid == 0) sD[0] = prev ? 0x8000u : 0u;
+  __syncthreads();
+#pragma unroll
+  for (u32 q = 0; q < 2; q++) {
+    const u32 w = 2 * tid + q, m = o.dm[q], before = ((m << 1) | (sD[w] >> 15)) & 0xFFFFu, v = valid_bits((int)(16 * w), 0, b);
+    o.st[q] = m & ~before & v;
+    o.en[q] = ~m & before & v;
+    o.nS += (u32)__popc(o.st[q]); o.nE += (u32)__popc(o.en[q]); o.nB += (u32)__popc(m);
+  }
+  const u32 wS = wave_sum(o.nS), wE = wave_sum(o.nE), wB = wave_sum(o.nB), wG = wave_sum(grains);
+  if (lane == 0) { sRed[wave] = wS; sRed[4 + wave] = wE; sRed[8 + wave] = wB; sRed[12 + wave] = wG; }
+  __syncthreads();
+  for (u32 w = 0; w < 4; w++) { o.totS += sRed[w]; o.totE += sRed[4 + w]; o.totB += sRed[8 + w]; o.totG += sRed[12 + w]; }
+  // the end behind the frame's last position of [0, C), when no tile holds it
+  const u32 eL = (u32)b - 1;
+  if (b64 == iHi && ((sD[(eL >> 4) + 1] >> (eL & 15)) & 1)) {
+    o.extraAt = fBase + b64;
+    if (o.extraAt == T.hi) o.extraEnd = true;
+    else if (s + 1 < T.nj) o.extraEnd = T.flags[s + 1] == 0;
+    else o.carryOut = true;
+  }
+}
+}  // namespace
+
+// zra_cmp_count_kernel for grains: tab[3 i] = the item's starts, tab[3 i + 1] = its ends, tab[3 i + 2] = its dirty bytes. The dirty
+// grains are summed into one word (a sum, not a position).
+extern "C" __global__ void __launch_bounds__(256) zra_diff_count_kernel(TileArgs T, u32 grain, u64* tab, u64* grains, u32* carryOut) {
+  __shared__ u32 sM[kChunks + 3], sD[kWords + 1], sRed[20];
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) { tab[0] = 0; tab[1] = (*T.carryIn != 0 && T.flags[0] == 0) ? 1 : 0; tab[2] = 0; }
+    return;
+  }
+  GrainOut o;
+  grain_tile(T, blockIdx.x - 1, grain, sM, sD, sRed, o);
+  if (threadIdx.x == 0) {
+    u64* const e = tab + 3 * (size_t)blockIdx.x;
+    e[0] = o.totS; e[1] = o.totE + (o.extraEnd ? 1 : 0); e[2] = o.totB;
+    if (o.totG) atomicAdd((unsigned long long*)grains, (unsigned long long)o.totG);
+    if (o.carryOut) *carryOut = 1;
+  }
+}
+
+// zra_cmp_scan_kernel with three columns: tab[3 i + c] = totIn[c] + column c of the items in front of item i, for i = 0 .. nItems;
+// totOut = the last entry.
+extern "C" __global__ void __launch_bounds__(1024) zra_diff_scan_kernel(u64* tab, u32 nItems, const u64* totIn, u64* totOut) {
+  __shared__ u64 sS[3][1024];
+  const u32 tid = threadIdx.x;
+  const u32 per = (nItems + 1023) / 1024;
+  const u32 i0 = min(nItems, tid * per), i1 = min(nItems, i0 + per);
+  u64 own[3] = {0, 0, 0};
+  for (u32 i = i0; i < i1; i++) for (u32 c = 0; c < 3; c++) own[c] += tab[3 * (size_t)i + c];
+  for (u32 c = 0; c < 3; c++) sS[c][tid] = own[c];
+  __syncthreads();
+  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
+    u64 x[3];
+    for (u32 c = 0; c < 3; c++) x[c] = tid >= d ? sS[c][tid - d] : 0;
+    __syncthreads();
+    for (u32 c = 0; c < 3; c++) sS[c][tid] += x[c];
+    __syncthreads();
+  }
+  u64 at[3];
+  for (u32 c = 0; c < 3; c++) at[c] = totIn[c] + sS[c][tid] - own[c];
+  for (u32 i = i0; i < i1; i++)
+    for (u32 c = 0; c < 3; c++) { const u64 n = tab[3 * (size_t)i + c]; tab[3 * (size_t)i + c] = at[c]; at[c] += n; }
+  if (tid == 1023)
+    for (u32 c = 0; c < 3; c++) { const u64 e = totIn[c] + sS[c][1023]; tab[3 * (size_t)nItems + c] = e; totOut[c] = e; }
+}
+
+// Workgroup i redoes item i's mask when it holds a listed start or end, or a dirty byte with a place in front of dataCap (an item
+// without any leaves at once). Starts and ends as zra_cmp_fill_kernel. A dirty byte's place in dData is the item's base, plus the
+// dirty bytes of the waves, lanes and words in front. A whole dirty word (16 positions: every word of a grain >= 16 but a clipped
+// one) whose place is 16-byte aligned leaves as one 16-byte store; anything else byte by byte, each byte checked against dataCap.
+extern "C" __global__ void __launch_bounds__(256) zra_diff_fill_kernel(TileArgs T, u32 grain, const u64* tab, u64* starts, u64* ends, u64 cap, u8* dData,
+                                                                       u64 dataCap) {
+  __shared__ u32 sM[kChunks + 3], sD[kWords + 1], sRed[20];
+  const u64* const e = tab + 3 * (size_t)blockIdx.x;
+  const u64 baseS = e[0], baseE = e[1], baseB = e[2];
+  const u64 cntS = e[3] - baseS, cntE = e[4] - baseE, cntB = e[5] - baseB;
+  if ((cntS == 0 || baseS >= cap) && (cntE == 0 || baseE >= cap) && (cntB == 0 || baseB >= dataCap)) return;   // (uniform in the workgroup)
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) ends[baseE] = T.first * T.fs;                       // (cntE == 1 and baseE < cap)
+    return;
+  }
+  GrainOut o;
+  grain_tile(T, blockIdx.x - 1, grain, sM, sD, sRed, o);
+  const u32 tid = threadIdx.x, wave = tid >> 6;
+  u64 atS = baseS + wave_incl_scan(o.nS) - o.nS, atE = baseE + wave_incl_scan(o.nE) - o.nE, atB = baseB + wave_incl_scan(o.nB) - o.nB;
+  for (u32 w = 0; w < wave; w++) { atS += sRed[w]; atE += sRed[4 + w]; atB += sRed[8 + w]; }
+#pragma unroll
+  for (u32 q = 0; q < 2; q++) {
+    const u32 r = 16 * (2 * tid + q);
+    const u64 p = o.pos0 + r;
+    for (u32 m = o.st[q]; m; m &= m - 1, atS++) if (atS < cap) starts[atS] = p + (u32)__builtin_ctz(m);
+    for (u32 m = o.en[q]; m; m &= m - 1, atE++) if (atE < cap) ends[atE] = p + (u32)__builtin_ctz(m);
+    const u8* const src = o.pB + r;
+    if (o.dm[q] == 0xFFFFu && atB + 16 <= dataCap && (((size_t)dData + atB) & 15) == 0) {
+      const u128_u v = *(const u128_u*)src;
+      *(uint4*)(dData + atB) = make_uint4(v.a, v.b, v.c, v.d);
+      atB += 16;
+    } else {
+      for (u32 m = o.dm[q]; m; m &= m - 1, atB++) if (atB < dataCap) dData[atB] = src[__builtin_ctz(m)];
+    }
+  }
+  if (tid == 0 && o.extraEnd && baseE + o.totE < cap) ends[baseE + o.totE] = o.extraAt;
+}
+
+// B's content behind C: the n bytes at src (one pass's run of the window) go to dData + *dirtyBytes + tailOff, 16 per lane, clipped
+// byte-exactly at dataCap. The base is read on the device: the dirty-bytes total of the last pair pass.
+extern "C" __global__ void __launch_bounds__(256) zra_diff_tail_kernel(const u8* src, u64 n, const u64* dirtyBytes, u64 tailOff, u8* dData, u64 dataCap) {
+  const u64 i = ((u64)blockIdx.x * 256 + threadIdx.x) * 16;
+  if (i >= n) return;
+  const u64 at = *dirtyBytes + tailOff + i;
+  if (i + 16 <= n && at + 16 <= dataCap && (((size_t)dData + at) & 15) == 0) {
+    const u128_u v = *(const u128_u*)(src + i);
+    *(uint4*)(dData + at) = make_uint4(v.a, v.b, v.c, v.d);
+  } else {
+    for (u32 j = 0; j < 16 && i + j < n; j++) if (at + j < dataCap) dData[at + j] = src[i + j];
+  }
+}
+
+// =================================================================================================
 namespace zra_eng {
 
 struct CompareImpl {
@@ -426,6 +646,157 @@ Status CompareImpl::run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_
   const uint64_t st8[8] = {n, n - decoded, decoded, h8[kOffBytes / 8], total, nOut, passes, 0};
   for (int i = 0; i < 8; i++) E.cstats_[i] = st8[i];
   E.cmpSizes_[0] = A.U; E.cmpSizes_[1] = B.U;
+  return ok();
+}
+
+// ---- diff
+struct DiffImpl {
+  static Status run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
+                    uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
+                    uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
+};
+
+Status Engine::diff_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
+                             uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
+                             uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
+  for (auto& v : fstats_) v = 0;
+  diffMs_ = 0;
+  for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;
+  const Status st = DiffImpl::run(*this, dA, sizeA, dB, sizeB, mode, grain, stagingBytes, hOff, hSize, hDataOff, writeCap, nWrites, dData, dataCap, dataSize,
+                                  appendOffset, appendSize);
+  if (st.zra) {
+    diffMs_ = 0;
+    if (st.zra != kOutputTooSmall) for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;   // (rule 8 alone leaves what is needed)
+  }
+  return st;
+}
+
+Status DiffImpl::run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
+                     uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
+                     uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
+  constexpr uint32_t kDecodeAll = 1u;                                         // ZRA_HIP_DIFF_DECODE_ALL
+  // ---- 1. arguments, 2. overlap
+  if (!nWrites || !dataSize || !appendOffset || !appendSize || (!dA && sizeA) || (!dB && sizeB) || (writeCap && (!hOff || !hSize || !hDataOff)) ||
+      (!dData && dataCap) || (mode & ~kDecodeAll) || grain == 0 || grain > kTile || (grain & (grain - 1)))
+    return zerr(42);
+  auto overlaps = [&](const uint8_t* p, size_t n) { return dataCap && n && (uintptr_t)dData < (uintptr_t)p + n && (uintptr_t)p < (uintptr_t)dData + dataCap; };
+  if (overlaps(dA, sizeA) || overlaps(dB, sizeB)) return zerr(42);
+  HIPCHK_CLR(hipSetDevice(E.device_));
+  hipStream_t s = E.stream_;
+  E.reset_decode_stats();
+  // ---- 3. headers, A then B, 4. one frame size, 5. an update cannot shorten content
+  ArchiveView A, B;
+  { Status st = E.archive_view(dA, sizeA, &A); if (st.zra) return st; }
+  if (A.fs == 0) return {kHeaderInvalid, 0};
+  { Status st = E.archive_view(dB, sizeB, &B); if (st.zra) return st; }
+  if (B.fs == 0) return {kHeaderInvalid, 0};
+  if (A.fs != B.fs) return zerr(40);
+  if (B.U < A.U) return zerr(40);
+  const uint64_t fs = A.fs, C = A.U, tailBytes = B.U - A.U;
+  const uint64_t n = (C + fs - 1) / fs;                                       // frames of [0, C), of both archives
+  const uint64_t fT0 = C / fs, nTail = tailBytes ? (B.U + fs - 1) / fs - fT0 : 0;   // B's frames that hold content behind C
+  // ---- 6. scratch
+  const uint32_t passSlots = pass_slots(2 * fs, stagingBytes), tailSlots = pass_slots(fs, stagingBytes);
+  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n), nTSlots = (uint32_t)std::min<uint64_t>(tailSlots, nTail);
+  const uint64_t passes = (n + passSlots - 1) / passSlots, tailPasses = (nTail + tailSlots - 1) / tailSlots;
+  const uint64_t half = ((uint64_t)nSlots * fs + 15) & ~15ull;
+  const uint32_t tpf = (uint32_t)((fs + kTile - 1) / kTile);
+  const size_t itemsMax = 1 + (size_t)nSlots * tpf;
+  const size_t listCap = (size_t)std::min<uint64_t>(writeCap, (C + 1) / 2);   // (writes are at least one byte long and one byte apart)
+  const size_t jobsMax = std::max<size_t>(2 * (size_t)nSlots, nTSlots), slotsMax = std::max<size_t>(nSlots, nTSlots);
+  if (!E.stage_.reserve((size_t)std::max<uint64_t>(2 * half, (uint64_t)nTSlots * fs) + 64) || !E.cmp_.flags.reserve((size_t)nSlots + 64) ||
+      !E.cmp_.tables.reserve(kDiffHdrBytes + (itemsMax + 1) * 24 + 64) || !E.cmp_.list.reserve(listCap * 16 + 64) ||
+      !E.frameOff_.reserve((jobsMax + 1) * 16) || !E.outOff_.reserve((slotsMax + 1) * 8) || !E.expect_.reserve((jobsMax + 1) * 4))
+    return zerr(64);
+  if (!E.call_events()) return zerr(1);
+  uint8_t* const winA = E.stage_.as<uint8_t>();
+  uint8_t* const winB = winA + half;
+  uint8_t* const flags = E.cmp_.flags.as<uint8_t>();
+  uint8_t* const hdr = E.cmp_.tables.as<uint8_t>();
+  uint64_t* const tot = (uint64_t*)(hdr + kOffTot3);
+  uint32_t* const carry = (uint32_t*)(hdr + kOffCarry);
+  uint64_t* const tab = (uint64_t*)(hdr + kDiffHdrBytes);
+  uint64_t* const starts = E.cmp_.list.as<uint64_t>();
+  uint64_t* const ends = starts + listCap;
+  HIPCHK_CLR(hipMemsetAsync(hdr, 0, kDiffHdrBytes, s));
+  // ---- pair passes: the compare's, with the grain kernels
+  uint64_t decoded = 0;
+  // evCall_[0] .. evCall_[1] spans the diff's own launches between two decodes, as in the compare
+  auto take_time = [&]() { E.diffMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
+  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
+  for (uint64_t p = 0; p < passes; p++) {
+    const uint64_t first = p * passSlots;
+    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
+    if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(flags, 1, nj, s));
+    else
+      hipLaunchKernelGGL(zra_cmp_spans_kernel, dim3((nj + 3) / 4), dim3(256), 0, s, A.table, A.body, (u64)A.bodyBytes, B.table, B.body, (u64)B.bodyBytes, (u64)first,
+                         nj, flags);
+    hipLaunchKernelGGL(zra_cmp_jobs_kernel, dim3(1), dim3(1024), 0, s, flags, nj, A.table, (u64)A.U, B.table, (u64)B.U, (u64)fs, (u64)first, (u64)0, (u64)C,
+                       E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), nSlots, hdr);
+    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
+    uint32_t nDec = 0;
+    HIPCHK_CLR(hipMemcpyAsync(&nDec, hdr + kOffJobs, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
+    HIPCHK_CLR(hipGetLastError());
+    take_time();
+    if (nDec > nj) return zerr(1);                                            // (cannot happen)
+    if (nDec) {
+      unsigned long long errA, errB;
+      { Status st = E.staged_pass(A, 0, nDec, winA, &errA); if (st.zra) return st; }
+      { Status st = E.staged_pass(B, nSlots, nDec, winB, &errB); if (st.zra) return st; }
+      if (errA != ~0ull || errB != ~0ull) return zerr(reported_code((errB >> 8) < (errA >> 8) ? errB : errA));
+      decoded += nDec;
+    }
+    const uint32_t items = 1 + nDec * tpf;
+    TileArgs T;
+    T.winA = winA; T.winB = winB; T.outOff = E.outOff_.as<uint64_t>(); T.flags = flags; T.fs = fs; T.first = first; T.lo = 0; T.hi = C; T.nj = nj; T.tpf = tpf;
+    T.carryIn = carry + (p & 1);
+    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
+    HIPCHK_CLR(hipMemsetAsync(carry + ((p + 1) & 1), 0, 4, s));
+    hipLaunchKernelGGL(zra_diff_count_kernel, dim3(items), dim3(256), 0, s, T, grain, tab, (u64*)(hdr + kOffDiff), carry + ((p + 1) & 1));
+    hipLaunchKernelGGL(zra_diff_scan_kernel, dim3(1), dim3(1024), 0, s, tab, items, tot + 3 * (p & 1), tot + 3 * ((p + 1) & 1));
+    if (listCap || dataCap)
+      hipLaunchKernelGGL(zra_diff_fill_kernel, dim3(items), dim3(256), 0, s, T, grain, tab, starts, ends, (u64)listCap, dData, (u64)dataCap);
+  }
+  // ---- tail passes: B's frames from the one that holds C on, decoded on their own; their bytes behind C follow the dirty bytes
+  const uint64_t* const totEnd = tot + 3 * (passes & 1);                       // {writes, ends, dirty bytes} behind the last pair pass
+  for (uint64_t p = 0; p < tailPasses; p++) {
+    const uint64_t first = fT0 + p * tailSlots;
+    const uint32_t nj = (uint32_t)std::min<uint64_t>(tailSlots, nTail - p * tailSlots);
+    search_launch_jobs(s, B.table, fs, B.U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
+    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
+    unsigned long long errB;
+    { Status st = E.staged_pass(B, 0, nj, winA, &errB); if (st.zra) return st; }
+    take_time();
+    if (errB != ~0ull) return zerr(reported_code(errB));
+    const uint64_t pLo = std::max<uint64_t>(C, first * fs), pHi = std::min<uint64_t>(B.U, (first + nj) * fs), len = pHi - pLo;
+    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
+    if (dataCap)
+      hipLaunchKernelGGL(zra_diff_tail_kernel, dim3((unsigned)((len + 4095) / 4096)), dim3(256), 0, s, winA + (pLo - first * fs), (u64)len, totEnd + 2, (u64)(pLo - C),
+                         dData, (u64)dataCap);
+  }
+  // ---- the counts, then the lists, once
+  uint64_t h16[kDiffHdrBytes / 8] = {0};
+  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
+  HIPCHK_CLR(hipMemcpyAsync(h16, hdr, kDiffHdrBytes, hipMemcpyDeviceToHost, s));
+  HIPCHK_CLR(hipStreamSynchronize(s));
+  HIPCHK_CLR(hipGetLastError());
+  take_time();
+  const uint64_t* const t3 = h16 + kOffTot3 / 8 + 3 * (passes & 1);
+  const uint64_t total = t3[0], dirty = t3[2];
+  if (t3[1] != total) return zerr(1);                                         // (cannot happen: every write has one start and one end)
+  *nWrites = total; *dataSize = dirty + tailBytes; *appendOffset = dirty; *appendSize = tailBytes;
+  if (total > writeCap || dirty + tailBytes > dataCap) return {kOutputTooSmall, 0};
+  if (total) {
+    std::vector<uint64_t> se(2 * (size_t)total);
+    HIPCHK_CLR(hipMemcpyAsync(se.data(), starts, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipMemcpyAsync(se.data() + total, ends, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
+    uint64_t at = 0;
+    for (size_t i = 0; i < total; i++) { hOff[i] = se[i]; hSize[i] = se[total + i] - se[i]; hDataOff[i] = at; at += hSize[i]; }
+  }
+  const uint64_t st8[8] = {n, n - decoded, decoded, nTail, total, dirty, passes + tailPasses, h16[kOffDiff / 8]};
+  for (int i = 0; i < 8; i++) E.fstats_[i] = st8[i];
   return ok();
 }
 

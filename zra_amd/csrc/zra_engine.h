@@ -224,6 +224,19 @@ class Engine {
   // bring-up: HIP-event time of the last compare's own launches (spans, jobs, count, scan, fill), summed over its passes
   double compare_ms() const { return compareMs_; }
 
+  // ---- diff (zra_compare.hip): the patch that turns the content of the archive at dA into that of the archive at dB, in the shape
+  // update_archive takes: the maximal runs of dirty grains of [0, UA) as writes in three host arrays, B's bytes of those runs packed
+  // at dData, B's content behind UA after them. One pass over both archives, the compare's. Statuses and their order: zra_hip.h,
+  // ZraHipDiffArchives.
+  Status diff_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
+                       uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
+                       uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
+  // the last diff_archives: {frames of [0, C), equal by compressed bytes, frame pairs decoded, tail frames of B decoded, writes, dirty
+  // bytes, passes (pair + tail), dirty grains}; all zero unless it succeeded
+  void diff_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = fstats_[i]; }
+  // bring-up: HIP-event time of the last diff's own launches (spans, jobs, count, scan, fill, tail jobs, tail copy), summed over its passes
+  double diff_ms() const { return diffMs_; }
+
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
@@ -284,7 +297,7 @@ class Engine {
   bool raVerifyWholeFrames_ = false;     // batched random access decodes every touched frame in full and checks its checksum
   DevBuf status_, produced_, frameMeta_, frameOff_, outOff_, expect_, result_, qmeta_;
   // THE plaintext staging window of the device-archive calls (batch, update, verify, search, compare): whole frames of one decode pass, slot s at
-  // s * frameSize; the search keeps its carry area in front of slot 0, the compare two halves of slots. Every engine call runs on stream_ and returns synchronised, so one
+  // s * frameSize; the search keeps its carry area in front of slot 0, the compare and the diff two halves of slots. Every engine call runs on stream_ and returns synchronised, so one
   // window is live at a time. THE RULE: a call reserves the window once, before it takes a pointer into it (reserve may move the buffer),
   // and from there to its last use calls nothing that reserves it. decode_jobs / decode_pass / staged_pass and compress_frames do not
   // (decoder and encoder scratch). The handle's read and update call ra_batch_body / update_archive, which do, but hold no window then.
@@ -309,7 +322,7 @@ class Engine {
   // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
   struct UpdScratch { DevBuf plan, packed, encSizes, frames, table, copies; } upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // around a pass's stage-from-cache kernel (update through a handle), scan launches (search) or own launches (compare); they never run inside each other
+  // around a pass's stage-from-cache kernel (update through a handle), scan launches (search) or own launches (compare, diff); they never run inside each other
   hipEvent_t evCall_[2] = {nullptr, nullptr};
   double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list
@@ -327,12 +340,16 @@ class Engine {
   struct CompareScratch { DevBuf flags, tables, list; } cmp_;
   uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
   double compareMs_ = 0;
+  // diff (zra_compare.hip): the compare's scratch (one of the two runs at a time), its own counters
+  uint64_t fstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double diffMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
   friend struct MSearchImpl;       // the multi-pattern search does the same (zra_msearch.hip)
   friend struct CompareImpl;       // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
+  friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

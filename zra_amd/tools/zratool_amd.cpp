@@ -14,6 +14,8 @@
 //         and a summary; exit status as g
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
+//   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
+//         per write, the tail and a summary; -g {grain}: a power of two from 1 to 8192 (default 1); exit status 0 empty patch, 1 not empty, 2 trouble
 #include <zra.hpp>
 #include <zra.h>
 #include <zra_hip.h>
@@ -234,6 +236,34 @@ int compare_archives(const char* pathA, const char* pathB) {
   if (u2[0] != u2[1]) std::printf("sizes differ: %llu %llu\n", (unsigned long long)u2[0], (unsigned long long)u2[1]);
   return n || u2[0] != u2[1] ? 1 : 0;
 }
+
+// mode diff: a sizing call, then the call with buffers of exactly that size. Nothing goes to stdout when a call fails.
+int diff_archives(const char* pathA, const char* pathB, uint32_t grain) {
+  zra::Buffer a = read_file(pathA), b = read_file(pathB);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", pathA, ZraGetErrorString(st)); return 2; }
+  void* dA = nullptr; void* dB = nullptr; void* dData = nullptr;
+  if (!to_device(pathA, a, &dA)) { ZraHipDestroyEngine(eng); return 2; }
+  if (!to_device(pathB, b, &dB)) { if (dA) (void)hipFree(dA); ZraHipDestroyEngine(eng); return 2; }
+  uint64_t n = 0, bytes = 0, at = 0, app = 0;
+  std::vector<uint64_t> off, size, dataOff;
+  st = ZraHipDiffArchives(eng, dA, a.size(), dB, b.size(), 0, grain, 0, nullptr, nullptr, nullptr, 0, &n, nullptr, 0, &bytes, &at, &app);
+  if (st.zra == OutputBufferTooSmall) {
+    off.resize(n); size.resize(n); dataOff.resize(n);
+    if (bytes && hipMalloc(&dData, bytes) != hipSuccess) { dData = nullptr; st.zra = ZStdError; st.zstd = 64; }
+    else st = ZraHipDiffArchives(eng, dA, a.size(), dB, b.size(), 0, grain, 0, off.data(), size.data(), dataOff.data(), off.size(), &n, dData, bytes, &bytes, &at, &app);
+  }
+  if (dA) (void)hipFree(dA);
+  if (dB) (void)hipFree(dB);
+  if (dData) (void)hipFree(dData);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s %s: cannot diff: %s\n", pathA, pathB, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < n; i++) std::printf("%llu %llu\n", (unsigned long long)off[i], (unsigned long long)size[i]);
+  std::printf("append %llu\n", (unsigned long long)app);
+  std::printf("%llu writes, %llu bytes written, %llu bytes of patch data\n", (unsigned long long)n, (unsigned long long)at, (unsigned long long)bytes);
+  return n || app ? 1 : 0;
+}
 }  // namespace
 
 // argv of the reference tool, position by position (zratool.cpp:98-125,213-221):
@@ -246,6 +276,7 @@ int compare_archives(const char* pathA, const char* pathB) {
 //       g {file} {pattern | hex:digits}
 //       gm {file} {pattern | hex:digits}...
 //       cmp {file A} {file B}
+//       diff {file A} {file B} {-g grain}
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::printf("%s {mode} {file} ...\n"
@@ -257,7 +288,8 @@ int main(int argc, char** argv) {
                 "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n"
                 "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n"
                 "gm {file} {pattern | hex:digits}... - Search an archive on the device for 1 to 64 patterns in one pass: offset and pattern index of every match (exit status as g)\n"
-                "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n",
+                "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
+                "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n",
                 argv[0]);
     return 0;
   }
@@ -274,6 +306,10 @@ int main(int argc, char** argv) {
   if (mode == "cmp") {
     if (argc < 4) { std::fprintf(stderr, "cmp {file A} {file B}\n"); return 2; }
     return compare_archives(argv[2], argv[3]);
+  }
+  if (mode == "diff") {
+    if (argc != 4 && !(argc == 6 && std::string(argv[4]) == "-g")) { std::fprintf(stderr, "diff {file A} {file B} {-g grain}\n"); return 2; }
+    return diff_archives(argv[2], argv[3], argc == 6 ? (uint32_t)std::strtoul(argv[5], nullptr, 10) : 1u);
   }
   const bool comp = mode == "c" || mode == "imc" || mode == "b";
   const zra::i8 level = comp && argc > 3 ? (zra::i8)std::atoi(argv[3]) : 0;
