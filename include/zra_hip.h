@@ -497,6 +497,102 @@ ZRA_EXPORT void ZraHipGetDiffStats(ZraHipEngine* engine, uint64_t* out8);
  *  engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugDiffMs(ZraHipEngine* engine);
 
+/* ---- content signatures: diff a device-resident archive against a replica that lies elsewhere ----
+ * ZraHipDiffArchives needs both archives in one device's memory. A replica on another GPU or host sends a SIGNATURE of its content
+ * instead: a few 64-bit words per frame. The side that holds the new archive diffs against the signature and ships the patch.
+ * Updates overwrite in place and append (no insertions), so hashes of aligned grains are enough: no rolling hash.
+ * THE SIGNATURE. With fs the frame size, grain a power of two from ZRA_HIP_SIGN_MIN_GRAIN to ZRA_HIP_SIGN_MAX_GRAIN and gpf =
+ * ceil(fs / grain), the signature of an archive of F frames is F records of 1 + gpf 64-bit words in device memory, record f at word
+ * f * (1 + gpf):
+ *  - word 0, the frame word: XXH64 with `seed` of the frame's compressed bytes, its seek-table span [a, b) of the body;
+ *  - word 1 + g, a grain word: XXH64 with `seed` of grain g of frame f, grains cut as ZraHipDiffArchives cuts them (`grain` bytes
+ *    counted from the frame's own first byte, clipped to the frame and to the content size). The grain words of a short last frame
+ *    that have no byte are 0.
+ * The record stride depends on fs and grain only: when an update appends frames the old records keep their places and new ones
+ * follow; the old last frame, grown by the append, is signed again inside its own record. What describes a signature stays on the
+ * host (ZraHipSignature, 40 bytes) and travels with the words. */
+#define ZRA_HIP_SIGN_MIN_GRAIN 64u
+#define ZRA_HIP_SIGN_MAX_GRAIN 8192u
+#define ZRA_HIP_SIGDIFF_DECODE_ALL 1u   /* every frame of [0, C) is decoded and its grains hashed, whatever its frame word says */
+typedef struct ZraHipSignature { uint64_t contentSize; uint32_t frameSize; uint32_t grain; uint64_t seed; uint64_t frames; uint64_t words; } ZraHipSignature;
+
+/** Signs frames [firstFrame, firstFrame + frameCount) (frameCount UINT64_MAX: to the last frame; ZraHipVerifyArchive's range) of
+ *  the archive at dArchive (device memory): their words go into their records of dSig (device memory, sigCapacityWords words).
+ *  *info always describes the WHOLE archive (words = frames * (1 + gpf)) and sigCapacityWords is always measured against info->words:
+ *  a caller who has just updated signs the touched frames into the signature it already holds. Synchronous; the archive is only
+ *  read; stream ordering as the other compute calls (ZraHipWaitStream).
+ *  Statuses, checked in this order:
+ *   1. engine or info NULL; dArchive NULL with a size other than 0; dSig NULL with sigCapacityWords != 0; grain not a power of two
+ *      in 64 .. 8192 -> {ZStdError, 42}.
+ *   2. [dSig, dSig + 8 * sigCapacityWords) overlaps the archive -> {ZStdError, 42}.
+ *   3. Header problems -> the statuses of ZraHipArchiveOpen; a frame size of 0 -> HeaderInvalid. The header's CRC-32 is not checked.
+ *   4. firstFrame > frames, or frameCount != UINT64_MAX and frameCount > frames - firstFrame -> OutOfBoundsAccess. The empty range is
+ *      Success.
+ *   5. sigCapacityWords < info->words -> OutputBufferTooSmall with *info filled: the sizing call, pure header arithmetic. Nothing is
+ *      decoded and nothing is written to dSig.
+ *   6. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's (ZraHipReleaseScratch returns it): the staging
+ *      window, the decoder's job arrays and the decoder's own scratch for one pass.
+ *   7. A frame that fails to decode -> the status ZraHipDecompressRABatch gives under ZRA_HIP_OPT_RA_WHOLE_FRAMES for a query inside
+ *      it; of several failing frames the one with the lowest index (passes run in frame order and the call stops behind the first pass
+ *      with a failing frame).
+ *  *info is set on Success and on OutputBufferTooSmall; on every other status it is zeroed and the stats are zero. After rule 7 the
+ *  words of the range's records are undefined. No word outside the records of the range, and none at or behind sigCapacityWords, is
+ *  ever written, whatever the outcome.
+ *  Passes: max(1, min(65,536, stagingBytes / frameSize)) frames each (stagingBytes 0: 4 GiB). Every frame of the range is decoded
+ *  whole with its checksum verified: A SIGNATURE NEVER DESCRIBES CONTENT THAT DOES NOT DECODE. The frame word of a frame whose span is
+ *  not well formed (the decoder's convention: a <= b <= body size) is never computed from bytes outside the span: the frame is
+ *  skipped there, and its decode then fails the call.
+ *  Not covered: a rolling hash for shifted content, a variant on ZraHipArchive handles, the shards of a distributed archive, the
+ *  host-pointer API, a signature of a content sub-range other than whole frames. */
+ZRA_EXPORT ZraStatus ZraHipSignArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t grain, uint64_t seed,
+    uint64_t firstFrame, uint64_t frameCount, size_t stagingBytes, uint64_t* dSig, size_t sigCapacityWords, ZraHipSignature* info);
+/** The last ZraHipSignArchive on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, frames signed, grain words written (non-empty grains), content bytes hashed, compressed bytes
+ *  hashed, passes, 0, 0}. */
+ZRA_EXPORT void ZraHipGetSignStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugDiffMs: HIP-event time of the last sign call's own launches (span hash, grain hash), summed over its
+ *  passes; its decodes are in ZraHipGetKernelStats. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugSignMs(ZraHipEngine* engine);
+
+/** ZraHipDiffArchives with A given by its signature (*sigA on the host, its sigWords words at dSigA in device memory) and B by the
+ *  archive at dB. The outputs are defined exactly as there at grain = sigA->grain with UA = sigA->contentSize (C = UA): writes are
+ *  maximal runs of dirty grains, continuing across frames and passes; B's bytes of the dirty grains are packed into dData; B's tail
+ *  [UA, UB) lies behind them; the four output words are the diff's. A grain is DIRTY when its word in dSigA differs from XXH64 with
+ *  sigA->seed of B's bytes of the same clipped grain. A call with A's signature gives, word for word and byte for byte, what
+ *  ZraHipDiffArchives(A, B, grain) gives, with one exception, the documented limit: equal 64-bit words are taken as equal content, so
+ *  SIGNATURE DIFF IS NOT COMPARE. A caller that wants 128 bits signs twice with two seeds and takes the union of the two patches.
+ *  Statuses, checked in this order:
+ *   1. the NULLs of rule 1 of ZraHipDiffArchives; sigA NULL; dSigA NULL with sigWords != 0; mode with bits other than
+ *      ZRA_HIP_SIGDIFF_DECODE_ALL; an inconsistent *sigA (grain not a power of two in 64 .. 8192, frameSize 0, frames !=
+ *      ceil(contentSize / frameSize), words != frames * (1 + gpf), sigWords < words) -> {ZStdError, 42}.
+ *   2. [dData, dData + dataCapacity) overlaps B or the signature -> {ZStdError, 42}.
+ *   3. Header problems of B, as rule 3 of ZraHipSignArchive.
+ *   4. B's frame size differs from sigA->frameSize -> {ZStdError, 40}.
+ *   5. UB < UA -> {ZStdError, 40}.
+ *   6. Scratch that cannot be allocated -> {ZStdError, 64}: the staging window, 1 byte per slot and 1 byte per grain of a pass, 24
+ *      bytes per 256 grains of a pass, 16 bytes per write up to writeCapacity, the decoder's job arrays and own scratch.
+ *   7. A frame of B that has to be decoded and fails, as rule 7 of ZraHipDiffArchives. The tail frames come behind all other passes.
+ *   8. *nWrites > writeCapacity or *dataSize > dataCapacity -> OutputBufferTooSmall with the four words set: the sizing call.
+ *  Everything ZraHipDiffArchives promises about untouched host arrays, dData behind dataCapacity and "no list entry before the last
+ *  pass" holds here too.
+ *  THE SHORTCUT. Without ZRA_HIP_SIGDIFF_DECODE_ALL a frame of [0, ceil(C / fs)) is clean without being decoded when B's span is well
+ *  formed and its XXH64 equals A's frame word; anything else is decoded, whole, checksum verified, and its grains are hashed and
+ *  compared. After an update every carried-over frame is skipped, so the cost follows the touched frames. A signature against an
+ *  identical archive gives 0 writes and no decode launch; the same content at another level decodes every frame and gives 0 writes.
+ *  Passes: max(1, min(65,536, stagingBytes / frameSize)) frames each: only B is decoded, the window is not halved. Tail passes are
+ *  the diff's. */
+ZRA_EXPORT ZraStatus ZraHipDiffSignature(ZraHipEngine* engine, const ZraHipSignature* sigA, const uint64_t* dSigA, size_t sigWords,
+    const void* dB, size_t sizeB, uint32_t mode, size_t stagingBytes,
+    uint64_t* hOffsets, uint64_t* hSizes, uint64_t* hDataOffsets, size_t writeCapacity, uint64_t* nWrites,
+    void* dData, size_t dataCapacity, uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
+/** The last ZraHipDiffSignature on the engine, in the shape of ZraHipGetDiffStats (all zero after any outcome other than Success):
+ *  out8 = {frames of [0, C), frames equal by their frame word, frames decoded, tail frames decoded, writes, dirty bytes, passes, dirty
+ *  grains}. A signature diff does not touch ZraHipGetDiffStats, and the other way round. */
+ZRA_EXPORT void ZraHipGetDiffSignatureStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid: HIP-event time of the last signature diff's own launches (span hash, job build, grain hash, count, scan, fill with
+ *  the gather copy, tail jobs and tail copy), summed over its passes. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugDiffSignatureMs(ZraHipEngine* engine);
+
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody
  *  (capacity nFrames*ZSTD_compressBound(frameSize)); writes the nFrames local frame sizes (u64, device) to dSizes and the

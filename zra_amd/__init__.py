@@ -5,6 +5,7 @@ with ctypes and mirrors the reference's interface names (include/zra.h of zraorg
 ZraDecompressBuffer, ZraDecompressRA, ... + the additive device-pointer calls of include/zra_hip.h).
 There is NO CPU codec here: without the built extension or without a GPU the compute calls raise.
 """
+import collections
 import ctypes
 import os
 import sys
@@ -60,6 +61,14 @@ EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctyp
 
 class ZraHipHostTransport(ctypes.Structure):
     _fields_ = [("user", ctypes.c_void_p), ("allgather", ALLGATHER_FN), ("exchange", EXCHANGE_FN)]
+
+
+class ZraHipSignature(ctypes.Structure):
+    _fields_ = [("contentSize", ctypes.c_uint64), ("frameSize", ctypes.c_uint32), ("grain", ctypes.c_uint32), ("seed", ctypes.c_uint64),
+                ("frames", ctypes.c_uint64), ("words", ctypes.c_uint64)]
+
+
+Signature = collections.namedtuple("Signature", "content_size frame_size grain seed frames words")
 
 _lib = None
 
@@ -163,6 +172,13 @@ def load():
         "ZraHipDiffArchives": (S, [vp, vp, sz, vp, sz, u32, u32, sz, u64p, u64p, u64p, sz, u64p, vp, sz, u64p, u64p, u64p]),
         "ZraHipGetDiffStats": (None, [vp, u64p]),
         "ZraHipDebugDiffMs": (ctypes.c_double, [vp]),
+        # content signatures
+        "ZraHipSignArchive": (S, [vp, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz, vp, sz, ctypes.POINTER(ZraHipSignature)]),
+        "ZraHipGetSignStats": (None, [vp, u64p]),
+        "ZraHipDebugSignMs": (ctypes.c_double, [vp]),
+        "ZraHipDiffSignature": (S, [vp, ctypes.POINTER(ZraHipSignature), vp, sz, vp, sz, u32, sz, u64p, u64p, u64p, sz, u64p, vp, sz, u64p, u64p, u64p]),
+        "ZraHipGetDiffSignatureStats": (None, [vp, u64p]),
+        "ZraHipDebugDiffSignatureMs": (ctypes.c_double, [vp]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -212,7 +228,9 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
-                   "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs"]
+                   "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
+                   "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
+                   "ZraHipDiffSignature", "ZraHipGetDiffSignatureStats", "ZraHipDebugDiffSignatureMs"]
 
 
 def _chk(st, what=""):
@@ -536,6 +554,63 @@ class Engine:
         """bring-up: HIP-event time of the last diff()'s own launches, summed over its passes (its decodes: kernel_stats()['dec_ms'])."""
         return self.L.ZraHipDebugDiffMs(self.h)
 
+    def sign(self, d_archive, size, d_sig, sig_cap_words, *, grain=4096, seed=0, first_frame=0, frame_count=None, staging_bytes=0):
+        """ZraHipSignArchive: the XXH64 words of frames [first_frame, first_frame + frame_count) (None: to the last frame) of the
+        archive at d_archive go into their records of the signature at d_sig (sig_cap_words 64-bit words, device memory): per frame
+        one word over its compressed bytes and one per grain of its content. Returns the Signature of the WHOLE archive
+        (content_size, frame_size, grain, seed, frames, words), which is what diff_signature() takes and what travels with the
+        words. OutputBufferTooSmall (sig_cap_words < words) carries the words needed in ZraError.needed_words. ZraError otherwise
+        is a call that could not sign (bad header, range outside the frames, a frame that does not decode, no memory)."""
+        info = ZraHipSignature()
+        self._order()
+        st = self.L.ZraHipSignArchive(self.h, d_archive or None, size, grain, seed, first_frame, 0xFFFFFFFFFFFFFFFF if frame_count is None else frame_count,
+                                      staging_bytes, d_sig or None, sig_cap_words, ctypes.byref(info))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipSignArchive")
+            e.needed_words = info.words
+            raise e
+        return Signature(info.contentSize, info.frameSize, info.grain, info.seed, info.frames, info.words)
+
+    def sign_stats(self):
+        """Counters of the last sign() on this engine (all zero unless it succeeded), keyed by SIGN_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetSignStats(self.h, a)
+        return dict(zip(SIGN_STATS, (int(v) for v in a)))
+
+    def sign_ms(self):
+        """bring-up: HIP-event time of the last sign()'s own launches (span hash, grain hash), summed over its passes."""
+        return self.L.ZraHipDebugSignMs(self.h)
+
+    def diff_signature(self, sig, d_sig, sig_words, d_b, size_b, d_data, data_cap, *, decode_all=False, staging_bytes=0, max_writes=1 << 16):
+        """ZraHipDiffSignature: diff() of the archive at d_b against the SIGNATURE (sig: a Signature, d_sig: its sig_words words in
+        device memory) of an archive that lies elsewhere, at the signature's grain. Returns what diff() returns and raises what it
+        raises; equal 64-bit words are taken as equal content."""
+        import numpy as np
+        o, s, do = (np.zeros(max_writes, dtype=np.uint64) for _ in range(3))
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if max_writes else None
+        n, ds, ao, asz = (ctypes.c_uint64(0) for _ in range(4))
+        info = ZraHipSignature(*sig)
+        self._order()
+        st = self.L.ZraHipDiffSignature(self.h, ctypes.byref(info), d_sig or None, sig_words, d_b or None, size_b, SIGDIFF_DECODE_ALL if decode_all else 0,
+                                        staging_bytes, p(o), p(s), p(do), max_writes, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds),
+                                        ctypes.byref(ao), ctypes.byref(asz))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipDiffSignature")
+            e.needed_writes, e.needed_data = n.value, ds.value
+            raise e
+        k = n.value
+        return (o[:k].copy(), s[:k].copy(), do[:k].copy()), ao.value, asz.value, ds.value
+
+    def diff_signature_stats(self):
+        """Counters of the last diff_signature() on this engine (all zero unless it succeeded), keyed by SIGDIFF_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetDiffSignatureStats(self.h, a)
+        return dict(zip(SIGDIFF_STATS, (int(v) for v in a)))
+
+    def diff_signature_ms(self):
+        """bring-up: HIP-event time of the last diff_signature()'s own launches, summed over its passes."""
+        return self.L.ZraHipDebugDiffSignatureMs(self.h)
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
@@ -558,6 +633,17 @@ COMPARE_STATS = ("frames", "equal_compressed", "decoded", "content_bytes", "rang
 DIFF_DECODE_ALL = 1                          # ZRA_HIP_DIFF_DECODE_ALL
 DIFF_MAX_GRAIN = 8192                        # ZRA_HIP_DIFF_MAX_GRAIN
 DIFF_STATS = ("frames", "equal_compressed", "decoded", "tail_decoded", "writes", "dirty_bytes", "passes", "dirty_grains")
+
+SIGN_MIN_GRAIN = 64                          # ZRA_HIP_SIGN_MIN_GRAIN
+SIGN_MAX_GRAIN = 8192                        # ZRA_HIP_SIGN_MAX_GRAIN
+SIGDIFF_DECODE_ALL = 1                       # ZRA_HIP_SIGDIFF_DECODE_ALL
+SIGN_STATS = ("frames", "signed", "grain_words", "content_bytes", "compressed_bytes", "passes")
+SIGDIFF_STATS = DIFF_STATS                   # the diff's shape; equal_compressed: frames whose span hashes to A's frame word
+
+
+def signature_words(content_size, frame_size, grain):
+    """64-bit words of the signature of content_size bytes in frames of frame_size at `grain`: frames x (1 + ceil(frame_size / grain))."""
+    return -(-content_size // frame_size) * (1 + -(-frame_size // grain))
 
 
 class Archive:

@@ -823,6 +823,35 @@ void ZraHipGetDiffStats(ZraHipEngine* engine, uint64_t* out8) {
   if (engine) engine->e->diff_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugDiffMs(ZraHipEngine* engine) { return engine ? engine->e->diff_ms() : 0.0; }
+ZraStatus ZraHipSignArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t grain, uint64_t seed, uint64_t firstFrame, uint64_t frameCount,
+                            size_t stagingBytes, uint64_t* dSig, size_t sigCapacityWords, ZraHipSignature* info) {
+  static_assert(sizeof(ZraHipSignature) == 40, "the signature file's 40-byte head");
+  if (info) *info = ZraHipSignature{0, 0, 0, 0, 0, 0};
+  if (!engine || !info) return mk(ZStdError, 42);
+  uint64_t w[6] = {0, 0, 0, 0, 0, 0};
+  const ZraStatus st = mk(engine->e->sign_archive((const uint8_t*)dArchive, archiveSize, grain, seed, firstFrame, frameCount, stagingBytes, dSig, sigCapacityWords, w));
+  *info = ZraHipSignature{w[0], (uint32_t)w[1], (uint32_t)w[2], w[3], w[4], w[5]};
+  return st;
+}
+void ZraHipGetSignStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->sign_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugSignMs(ZraHipEngine* engine) { return engine ? engine->e->sign_ms() : 0.0; }
+ZraStatus ZraHipDiffSignature(ZraHipEngine* engine, const ZraHipSignature* sigA, const uint64_t* dSigA, size_t sigWords, const void* dB, size_t sizeB, uint32_t mode,
+                              size_t stagingBytes, uint64_t* hOffsets, uint64_t* hSizes, uint64_t* hDataOffsets, size_t writeCapacity, uint64_t* nWrites, void* dData,
+                              size_t dataCapacity, uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
+  for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;
+  if (!engine || !sigA) return mk(ZStdError, 42);
+  const uint64_t w[6] = {sigA->contentSize, sigA->frameSize, sigA->grain, sigA->seed, sigA->frames, sigA->words};
+  return mk(engine->e->diff_signature(w, dSigA, sigWords, (const uint8_t*)dB, sizeB, mode, stagingBytes, hOffsets, hSizes, hDataOffsets, writeCapacity, nWrites,
+                                      (uint8_t*)dData, dataCapacity, dataSize, appendOffset, appendSize));
+}
+void ZraHipGetDiffSignatureStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->diff_signature_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugDiffSignatureMs(ZraHipEngine* engine) { return engine ? engine->e->diff_signature_ms() : 0.0; }
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

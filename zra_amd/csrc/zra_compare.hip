@@ -521,6 +521,13 @@ extern "C" __global__ void __launch_bounds__(256) zra_diff_tail_kernel(const u8*
 // =================================================================================================
 namespace zra_eng {
 
+void diff_launch_scan(hipStream_t s, uint64_t* tab, uint32_t nItems, const uint64_t* totIn, uint64_t* totOut) {
+  hipLaunchKernelGGL(zra_diff_scan_kernel, dim3(1), dim3(1024), 0, s, (u64*)tab, nItems, (const u64*)totIn, (u64*)totOut);
+}
+void diff_launch_tail(hipStream_t s, const uint8_t* src, uint64_t n, const uint64_t* dirtyBytes, uint64_t tailOff, uint8_t* dData, uint64_t dataCap) {
+  hipLaunchKernelGGL(zra_diff_tail_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, src, (u64)n, (const u64*)dirtyBytes, (u64)tailOff, dData, (u64)dataCap);
+}
+
 struct CompareImpl {
   static Status run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                     size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes);

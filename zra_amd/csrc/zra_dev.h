@@ -251,5 +251,40 @@ __device__ inline u64 zra_xxh64_quad(const u8* p, u32 n, int j) {
   return h;
 }
 
+// XXH64 with a seed of n bytes at p (any alignment, n up to a seek-table span), by a group of 4 consecutive lanes like zra_xxh64_quad:
+// the content signatures (zra_sign.hip). A function of its own: the encoder's and the decoder's register budgets were measured with
+// the seed-0 one above. All four lanes of the group have to call it with the same p, n and seed; the result is valid on j == 0. Only
+// the bytes [p, p + n) are read.
+__device__ inline u64 zra_xxh64_quad_seed(const u8* p, u64 n, int j, u64 seed) {
+  u64 v = seed + (j == 0 ? XP1 + XP2 : j == 1 ? XP2 : j == 2 ? 0 : (0 - XP1));
+  const u64 stripes = n >> 5;
+  const u8* q = p + 8 * j;
+  u64 s = 0;
+  for (; s + 8 <= stripes; s += 8) {
+    u64 x[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) x[k] = ld64(q + 32 * (size_t)(s + k));
+#pragma unroll
+    for (int k = 0; k < 8; k++) v = xxround(v, x[k]);
+  }
+  for (; s < stripes; s++) v = xxround(v, ld64(q + 32 * (size_t)s));
+  const int base = (threadIdx.x & 63) & ~3;
+  const u64 v1 = __shfl(v, base + 0, 64), v2 = __shfl(v, base + 1, 64), v3 = __shfl(v, base + 2, 64), v4 = __shfl(v, base + 3, 64);
+  u64 h;
+  if (n >= 32) {
+    h = rotl64(v1, 1) + rotl64(v2, 7) + rotl64(v3, 12) + rotl64(v4, 18);
+    h = xxmerge(h, v1); h = xxmerge(h, v2); h = xxmerge(h, v3); h = xxmerge(h, v4);
+  } else h = seed + XP5;
+  h += n;
+  if (j == 0) {
+    const u8* t = p + ((size_t)stripes << 5); u32 rem = (u32)(n & 31);
+    while (rem >= 8) { h = rotl64(h ^ xxround(0, ld64(t)), 27) * XP1 + XP4; t += 8; rem -= 8; }
+    if (rem >= 4) { h = rotl64(h ^ ((u64)ld32(t) * XP1), 23) * XP2 + XP3; t += 4; rem -= 4; }
+    while (rem) { h = rotl64(h ^ ((u64)*t * XP5), 11) * XP1; t++; rem--; }
+    h ^= h >> 33; h *= XP2; h ^= h >> 29; h *= XP3; h ^= h >> 32;
+  }
+  return h;
+}
+
 
 }  // namespace zra_dev

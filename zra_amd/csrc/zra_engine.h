@@ -33,7 +33,7 @@ struct HeaderInfo {
 };
 // parse the 38 fixed bytes; returns a ZRA status code (0 ok)
 int parse_fixed_header(const uint8_t* fixed38, HeaderInfo* h);
-// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search, compare): the checked header and
+// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search, compare, diff, sign): the checked header and
 // where its parts lie. Built once per call, by Engine::archive_view or, from a header checked before (a handle's), by `over`. A shard of
 // a distributed archive (zra_comm.hip) overrides body / bodyBytes with the bytes [bodyBase, bodyBase + bodyBytes) of the body it holds.
 struct ArchiveView {
@@ -237,6 +237,28 @@ class Engine {
   // bring-up: HIP-event time of the last diff's own launches (spans, jobs, count, scan, fill, tail jobs, tail copy), summed over its passes
   double diff_ms() const { return diffMs_; }
 
+  // ---- content signatures (zra_sign.hip): XXH64 words of the archive at dArc, a record of 1 + ceil(frameSize / grain) words per frame
+  // (the frame's compressed span, then its grains as the diff cuts them), written into the records of frames [first, first + count) of
+  // dSig. info6 = ZraHipSignature's six words {content size, frame size, grain, seed, frames, words}, of the WHOLE archive. Statuses
+  // and their order: zra_hip.h, ZraHipSignArchive.
+  Status sign_archive(const uint8_t* dArc, size_t arcSize, uint32_t grain, uint64_t seed, uint64_t first, uint64_t count, size_t stagingBytes,
+                      uint64_t* dSig, size_t sigCapWords, uint64_t info6[6]);
+  // the last sign_archive: {frames of the archive, frames signed, grain words written, content bytes hashed, compressed bytes hashed,
+  // passes, 0, 0}; all zero unless it succeeded
+  void sign_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = gstats_[i]; }
+  // bring-up: HIP-event time of the last sign's own launches (span hash, grain hash), summed over its passes
+  double sign_ms() const { return signMs_; }
+  // The diff of archive B against the SIGNATURE of an archive A that lies elsewhere: diff_archives' outputs at grain sig6[2], a grain
+  // dirty when its word differs. sig6: ZraHipSignature's six words; dSigA: its words. Statuses and their order: zra_hip.h,
+  // ZraHipDiffSignature.
+  Status diff_signature(const uint64_t sig6[6], const uint64_t* dSigA, size_t sigWords, const uint8_t* dB, size_t sizeB, uint32_t mode, size_t stagingBytes,
+                        uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
+                        uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
+  // the last diff_signature, in diff_stats' shape: {frames of [0, C), equal by their frame word, decoded, tail frames decoded, writes,
+  // dirty bytes, passes, dirty grains}; all zero unless it succeeded
+  void diff_signature_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = hstats_[i]; }
+  double diff_signature_ms() const { return sigDiffMs_; }
+
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
@@ -343,6 +365,11 @@ class Engine {
   // diff (zra_compare.hip): the compare's scratch (one of the two runs at a time), its own counters
   uint64_t fstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double diffMs_ = 0;
+  // signatures (zra_sign.hip): a decode flag per slot, a dirty flag per grain of a pass, the totals + carry + per-item table, the
+  // starts and ends of the listed writes; the counters of the sign call and of the signature diff
+  struct SignScratch { DevBuf flags, dirty, tables, list; } sig_;
+  uint64_t gstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double signMs_ = 0, sigDiffMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
@@ -350,6 +377,7 @@ class Engine {
   friend struct MSearchImpl;       // the multi-pattern search does the same (zra_msearch.hip)
   friend struct CompareImpl;       // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
+  friend struct SignImpl;          // the signature calls drive the decoder's job arrays of one archive (zra_sign.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 
@@ -360,5 +388,9 @@ void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64
                         uint32_t* expect);
 void search_launch_scan(hipStream_t s, const uint32_t* counts, uint32_t nItems, uint64_t* bases, const uint64_t* cntIn, uint64_t* cntOut);
 void search_launch_carry(hipStream_t s, uint8_t* win, uint64_t L, uint32_t n);
+// The diff's steps that do not depend on how a grain became dirty (zra_compare.hip; the signature diff shares them): the three-column
+// scan of zra_diff_scan_kernel over tab[3 * (nItems + 1)], and the tail copy of zra_diff_tail_kernel.
+void diff_launch_scan(hipStream_t s, uint64_t* tab, uint32_t nItems, const uint64_t* totIn, uint64_t* totOut);
+void diff_launch_tail(hipStream_t s, const uint8_t* src, uint64_t n, const uint64_t* dirtyBytes, uint64_t tailOff, uint8_t* dData, uint64_t dataCap);
 
 }  // namespace zra_eng

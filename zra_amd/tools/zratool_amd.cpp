@@ -16,6 +16,9 @@
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
 //         per write, the tail and a summary; -g {grain}: a power of two from 1 to 8192 (default 1); exit status 0 empty patch, 1 not empty, 2 trouble
+//   sign: the content signature of an archive (ZraHipSignArchive, on the device) into a file: the 40-byte little-endian ZraHipSignature,
+//         then its words; -g {grain}: a power of two from 64 to 8192 (default 4096), -s {seed} (default 0); exit status 0 written, 2 trouble
+//   sigdiff: diff with archive A given by its signature file (ZraHipDiffSignature): output and exit status of diff at the signature's grain
 #include <zra.hpp>
 #include <zra.h>
 #include <zra_hip.h>
@@ -28,6 +31,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -264,6 +268,84 @@ int diff_archives(const char* pathA, const char* pathB, uint32_t grain) {
   std::printf("%llu writes, %llu bytes written, %llu bytes of patch data\n", (unsigned long long)n, (unsigned long long)at, (unsigned long long)bytes);
   return n || app ? 1 : 0;
 }
+
+// mode sign: the 40-byte little-endian ZraHipSignature, then the words. Nothing goes to stdout when a call fails.
+int sign_archive(const char* path, const char* outPath, uint32_t grain, uint64_t seed) {
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr; void* dSig = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  ZraHipSignature info;
+  std::vector<uint64_t> words;
+  st = ZraHipSignArchive(eng, dArc, arc.size(), grain, seed, 0, UINT64_MAX, 0, nullptr, 0, &info);
+  if (st.zra == OutputBufferTooSmall) {
+    words.resize(info.words);
+    if (hipMalloc(&dSig, info.words * 8) != hipSuccess) { dSig = nullptr; st.zra = ZStdError; st.zstd = 64; }
+    else {
+      st = ZraHipSignArchive(eng, dArc, arc.size(), grain, seed, 0, UINT64_MAX, 0, (uint64_t*)dSig, info.words, &info);
+      if (st.zra == Success && hipMemcpy(words.data(), dSig, info.words * 8, hipMemcpyDeviceToHost) != hipSuccess) { st.zra = ZStdError; st.zstd = 1; }
+    }
+  }
+  if (dArc) (void)hipFree(dArc);
+  if (dSig) (void)hipFree(dSig);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot sign: %s\n", path, ZraGetErrorString(st)); return 2; }
+  std::vector<uint64_t> head = {info.contentSize, (uint64_t)info.frameSize | ((uint64_t)info.grain << 32), info.seed, info.frames, info.words};
+  std::string bytes;
+  for (const std::vector<uint64_t>* v : {&head, &words})
+    for (uint64_t w : *v) for (int i = 0; i < 8; i++) bytes.push_back((char)(w >> (8 * i)));
+  std::ofstream out(outPath, std::ios::binary);
+  out.write(bytes.data(), (std::streamsize)bytes.size());
+  out.close();
+  if (!out) { std::fprintf(stderr, "%s: cannot write\n", outPath); return 2; }
+  std::printf("%llu frames, %llu words, grain %u\n", (unsigned long long)info.frames, (unsigned long long)info.words, info.grain);
+  return 0;
+}
+
+// mode sigdiff: the diff mode with A given by a signature file. Nothing goes to stdout when a call fails.
+int diff_signature(const char* pathSig, const char* pathB) {
+  std::ifstream in(pathSig, std::ios::binary);
+  std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+  if (!in.good() && !in.eof()) raw.clear();
+  if (raw.size() < 40 || raw.size() % 8) { std::fprintf(stderr, "%s: not a signature file\n", pathSig); return 2; }
+  std::vector<uint64_t> w(raw.size() / 8);
+  for (size_t i = 0; i < w.size(); i++) { uint64_t x = 0; for (int k = 0; k < 8; k++) x |= (uint64_t)(uint8_t)raw[8 * i + k] << (8 * k); w[i] = x; }
+  const ZraHipSignature sig = {w[0], (uint32_t)w[1], (uint32_t)(w[1] >> 32), w[2], w[3], w[4]};
+  const size_t sigWords = w.size() - 5;
+  zra::Buffer b = read_file(pathB);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", pathSig, ZraGetErrorString(st)); return 2; }
+  void* dSig = nullptr; void* dB = nullptr; void* dData = nullptr;
+  if (!to_device(pathB, b, &dB)) { ZraHipDestroyEngine(eng); return 2; }
+  if (sigWords && (hipMalloc(&dSig, sigWords * 8) != hipSuccess || hipMemcpy(dSig, w.data() + 5, sigWords * 8, hipMemcpyHostToDevice) != hipSuccess)) {
+    std::fprintf(stderr, "%s: no device memory\n", pathSig);
+    if (dSig) (void)hipFree(dSig);
+    if (dB) (void)hipFree(dB);
+    ZraHipDestroyEngine(eng);
+    return 2;
+  }
+  uint64_t n = 0, bytes = 0, at = 0, app = 0;
+  std::vector<uint64_t> off, size, dataOff;
+  st = ZraHipDiffSignature(eng, &sig, (const uint64_t*)dSig, sigWords, dB, b.size(), 0, 0, nullptr, nullptr, nullptr, 0, &n, nullptr, 0, &bytes, &at, &app);
+  if (st.zra == OutputBufferTooSmall) {
+    off.resize(n); size.resize(n); dataOff.resize(n);
+    if (bytes && hipMalloc(&dData, bytes) != hipSuccess) { dData = nullptr; st.zra = ZStdError; st.zstd = 64; }
+    else st = ZraHipDiffSignature(eng, &sig, (const uint64_t*)dSig, sigWords, dB, b.size(), 0, 0, off.data(), size.data(), dataOff.data(), off.size(), &n, dData, bytes,
+                                  &bytes, &at, &app);
+  }
+  if (dSig) (void)hipFree(dSig);
+  if (dB) (void)hipFree(dB);
+  if (dData) (void)hipFree(dData);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s %s: cannot diff: %s\n", pathSig, pathB, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < n; i++) std::printf("%llu %llu\n", (unsigned long long)off[i], (unsigned long long)size[i]);
+  std::printf("append %llu\n", (unsigned long long)app);
+  std::printf("%llu writes, %llu bytes written, %llu bytes of patch data\n", (unsigned long long)n, (unsigned long long)at, (unsigned long long)bytes);
+  return n || app ? 1 : 0;
+}
 }  // namespace
 
 // argv of the reference tool, position by position (zratool.cpp:98-125,213-221):
@@ -277,6 +359,8 @@ int diff_archives(const char* pathA, const char* pathB, uint32_t grain) {
 //       gm {file} {pattern | hex:digits}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
+//       sign {file} {signature file} {-g grain} {-s seed}
+//       sigdiff {signature file of A} {file B}
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::printf("%s {mode} {file} ...\n"
@@ -289,7 +373,9 @@ int main(int argc, char** argv) {
                 "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n"
                 "gm {file} {pattern | hex:digits}... - Search an archive on the device for 1 to 64 patterns in one pass: offset and pattern index of every match (exit status as g)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
-                "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n",
+                "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
+                "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
+                "sigdiff {signature file of A} {file B} - diff with archive A given by its signature (output and exit status as diff)\n",
                 argv[0]);
     return 0;
   }
@@ -310,6 +396,25 @@ int main(int argc, char** argv) {
   if (mode == "diff") {
     if (argc != 4 && !(argc == 6 && std::string(argv[4]) == "-g")) { std::fprintf(stderr, "diff {file A} {file B} {-g grain}\n"); return 2; }
     return diff_archives(argv[2], argv[3], argc == 6 ? (uint32_t)std::strtoul(argv[5], nullptr, 10) : 1u);
+  }
+  if (mode == "sign") {
+    uint32_t grain = 4096; uint64_t seed = 0;
+    bool good = argc >= 4 && (argc - 4) % 2 == 0;
+    for (int i = 4; good && i + 1 < argc; i += 2) {
+      const std::string opt = argv[i];
+      char* end = nullptr;
+      const unsigned long long v = std::strtoull(argv[i + 1], &end, 0);
+      if (!*argv[i + 1] || *end) good = false;
+      else if (opt == "-g") grain = v > 0xFFFFFFFFull ? 0u : (uint32_t)v;
+      else if (opt == "-s") seed = v;
+      else good = false;
+    }
+    if (!good) { std::fprintf(stderr, "sign {file} {signature file} {-g grain} {-s seed}\n"); return 2; }
+    return sign_archive(argv[2], argv[3], grain, seed);
+  }
+  if (mode == "sigdiff") {
+    if (argc != 4) { std::fprintf(stderr, "sigdiff {signature file of A} {file B}\n"); return 2; }
+    return diff_signature(argv[2], argv[3]);
   }
   const bool comp = mode == "c" || mode == "imc" || mode == "b";
   const zra::i8 level = comp && argc > 3 ? (zra::i8)std::atoi(argv[3]) : 0;
