@@ -364,6 +364,65 @@ ZRA_EXPORT void ZraHipGetSearchMultiStats(ZraHipEngine* engine, uint64_t* out8);
 /** Bring-up aid, like ZraHipDebugSearchScanMs: HIP-event time of the scan launches of the last multi search. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugSearchMultiScanMs(ZraHipEngine* engine);
 
+/* ---- grep: the records of a device-resident archive that hold a match, without an output buffer for the content ----
+ * What `grep` itself returns: the lines. The searches above return byte offsets, and a caller who wants the record around a hit has to
+ * find the delimiter in front of it and the one behind it, which means decoding the content a second time into a buffer of their own.
+ * "How many lines match", "which lines hold any of these 40 request ids" and "which lines hold none of them" all need one pass over
+ * the plaintext, and the multi search already pays for that pass. This call adds the delimiter to it. */
+#define ZRA_HIP_GREP_INVERT 1u   /* select the records that hold NO match (grep -v) */
+
+typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipContentRange;
+
+/** Lists the records of the content range [offset, offset + size) of the archive at dArchive in which one of nPatterns byte patterns
+ *  occurs. Patterns and their limits (ZRA_HIP_SEARCH_MAX_PATTERNS, _MAX_PATTERN, _MAX_PATTERN_BYTES), the range [lo, hi) with its
+ *  inclusive bound and size = UINT64_MAX, stagingBytes, passes, whole frames with verified checksums, "only the frames of the range",
+ *  host synchrony and stream ordering: ZraHipSearchArchiveMulti's, word for word.
+ *  Records. Let t_0 < t_1 < ... be the positions of [lo, hi) whose byte equals `delimiter`.
+ *  - For every t_k there is a record [s_k, t_k), with s_0 = lo and s_k = t_(k-1) + 1.
+ *  - A last record [s_last, hi) follows iff s_last < hi. With no delimiter at all that is the one record [lo, hi) iff lo < hi.
+ *  - A record never contains its delimiter, and may be empty (two delimiters in a row). Content that ends in a delimiter has no
+ *    trailing empty record. lo and hi act as record boundaries: a record the range cuts is reported clipped.
+ *  Selection. A match is the multi search's: (p, i) with lo <= p, p + m_i <= hi and content[p, p + m_i) == pattern i. No pattern may
+ *  contain the delimiter (rule 1), so an occurrence lies inside one record.
+ *  - Without ZRA_HIP_GREP_INVERT a record is selected iff a match starts in it.
+ *  - With ZRA_HIP_GREP_INVERT a record is selected iff none does. Empty records are then selected.
+ *  Result.
+ *  - *nRecords = the number of selected records; it may exceed recordCapacity. The first min(*nRecords, recordCapacity) selected
+ *    records are written to hRecords (a HOST array) as {offset, size}, ascending, each exactly once; nothing is written behind them.
+ *    hRecords may be NULL when recordCapacity is 0: that is `grep -c`.
+ *  - On any status other than Success nothing is written to hRecords, *nRecords is 0 and all stats are zero. No entry reaches the
+ *    host before the last pass is done.
+ *  Statuses, checked in this order:
+ *   1. ZraHipSearchArchiveMulti's rule 1 (hRecords, recordCapacity and nRecords in the place of hMatches, matchCapacity and nMatches);
+ *      mode with bits other than ZRA_HIP_GREP_INVERT; a pattern that contains `delimiter` -> {ZStdError, 42}.
+ *   2. Header problems: ZraHipSearchArchive's rule 2.
+ *   3. The range: ZraHipSearchArchive's rule 3. The empty range is Success with 0 records in both modes. Without INVERT a range shorter
+ *      than the shortest pattern is Success with 0 records: nothing is decoded, and the stats are {frames, 0, ...}, as the multi
+ *      search's same shortcut. With INVERT that range is scanned like any other, and every record of it is selected.
+ *   4. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's: the staging window with its carry area, 16 bytes
+ *      per listed record, 32 bytes per 8 KiB of window for the per-tile tables, 14 KiB for the pattern table, 128 bytes for the
+ *      carried record state and the totals, the decoder's own scratch for one pass.
+ *   5. A decoded frame that fails: ZraHipSearchArchive's rule 5.
+ *  A record is attributed to the delimiter that ends it (the last one to hi), by the pass that owns that position under the multi
+ *  search's rule; a record that spans frames or passes is one record.
+ *  Cost: one decode of the range and the multi search's filter; on top of it one byte compare per position and a segmented reduction
+ *  over the positions between delimiters (profiles/grep_scan.md).
+ *  Not covered: the BYTES of the records (fetch them with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under
+ *  those calls' own bound rule), regular expressions and case folding, multi-byte delimiters, a handle variant, shards, the
+ *  host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+/** The last ZraHipGrepArchive on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, frames decoded, content bytes regenerated, records of the range (selected or not), records selected,
+ *  records listed, decode passes, matches}. matches = the (p, i) pairs, *nMatches of ZraHipSearchArchiveMulti on the same range, in
+ *  both modes. A grep touches neither ZraHipGetSearchStats nor ZraHipGetSearchMultiStats, and the other way round. */
+ZRA_EXPORT void ZraHipGetGrepStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugSearchMultiScanMs: HIP-event time of the scan launches of the last grep. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugGrepScanMs(ZraHipEngine* engine);
+
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte
  * ranges; the same content written at two levels raises the same question. A caller would have to ZraHipDecompressBuffer both contents
@@ -371,7 +430,7 @@ ZRA_EXPORT double ZraHipDebugSearchMultiScanMs(ZraHipEngine* engine);
  * independent frames: identical compressed bytes of a frame mean identical content, decided at the bandwidth of the compressed data. */
 #define ZRA_HIP_COMPARE_DECODE_ALL 1u   /* no compressed-bytes shortcut: every frame of the range is decoded on both sides */
 
-typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipContentRange;
+/* ZraHipContentRange {offset, size}: declared above, with ZraHipGrepArchive, which lists records in the same shape. */
 
 /** Compares the content of the archive at dA (sizeA bytes, device memory) with that of the archive at dB (sizeB bytes, device memory)
  *  inside the content range [offset, offset + size); size = UINT64_MAX: to C = min(UA, UB), the end of the shorter content.

@@ -163,6 +163,10 @@ def load():
                                          u64p, u64p]),
         "ZraHipGetSearchMultiStats": (None, [vp, u64p]),
         "ZraHipDebugSearchMultiScanMs": (ctypes.c_double, [vp]),
+        # grep
+        "ZraHipGrepArchive": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipGetGrepStats": (None, [vp, u64p]),
+        "ZraHipDebugGrepScanMs": (ctypes.c_double, [vp]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -227,6 +231,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
+                   "ZraHipGrepArchive", "ZraHipGetGrepStats", "ZraHipDebugGrepScanMs",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -490,6 +495,32 @@ class Engine:
         """bring-up: HIP-event time of the last search_multi()'s scan launches, summed over its passes."""
         return self.L.ZraHipDebugSearchMultiScanMs(self.h)
 
+    def grep(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20):
+        """ZraHipGrepArchive: the records of [offset, offset + length) (None: to the end) of the content of the archive at d_archive,
+        cut at the byte `delimiter`, in which one of `patterns` (search_multi's, none holding the delimiter) occurs; invert: those in
+        which none does. Returns (n_records, [(offset, size)]): every selected record is counted and the first max_records are listed
+        in ascending order, without their delimiter. max_records=0 is `grep -c`. ZraError is a call that could not grep."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n = ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipGrepArchive(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter,
+                                      GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                                      max_records, ctypes.byref(n)), "ZraHipGrepArchive")
+        k = min(n.value, max_records)
+        return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_stats(self):
+        """Counters of the last grep() on this engine (all zero unless it succeeded), keyed by GREP_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetGrepStats(self.h, a)
+        return dict(zip(GREP_STATS, (int(v) for v in a)))
+
+    def grep_scan_ms(self):
+        """bring-up: HIP-event time of the last grep()'s scan launches, summed over its passes."""
+        return self.L.ZraHipDebugGrepScanMs(self.h)
+
     def compare(self, d_a, size_a, d_b, size_b, *, decode_all=False, offset=0, length=None, staging_bytes=0, max_ranges=1 << 16):
         """ZraHipCompareArchives: the maximal runs of content positions inside [offset, offset + length) (None: to the end of the
         shorter content) at which the archives at d_a and d_b differ. Returns (n_ranges, differing_bytes, [(offset, size)]): every
@@ -626,6 +657,8 @@ SEARCH_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "pass
 SEARCH_MAX_PATTERNS = 64                     # ZRA_HIP_SEARCH_MAX_PATTERNS
 SEARCH_MAX_PATTERN_BYTES = 4096              # ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
 SEARCH_MULTI_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes", "patterns", "survivors")
+GREP_INVERT = 1                              # ZRA_HIP_GREP_INVERT
+GREP_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "listed", "passes", "matches")
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
 COMPARE_STATS = ("frames", "equal_compressed", "decoded", "content_bytes", "ranges", "listed", "passes")

@@ -211,6 +211,17 @@ class Engine {
   // bring-up: HIP-event time of the last multi search's scan launches (count, scan, fill, carry), summed over its passes
   double search_multi_scan_ms() const { return msearchScanMs_; }
 
+  // ---- grep (zra_grep.hip): the records of [offset, offset + size) (size ~0: to the end), cut at `delimiter`, in which a match of one
+  // of the nPatterns host patterns starts (mode 1: in which none does), ascending, as {offset, size} pairs in hRecords, in ONE decode of
+  // the range's frames. Patterns, range and passes are search_archive_multi's. Statuses and their order: zra_hip.h, ZraHipGrepArchive.
+  Status grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+                      uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
+  // the last grep_archive: {frames, decoded, content bytes regenerated, records of the range, records selected, records listed, passes,
+  // matches}; all zero unless it succeeded. The searches and the grep leave each other's counters alone
+  void grep_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = rstats_[i]; }
+  // bring-up: HIP-event time of the last grep's scan launches (count, scan, fill, carry), summed over its passes
+  double grep_scan_ms() const { return grepScanMs_; }
+
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
   // the same in both archives is equal without a decode (mode 1: every frame is decoded); the others are decoded whole on both sides, a
@@ -358,6 +369,10 @@ class Engine {
   struct MSearchScratch { DevBuf tables, list; } msrch_;
   uint64_t mstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double msearchScanMs_ = 0;
+  // grep scratch (zra_grep.hip): the pattern table + totals and carried record state + per-tile tables, the list of {offset, size} pairs
+  struct GrepScratch { DevBuf tables, list; } grep_;
+  uint64_t rstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double grepScanMs_ = 0;
   // compare scratch (zra_compare.hip): a flag per slot, the totals + carry + per-item table, the starts and ends of the listed ranges
   struct CompareScratch { DevBuf flags, tables, list; } cmp_;
   uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
@@ -375,6 +390,7 @@ class Engine {
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
   friend struct MSearchImpl;       // the multi-pattern search does the same (zra_msearch.hip)
+  friend struct GrepImpl;          // the grep does the same (zra_grep.hip)
   friend struct CompareImpl;       // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
   friend struct SignImpl;          // the signature calls drive the decoder's job arrays of one archive (zra_sign.hip)

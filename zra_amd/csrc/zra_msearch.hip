@@ -9,10 +9,7 @@
 //      monotone in p, so every position of [lo, hi) has one owner and the list ascends across passes whatever the pattern lengths
 //      are. A pass that is not the range's last owns only p with p + M - 1 < passEnd < hi: every byte any pattern needs is there. The
 //      last pass owns every remaining start up to hi - 1 and tests pattern i only where p + m_i <= hi.
-//  (filter) a 65,536-bit table in LDS: bit (b0 | b1 << 8) is set iff some pattern begins with b0 and is one byte long or goes on with
-//      b1. A position whose byte pair has no bit costs that one bit test; only a survivor is compared, against the patterns that begin
-//      with its first byte (bucketed on the host). The position hi - 1 has no second byte: it is a survivor iff a 1-byte pattern
-//      matches it. A survivor's hits are a 64-bit mask over the pattern indices.
+//  (filter) the 65,536-bit first-two-bytes table in LDS and the bucketed compare of a survivor: zra_patterns.h.
 //  (order) count gives per tile the sum of popcount(mask), and beside it the four sums of the tile's waves; the scan turns the tile
 //      sums into list bases; the fill redoes a tile that holds a listed match and writes (offset, pattern) pairs, positions ascending
 //      and inside a position the set bits of the mask from the lowest: a place in the list is the tile's base, plus the waves in front,
@@ -20,83 +17,12 @@
 //  (totals) matches per pattern and survivors are order-independent sums: LDS counters, then one global atomic add per non-zero
 //      pattern and workgroup. They come to the host once, with the count.
 // A workgroup takes kGroup consecutive tiles, so that the 13 KiB pattern table is staged once per 64 KiB of positions.
-#include "zra_host.h"
-#include "zra_dev.h"
-#include <algorithm>
-#include <cstring>
-
-using namespace zra_dev;
+#include "zra_patterns.h"   // the pattern table, its staging and the test of one position: shared with zra_grep.hip
 
 namespace {
-constexpr u32 kMaxPattern = 256;          // ZRA_HIP_SEARCH_MAX_PATTERN
-constexpr u32 kMaxPatterns = 64;          // ZRA_HIP_SEARCH_MAX_PATTERNS
-constexpr u32 kMaxPatternBytes = 4096;    // ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
-// the tile of zra_search.hip: 8 KiB of start positions per trip of a 256-lane workgroup, a wave takes 2,048 consecutive ones
-constexpr u32 kTile = 8192;
-constexpr u32 kWavePos = kTile / 4;
-constexpr u32 kWaveIters = kWavePos / 64;
-constexpr u32 kGroup = 8;                 // consecutive tiles of one workgroup
-// staged bytes: up to 15 in front (the 16-byte alignment of the first global load), the tile, M - 1 halo bytes, rounded up to 16; the
-// compare reads whole words and may look up to 7 bytes beyond a pattern's end (masked off)
-constexpr u32 kLdsWords = (kTile + kMaxPattern + 64) / 4;
-
-// What the host makes of the patterns, as it lies in device memory and in LDS (13,376 bytes).
-struct __attribute__((aligned(16))) Table {
-  u32 filter[65536 / 32];
-  u32 pat[(kMaxPatternBytes + 4 * kMaxPatterns) / 4];   // every pattern begins on a word; the bytes behind its end are zero
-  u16 off[kMaxPatterns];                                 // pattern i: word index into pat
-  u16 len[kMaxPatterns];
-  u16 bucket[256];                                       // first byte b: the patterns order[bucket & 255 .. + (bucket >> 8))
-  u8 order[kMaxPatterns];                                // pattern indices sorted by first byte
-};
-static_assert(sizeof(Table) % 16 == 0 && sizeof(Table) == 13376, "staged 16 bytes at a time");
 // The words the launches of a call add up, zeroed with the table's upload: the ping-pong match count (c), matches per pattern, survivors.
 struct Totals { u64 cnt[2], pad0[6], per[kMaxPatterns], survivors, pad1[7]; };
 struct __attribute__((aligned(16))) Match { u64 offset; u32 pattern, reserved; };   // ZraHipPatternMatch
-
-// the four bytes at byte index i of an LDS word array
-__device__ __forceinline__ u32 lds_word(const u32* s, u32 i) {
-  const u64 pair = ((u64)s[(i >> 2) + 1] << 32) | s[i >> 2];
-  return (u32)(pair >> ((i & 3) * 8));
-}
-
-__device__ __forceinline__ void stage_table(const Table* tbl, Table* sT) {
-  for (u32 c = threadIdx.x; c < sizeof(Table) / 16; c += 256) lds_st128((u8*)sT + 16 * (size_t)c, ((const uint4*)tbl)[c]);
-}
-
-// `bytes` bytes at src -> sTile, 16-byte global loads from the aligned address at or below src: at most 15 bytes in front (inside the
-// carry area) and 15 behind (inside the run or the buffer's slack). Returns the index of src's first byte in sTile.
-__device__ __forceinline__ u32 stage_tile(const u8* src, u32 bytes, u32* sTile) {
-  const u32 d = (u32)((size_t)src & 15);
-  const uint4* const g = (const uint4*)(src - d);
-  const u32 chunks = (d + bytes + 15) >> 4;
-  for (u32 c = threadIdx.x; c < chunks; c += 256) lds_st128((u8*)sTile + 16 * (size_t)c, g[c]);
-  return d;
-}
-
-// The patterns that occur at the position whose first byte is byte i of sTile, as a mask over their indices; avail = min(hi - p, 256)
-// bytes of the range lie at and behind the position. *surv: (filter)'s survivor.
-__device__ __forceinline__ u64 position_mask(const Table* sT, const u32* sTile, u32 i, u32 avail, bool* surv) {
-  const u32 w = lds_word(sTile, i), pair = w & 0xFFFF;
-  u64 mask = 0;
-  *surv = avail >= 2 && ((sT->filter[pair >> 5] >> (pair & 31)) & 1);
-  if (*surv || avail < 2) {
-    const u32 bk = sT->bucket[w & 0xFF];
-    for (u32 k = bk & 0xFF, e = k + (bk >> 8); k < e; k++) {
-      const u32 pi = sT->order[k], m = sT->len[pi];
-      if (m > avail) continue;
-      const u32* const pw = sT->pat + sT->off[pi];
-      bool hit = true;
-      for (u32 q = 0; q < m; q += 4) {
-        const u32 mm = m - q >= 4 ? 0xFFFFFFFFu : (1u << (8 * (m - q))) - 1;
-        if ((lds_word(sTile, i + q) ^ pw[q >> 2]) & mm) { hit = false; break; }
-      }
-      if (hit) mask |= 1ull << pi;
-    }
-    if (avail < 2) *surv = mask != 0;
-  }
-  return mask;
-}
 }  // namespace
 
 // The run of a pass: win = slot 0, position x is the byte win[x]; the start positions of the pass are xLo + [0, nPos), xHi is the
@@ -200,13 +126,9 @@ Status Engine::search_archive_multi(const uint8_t* dArc, size_t arcSize, const v
 Status MSearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
                         size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
   // ---- 1. arguments
-  if (!nMatches || !hPat || !hSizes || (!dArc && arcSize) || (!hMatches && matchCap) || nPat == 0 || nPat > kMaxPatterns) return zerr(42);
-  uint32_t M = 0, mMin = kMaxPattern, sum = 0;
-  for (size_t i = 0; i < nPat; i++) {
-    if (hSizes[i] == 0 || hSizes[i] > kMaxPattern) return zerr(42);
-    M = std::max(M, hSizes[i]); mMin = std::min(mMin, hSizes[i]); sum += hSizes[i];
-  }
-  if (sum > kMaxPatternBytes) return zerr(42);
+  if (!nMatches || !hPat || !hSizes || (!dArc && arcSize) || (!hMatches && matchCap)) return zerr(42);
+  uint32_t M = 0, mMin = kMaxPattern;
+  if (!pattern_sizes_ok(hSizes, nPat, &M, &mMin)) return zerr(42);
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   E.reset_decode_stats();
@@ -252,25 +174,7 @@ Status MSearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
   Match* const list = E.msrch_.list.as<Match>();
   {
     std::vector<uint8_t> head(kHead, 0);                                     // (the totals go up as zeros)
-    Table& T = *(Table*)head.data();
-    uint8_t* const pb = (uint8_t*)T.pat;
-    uint32_t at = 0, first[257] = {0};
-    const uint8_t* src = hPat;
-    for (size_t i = 0; i < nPat; i++) {
-      const uint32_t m = hSizes[i];
-      std::memcpy(pb + at, src, m);
-      T.off[i] = (u16)(at / 4); T.len[i] = (u16)m;
-      for (uint32_t b1 = 0; b1 < 256; b1++) {
-        if (m > 1 && b1 != src[1]) continue;
-        const uint32_t bit = src[0] | b1 << 8;
-        T.filter[bit >> 5] |= 1u << (bit & 31);
-      }
-      first[src[0] + 1]++;
-      at += (m + 3) & ~3u; src += m;
-    }
-    for (int b = 0; b < 256; b++) { T.bucket[b] = (u16)(first[b] | first[b + 1] << 8); first[b + 1] += first[b]; }
-    src = hPat;
-    for (size_t i = 0; i < nPat; i++) { T.order[first[src[0]]++] = (u8)i; src += hSizes[i]; }
+    build_table(*(Table*)head.data(), hPat, hSizes, nPat);
     HIPCHK_CLR(hipMemcpyAsync(tb, head.data(), kHead, hipMemcpyHostToDevice, s));
     HIPCHK_CLR(hipStreamSynchronize(s));                                    // (`head` goes out of scope)
   }

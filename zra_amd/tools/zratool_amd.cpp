@@ -12,6 +12,9 @@
 //         and a summary; exit status as grep: 0 matches, 1 none, 2 trouble
 //   gm  : the same for 1 to 64 patterns in one pass, like `grep -F -f` (ZraHipSearchArchiveMulti); `offset<TAB>pattern index` per line
 //         and a summary; exit status as g
+//   gl  : the records (lines) that hold a match, like `grep -F -f -b` without the text (ZraHipGrepArchive); -v: the records that hold
+//         none, -d {hex byte}: the delimiter (default 0a); `offset<TAB>size` per selected record (the first 2^20; the summary counts
+//         all) and a summary; exit status as grep: 0 some, 1 none, 2 trouble
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
@@ -218,6 +221,40 @@ int search_archive_multi(const char* path, char** texts, int n) {
   return total ? 0 : 1;
 }
 
+// mode gl: the patterns texts[0 .. n)
+int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts, int n) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  for (int i = 0; i < n; i++) {
+    std::string pat;
+    if (!parse_pattern(texts[i], &pat)) return 2;
+    all += pat;
+    sizes.push_back((uint32_t)pat.size());
+  }
+  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all.size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
+    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
+    return 2;
+  }
+  if (all.find((char)delimiter) != std::string::npos) { std::fprintf(stderr, "a pattern holds the delimiter %02x\n", delimiter); return 2; }
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  std::vector<ZraHipContentRange> at(1u << 20);
+  uint64_t total = 0;
+  st = ZraHipGrepArchive(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, invert ? ZRA_HIP_GREP_INVERT : 0u, 0, UINT64_MAX, 0, at.data(),
+                         at.size(), &total);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot grep: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(total, at.size()); i++) std::printf("%llu\t%llu\n", (unsigned long long)at[i].offset, (unsigned long long)at[i].size);
+  if (total > at.size()) std::printf("... and %llu more\n", (unsigned long long)(total - at.size()));
+  std::printf("%llu records\n", (unsigned long long)total);
+  return total ? 0 : 1;
+}
+
 // mode cmp. Nothing goes to stdout when the call fails.
 int compare_archives(const char* pathA, const char* pathB) {
   zra::Buffer a = read_file(pathA), b = read_file(pathB);
@@ -357,6 +394,7 @@ int diff_signature(const char* pathSig, const char* pathB) {
 // ours: t {file}
 //       g {file} {pattern | hex:digits}
 //       gm {file} {pattern | hex:digits}...
+//       gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
@@ -372,6 +410,7 @@ int main(int argc, char** argv) {
                 "t  {file} - Test an archive on the device: every faulty frame (exit status 0 clean, 1 faults, 2 cannot verify)\n"
                 "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n"
                 "gm {file} {pattern | hex:digits}... - Search an archive on the device for 1 to 64 patterns in one pass: offset and pattern index of every match (exit status as g)\n"
+                "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}... - Grep an archive on the device: offset and size of every record (line) that holds a match, -v: that holds none (exit status 0 some, 1 none, 2 trouble)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -388,6 +427,22 @@ int main(int argc, char** argv) {
   if (mode == "gm") {
     if (argc < 4) { std::fprintf(stderr, "gm {file} {pattern | hex:digits}...\n"); return 2; }
     return search_archive_multi(argv[2], argv + 3, argc - 3);
+  }
+  if (mode == "gl") {
+    bool invert = false;
+    unsigned long delimiter = 0x0A;
+    int i = 3;
+    for (; i < argc; i++) {
+      const std::string opt = argv[i];
+      if (opt == "-v") invert = true;
+      else if (opt == "-d") {
+        char* end = nullptr;
+        if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
+        if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
+      } else break;
+    }
+    if (i >= argc) { std::fprintf(stderr, "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}...\n"); return 2; }
+    return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i);
   }
   if (mode == "cmp") {
     if (argc < 4) { std::fprintf(stderr, "cmp {file A} {file B}\n"); return 2; }
