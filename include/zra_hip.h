@@ -407,8 +407,8 @@ typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipCont
  *  search's rule; a record that spans frames or passes is one record.
  *  Cost: one decode of the range and the multi search's filter; on top of it one byte compare per position and a segmented reduction
  *  over the positions between delimiters (profiles/grep_scan.md).
- *  Not covered: the BYTES of the records (fetch them with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under
- *  those calls' own bound rule), regular expressions and case folding, multi-byte delimiters, a handle variant, shards, the
+ *  Not covered: the BYTES of the records (ZraHipExtractRecords below keeps them from the same pass; with this call alone, fetch them
+ *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), regular expressions and case folding, multi-byte delimiters, a handle variant, shards, the
  *  host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
@@ -422,6 +422,49 @@ ZRA_EXPORT ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchiv
 ZRA_EXPORT void ZraHipGetGrepStats(ZraHipEngine* engine, uint64_t* out8);
 /** Bring-up aid, like ZraHipDebugSearchMultiScanMs: HIP-event time of the scan launches of the last grep. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugGrepScanMs(ZraHipEngine* engine);
+
+/** The grep that returns the lines: the selected records of ZraHipGrepArchive AND their bytes, from the same decode pass. Patterns and
+ *  their limits, `delimiter`, `mode` (ZRA_HIP_GREP_INVERT only), the range [lo, hi) with its inclusive bound, stagingBytes, passes,
+ *  "only the frames of the range", whole frames with verified checksums, the records and the selection: ZraHipGrepArchive's, word for
+ *  word. The archive is only read.
+ *  Result. Let the selected records be r_0 < r_1 < ..., r_i = [o_i, o_i + n_i).
+ *  - *nRecords = their number, *dataSize = the sum of (n_i + 1).
+ *  - dData (DEVICE memory, any alignment) receives, for each i in order, the n_i content bytes of r_i and then one byte `delimiter`.
+ *    The last record, which hi ends rather than a delimiter, gets its delimiter too; an empty selected record is the one delimiter
+ *    byte. Record i starts at d_i = the sum of (n_j + 1) over j < i: the host derives that from the list, there is no offsets array.
+ *    The result is the text `grep -F` prints, and can go straight into ZraHipCompressBuffer.
+ *  - A list is wanted iff recordCapacity != 0: it is written to hRecords (a HOST array) as the grep's list is, after the last pass,
+ *    once. With recordCapacity == 0, hRecords may be NULL and only the bytes come back.
+ *  - After Success the bytes of dData in [*dataSize, dataCapacity) are undefined. No byte in front of dData or at or behind dData +
+ *    dataCapacity is ever written, whatever the outcome.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchive's rule 1; dataSize NULL; hRecords NULL with recordCapacity != 0; dData NULL with dataCapacity != 0
+ *      -> {ZStdError, 42}.
+ *   2. [dData, dData + dataCapacity) overlaps [dArchive, dArchive + archiveSize) -> {ZStdError, 42}.
+ *   3. Header problems: ZraHipGrepArchive's rule 2.
+ *   4. The range: ZraHipGrepArchive's rule 3, with the same two shortcuts (the empty range: Success, 0 records, 0 bytes; without
+ *      INVERT a range shorter than the shortest pattern: Success with nothing decoded).
+ *   5. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the grep's with 64 bytes per 8 KiB of window for the per-tile
+ *      tables, and 16 bytes per listed record up to recordCapacity; never an array per record of the pass.
+ *   6. A decoded frame that fails: ZraHipGrepArchive's rule 5.
+ *   7. OutputBufferTooSmall when recordCapacity != 0 && *nRecords > recordCapacity, or when *dataSize > dataCapacity. The two words
+ *      hold what the call needs: the one outcome other than Success that sets them. Capacities 0 / 0 is the sizing call (Success
+ *      when nothing is selected). Nothing is written to hRecords; the first dataCapacity bytes of dData are undefined.
+ *  On every status other than Success the stats are zero and hRecords is untouched; apart from rule 7, *nRecords = *dataSize = 0.
+ *  Cost: the grep's, plus one byte store per copied position (profiles/extract_scan.md).
+ *  Not covered: record numbers and context lines, output without the delimiter bytes, and what ZraHipGrepArchive does not cover. */
+ZRA_EXPORT ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** The last ZraHipExtractRecords on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, frames decoded, content bytes regenerated, records of the range, records selected, packed bytes
+ *  (= *dataSize), decode passes, matches}. An extract touches neither the grep's stats nor the searches', and the other way round. */
+ZRA_EXPORT void ZraHipGetExtractStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugGrepScanMs: HIP-event time of the last extract's own launches, summed over its passes. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugExtractMs(ZraHipEngine* engine);
 
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte

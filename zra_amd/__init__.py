@@ -167,6 +167,11 @@ def load():
         "ZraHipGrepArchive": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipGetGrepStats": (None, [vp, u64p]),
         "ZraHipDebugGrepScanMs": (ctypes.c_double, [vp]),
+        # extract
+        "ZraHipExtractRecords": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz,
+                                     u64p]),
+        "ZraHipGetExtractStats": (None, [vp, u64p]),
+        "ZraHipDebugExtractMs": (ctypes.c_double, [vp]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -232,6 +237,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
                    "ZraHipGrepArchive", "ZraHipGetGrepStats", "ZraHipDebugGrepScanMs",
+                   "ZraHipExtractRecords", "ZraHipGetExtractStats", "ZraHipDebugExtractMs",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -521,6 +527,37 @@ class Engine:
         """bring-up: HIP-event time of the last grep()'s scan launches, summed over its passes."""
         return self.L.ZraHipDebugGrepScanMs(self.h)
 
+    def extract(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0):
+        """ZraHipExtractRecords: grep()'s selected records with their bytes, from one decode pass. For each selected record, in ascending
+        order, its content and then one `delimiter` byte lie packed at d_data (data_cap bytes, device memory): the text `grep` prints.
+        Returns (n_records, data_size, [(offset, size)]); the list is filled iff max_records != 0. OutputBufferTooSmall (more than
+        max_records records when a list is wanted, or more than data_cap bytes) carries what the call needs in ZraError.needed_records
+        and ZraError.needed_data; d_data=0, data_cap=0 is the sizing call. ZraError otherwise is a call that could not extract."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._order()
+        st = self.L.ZraHipExtractRecords(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter,
+                                         GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                                         max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipExtractRecords")
+            e.needed_records, e.needed_data = n.value, ds.value
+            raise e
+        k = n.value if max_records else 0
+        return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def extract_stats(self):
+        """Counters of the last extract() on this engine (all zero unless it succeeded), keyed by EXTRACT_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetExtractStats(self.h, a)
+        return dict(zip(EXTRACT_STATS, (int(v) for v in a)))
+
+    def extract_ms(self):
+        """bring-up: HIP-event time of the last extract()'s own launches, summed over its passes."""
+        return self.L.ZraHipDebugExtractMs(self.h)
+
     def compare(self, d_a, size_a, d_b, size_b, *, decode_all=False, offset=0, length=None, staging_bytes=0, max_ranges=1 << 16):
         """ZraHipCompareArchives: the maximal runs of content positions inside [offset, offset + length) (None: to the end of the
         shorter content) at which the archives at d_a and d_b differ. Returns (n_ranges, differing_bytes, [(offset, size)]): every
@@ -659,6 +696,7 @@ SEARCH_MAX_PATTERN_BYTES = 4096              # ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
 SEARCH_MULTI_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes", "patterns", "survivors")
 GREP_INVERT = 1                              # ZRA_HIP_GREP_INVERT
 GREP_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "listed", "passes", "matches")
+EXTRACT_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "packed_bytes", "passes", "matches")
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
 COMPARE_STATS = ("frames", "equal_compressed", "decoded", "content_bytes", "ranges", "listed", "passes")

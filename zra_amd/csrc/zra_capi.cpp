@@ -805,6 +805,20 @@ void ZraHipGetGrepStats(ZraHipEngine* engine, uint64_t* out8) {
   if (engine) engine->e->grep_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugGrepScanMs(ZraHipEngine* engine) { return engine ? engine->e->grep_scan_ms() : 0.0; }
+ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes,
+                               size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes,
+                               ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->extract_records((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes,
+                                       (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+}
+void ZraHipGetExtractStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->extract_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugExtractMs(ZraHipEngine* engine) { return engine ? engine->e->extract_ms() : 0.0; }
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {
   static_assert(sizeof(ZraHipContentRange) == 16, "two 64-bit words per range");

@@ -222,6 +222,18 @@ class Engine {
   // bring-up: HIP-event time of the last grep's scan launches (count, scan, fill, carry), summed over its passes
   double grep_scan_ms() const { return grepScanMs_; }
 
+  // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
+  // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:
+  // the packed bytes. Statuses and their order: zra_hip.h, ZraHipExtractRecords.
+  Status extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+                         uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
+                         uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+  // the last extract_records: {frames, decoded, content bytes regenerated, records of the range, records selected, packed bytes,
+  // passes, matches}; all zero unless it succeeded. The searches, the grep and the extract leave each other's counters alone
+  void extract_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = xstats_[i]; }
+  // bring-up: HIP-event time of the last extract's own launches (count, scan, copy, carry), summed over its passes
+  double extract_ms() const { return extractMs_; }
+
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
   // the same in both archives is equal without a decode (mode 1: every frame is decoded); the others are decoded whole on both sides, a
@@ -373,6 +385,10 @@ class Engine {
   struct GrepScratch { DevBuf tables, list; } grep_;
   uint64_t rstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double grepScanMs_ = 0;
+  // extract scratch (zra_extract.hip): the grep's, with 64 bytes per tile; its own counters
+  struct ExtractScratch { DevBuf tables, list; } ext_;
+  uint64_t xstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double extractMs_ = 0;
   // compare scratch (zra_compare.hip): a flag per slot, the totals + carry + per-item table, the starts and ends of the listed ranges
   struct CompareScratch { DevBuf flags, tables, list; } cmp_;
   uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
@@ -391,7 +407,8 @@ class Engine {
   friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
   friend struct MSearchImpl;       // the multi-pattern search does the same (zra_msearch.hip)
   friend struct GrepImpl;          // the grep does the same (zra_grep.hip)
-  friend struct CompareImpl;       // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
+  friend struct ExtractImpl;       // the extract does the same (zra_extract.hip)
+  friend struct CompareImpl;      // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
   friend struct SignImpl;          // the signature calls drive the decoder's job arrays of one archive (zra_sign.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)

@@ -1,7 +1,7 @@
 // zra_amd — the pattern table of the calls that look for several byte patterns in one pass over a staging window's plaintext
-// (zra_msearch.hip: ZraHipSearchArchiveMulti; zra_grep.hip: ZraHipGrepArchive): its layout in device memory and in LDS, the host code
-// that builds it, and the device code that stages it and a tile of the window and tests one position. Included by those two files only
-// (device code: a .hip translation unit).
+// (zra_msearch.hip: ZraHipSearchArchiveMulti; zra_grep.hip: ZraHipGrepArchive; zra_extract.hip: ZraHipExtractRecords): its layout in
+// device memory and in LDS, the host code that builds it, and the device code that stages it and a tile of the window and tests one
+// position. Included by those three files only (device code: a .hip translation unit).
 //  (filter) a 65,536-bit table in LDS: bit (b0 | b1 << 8) is set iff some pattern begins with b0 and is one byte long or goes on with
 //      b1. A position whose byte pair has no bit costs that one bit test; only a survivor is compared, against the patterns that begin
 //      with its first byte (bucketed on the host). The position hi - 1 has no second byte: it is a survivor iff a 1-byte pattern

@@ -15,6 +15,8 @@
 //   gl  : the records (lines) that hold a match, like `grep -F -f -b` without the text (ZraHipGrepArchive); -v: the records that hold
 //         none, -d {hex byte}: the delimiter (default 0a); `offset<TAB>size` per selected record (the first 2^20; the summary counts
 //         all) and a summary; exit status as grep: 0 some, 1 none, 2 trouble
+//   gx  : the text of those records, what `grep -F -f` prints (ZraHipExtractRecords): every selected record and its delimiter, packed on
+//         the device, to stdout or with -o {file} to a file; -v and -d as gl; exit status as grep, and no output when nothing is selected
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
@@ -255,6 +257,58 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   return total ? 0 : 1;
 }
 
+// mode gx: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to stdout when it is
+// null. Nothing is written when a call fails or when nothing is selected.
+int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  for (int i = 0; i < n; i++) {
+    std::string pat;
+    if (!parse_pattern(texts[i], &pat)) return 2;
+    all += pat;
+    sizes.push_back((uint32_t)pat.size());
+  }
+  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all.size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
+    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
+    return 2;
+  }
+  if (all.find((char)delimiter) != std::string::npos) { std::fprintf(stderr, "a pattern holds the delimiter %02x\n", delimiter); return 2; }
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr; void* dData = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  const uint32_t mode = invert ? ZRA_HIP_GREP_INVERT : 0u;
+  uint64_t total = 0, bytes = 0;
+  std::string text;
+  st = ZraHipExtractRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, nullptr, 0, &bytes);
+  if (st.zra == OutputBufferTooSmall) {
+    text.resize(bytes);
+    if (hipMalloc(&dData, bytes) != hipSuccess) { dData = nullptr; st.zra = ZStdError; st.zstd = 64; }
+    else {
+      st = ZraHipExtractRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dData, bytes,
+                                &bytes);
+      if (st.zra == Success && hipMemcpy(&text[0], dData, bytes, hipMemcpyDeviceToHost) != hipSuccess) { st.zra = ZStdError; st.zstd = 1; }
+    }
+  }
+  if (dArc) (void)hipFree(dArc);
+  if (dData) (void)hipFree(dData);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot extract: %s\n", path, ZraGetErrorString(st)); return 2; }
+  if (!total) return 1;
+  if (outPath) {
+    std::ofstream out(outPath, std::ios::binary);
+    out.write(text.data(), (std::streamsize)text.size());
+    out.close();
+    if (!out) { std::fprintf(stderr, "%s: cannot write\n", outPath); return 2; }
+  } else if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0) {
+    std::fprintf(stderr, "cannot write to stdout\n");
+    return 2;
+  }
+  return 0;
+}
+
 // mode cmp. Nothing goes to stdout when the call fails.
 int compare_archives(const char* pathA, const char* pathB) {
   zra::Buffer a = read_file(pathA), b = read_file(pathB);
@@ -395,6 +449,7 @@ int diff_signature(const char* pathSig, const char* pathB) {
 //       g {file} {pattern | hex:digits}
 //       gm {file} {pattern | hex:digits}...
 //       gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}...
+//       gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
@@ -411,6 +466,7 @@ int main(int argc, char** argv) {
                 "g  {file} {pattern | hex:digits} - Search an archive on the device: every offset of the pattern (exit status 0 matches, 1 none, 2 trouble)\n"
                 "gm {file} {pattern | hex:digits}... - Search an archive on the device for 1 to 64 patterns in one pass: offset and pattern index of every match (exit status as g)\n"
                 "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}... - Grep an archive on the device: offset and size of every record (line) that holds a match, -v: that holds none (exit status 0 some, 1 none, 2 trouble)\n"
+                "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -428,20 +484,26 @@ int main(int argc, char** argv) {
     if (argc < 4) { std::fprintf(stderr, "gm {file} {pattern | hex:digits}...\n"); return 2; }
     return search_archive_multi(argv[2], argv + 3, argc - 3);
   }
-  if (mode == "gl") {
+  if (mode == "gl" || mode == "gx") {
+    const bool text = mode == "gx";
     bool invert = false;
     unsigned long delimiter = 0x0A;
+    const char* outPath = nullptr;
     int i = 3;
     for (; i < argc; i++) {
       const std::string opt = argv[i];
       if (opt == "-v") invert = true;
-      else if (opt == "-d") {
+      else if (text && opt == "-o") {
+        if (++i >= argc || !*argv[i]) { std::fprintf(stderr, "-o takes a file name\n"); return 2; }
+        outPath = argv[i];
+      } else if (opt == "-d") {
         char* end = nullptr;
         if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
         if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
       } else break;
     }
-    if (i >= argc) { std::fprintf(stderr, "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}...\n"); return 2; }
+    if (i >= argc) { std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s{pattern | hex:digits}...\n", mode.c_str(), text ? "{-o file} " : ""); return 2; }
+    if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i);
     return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i);
   }
   if (mode == "cmp") {
