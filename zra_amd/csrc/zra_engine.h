@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <vector>
 #include "zra_kernels.h"
+#include "zra_scan_plan.h"   // pass_slots and the pass geometry of the range scans (host only)
 
 namespace zra_eng {
 
@@ -33,7 +34,7 @@ struct HeaderInfo {
 };
 // parse the 38 fixed bytes; returns a ZRA status code (0 ok)
 int parse_fixed_header(const uint8_t* fixed38, HeaderInfo* h);
-// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search, compare, diff, sign): the checked header and
+// A device-resident archive as the device-archive calls see it (random access, handle, update, verify, search, grep, extract, compare, diff, sign): the checked header and
 // where its parts lie. Built once per call, by Engine::archive_view or, from a header checked before (a handle's), by `over`. A shard of
 // a distributed archive (zra_comm.hip) overrides body / bodyBytes with the bytes [bodyBase, bodyBase + bodyBytes) of the body it holds.
 struct ArchiveView {
@@ -48,14 +49,8 @@ struct ArchiveView {
     return a;
   }
 };
-// Slots of one staged pass (whole frames, slot s at s * frameSize of the staging window): at most kPassFrames (one internal pass of
-// Engine::decode_jobs) and what fits stagingBytes (0: kStageBytes, which 65,536 frames of the headline 64 KiB fill exactly), at least one.
-constexpr uint32_t kPassFrames = 1u << 16;
-constexpr uint64_t kStageBytes = 4ull << 30;
-inline uint32_t pass_slots(uint64_t fs, uint64_t stagingBytes = 0, uint64_t maxFrames = kPassFrames) {
-  const uint64_t fit = (stagingBytes ? stagingBytes : kStageBytes) / (fs ? fs : 1);
-  return (uint32_t)(fit < 1 ? 1 : fit < maxFrames ? fit : maxFrames);
-}
+// The range scans (search, multi-pattern search, grep, extract; one host driver, zra_scan.h): the index of a call's counters
+enum : int { kScanSearch = 0, kScanMulti, kScanGrep, kScanExtract, kScanCalls };
 // the code a failing frame is reported with: 255 (the decoder's own "regenerated another size than its slot") is corruption_detected
 __host__ __device__ inline int reported_code(unsigned long long firstError) { const int c = (int)(firstError & 0xFF); return c == 255 ? 20 : c; }
 // An update through an archive handle (zra_archive.hip, ZraHipArchiveUpdate): what the handle lends to Engine::update_archive and what
@@ -145,7 +140,7 @@ class Engine {
     if (hipMemcpyAsync(qmeta_.as<uint64_t>() + 4 * q0, pinQ_ + 4 * q0, (q1 - q0) * 32, hipMemcpyHostToDevice, stream_) == hipSuccess) return ok();
     (void)hipGetLastError(); return zerr(1);
   }
-  // One staged pass (verify, search, compare): jobs [j0, j0 + n) of frameOff_ / expect_ decoded whole, checksums verified, into `window`, job j0 + k at
+  // One staged pass (verify, the range scans, compare, diff, sign): jobs [j0, j0 + n) of frameOff_ / expect_ decoded whole, checksums verified, into `window`, job j0 + k at
   // outOff_[k] (the same slots every pass). *firstError = decode_pass' word (~0: none failed); status_ / produced_: every job's own. Synchronised.
   Status staged_pass(const ArchiveView& a, uint32_t j0, uint32_t n, uint8_t* window, unsigned long long* firstError);
   // Host-walked frame list (reference semantics of DecompressBuffer: seek table not consulted). hFrameOff has nFrames+1 entries
@@ -195,9 +190,9 @@ class Engine {
   Status search_archive(const uint8_t* dArc, size_t arcSize, const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size,
                         size_t stagingBytes, uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
   // the last search_archive: {frames, decoded, content bytes regenerated, matches, matches listed, passes, 0, 0}; all zero unless it succeeded
-  void search_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = sstats_[i]; }
+  void search_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanSearch][i]; }
   // bring-up: HIP-event time of the last search's scan launches (count, scan, fill, carry), summed over its passes
-  double search_scan_ms() const { return searchScanMs_; }
+  double search_scan_ms() const { return scanMs_[kScanSearch]; }
 
   // ---- search for several patterns (zra_msearch.hip): every (content offset, pattern index) at which one of the nPatterns host
   // patterns (laid end to end at hPatterns, pattern i of hPatternSizes[i] bytes) occurs whole inside the range, ascending, in ONE
@@ -207,9 +202,9 @@ class Engine {
                               uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
   // the last search_archive_multi: {frames, decoded, content bytes regenerated, matches, matches listed, passes, patterns, filter
   // survivors}; all zero unless it succeeded. The single-pattern search and this one leave each other's counters alone
-  void search_multi_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = mstats_[i]; }
+  void search_multi_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanMulti][i]; }
   // bring-up: HIP-event time of the last multi search's scan launches (count, scan, fill, carry), summed over its passes
-  double search_multi_scan_ms() const { return msearchScanMs_; }
+  double search_multi_scan_ms() const { return scanMs_[kScanMulti]; }
 
   // ---- grep (zra_grep.hip): the records of [offset, offset + size) (size ~0: to the end), cut at `delimiter`, in which a match of one
   // of the nPatterns host patterns starts (mode 1: in which none does), ascending, as {offset, size} pairs in hRecords, in ONE decode of
@@ -218,9 +213,9 @@ class Engine {
                       uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
   // the last grep_archive: {frames, decoded, content bytes regenerated, records of the range, records selected, records listed, passes,
   // matches}; all zero unless it succeeded. The searches and the grep leave each other's counters alone
-  void grep_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = rstats_[i]; }
+  void grep_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanGrep][i]; }
   // bring-up: HIP-event time of the last grep's scan launches (count, scan, fill, carry), summed over its passes
-  double grep_scan_ms() const { return grepScanMs_; }
+  double grep_scan_ms() const { return scanMs_[kScanGrep]; }
 
   // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
   // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:
@@ -230,9 +225,9 @@ class Engine {
                          uint8_t* dData, size_t dataCap, uint64_t* dataSize);
   // the last extract_records: {frames, decoded, content bytes regenerated, records of the range, records selected, packed bytes,
   // passes, matches}; all zero unless it succeeded. The searches, the grep and the extract leave each other's counters alone
-  void extract_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = xstats_[i]; }
+  void extract_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanExtract][i]; }
   // bring-up: HIP-event time of the last extract's own launches (count, scan, copy, carry), summed over its passes
-  double extract_ms() const { return extractMs_; }
+  double extract_ms() const { return scanMs_[kScanExtract]; }
 
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
@@ -341,8 +336,9 @@ class Engine {
   int decOccParse_ = 0, decOccExec_ = 0, decOccHuf_ = 0; // resident workgroups per CU of the parse / execute kernels
   bool raVerifyWholeFrames_ = false;     // batched random access decodes every touched frame in full and checks its checksum
   DevBuf status_, produced_, frameMeta_, frameOff_, outOff_, expect_, result_, qmeta_;
-  // THE plaintext staging window of the device-archive calls (batch, update, verify, search, compare): whole frames of one decode pass, slot s at
-  // s * frameSize; the search keeps its carry area in front of slot 0, the compare and the diff two halves of slots. Every engine call runs on stream_ and returns synchronised, so one
+  // THE plaintext staging window of the device-archive calls (batch, update, verify, search, multi-pattern search, grep, extract, compare,
+  // diff, sign, signature diff): whole frames of one decode pass, slot s at s * frameSize; the range scans keep their carry area in
+  // front of slot 0 (zra_scan.h), the compare and the diffs two halves of slots. Every engine call runs on stream_ and returns synchronised, so one
   // window is live at a time. THE RULE: a call reserves the window once, before it takes a pointer into it (reserve may move the buffer),
   // and from there to its last use calls nothing that reserves it. decode_jobs / decode_pass / staged_pass and compress_frames do not
   // (decoder and encoder scratch). The handle's read and update call ra_batch_body / update_archive, which do, but hold no window then.
@@ -367,28 +363,18 @@ class Engine {
   // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
   struct UpdScratch { DevBuf plan, packed, encSizes, frames, table, copies; } upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // around a pass's stage-from-cache kernel (update through a handle), scan launches (search) or own launches (compare, diff); they never run inside each other
+  // around a pass's stage-from-cache kernel (update through a handle), own launches (the range scans, compare, diff, sign); they never run inside each other
   hipEvent_t evCall_[2] = {nullptr, nullptr};
   double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list
   struct VerifyScratch { DevBuf plan, faults; } vfy_;
   uint64_t vstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // search scratch (zra_search.hip): the pattern + match count + per-tile tables, the match list
-  struct SearchScratch { DevBuf tables, list; } srch_;
-  uint64_t sstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double searchScanMs_ = 0;
-  // multi-pattern search scratch (zra_msearch.hip): the pattern table + totals + per-tile tables, the list of (offset, pattern) pairs
-  struct MSearchScratch { DevBuf tables, list; } msrch_;
-  uint64_t mstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double msearchScanMs_ = 0;
-  // grep scratch (zra_grep.hip): the pattern table + totals and carried record state + per-tile tables, the list of {offset, size} pairs
-  struct GrepScratch { DevBuf tables, list; } grep_;
-  uint64_t rstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double grepScanMs_ = 0;
-  // extract scratch (zra_extract.hip): the grep's, with 64 bytes per tile; its own counters
-  struct ExtractScratch { DevBuf tables, list; } ext_;
-  uint64_t xstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double extractMs_ = 0;
+  // range-scan scratch (zra_scan.h: search, multi-pattern search, grep, extract): the call's pattern table + totals + per-tile tables
+  // (each call its own layout, uploaded before its first launch), its list. One pair: a call returns synchronised, so one is live at a
+  // time. The counters and the HIP-event time of each call's own launches stay apart: the calls leave each other's alone
+  struct ScanScratch { DevBuf tables, list; } scan_;
+  uint64_t scanStats_[kScanCalls][8] = {};
+  double scanMs_[kScanCalls] = {};
   // compare scratch (zra_compare.hip): a flag per slot, the totals + carry + per-item table, the starts and ends of the listed ranges
   struct CompareScratch { DevBuf flags, tables, list; } cmp_;
   uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
@@ -404,18 +390,16 @@ class Engine {
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
-  friend struct SearchImpl;        // the search drives the decoder's job arrays as the verifier does (zra_search.hip)
-  friend struct MSearchImpl;       // the multi-pattern search does the same (zra_msearch.hip)
-  friend struct GrepImpl;          // the grep does the same (zra_grep.hip)
-  friend struct ExtractImpl;       // the extract does the same (zra_extract.hip)
+  friend struct ScanImpl;          // the range scans drive the decoder's job arrays as the verifier does (zra_scan.h and the four calls' files)
   friend struct CompareImpl;      // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
   friend struct SignImpl;          // the signature calls drive the decoder's job arrays of one archive (zra_sign.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 
-// The search's per-pass steps that do not depend on the pattern, launched on stream s (zra_search.hip; the multi-pattern search
-// shares them): the decode jobs of frames [first, first + n) into slots 0 .. n - 1; bases[t] = *cntIn + the counts in front of item
+// The range scans' per-pass steps that do not depend on the pattern, launched on stream s (zra_search.hip; the driver in zra_scan.h
+// makes the first and the third for all four calls, the multi-pattern search shares the second; the diffs and the sign call use the
+// first for their own passes): the decode jobs of frames [first, first + n) into slots 0 .. n - 1; bases[t] = *cntIn + the counts in front of item
 // t, *cntOut = *cntIn + all of them; the last n bytes of the run win[.., L) moved to win[-n, 0), n <= 255.
 void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,
                         uint32_t* expect);

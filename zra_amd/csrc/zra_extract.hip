@@ -2,9 +2,9 @@
 // their bytes, packed into a device buffer in ascending order, each followed by the delimiter: the text `grep -F -f patterns` (and `-v`)
 // prints, from the one decode pass that selects the records.
 //
-// The passes (header, jobs per pass, Engine::staged_pass, the staging window [ carry area | slot 0 | ... ], the carry move), the
-// pattern table and the test of one position (zra_patterns.h), the records, the selection, (stream), (forward) and (order) are the
-// grep's, word for word. What differs:
+// The passes, the staging window and the conditions (contiguity), (carry), (ownership) with trim = 0 and (d) are those of the range scans'
+// one driver (zra_scan.h); the pattern table, the test of one position and a position's two flags are zra_patterns.h's; the records, the
+// selection, (stream), (forward) and (order) are the grep's (zra_grep.hip), word for word. This call's own:
 //  (compaction) a position q of [lo, hi) belongs to the record it lies in, a delimiter to the record it ends. The packed text is the
 //      stream compaction of the positions whose record is selected: the byte of q goes to dData[d + (q - s)], s = its record's start,
 //      d = the packed bytes of the selected records in front of that record, and the delimiter at t is the same formula with q = t. The
@@ -36,8 +36,6 @@ struct __attribute__((aligned(16))) XHead { u64 base, open, at, look; };
 // the state carried from pass to pass; tail: the last pass ended an open record at hi; bytes: packed so far (provisional tail)'s D
 struct XState { u64 start, hit, sel, tail, bytes, pad[3]; };
 struct XTotals { XState st[2]; u64 matches, delims, pad[6]; };
-struct __attribute__((aligned(16))) Range { u64 offset, size; };   // ZraHipContentRange
-constexpr u64 kHitBit = 1ull << 63;
 
 // a summary in registers; sel and bytes are kept wide by the scan
 struct Run { u32 f; u64 first, last, sel, bytes; };
@@ -60,21 +58,6 @@ __device__ __forceinline__ void advance(Front& e, u32 f, u64 first, u64 last, u6
   e.idx += sel + s;
   e.at += bytes + (s ? first - e.start + 1 : 0);
   e.hit = (f & 4) != 0; e.start = last;
-}
-
-// The two ballots of trip t of a wave (tile position j = w0 + 64 t + lane; d = the index of the tile's first byte in sTile; toHi = the
-// bytes of the range at and behind the tile's first position), and the lane's matches as (position, pattern) pairs.
-__device__ __forceinline__ void trip_flags(const Table* sT, const u32* sTile, u32 d, u32 j, u32 n, long long toHi, u32 delim, u64* dm, u64* hm, u32* pairs) {
-  bool isD = false, hit = false;
-  if (j < n) {
-    isD = (lds_word(sTile, d + j) & 0xFF) == delim;
-    bool surv;
-    const u64 mask = position_mask(sT, sTile, d + j, (u32)min(toHi - (long long)j, (long long)kMaxPattern), &surv);
-    hit = mask != 0;
-    *pairs += (u32)__popcll(mask);
-  }
-  *dm = __ballot(isD);
-  *hm = __ballot(hit);
 }
 
 // The summary of one trip from its ballots; pos = the content offset of lane 0's position. A delimiter lane other than the first looks
@@ -339,44 +322,22 @@ extern "C" __global__ void __launch_bounds__(256) zra_extract_copy_kernel(const 
 // =================================================================================================
 namespace zra_eng {
 
-struct ExtractImpl {
-  static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                    uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                    uint64_t* dataSize);
-};
-
 Status Engine::extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
                                uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
                                uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
-  for (auto& v : xstats_) v = 0;
-  extractMs_ = 0;
-  if (nRecords) *nRecords = 0;
-  if (dataSize) *dataSize = 0;
-  Status st = ExtractImpl::run(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
-                               recordCap, nRecords, dData, dataCap, dataSize);
-  if (st.zra) {
-    for (auto& v : xstats_) v = 0;
-    extractMs_ = 0;
-    if (st.zra != kOutputTooSmall) {                                         // (rule 7 alone leaves what is needed)
-      if (nRecords) *nRecords = 0;
-      if (dataSize) *dataSize = 0;
-    }
-  }
-  return st;
+  return ScanImpl::call(*this, kScanExtract, nRecords, dataSize, [&] {
+    return ScanImpl::extract(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
+                             recordCap, nRecords, dData, dataCap, dataSize);
+  });
 }
 
-Status ExtractImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                        uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                        uint64_t* dataSize) {
+Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
+                         uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
+                         uint64_t* dataSize) {
   // ---- 1. arguments
   if (!nRecords || !dataSize || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (!dData && dataCap) || (mode & ~1u)) return zerr(42);
   uint32_t M = 0, mMin = kMaxPattern;
-  if (!pattern_sizes_ok(hSizes, nPat, &M, &mMin)) return zerr(42);
-  {
-    size_t bytes = 0;
-    for (size_t i = 0; i < nPat; i++) bytes += hSizes[i];
-    if (std::memchr(hPat, delimiter, bytes)) return zerr(42);                // (an occurrence lies inside one record)
-  }
+  if (!record_patterns_ok(hPat, hSizes, nPat, delimiter, &M, &mMin)) return zerr(42);
   // ---- 2. overlap
   if (dataCap && arcSize && (uintptr_t)dData < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dData + dataCap) return zerr(42);
   const uint32_t inv = mode & 1u;
@@ -386,101 +347,51 @@ Status ExtractImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
   // ---- 3. header: the statuses of ZraHipArchiveOpen, as the grep
   ArchiveView arc;
   { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
-  const uint32_t F = arc.frames;
-  const uint64_t fs = arc.fs, U = arc.U;
-  // ---- 4. the range [lo, hi), inclusive bound
-  if (offset > U || (size != ~0ull && (offset + size < offset || offset + size > U))) return {kOutOfBounds, 0};
-  const uint64_t lo = offset, hi = size == ~0ull ? U : offset + size;
-  if (hi == lo || (!inv && hi - lo < mMin)) { E.xstats_[0] = F; return ok(); }   // no record, or none that could hold a match
-  if (fs == 0 || F == 0) return {kHeaderInvalid, 0};
-  const uint64_t f0 = lo / fs, f1 = (hi - 1) / fs, n = f1 - f0 + 1;
-  // ---- 5. scratch
-  const uint32_t passSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
-  const uint64_t passes = (n + passSlots - 1) / passSlots;
-  const uint64_t window = (uint64_t)nSlots * fs;
-  // (the last pass owns up to M - 1 positions inside the carry area on top of a window's worth)
-  const size_t tilesMax = (size_t)((window + kMaxPattern + kTile - 1) / kTile);
+  // ---- 4. the range [lo, hi)
+  uint64_t lo, hi;
+  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
+  uint64_t* const stats = E.scanStats_[kScanExtract];
+  if (hi == lo || (!inv && hi - lo < mMin)) { stats[0] = arc.frames; return ok(); }   // no record, or none that could hold a match
+  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
+  // ---- 5. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | XTotals | sums[tiles] | heads[tiles]
+  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
   const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  // tables: Table | XTotals | sums[tiles] | heads[tiles]
-  constexpr size_t kHead = sizeof(Table) + 64 + sizeof(XTotals);
+  constexpr size_t kTotals = sizeof(Table) + 64, kHead = kTotals + sizeof(XTotals);
   static_assert(kHead % 16 == 0 && sizeof(XSum) == 32 && sizeof(XHead) == 32 && sizeof(Range) == 16 && sizeof(XState) == 64, "16-byte entries behind a 16-byte head");
-  if (!E.stage_.reserve(kMaxPattern + (size_t)window + 64) || !E.ext_.tables.reserve(kHead + tilesMax * (sizeof(XSum) + sizeof(XHead)) + 64) ||
-      !E.ext_.list.reserve(listCap * sizeof(Range) + 64) || !E.frameOff_.reserve(((size_t)nSlots + 1) * 16) ||
-      !E.outOff_.reserve(((size_t)nSlots + 1) * 8) || !E.expect_.reserve(((size_t)nSlots + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const win = E.stage_.as<uint8_t>() + kMaxPattern;                // slot 0; the carry area lies in front of it
-  uint8_t* const tb = E.ext_.tables.as<uint8_t>();
-  const Table* const tbl = (const Table*)tb;
-  XTotals* const tot = (XTotals*)(tb + sizeof(Table) + 64);
-  XSum* const sums = (XSum*)(tb + kHead);
-  XHead* const heads = (XHead*)(sums + tilesMax);
-  Range* const list = E.ext_.list.as<Range>();
-  {
-    std::vector<uint8_t> head(kHead, 0);                                     // (the totals go up as zeros, the state as "a record opens at lo")
-    build_table(*(Table*)head.data(), hPat, hSizes, nPat);
-    ((XTotals*)(head.data() + sizeof(Table) + 64))->st[0].start = lo;
-    HIPCHK_CLR(hipMemcpyAsync(tb, head.data(), kHead, hipMemcpyHostToDevice, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));                                    // (`head` goes out of scope)
-  }
-  // ---- passes
-  uint32_t launches = 0, carry = 0;
-  bool timed = false;
-  // (behind a synchronisation of the stream)
-  auto take_time = [&]() { if (timed) E.extractMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); timed = false; };
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t first = f0 + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    search_launch_jobs(s, arc.table, fs, U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    unsigned long long firstError;
-    Status st = E.staged_pass(arc, 0, nj, win, &firstError);
-    take_time();
-    if (st.zra) return st;
-    if (firstError != ~0ull) return zerr(reported_code(firstError));         // the lowest failing frame of the first failing pass
-    // (contiguity) the run of this pass, and (ownership) the positions it owns, relative to slot 0
-    const bool lastPass = p + 1 == passes;
-    const uint64_t passBase = first * fs, passEnd = std::min<uint64_t>(U, (first + nj) * fs), L = passEnd - passBase;
-    const long long xLo = lo > passBase ? (long long)(lo - passBase) : -(long long)std::min<uint64_t>(M - 1, passBase - lo);
-    const long long xHi = (long long)(hi - passBase);
-    const long long xEnd = lastPass ? xHi : (long long)L - (long long)M + 1;
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    if (xEnd > xLo) {                                                        // (the last pass always: it holds byte hi - 1)
-      const uint64_t nPos = (uint64_t)(xEnd - xLo), p0 = passBase + xLo;
-      const uint32_t tiles = (uint32_t)((nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-      hipLaunchKernelGGL(zra_extract_count_kernel, dim3(groups), dim3(256), 0, s, win, xLo, xHi, (u64)nPos, M, tbl, (u32)delimiter, inv, (u64)p0, sums, tot);
-      hipLaunchKernelGGL(zra_extract_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
-                         (u32)lastPass, (u64)hi, (u64)p0, (u64)nPos, list, (u64)listCap, dData, (u64)dataCap, (u32)delimiter);
-      launches++;
-      if (listCap || dataCap)
-        hipLaunchKernelGGL(zra_extract_copy_kernel, dim3(groups), dim3(256), 0, s, win, xLo, xHi, (u64)nPos, M, tbl, (u32)delimiter, inv, (u64)p0, sums, heads, list,
-                           (u64)listCap, dData, (u64)dataCap);
-    }
-    if (!lastPass && M > 1) {
-      carry = (uint32_t)std::min<uint64_t>(M - 1, carry + L);
-      search_launch_carry(s, win, L, carry);
-    }
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    timed = true;
-  }
-  // ---- the totals, then the list, once
-  XTotals h;
-  std::memset(&h, 0, sizeof(h));
-  HIPCHK_CLR(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
+  std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo")
+  build_table(*(Table*)head.data(), hPat, hSizes, nPat);
+  ((XTotals*)(head.data() + kTotals))->st[0].start = lo;
+  uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
+  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanExtract], head.data(), kHead, kTotals, sizeof(XTotals), kHead + P.tilesMax * (sizeof(XSum) + sizeof(XHead)) + 64,
+                               listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
+    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
+    const Table* const tbl = (const Table*)tb;
+    XTotals* const tot = (XTotals*)(tb + kTotals);
+    XSum* const sums = (XSum*)(tb + kHead);
+    XHead* const heads = (XHead*)(sums + P.tilesMax);
+    Range* const list = E.scan_.list.as<Range>();
+    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
+    hipLaunchKernelGGL(zra_extract_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+    hipLaunchKernelGGL(zra_extract_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
+                       (u32)ps.lastPass, (u64)hi, (u64)ps.p0, (u64)ps.nPos, list, (u64)listCap, dData, (u64)dataCap, (u32)delimiter);
+    if (listCap || dataCap)
+      hipLaunchKernelGGL(zra_extract_copy_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums,
+                         heads, list, (u64)listCap, dData, (u64)dataCap);
+  }, &launches);
+  if (st.zra) return st;
+  // ---- 6. the totals (they came back with the last synchronisation), then the list, once
+  const XTotals& h = *(const XTotals*)(head.data() + kTotals);
   const XState& fin = h.st[launches & 1];
   const uint64_t total = fin.sel, packed = fin.bytes;
   *nRecords = total;
   *dataSize = packed;
   if ((recordCap && total > recordCap) || packed > dataCap) return {kOutputTooSmall, 0};   // 7: the two words say what the call needs
   if (recordCap && total) {
-    HIPCHK_CLR(hipMemcpyAsync(hRecords, list, (size_t)total * sizeof(Range), hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, (size_t)total * sizeof(Range), hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
-  const uint64_t st8[8] = {F, n, std::min<uint64_t>(U, (f1 + 1) * fs) - f0 * fs, h.delims + fin.tail, total, packed, passes, h.matches};
-  for (int i = 0; i < 8; i++) E.xstats_[i] = st8[i];
+  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, h.delims + fin.tail, total, packed, P.passes, h.matches};
+  std::copy(st8, st8 + 8, stats);
   return ok();
 }
 

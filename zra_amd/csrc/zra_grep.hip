@@ -2,10 +2,9 @@
 // that hold a match of one of up to 64 byte patterns (or, inverted, none), as ascending {offset, size} pairs, without an output buffer
 // for the content. What `grep -F -f patterns -b` (and `-v`, `-c`) is to `zstdgrep`: the lines, not the offsets of the hits.
 //
-// The passes are those of zra_msearch.hip (header, jobs per pass, Engine::staged_pass, the staging window [ carry area | slot 0 | ... ],
-// the carry move; search_launch_jobs and search_launch_carry are used as they are), its conditions (contiguity), (carry) with m = M,
-// (ownership) and (filter) hold word for word, and the pattern table and the test of one position are the same code (zra_patterns.h).
-// What differs:
+// The passes, the staging window and the conditions (contiguity), (carry), (ownership) with trim = 0 and (d) are those of the range scans'
+// one driver (zra_scan.h); (filter), the pattern table, the test of one position and a position's two flags are zra_patterns.h's, shared
+// with zra_msearch.hip and zra_extract.hip. This call's own:
 //  (stream) the positions of [lo, hi) form one ascending stream, a pass owns the positions the multi search gives it, and a position
 //      carries two flags that are both evaluated by its owner: `delimiter` (its byte, read from the carry area as often as from a slot)
 //      and `hit` (a match starts here: position_mask != 0). No pattern holds the delimiter, so the two exclude each other and an
@@ -40,8 +39,6 @@ struct __attribute__((aligned(16))) Head { u64 base, open; };
 struct State { u64 start, hit, sel, tail; };
 // The words the launches of a call add up, uploaded with the table: the ping-pong state (c), then the atomics.
 struct Totals { State st[2]; u64 matches, delims, pad[6]; };
-struct __attribute__((aligned(16))) Range { u64 offset, size; };   // ZraHipContentRange
-constexpr u64 kHitBit = 1ull << 63;
 
 // the summary of run A followed by run B. sel is kept wide by the scan: selA + selB + the record B's first delimiter ends
 __device__ __forceinline__ void combine(u32& fA, u64& selA, u64& lastA, u32 fB, u64 selB, u64 lastB, u32 inv) {
@@ -87,21 +84,6 @@ __device__ __forceinline__ Sum walk_sum(const Walk& s) {
   r.last = s.start; r.sel = s.sel;
   r.flags = s.seen ? 1u | (s.hitFirst ? 2u : 0u) | (s.hit ? 4u : 0u) : (s.hit ? 6u : 0u);
   return r;
-}
-
-// The two ballots of trip t of this wave (tile position j = w0 + 64 t + lane; d = the index of the tile's first byte in sTile; toHi =
-// the bytes of the range at and behind the tile's first position), and the lane's matches as (position, pattern) pairs.
-__device__ __forceinline__ void trip_flags(const Table* sT, const u32* sTile, u32 d, u32 j, u32 n, long long toHi, u32 delim, u64* dm, u64* hm, u32* pairs) {
-  bool isD = false, hit = false;
-  if (j < n) {
-    isD = (lds_word(sTile, d + j) & 0xFF) == delim;
-    bool surv;
-    const u64 mask = position_mask(sT, sTile, d + j, (u32)min(toHi - (long long)j, (long long)kMaxPattern), &surv);
-    hit = mask != 0;
-    *pairs += (u32)__popcll(mask);
-  }
-  *dm = __ballot(isD);
-  *hm = __ballot(hit);
 }
 }  // namespace
 
@@ -254,31 +236,20 @@ extern "C" __global__ void __launch_bounds__(256) zra_grep_fill_kernel(const u8*
 // =================================================================================================
 namespace zra_eng {
 
-struct GrepImpl {
-  static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                    uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-};
-
 Status Engine::grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
                             uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
-  for (auto& v : rstats_) v = 0;
-  grepScanMs_ = 0;
-  if (nRecords) *nRecords = 0;
-  return GrepImpl::run(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
-                       recordCap, nRecords);
+  return ScanImpl::call(*this, kScanGrep, nRecords, nullptr, [&] {
+    return ScanImpl::grep(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
+                          recordCap, nRecords);
+  });
 }
 
-Status GrepImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                     uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
+Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
+                      uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
   // ---- 1. arguments
   if (!nRecords || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (mode & ~1u)) return zerr(42);
   uint32_t M = 0, mMin = kMaxPattern;
-  if (!pattern_sizes_ok(hSizes, nPat, &M, &mMin)) return zerr(42);
-  {
-    size_t bytes = 0;
-    for (size_t i = 0; i < nPat; i++) bytes += hSizes[i];
-    if (std::memchr(hPat, delimiter, bytes)) return zerr(42);                // (an occurrence lies inside one record)
-  }
+  if (!record_patterns_ok(hPat, hSizes, nPat, delimiter, &M, &mMin)) return zerr(42);
   const uint32_t inv = mode & 1u;
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
@@ -286,103 +257,50 @@ Status GrepImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8
   // ---- 2. header: the statuses of ZraHipArchiveOpen, as the search
   ArchiveView arc;
   { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
-  const uint32_t F = arc.frames;
-  const uint64_t fs = arc.fs, U = arc.U;
-  // ---- 3. the range [lo, hi), inclusive bound
-  if (offset > U || (size != ~0ull && (offset + size < offset || offset + size > U))) return {kOutOfBounds, 0};
-  const uint64_t lo = offset, hi = size == ~0ull ? U : offset + size;
-  if (hi == lo || (!inv && hi - lo < mMin)) { E.rstats_[0] = F; return ok(); }   // no record, or none that could hold a match
-  if (fs == 0 || F == 0) return {kHeaderInvalid, 0};
-  const uint64_t f0 = lo / fs, f1 = (hi - 1) / fs, n = f1 - f0 + 1;
-  // ---- 4. scratch
-  const uint32_t passSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
-  const uint64_t passes = (n + passSlots - 1) / passSlots;
-  const uint64_t window = (uint64_t)nSlots * fs;
-  // (the last pass owns up to M - 1 positions inside the carry area on top of a window's worth)
-  const size_t tilesMax = (size_t)((window + kMaxPattern + kTile - 1) / kTile);
+  // ---- 3. the range [lo, hi)
+  uint64_t lo, hi;
+  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
+  uint64_t* const stats = E.scanStats_[kScanGrep];
+  if (hi == lo || (!inv && hi - lo < mMin)) { stats[0] = arc.frames; return ok(); }   // no record, or none that could hold a match
+  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
+  // ---- 4. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | Totals | sums[tiles] | heads[tiles]
+  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
   const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  // tables: Table | Totals | sums[tiles] | heads[tiles]
-  constexpr size_t kHead = sizeof(Table) + 64 + sizeof(Totals);
+  constexpr size_t kTotals = sizeof(Table) + 64, kHead = kTotals + sizeof(Totals);
   static_assert(kHead % 16 == 0 && sizeof(Sum) == 16 && sizeof(Head) == 16 && sizeof(Range) == 16, "16-byte entries behind a 16-byte head");
-  if (!E.stage_.reserve(kMaxPattern + (size_t)window + 64) || !E.grep_.tables.reserve(kHead + tilesMax * (sizeof(Sum) + sizeof(Head)) + 64) ||
-      !E.grep_.list.reserve(listCap * sizeof(Range) + 64) || !E.frameOff_.reserve(((size_t)nSlots + 1) * 16) ||
-      !E.outOff_.reserve(((size_t)nSlots + 1) * 8) || !E.expect_.reserve(((size_t)nSlots + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const win = E.stage_.as<uint8_t>() + kMaxPattern;                // slot 0; the carry area lies in front of it
-  uint8_t* const tb = E.grep_.tables.as<uint8_t>();
-  const Table* const tbl = (const Table*)tb;
-  Totals* const tot = (Totals*)(tb + sizeof(Table) + 64);
-  Sum* const sums = (Sum*)(tb + kHead);
-  Head* const heads = (Head*)(sums + tilesMax);
-  Range* const list = E.grep_.list.as<Range>();
-  {
-    std::vector<uint8_t> head(kHead, 0);                                     // (the totals go up as zeros, the state as "a record opens at lo")
-    build_table(*(Table*)head.data(), hPat, hSizes, nPat);
-    ((Totals*)(head.data() + sizeof(Table) + 64))->st[0].start = lo;
-    HIPCHK_CLR(hipMemcpyAsync(tb, head.data(), kHead, hipMemcpyHostToDevice, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));                                    // (`head` goes out of scope)
-  }
-  // ---- passes
-  uint32_t launches = 0, carry = 0;
-  bool timed = false;
-  // (behind a synchronisation of the stream)
-  auto take_time = [&]() { if (timed) E.grepScanMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); timed = false; };
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t first = f0 + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    search_launch_jobs(s, arc.table, fs, U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    unsigned long long firstError;
-    Status st = E.staged_pass(arc, 0, nj, win, &firstError);
-    take_time();
-    if (st.zra) { E.grepScanMs_ = 0; return st; }
-    if (firstError != ~0ull) {                                              // the lowest failing frame of the first failing pass
-      E.grepScanMs_ = 0;
-      return zerr(reported_code(firstError));
-    }
-    // (contiguity) the run of this pass, and (ownership) the positions it owns, relative to slot 0
-    const bool lastPass = p + 1 == passes;
-    const uint64_t passBase = first * fs, passEnd = std::min<uint64_t>(U, (first + nj) * fs), L = passEnd - passBase;
-    const long long xLo = lo > passBase ? (long long)(lo - passBase) : -(long long)std::min<uint64_t>(M - 1, passBase - lo);
-    const long long xHi = (long long)(hi - passBase);
-    const long long xEnd = lastPass ? xHi : (long long)L - (long long)M + 1;
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    if (xEnd > xLo) {                                                        // (the last pass always: it holds byte hi - 1)
-      const uint64_t nPos = (uint64_t)(xEnd - xLo), p0 = passBase + xLo;
-      const uint32_t tiles = (uint32_t)((nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-      hipLaunchKernelGGL(zra_grep_count_kernel, dim3(groups), dim3(256), 0, s, win, xLo, xHi, (u64)nPos, M, tbl, (u32)delimiter, inv, (u64)p0, sums, tot);
-      hipLaunchKernelGGL(zra_grep_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
-                         (u32)lastPass, (u64)hi, list, (u64)listCap);
-      launches++;
-      if (listCap)
-        hipLaunchKernelGGL(zra_grep_fill_kernel, dim3(groups), dim3(256), 0, s, win, xLo, xHi, (u64)nPos, M, tbl, (u32)delimiter, inv, (u64)p0, sums, heads, list,
-                           (u64)listCap);
-    }
-    if (!lastPass && M > 1) {
-      carry = (uint32_t)std::min<uint64_t>(M - 1, carry + L);
-      search_launch_carry(s, win, L, carry);
-    }
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    timed = true;
-  }
-  // ---- the totals, then the list, once
-  Totals h;
-  std::memset(&h, 0, sizeof(h));
-  HIPCHK_CLR(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
+  std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo")
+  build_table(*(Table*)head.data(), hPat, hSizes, nPat);
+  ((Totals*)(head.data() + kTotals))->st[0].start = lo;
+  uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
+  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanGrep], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * (sizeof(Sum) + sizeof(Head)) + 64,
+                               listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
+    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
+    const Table* const tbl = (const Table*)tb;
+    Totals* const tot = (Totals*)(tb + kTotals);
+    Sum* const sums = (Sum*)(tb + kHead);
+    Head* const heads = (Head*)(sums + P.tilesMax);
+    Range* const list = E.scan_.list.as<Range>();
+    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
+    hipLaunchKernelGGL(zra_grep_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+    hipLaunchKernelGGL(zra_grep_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
+                       (u32)ps.lastPass, (u64)hi, list, (u64)listCap);
+    if (listCap)
+      hipLaunchKernelGGL(zra_grep_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, heads,
+                         list, (u64)listCap);
+  }, &launches);
+  if (st.zra) return st;
+  // ---- 5. the totals (they came back with the last synchronisation), then the list, once
+  const Totals& h = *(const Totals*)(head.data() + kTotals);
   const State& fin = h.st[launches & 1];
   const uint64_t total = fin.sel;
   const size_t nOut = (size_t)std::min<uint64_t>(total, listCap);
   if (nOut) {
-    HIPCHK_CLR(hipMemcpyAsync(hRecords, list, nOut * sizeof(Range), hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, nOut * sizeof(Range), hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
   *nRecords = total;
-  const uint64_t st8[8] = {F, n, std::min<uint64_t>(U, (f1 + 1) * fs) - f0 * fs, h.delims + fin.tail, total, nOut, passes, h.matches};
-  for (int i = 0; i < 8; i++) E.rstats_[i] = st8[i];
+  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, h.delims + fin.tail, total, nOut, P.passes, h.matches};
+  std::copy(st8, st8 + 8, stats);
   return ok();
 }
 

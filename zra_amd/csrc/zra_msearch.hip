@@ -2,13 +2,8 @@
 // (content offset, pattern index) at which one of up to 64 byte patterns occurs inside a content range, ascending, without an output
 // buffer for the content. What `grep -F -f patterns` is to `grep`: the frames are decoded once, whatever the number of patterns.
 //
-// The passes are those of zra_search.hip (header, jobs per pass, Engine::staged_pass, the staging window [ carry area | slot 0 | ... ],
-// the prefix scan chained by a ping-pong count, the carry move; its launch wrappers are used as they are), and so are its conditions
-// (contiguity), (carry) with m = M, the longest pattern, (c) and (d). What differs:
-//  (ownership) a start position p belongs to the pass that holds content byte min(p + M - 1, hi - 1): one rule for all patterns,
-//      monotone in p, so every position of [lo, hi) has one owner and the list ascends across passes whatever the pattern lengths
-//      are. A pass that is not the range's last owns only p with p + M - 1 < passEnd < hi: every byte any pattern needs is there. The
-//      last pass owns every remaining start up to hi - 1 and tests pattern i only where p + m_i <= hi.
+// The passes, the staging window and the conditions (contiguity), (carry), (ownership) with trim = 0, (c) and (d) are those of the range
+// scans' one driver (zra_scan.h); the prefix scan chained by the ping-pong count is zra_search.hip's, used as it is. This call's own:
 //  (filter) the 65,536-bit first-two-bytes table in LDS and the bucketed compare of a survivor: zra_patterns.h.
 //  (order) count gives per tile the sum of popcount(mask), and beside it the four sums of the tile's waves; the scan turns the tile
 //      sums into list bases; the fill redoes a tile that holds a listed match and writes (offset, pattern) pairs, positions ascending
@@ -109,22 +104,16 @@ extern "C" __global__ void __launch_bounds__(256) zra_msearch_fill_kernel(const 
 // =================================================================================================
 namespace zra_eng {
 
-struct MSearchImpl {
-  static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
-                    size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
-};
-
 Status Engine::search_archive_multi(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset,
                                     uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
-  for (auto& v : mstats_) v = 0;
-  msearchScanMs_ = 0;
-  if (nMatches) *nMatches = 0;
-  return MSearchImpl::run(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCap, nMatches,
-                          hPerPattern);
+  return ScanImpl::call(*this, kScanMulti, nMatches, nullptr, [&] {
+    return ScanImpl::msearch(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCap, nMatches,
+                             hPerPattern);
+  });
 }
 
-Status MSearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
-                        size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
+Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
+                         size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
   // ---- 1. arguments
   if (!nMatches || !hPat || !hSizes || (!dArc && arcSize) || (!hMatches && matchCap)) return zerr(42);
   uint32_t M = 0, mMin = kMaxPattern;
@@ -135,106 +124,53 @@ Status MSearchImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
   // ---- 2. header: the statuses of ZraHipArchiveOpen, as the search
   ArchiveView arc;
   { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
-  const uint32_t F = arc.frames;
-  const uint64_t fs = arc.fs, U = arc.U;
-  // ---- 3. the range [lo, hi), inclusive bound
-  if (offset > U || (size != ~0ull && (offset + size < offset || offset + size > U))) return {kOutOfBounds, 0};
-  const uint64_t lo = offset, hi = size == ~0ull ? U : offset + size;
+  // ---- 3. the range [lo, hi)
+  uint64_t lo, hi;
+  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
+  uint64_t* const stats = E.scanStats_[kScanMulti];
   if (hi - lo < mMin) {
     if (hPerPattern) std::fill(hPerPattern, hPerPattern + nPat, 0ull);
-    E.mstats_[0] = F; E.mstats_[6] = nPat;
+    stats[0] = arc.frames; stats[6] = nPat;
     return ok();
   }
-  if (fs == 0 || F == 0) return {kHeaderInvalid, 0};
-  const uint64_t f0 = lo / fs, f1 = (hi - 1) / fs, n = f1 - f0 + 1;
-  // ---- 4. scratch
-  const uint32_t passSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
-  const uint64_t passes = (n + passSlots - 1) / passSlots;
-  const uint64_t window = (uint64_t)nSlots * fs;
-  // (the last pass owns up to M - 1 starts inside the carry area on top of a window's worth)
-  const size_t tilesMax = (size_t)((window + kMaxPattern + kTile - 1) / kTile);
+  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
+  // ---- 4. the passes. tables: Table | Totals | bases[tiles] | counts[tiles] | waveCnt[4 * tiles]
+  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
   uint64_t possible = 0;                                                     // no list is longer: a start per pattern that fits the range
   for (size_t i = 0; i < nPat && possible < matchCap; i++) possible += hi - lo >= hSizes[i] ? hi - lo - hSizes[i] + 1 : 0;
   const size_t listCap = (size_t)std::min<uint64_t>(matchCap, possible);
-  // tables: Table | Totals | bases[tiles] | counts[tiles] | waveCnt[4 * tiles]
-  constexpr size_t kHead = sizeof(Table) + 64 + sizeof(Totals);
-  if (!E.stage_.reserve(kMaxPattern + (size_t)window + 64) || !E.msrch_.tables.reserve(kHead + tilesMax * 28 + 64) ||
-      !E.msrch_.list.reserve(listCap * sizeof(Match) + 64) || !E.frameOff_.reserve(((size_t)nSlots + 1) * 16) ||
-      !E.outOff_.reserve(((size_t)nSlots + 1) * 8) || !E.expect_.reserve(((size_t)nSlots + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const win = E.stage_.as<uint8_t>() + kMaxPattern;                // slot 0; the carry area lies in front of it
-  uint8_t* const tb = E.msrch_.tables.as<uint8_t>();
-  const Table* const tbl = (const Table*)tb;
-  Totals* const tot = (Totals*)(tb + sizeof(Table) + 64);
-  uint64_t* const bases = (uint64_t*)(tb + kHead);
-  uint32_t* const counts = (uint32_t*)(bases + tilesMax);
-  uint32_t* const waveCnt = counts + tilesMax;
-  Match* const list = E.msrch_.list.as<Match>();
-  {
-    std::vector<uint8_t> head(kHead, 0);                                     // (the totals go up as zeros)
-    build_table(*(Table*)head.data(), hPat, hSizes, nPat);
-    HIPCHK_CLR(hipMemcpyAsync(tb, head.data(), kHead, hipMemcpyHostToDevice, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));                                    // (`head` goes out of scope)
-  }
-  // ---- passes
-  uint32_t launches = 0, carry = 0;
-  bool timed = false;
-  // (behind a synchronisation of the stream)
-  auto take_time = [&]() { if (timed) E.msearchScanMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); timed = false; };
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t first = f0 + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    search_launch_jobs(s, arc.table, fs, U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    unsigned long long firstError;
-    Status st = E.staged_pass(arc, 0, nj, win, &firstError);
-    take_time();
-    if (st.zra) { E.msearchScanMs_ = 0; return st; }
-    if (firstError != ~0ull) {                                              // the lowest failing frame of the first failing pass
-      E.msearchScanMs_ = 0;
-      return zerr(reported_code(firstError));
-    }
-    // (contiguity) the run of this pass, and (ownership) the start positions it owns, relative to slot 0
-    const uint64_t passBase = first * fs, passEnd = std::min<uint64_t>(U, (first + nj) * fs), L = passEnd - passBase;
-    const long long xLo = lo > passBase ? (long long)(lo - passBase) : -(long long)std::min<uint64_t>(M - 1, passBase - lo);
-    const long long xHi = (long long)(hi - passBase);
-    const long long xEnd = p + 1 == passes ? xHi : (long long)L - (long long)M + 1;
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    if (xEnd > xLo) {
-      const uint64_t nPos = (uint64_t)(xEnd - xLo);
-      const uint32_t tiles = (uint32_t)((nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-      hipLaunchKernelGGL(zra_msearch_count_kernel, dim3(groups), dim3(256), 0, s, win, xLo, xHi, (u64)nPos, M, tbl, (u32)nPat, counts, waveCnt, tot);
-      search_launch_scan(s, counts, tiles, bases, tot->cnt + (launches & 1), tot->cnt + ((launches + 1) & 1));
-      launches++;
-      if (listCap)
-        hipLaunchKernelGGL(zra_msearch_fill_kernel, dim3(groups), dim3(256), 0, s, win, xLo, xHi, (u64)nPos, M, tbl, counts, waveCnt, bases,
-                           (u64)(passBase + xLo), list, (u64)listCap);
-    }
-    if (p + 1 < passes && M > 1) {
-      carry = (uint32_t)std::min<uint64_t>(M - 1, carry + L);
-      search_launch_carry(s, win, L, carry);
-    }
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    timed = true;
-  }
-  // ---- the totals, then the list, once
-  Totals h;
-  std::memset(&h, 0, sizeof(h));
-  if (launches) HIPCHK_CLR(hipMemcpyAsync(&h, tot, sizeof(h), hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
+  constexpr size_t kTotals = sizeof(Table) + 64, kHead = kTotals + sizeof(Totals);
+  std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros)
+  build_table(*(Table*)head.data(), hPat, hSizes, nPat);
+  uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
+  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanMulti], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * 28 + 64, listCap * sizeof(Match) + 64, true,
+                               [&](const ScanPass& ps) {
+    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
+    const Table* const tbl = (const Table*)tb;
+    Totals* const tot = (Totals*)(tb + kTotals);
+    uint64_t* const bases = (uint64_t*)(tb + kHead);
+    uint32_t* const counts = (uint32_t*)(bases + P.tilesMax);
+    uint32_t* const waveCnt = counts + P.tilesMax;
+    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
+    hipLaunchKernelGGL(zra_msearch_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)nPat, counts, waveCnt, tot);
+    search_launch_scan(s, counts, tiles, bases, tot->cnt + (launches & 1), tot->cnt + ((launches + 1) & 1));
+    if (listCap)
+      hipLaunchKernelGGL(zra_msearch_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, counts, waveCnt, bases, (u64)ps.p0,
+                         E.scan_.list.as<Match>(), (u64)listCap);
+  }, &launches);
+  if (st.zra) return st;
+  // ---- 5. the totals (they came back with the last synchronisation), then the list, once
+  const Totals& h = *(const Totals*)(head.data() + kTotals);
   const uint64_t total = h.cnt[launches & 1];
   const size_t nOut = (size_t)std::min<uint64_t>(total, listCap);
   if (nOut) {
-    HIPCHK_CLR(hipMemcpyAsync(hMatches, list, nOut * sizeof(Match), hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipMemcpyAsync(hMatches, E.scan_.list.p, nOut * sizeof(Match), hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
   if (hPerPattern) std::copy(h.per, h.per + nPat, hPerPattern);
   *nMatches = total;
-  const uint64_t st8[8] = {F, n, std::min<uint64_t>(U, (f1 + 1) * fs) - f0 * fs, total, nOut, passes, nPat, h.survivors};
-  for (int i = 0; i < 8; i++) E.mstats_[i] = st8[i];
+  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, total, nOut, P.passes, nPat, h.survivors};
+  std::copy(st8, st8 + 8, stats);
   return ok();
 }
 

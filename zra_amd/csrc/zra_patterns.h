@@ -1,31 +1,22 @@
 // zra_amd — the pattern table of the calls that look for several byte patterns in one pass over a staging window's plaintext
 // (zra_msearch.hip: ZraHipSearchArchiveMulti; zra_grep.hip: ZraHipGrepArchive; zra_extract.hip: ZraHipExtractRecords): its layout in
 // device memory and in LDS, the host code that builds it, and the device code that stages it and a tile of the window and tests one
-// position. Included by those three files only (device code: a .hip translation unit).
+// position; for the two calls that cut the range into records, the two flags of a position and the list entry. Included by those three
+// files only (device code: a .hip translation unit). The tile and its staging: zra_scan_tile.h, shared with zra_search.hip.
 //  (filter) a 65,536-bit table in LDS: bit (b0 | b1 << 8) is set iff some pattern begins with b0 and is one byte long or goes on with
 //      b1. A position whose byte pair has no bit costs that one bit test; only a survivor is compared, against the patterns that begin
 //      with its first byte (bucketed on the host). The position hi - 1 has no second byte: it is a survivor iff a 1-byte pattern
 //      matches it. A survivor's hits are a 64-bit mask over the pattern indices.
 #pragma once
-#include "zra_host.h"
-#include "zra_dev.h"
+#include "zra_scan.h"
+#include "zra_scan_tile.h"
 #include <algorithm>
 #include <cstring>
 
-using namespace zra_dev;
-
 namespace {
-constexpr u32 kMaxPattern = 256;          // ZRA_HIP_SEARCH_MAX_PATTERN
 constexpr u32 kMaxPatterns = 64;          // ZRA_HIP_SEARCH_MAX_PATTERNS
 constexpr u32 kMaxPatternBytes = 4096;    // ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
-// the tile of zra_search.hip: 8 KiB of start positions per trip of a 256-lane workgroup, a wave takes 2,048 consecutive ones
-constexpr u32 kTile = 8192;
-constexpr u32 kWavePos = kTile / 4;
-constexpr u32 kWaveIters = kWavePos / 64;
 constexpr u32 kGroup = 8;                 // consecutive tiles of one workgroup
-// staged bytes: up to 15 in front (the 16-byte alignment of the first global load), the tile, M - 1 halo bytes, rounded up to 16; the
-// compare reads whole words and may look up to 7 bytes beyond a pattern's end (masked off)
-constexpr u32 kLdsWords = (kTile + kMaxPattern + 64) / 4;
 
 // What the host makes of the patterns, as it lies in device memory and in LDS (13,376 bytes).
 struct __attribute__((aligned(16))) Table {
@@ -38,7 +29,7 @@ struct __attribute__((aligned(16))) Table {
 };
 static_assert(sizeof(Table) % 16 == 0 && sizeof(Table) == 13376, "staged 16 bytes at a time");
 
-// Rule 1 of both calls as far as the sizes go: 1 .. 64 patterns of 1 .. 256 bytes, 4,096 bytes in all. *M: the longest, *mMin: the shortest.
+// Rule 1 of the three calls as far as the sizes go: 1 .. 64 patterns of 1 .. 256 bytes, 4,096 bytes in all. *M: the longest, *mMin: the shortest.
 inline bool pattern_sizes_ok(const uint32_t* hSizes, size_t nPat, uint32_t* M, uint32_t* mMin) {
   if (nPat == 0 || nPat > kMaxPatterns) return false;
   uint32_t sum = 0;
@@ -48,6 +39,14 @@ inline bool pattern_sizes_ok(const uint32_t* hSizes, size_t nPat, uint32_t* M, u
     *M = std::max(*M, hSizes[i]); *mMin = std::min(*mMin, hSizes[i]); sum += hSizes[i];
   }
   return sum <= kMaxPatternBytes;
+}
+
+// Rule 1 of the grep and the extract: the sizes, and no pattern holds the delimiter, so that an occurrence lies inside one record.
+inline bool record_patterns_ok(const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t* M, uint32_t* mMin) {
+  if (!pattern_sizes_ok(hSizes, nPat, M, mMin)) return false;
+  size_t bytes = 0;
+  for (size_t i = 0; i < nPat; i++) bytes += hSizes[i];
+  return std::memchr(hPat, delimiter, bytes) == nullptr;
 }
 
 // The table of the nPat patterns laid end to end at hPat, into T (zeroed by the caller).
@@ -72,24 +71,8 @@ inline void build_table(Table& T, const uint8_t* hPat, const uint32_t* hSizes, s
   for (size_t i = 0; i < nPat; i++) { T.order[first[src[0]]++] = (u8)i; src += hSizes[i]; }
 }
 
-// the four bytes at byte index i of an LDS word array
-__device__ __forceinline__ u32 lds_word(const u32* s, u32 i) {
-  const u64 pair = ((u64)s[(i >> 2) + 1] << 32) | s[i >> 2];
-  return (u32)(pair >> ((i & 3) * 8));
-}
-
 __device__ __forceinline__ void stage_table(const Table* tbl, Table* sT) {
   for (u32 c = threadIdx.x; c < sizeof(Table) / 16; c += 256) lds_st128((u8*)sT + 16 * (size_t)c, ((const uint4*)tbl)[c]);
-}
-
-// `bytes` bytes at src -> sTile, 16-byte global loads from the aligned address at or below src: at most 15 bytes in front (inside the
-// carry area) and 15 behind (inside the run or the buffer's slack). Returns the index of src's first byte in sTile.
-__device__ __forceinline__ u32 stage_tile(const u8* src, u32 bytes, u32* sTile) {
-  const u32 d = (u32)((size_t)src & 15);
-  const uint4* const g = (const uint4*)(src - d);
-  const u32 chunks = (d + bytes + 15) >> 4;
-  for (u32 c = threadIdx.x; c < chunks; c += 256) lds_st128((u8*)sTile + 16 * (size_t)c, g[c]);
-  return d;
 }
 
 // The patterns that occur at the position whose first byte is byte i of sTile, as a mask over their indices; avail = min(hi - p, 256)
@@ -114,5 +97,25 @@ __device__ __forceinline__ u64 position_mask(const Table* sT, const u32* sTile, 
     if (avail < 2) *surv = mask != 0;
   }
   return mask;
+}
+
+// ---- the grep and the extract: a position's two flags, a list entry
+struct __attribute__((aligned(16))) Range { u64 offset, size; };   // ZraHipContentRange
+constexpr u64 kHitBit = 1ull << 63;                                // the hit bit of the record open at a tile's head, beside its start
+
+// The two ballots of trip t of a wave (tile position j = w0 + 64 t + lane; d = the index of the tile's first byte in sTile; toHi = the
+// bytes of the range at and behind the tile's first position): `delimiter` (its byte) and `hit` (a match starts here), and the lane's
+// matches as (position, pattern) pairs.
+__device__ __forceinline__ void trip_flags(const Table* sT, const u32* sTile, u32 d, u32 j, u32 n, long long toHi, u32 delim, u64* dm, u64* hm, u32* pairs) {
+  bool isD = false, hit = false;
+  if (j < n) {
+    isD = (lds_word(sTile, d + j) & 0xFF) == delim;
+    bool surv;
+    const u64 mask = position_mask(sT, sTile, d + j, (u32)min(toHi - (long long)j, (long long)kMaxPattern), &surv);
+    hit = mask != 0;
+    *pairs += (u32)__popcll(mask);
+  }
+  *dm = __ballot(isD);
+  *hm = __ballot(hit);
 }
 }  // namespace

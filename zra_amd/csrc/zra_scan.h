@@ -1,0 +1,115 @@
+// zra_amd — the host driver of the range scans: ZraHipSearchArchive (zra_search.hip), ZraHipSearchArchiveMulti (zra_msearch.hip),
+// ZraHipGrepArchive (zra_grep.hip) and ZraHipExtractRecords (zra_extract.hip). The four calls decode the frames of a content range a
+// staging window at a time and scan the window's plaintext with kernels of their own; what they share is written once, here:
+//
+//   1. the fixed header comes to the host (Engine::archive_view); the range becomes frames [f0, f1]       scan_range, scan_plan
+//   2. per pass of at most passSlots consecutive frames: the frames become decode jobs                   zra_search_jobs_kernel
+//   3. the pass is decoded whole, checksums verified, into the staging window                            Engine::staged_pass
+//   4. the call's own launches over the start positions the pass owns                                    the per-pass callback
+//   5. the last M - 1 bytes seen so far move in front of slot 0 for the next pass                         zra_search_carry_kernel
+//   6. the call's totals come to the host with the last synchronisation; the call reads its list, once
+// The staging window (Engine::stage_, reserved kScanMaxPattern bytes larger) is  [ carry area | slot 0 | slot 1 | ... ]: slot s lies at
+// s * frameSize behind the carry area. The arithmetic of a pass is zra_scan_plan.h's (host only, checked exhaustively on the CPU).
+//
+// Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
+//  (contiguity) the frames of a pass are consecutive and all but the archive's last regenerate frameSize bytes (anything else is a
+//      failing frame and ends the call), so the slots hold the content [passBase, passEnd) as one run, passEnd = min(U, (last frame of
+//      the pass + 1) * frameSize). The scan's bounds come from that arithmetic alone: what lies behind a short last frame, and in slots a
+//      smaller last pass does not fill, is plaintext of earlier passes and is never compared.
+//  (carry) after pass k the carry area holds, right-aligned against slot 0, the last min(M - 1, bytes decoded so far) bytes of the
+//      content decoded so far, M the longest pattern. A pass can be shorter than M - 1 bytes, so source and destination of the move
+//      overlap: one workgroup reads all of its bytes, synchronises, then writes.
+//  (ownership) a start position p belongs to the pass that holds content byte min(p + M - 1, hi - 1): one rule for all patterns,
+//      monotone in p, so every position of [lo, hi) has one owner and a list ascends across passes whatever the pattern lengths are.
+//      A pass that is not the range's last owns only p with p + M - 1 < passEnd < hi: every byte any pattern needs is there; its
+//      starts begin up to M - 1 bytes inside the carry. The last pass owns every remaining start up to hi - 1 - trim: trim = 0 for a
+//      call that tests pattern i only where p + m_i <= hi, trim = M - 1 for the single search, which tests only p + M <= hi.
+//  (c) the launches of a call are chained by a state that ping-pongs between two words: the k-th pass whose callback runs reads word
+//      k & 1 and writes word (k + 1) & 1. A list position is a prefix count, never the result of an atomic, and no workgroup waits for
+//      another one. The driver returns the number of callbacks that ran: the parity of the final word.
+//  (d) nothing goes to the caller's arrays before the last pass is done: a call that fails midway writes nothing.
+#pragma once
+#include "zra_host.h"
+
+namespace zra_eng {
+
+struct ScanImpl {
+  // the four calls behind Engine's entry points, each in its own file
+  static Status search(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, size_t m, uint64_t offset, uint64_t size, size_t stagingBytes,
+                       uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
+  static Status msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
+                        size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
+  static Status grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
+                     uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
+  static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
+                        uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
+                        uint64_t* dataSize);
+
+  // What a call of the family leaves behind, decided here for all four. `which`: kScanSearch .. kScanExtract; out0 / out1: the call's
+  // output words (either may be nullptr). The counters, the milliseconds and the words are zero before `run`; on any failure the
+  // counters and the milliseconds are zero again, and so are the words unless the status is OutputTooSmall (the extract's rule 7,
+  // whose two words say what the call needs). A success keeps what `run` wrote, the early return with only `frames` set included.
+  template <class Run>
+  static Status call(Engine& E, int which, uint64_t* out0, uint64_t* out1, Run&& run) {
+    auto clear = [&](bool words) {
+      for (auto& v : E.scanStats_[which]) v = 0;
+      E.scanMs_[which] = 0;
+      if (words && out0) *out0 = 0;
+      if (words && out1) *out1 = 0;
+    };
+    clear(true);
+    const Status st = run();
+    if (st.zra) clear(st.zra != kOutputTooSmall);
+    return st;
+  }
+
+  static uint8_t* window(Engine& E) { return E.stage_.as<uint8_t>() + kScanMaxPattern; }   // slot 0; the carry area lies in front of it
+
+  // The passes of plan P over the archive `arc`. tableBytes / listBytes size the scratch pair Engine::scan_, whose `tables` begins
+  // with the headBytes bytes at `head`: uploaded before the first launch (then the stream is synchronised), and its bytes [backOff,
+  // backOff + backBytes), the words the call's launches add up, are copied back into `head` behind the last pass, in front of the
+  // final synchronisation. perPass(const ScanPass&) launches the call's own kernels on the engine's stream, for every pass, or,
+  // ownedOnly, for the passes that own a start position; *ran counts its invocations, (c). *ms gains the HIP-event time from in
+  // front of a pass's callback to behind its carry move. Returns synchronised; a frame that does not decode ends the call with the
+  // lowest failing frame's code of the first failing pass.
+  template <class PerPass>
+  static Status passes(Engine& E, const ArchiveView& arc, const ScanPlan& P, double* ms, void* head, size_t headBytes, size_t backOff, size_t backBytes,
+                       size_t tableBytes, size_t listBytes, bool ownedOnly, PerPass&& perPass, uint32_t* ran) {
+    const size_t jobs = (size_t)P.nSlots + 1;
+    if (!E.stage_.reserve(kScanMaxPattern + (size_t)P.window + 64) || !E.scan_.tables.reserve(tableBytes) || !E.scan_.list.reserve(listBytes) ||
+        !E.frameOff_.reserve(jobs * 16) || !E.outOff_.reserve(jobs * 8) || !E.expect_.reserve(jobs * 4))
+      return zerr(64);
+    if (!E.call_events()) return zerr(1);
+    hipStream_t s = E.stream_;
+    HIPCHK_CLR(hipMemcpyAsync(E.scan_.tables.p, head, headBytes, hipMemcpyHostToDevice, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
+    uint8_t* const win = window(E);
+    uint32_t carry = 0;
+    bool timed = false;
+    // (behind a synchronisation of the stream)
+    auto take_time = [&]() { if (timed) *ms += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); timed = false; };
+    *ran = 0;
+    for (uint64_t p = 0; p < P.passes; p++) {
+      const ScanPass ps = scan_pass(P, p, carry);
+      search_launch_jobs(s, arc.table, P.fs, P.U, ps.first, ps.nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
+      unsigned long long firstError;
+      const Status st = E.staged_pass(arc, 0, ps.nj, win, &firstError);
+      take_time();
+      if (st.zra) return st;
+      if (firstError != ~0ull) return zerr(reported_code(firstError));
+      HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
+      if (!ownedOnly || ps.nPos) { perPass(ps); ++*ran; }
+      if (!ps.lastPass && P.M > 1) search_launch_carry(s, win, ps.L, ps.carry);
+      carry = ps.carry;
+      HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
+      timed = true;
+    }
+    HIPCHK_CLR(hipMemcpyAsync((uint8_t*)head + backOff, E.scan_.tables.as<uint8_t>() + backOff, backBytes, hipMemcpyDeviceToHost, s));
+    HIPCHK_CLR(hipStreamSynchronize(s));
+    HIPCHK_CLR(hipGetLastError());
+    take_time();
+    return ok();
+  }
+};
+
+}  // namespace zra_eng
