@@ -452,7 +452,8 @@ ZRA_EXPORT double ZraHipDebugGrepScanMs(ZraHipEngine* engine);
  *      when nothing is selected). Nothing is written to hRecords; the first dataCapacity bytes of dData are undefined.
  *  On every status other than Success the stats are zero and hRecords is untouched; apart from rule 7, *nRecords = *dataSize = 0.
  *  Cost: the grep's, plus one byte store per copied position (profiles/extract_scan.md).
- *  Not covered: record numbers and context lines, output without the delimiter bytes, and what ZraHipGrepArchive does not cover. */
+ *  Not covered: context lines, output without the delimiter bytes, and what ZraHipGrepArchive does not cover. Records BY NUMBER are
+ *  the record index's: ZraHipIndexRecords, ZraHipLocateRecords and ZraHipReadRecords below. */
 ZRA_EXPORT ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
     uint8_t delimiter, uint32_t mode,
@@ -694,6 +695,113 @@ ZRA_EXPORT void ZraHipGetDiffSignatureStats(ZraHipEngine* engine, uint64_t* out8
 /** Bring-up aid: HIP-event time of the last signature diff's own launches (span hash, job build, grain hash, count, scan, fill with
  *  the gather copy, tail jobs and tail copy), summed over its passes. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugDiffSignatureMs(ZraHipEngine* engine);
+
+/* ---- record index: read the records of a device-resident archive by their number ----
+ * Every other read path addresses content by byte offset. A caller who keeps line-oriented data in an archive (logs, JSONL samples)
+ * addresses it by RECORD: "samples 17, 4,000,000 and 12". The index below makes that a lookup: one 64-bit word per frame.
+ * CONTENT AND DELIMITERS. The content is [0, U). The delimiters t_0 < ... < t_(D-1) are the positions whose byte equals `delimiter`.
+ * RECORDS. Record k < D is [s_k, t_k), with s_0 = 0 and s_k = t_(k-1) + 1. Record D is [s_D, U) iff s_D < U. R is the number of
+ * records; U = 0 gives R = 0. These are the records ZraHipGrepArchive defines for the range [0, U).
+ * THE INDEX. F 64-bit words in device memory, F = frames, word f belongs to frame f: bits 0..62 hold the number of delimiter bytes in
+ * frame f's content, bit 63 is set iff the frame's last content byte is not the delimiter. A word depends on its own frame only, so
+ * an append leaves old words in place and adds new ones behind them; after ZraHipUpdateArchive the words of the touched frames are
+ * refreshed with a sub-range call, as ZraHipSignArchive refreshes the records of a signature. D = the sum of the counts,
+ * R = D + bit 63 of word F-1. What describes an index stays on the host (ZraHipRecordIndex, 40 bytes) and travels with the words. */
+typedef struct ZraHipRecordIndex { uint64_t contentSize; uint32_t frameSize; uint32_t delimiter; uint64_t frames; uint64_t delimiters; uint64_t records; } ZraHipRecordIndex;
+
+/** Writes the words of frames [firstFrame, firstFrame + frameCount) (frameCount UINT64_MAX: to the last frame; ZraHipVerifyArchive's
+ *  range) of the archive at dArchive (device memory) into their places in dIndex (device memory, indexCapacityWords words).
+ *  Synchronous; the archive is only read; stream ordering as the other compute calls (ZraHipWaitStream).
+ *  Statuses, checked in this order:
+ *   1. engine or info NULL; dArchive NULL with a size other than 0; dIndex NULL with indexCapacityWords != 0; delimiter > 255
+ *      -> {ZStdError, 42}.
+ *   2. [dIndex, dIndex + 8 * indexCapacityWords) overlaps the archive -> {ZStdError, 42}.
+ *   3. Header problems -> the statuses of ZraHipArchiveOpen; a frame size of 0 -> HeaderInvalid.
+ *   4. firstFrame > frames, or frameCount != UINT64_MAX and frameCount > frames - firstFrame -> OutOfBoundsAccess. The empty range is
+ *      Success and writes nothing.
+ *   5. indexCapacityWords < frames -> OutputBufferTooSmall; *info has its first four fields filled and its totals 0. This is the
+ *      sizing call: nothing is decoded and nothing is written.
+ *   6. Scratch that cannot be allocated -> {ZStdError, 64}: the staging window, 4 bytes per 8 KiB tile of it, the decoder's job
+ *      arrays and own scratch.
+ *   7. A frame that does not decode -> the status ZraHipDecompressRABatch gives under ZRA_HIP_OPT_RA_WHOLE_FRAMES for a query inside
+ *      it: the lowest failing frame of the first failing pass. The words of the range are then undefined.
+ *  No word outside the range, and none at or behind indexCapacityWords, is ever written, whatever the outcome.
+ *  Passes: max(1, min(65,536, stagingBytes / frameSize)) frames each (stagingBytes 0: 4 GiB). Frames are decoded whole, with their
+ *  checksums verified.
+ *  On Success info->delimiters and info->records are computed on the device from ALL F words as they lie in dIndex after the call
+ *  (the empty range included, when indexCapacityWords >= frames): THEY ARE MEANINGFUL ONCE EVERY FRAME HAS BEEN INDEXED, by this call
+ *  or by earlier ones into the same buffer. *info is zeroed on every status other than Success and OutputBufferTooSmall.
+ *  Not covered: delimiters of more than one byte, a variant on ZraHipArchive handles, shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipIndexRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t delimiter,
+    uint64_t firstFrame, uint64_t frameCount, size_t stagingBytes, uint64_t* dIndex, size_t indexCapacityWords, ZraHipRecordIndex* info);
+/** The last ZraHipIndexRecords on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, frames indexed, content bytes scanned, delimiters in the range, passes, 0, 0, 0}. */
+ZRA_EXPORT void ZraHipGetIndexRecordsStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugSignMs: HIP-event time of the last index call's own launches (tile counts, frame words, totals),
+ *  summed over its passes; its decodes are in ZraHipGetKernelStats. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugIndexRecordsMs(ZraHipEngine* engine);
+
+/** hRanges[i] = {s_r, t_r - s_r} for r = hRecordNumbers[i] (record D: {s_D, U - s_D}). Both are host arrays of nRecords entries; the
+ *  output is in request order; any order and duplicates are allowed. *info and the indexWords words at dIndex (device memory) are
+ *  what ZraHipIndexRecords left. Synchronous; archive and index are only read.
+ *  Statuses, checked in this order:
+ *   1. engine, info NULL; dArchive NULL with a size other than 0; dIndex NULL with indexWords != 0; hRecordNumbers or hRanges NULL
+ *      with nRecords != 0; an inconsistent *info (frameSize 0, frames != ceil(contentSize / frameSize), delimiter > 255, indexWords <
+ *      frames) -> {ZStdError, 42}. nRecords above 2^32 - 16 -> {ZStdError, 64}, as the random-access batch.
+ *   2. Header problems: rule 3 of ZraHipIndexRecords.
+ *   3. The archive's content size, frame size or frame count differs from *info -> {ZStdError, 40}.
+ *   4. A record number >= R, R recomputed from the words and not taken from info->records -> OutOfBoundsAccess.
+ *   5. Scratch that cannot be allocated -> {ZStdError, 64}: 20 bytes per frame of the archive and 40 bytes per request, the staging
+ *      window of the NEEDED frames with 4 bytes per 8 KiB tile, the decoder's job arrays and own scratch.
+ *   6. A needed frame that fails to decode: rule 7 of ZraHipIndexRecords.
+ *   7. A STALE WORD: a decoded frame whose delimiter count, or whose bit 63, differs from its index word -> {ZStdError, 20}. Locate
+ *      never returns a range out of a frame whose word is wrong.
+ *  Frames that are not decoded are not checked: INDEX IS NOT VERIFY. A wrong word of a frame that holds no asked boundary shifts the
+ *  numbering behind it and goes unnoticed.
+ *  Nothing is written to hRanges unless the call succeeds; the list comes to the host once, behind the last pass.
+ *  Work, all of it on the device: the exclusive prefix of the counts; per request up to two boundaries, delimiter r - 1 and delimiter r
+ *  (the start of record 0 and the end of an open record D need no lookup); a binary search in the prefix gives each boundary's
+ *  (frame, ordinal in the frame) and flags the frame; the flagged frames, ascending, are decoded whole in passes of
+ *  max(1, min(65,536, stagingBytes / frameSize)) NEEDED frames; per pass the delimiters of each 8 KiB tile are counted, the tiles of a
+ *  frame prefixed, total and last byte compared with the word, and every boundary whose frame is in the pass is resolved by reading one
+ *  tile. The cost follows the records asked for, not the archive: 100 records in 3 frames decode 3 frames. Every pass launches one wave
+ *  per boundary of the call (those of other passes leave at once). */
+ZRA_EXPORT ZraStatus ZraHipLocateRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const ZraHipRecordIndex* info,
+    const uint64_t* dIndex, size_t indexWords, const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes,
+    ZraHipContentRange* hRanges);
+/** The last ZraHipLocateRecords on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, records asked, boundaries looked up, frames decoded, content bytes regenerated, passes, 0, 0}. */
+ZRA_EXPORT void ZraHipGetLocateRecordsStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid: HIP-event time of the last locate's own launches (prefix, boundaries, jobs, tile counts, frame check, select),
+ *  summed over its passes. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugLocateRecordsMs(ZraHipEngine* engine);
+
+/** ZraHipLocateRecords (hRanges optional: NULL is allowed), then the records' bytes at dData (device memory, dataCapacity bytes) in
+ *  request order, each record followed by one `delimiter` byte: the packing of ZraHipExtractRecords. *dataSize = the sum of
+ *  (n_i + 1); record i starts at the sum of (n_j + 1) over the requests before it.
+ *  Statuses: those of ZraHipLocateRecords in their order, with
+ *   - dataSize NULL, dData NULL with dataCapacity != 0 -> {ZStdError, 42} (rule 1);
+ *   - directly behind rule 1: [dData, dData + dataCapacity) overlaps the archive or the index -> {ZStdError, 42};
+ *   - behind rule 7: *dataSize > dataCapacity -> OutputBufferTooSmall with *dataSize set. The sizing call (capacity 0) costs the
+ *     locate sweep only; nothing is written to hRanges or dData;
+ *   - then the statuses of ZraHipDecompressRABatch for the read of the located ranges.
+ *  On every status other than Success and OutputBufferTooSmall *dataSize = 0; hRanges is written on Success only. No byte in front
+ *  of dData or at or behind dData + dataCapacity is ever written.
+ *  BUILT AS A COMPOSITION IN THIS VERSION: the locate sweep, then one batched read of the located ranges (record k < D as
+ *  [s_k, t_k + 1), so its delimiter comes from the content; only an open last record gets its delimiter byte stored separately).
+ *  THE KNOWN COST: a frame that holds a boundary is decoded by both sweeps. The read sweep decodes up to the last byte a record
+ *  needs, whatever ZRA_HIP_OPT_RA_WHOLE_FRAMES says (the boundary frames were decoded whole, checksums verified, by the locate sweep).
+ *  Fusing the two sweeps when all needed frames fit one window is not done. */
+ZRA_EXPORT ZraStatus ZraHipReadRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const ZraHipRecordIndex* info,
+    const uint64_t* dIndex, size_t indexWords, const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes,
+    ZraHipContentRange* hRanges, void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** The last ZraHipReadRecords on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
+ *  out8 = {frames in the archive, records, packed bytes (= *dataSize), frames decoded by the locate sweep, decode jobs of the read
+ *  sweep, locate passes, 0, 0}. None of the three record calls touches another one's stats. */
+ZRA_EXPORT void ZraHipGetReadRecordsStats(ZraHipEngine* engine, uint64_t* out8);
+/** Bring-up aid: HIP-event time of the last successful read's locate-sweep launches, summed over its passes; its read sweep is in
+ *  ZraHipGetKernelStats. engine NULL: 0. */
+ZRA_EXPORT double ZraHipDebugReadRecordsMs(ZraHipEngine* engine);
 
 /* ---- sharded compression (one process per GPU; frames [firstFrame, firstFrame+nFrames) of a larger input) ---- */
 /** Compresses nFrames frames of frameSize bytes (last may be shorter: inSize bytes total) from dIn into a packed body at dBody

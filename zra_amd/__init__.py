@@ -70,6 +70,14 @@ class ZraHipSignature(ctypes.Structure):
 
 Signature = collections.namedtuple("Signature", "content_size frame_size grain seed frames words")
 
+
+class ZraHipRecordIndex(ctypes.Structure):
+    _fields_ = [("contentSize", ctypes.c_uint64), ("frameSize", ctypes.c_uint32), ("delimiter", ctypes.c_uint32), ("frames", ctypes.c_uint64),
+                ("delimiters", ctypes.c_uint64), ("records", ctypes.c_uint64)]
+
+
+RecordIndex = collections.namedtuple("RecordIndex", "content_size frame_size delimiter frames delimiters records")
+
 _lib = None
 
 
@@ -188,6 +196,16 @@ def load():
         "ZraHipDiffSignature": (S, [vp, ctypes.POINTER(ZraHipSignature), vp, sz, vp, sz, u32, sz, u64p, u64p, u64p, sz, u64p, vp, sz, u64p, u64p, u64p]),
         "ZraHipGetDiffSignatureStats": (None, [vp, u64p]),
         "ZraHipDebugDiffSignatureMs": (ctypes.c_double, [vp]),
+        # record index
+        "ZraHipIndexRecords": (S, [vp, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, vp, sz, ctypes.POINTER(ZraHipRecordIndex)]),
+        "ZraHipGetIndexRecordsStats": (None, [vp, u64p]),
+        "ZraHipDebugIndexRecordsMs": (ctypes.c_double, [vp]),
+        "ZraHipLocateRecords": (S, [vp, vp, sz, ctypes.POINTER(ZraHipRecordIndex), vp, sz, u64p, sz, sz, u64p]),
+        "ZraHipGetLocateRecordsStats": (None, [vp, u64p]),
+        "ZraHipDebugLocateRecordsMs": (ctypes.c_double, [vp]),
+        "ZraHipReadRecords": (S, [vp, vp, sz, ctypes.POINTER(ZraHipRecordIndex), vp, sz, u64p, sz, sz, u64p, vp, sz, u64p]),
+        "ZraHipGetReadRecordsStats": (None, [vp, u64p]),
+        "ZraHipDebugReadRecordsMs": (ctypes.c_double, [vp]),
         # distributed archive
         "ZraHipShardRange": (None, [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u64p, u64p]),
         "ZraHipOwnerOfFrame": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
@@ -241,7 +259,10 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
-                   "ZraHipDiffSignature", "ZraHipGetDiffSignatureStats", "ZraHipDebugDiffSignatureMs"]
+                   "ZraHipDiffSignature", "ZraHipGetDiffSignatureStats", "ZraHipDebugDiffSignatureMs",
+                   "ZraHipIndexRecords", "ZraHipGetIndexRecordsStats", "ZraHipDebugIndexRecordsMs",
+                   "ZraHipLocateRecords", "ZraHipGetLocateRecordsStats", "ZraHipDebugLocateRecordsMs",
+                   "ZraHipReadRecords", "ZraHipGetReadRecordsStats", "ZraHipDebugReadRecordsMs"]
 
 
 def _chk(st, what=""):
@@ -679,6 +700,88 @@ class Engine:
         """bring-up: HIP-event time of the last diff_signature()'s own launches, summed over its passes."""
         return self.L.ZraHipDebugDiffSignatureMs(self.h)
 
+    def index_records(self, d_archive, size, d_index, index_cap_words, *, delimiter=0x0A, first_frame=0, frame_count=None, staging_bytes=0):
+        """ZraHipIndexRecords: the record-index words of frames [first_frame, first_frame + frame_count) (None: to the last frame) of
+        the archive at d_archive go into their places of the index at d_index (index_cap_words 64-bit words, device memory): per
+        frame its delimiter count, bit 63 set when its last byte is no delimiter. Returns the RecordIndex of the WHOLE archive
+        (content_size, frame_size, delimiter, frames, delimiters, records), the totals taken from all words as they lie at d_index:
+        meaningful once every frame has been indexed. OutputBufferTooSmall (index_cap_words < frames) carries the words needed in
+        ZraError.needed_words."""
+        info = ZraHipRecordIndex()
+        self._order()
+        st = self.L.ZraHipIndexRecords(self.h, d_archive or None, size, delimiter, first_frame, 0xFFFFFFFFFFFFFFFF if frame_count is None else frame_count,
+                                       staging_bytes, d_index or None, index_cap_words, ctypes.byref(info))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipIndexRecords")
+            e.needed_words = info.frames
+            raise e
+        return RecordIndex(info.contentSize, info.frameSize, info.delimiter, info.frames, info.delimiters, info.records)
+
+    def index_records_stats(self):
+        """Counters of the last index_records() on this engine (all zero unless it succeeded), keyed by INDEX_RECORDS_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetIndexRecordsStats(self.h, a)
+        return dict(zip(INDEX_RECORDS_STATS, (int(v) for v in a)))
+
+    def index_records_ms(self):
+        """bring-up: HIP-event time of the last index_records()'s own launches (tile counts, frame words, totals), summed over its passes."""
+        return self.L.ZraHipDebugIndexRecordsMs(self.h)
+
+    def locate_records(self, d_archive, size, index, d_index, index_words, numbers, *, staging_bytes=0):
+        """ZraHipLocateRecords: [(offset, size)] of the records `numbers` (any order, duplicates allowed) of the archive at d_archive,
+        in request order, by the RecordIndex `index` and its index_words words at d_index. Only the frames that hold a boundary
+        are decoded, and each is checked against its word: ZraError (1, 20) is a stale word, OutOfBoundsAccess a number >= records."""
+        import numpy as np
+        nums = np.ascontiguousarray(np.asarray(numbers, dtype=np.uint64))
+        n = int(nums.size)
+        out = np.zeros(2 * max(n, 1), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        info = ZraHipRecordIndex(*index)
+        self._order()
+        _chk(self.L.ZraHipLocateRecords(self.h, d_archive or None, size, ctypes.byref(info), d_index or None, index_words, p(nums) if n else None, n,
+                                        staging_bytes, p(out) if n else None), "ZraHipLocateRecords")
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)]
+
+    def locate_records_stats(self):
+        """Counters of the last locate_records() on this engine (all zero unless it succeeded), keyed by LOCATE_RECORDS_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetLocateRecordsStats(self.h, a)
+        return dict(zip(LOCATE_RECORDS_STATS, (int(v) for v in a)))
+
+    def locate_records_ms(self):
+        """bring-up: HIP-event time of the last locate_records()'s own launches, summed over its passes."""
+        return self.L.ZraHipDebugLocateRecordsMs(self.h)
+
+    def read_records(self, d_archive, size, index, d_index, index_words, numbers, d_data, data_cap, *, staging_bytes=0, ranges=True):
+        """ZraHipReadRecords: locate_records(), then the records' bytes packed at d_data (data_cap bytes, device memory) in request
+        order, each followed by one delimiter byte. Returns (data_size, [(offset, size)] or None without `ranges`).
+        OutputBufferTooSmall (data_cap too small) carries the bytes needed in ZraError.needed_data."""
+        import numpy as np
+        nums = np.ascontiguousarray(np.asarray(numbers, dtype=np.uint64))
+        n = int(nums.size)
+        out = np.zeros(2 * max(n, 1), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        info = ZraHipRecordIndex(*index)
+        ds = ctypes.c_uint64(0)
+        self._order()
+        st = self.L.ZraHipReadRecords(self.h, d_archive or None, size, ctypes.byref(info), d_index or None, index_words, p(nums) if n else None, n,
+                                      staging_bytes, p(out) if ranges and n else None, d_data or None, data_cap, ctypes.byref(ds))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipReadRecords")
+            e.needed_data = ds.value
+            raise e
+        return ds.value, ([(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)] if ranges else None)
+
+    def read_records_stats(self):
+        """Counters of the last read_records() on this engine (all zero unless it succeeded), keyed by READ_RECORDS_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetReadRecordsStats(self.h, a)
+        return dict(zip(READ_RECORDS_STATS, (int(v) for v in a)))
+
+    def read_records_ms(self):
+        """bring-up: HIP-event time of the last read_records()'s locate-sweep launches, summed over its passes."""
+        return self.L.ZraHipDebugReadRecordsMs(self.h)
+
 
 ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "uncompressed_size", "frame_size")
 
@@ -709,6 +812,9 @@ SIGN_MIN_GRAIN = 64                          # ZRA_HIP_SIGN_MIN_GRAIN
 SIGN_MAX_GRAIN = 8192                        # ZRA_HIP_SIGN_MAX_GRAIN
 SIGDIFF_DECODE_ALL = 1                       # ZRA_HIP_SIGDIFF_DECODE_ALL
 SIGN_STATS = ("frames", "signed", "grain_words", "content_bytes", "compressed_bytes", "passes")
+INDEX_RECORDS_STATS = ("frames", "indexed", "content_bytes", "delimiters", "passes")
+LOCATE_RECORDS_STATS = ("frames", "records", "boundaries", "decoded", "content_bytes", "passes")
+READ_RECORDS_STATS = ("frames", "records", "packed_bytes", "locate_decoded", "read_decoded", "locate_passes")
 SIGDIFF_STATS = DIFF_STATS                   # the diff's shape; equal_compressed: frames whose span hashes to A's frame word
 
 

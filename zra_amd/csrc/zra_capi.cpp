@@ -879,6 +879,46 @@ void ZraHipGetDiffSignatureStats(ZraHipEngine* engine, uint64_t* out8) {
   if (engine) engine->e->diff_signature_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugDiffSignatureMs(ZraHipEngine* engine) { return engine ? engine->e->diff_signature_ms() : 0.0; }
+ZraStatus ZraHipIndexRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t delimiter, uint64_t firstFrame, uint64_t frameCount,
+                             size_t stagingBytes, uint64_t* dIndex, size_t indexCapacityWords, ZraHipRecordIndex* info) {
+  static_assert(sizeof(ZraHipRecordIndex) == 40, "the index file's 40-byte head");
+  if (info) *info = ZraHipRecordIndex{0, 0, 0, 0, 0, 0};
+  if (!engine || !info) return mk(ZStdError, 42);
+  uint64_t w[6] = {0, 0, 0, 0, 0, 0};
+  const ZraStatus st = mk(engine->e->index_records((const uint8_t*)dArchive, archiveSize, delimiter, firstFrame, frameCount, stagingBytes, dIndex, indexCapacityWords, w));
+  *info = ZraHipRecordIndex{w[0], (uint32_t)w[1], (uint32_t)w[2], w[3], w[4], w[5]};
+  return st;
+}
+void ZraHipGetIndexRecordsStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->index_records_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugIndexRecordsMs(ZraHipEngine* engine) { return engine ? engine->e->index_records_ms() : 0.0; }
+ZraStatus ZraHipLocateRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const ZraHipRecordIndex* info, const uint64_t* dIndex, size_t indexWords,
+                              const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes, ZraHipContentRange* hRanges) {
+  if (!engine || !info) return mk(ZStdError, 42);
+  const uint64_t w[6] = {info->contentSize, info->frameSize, info->delimiter, info->frames, info->delimiters, info->records};
+  return mk(engine->e->locate_records((const uint8_t*)dArchive, archiveSize, w, dIndex, indexWords, hRecordNumbers, nRecords, stagingBytes, (uint64_t*)hRanges));
+}
+void ZraHipGetLocateRecordsStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->locate_records_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugLocateRecordsMs(ZraHipEngine* engine) { return engine ? engine->e->locate_records_ms() : 0.0; }
+ZraStatus ZraHipReadRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const ZraHipRecordIndex* info, const uint64_t* dIndex, size_t indexWords,
+                            const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes, ZraHipContentRange* hRanges, void* dData, size_t dataCapacity,
+                            uint64_t* dataSize) {
+  if (dataSize) *dataSize = 0;
+  if (!engine || !info) return mk(ZStdError, 42);
+  const uint64_t w[6] = {info->contentSize, info->frameSize, info->delimiter, info->frames, info->delimiters, info->records};
+  return mk(engine->e->read_records((const uint8_t*)dArchive, archiveSize, w, dIndex, indexWords, hRecordNumbers, nRecords, stagingBytes, (uint64_t*)hRanges,
+                                    (uint8_t*)dData, dataCapacity, dataSize));
+}
+void ZraHipGetReadRecordsStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->read_records_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugReadRecordsMs(ZraHipEngine* engine) { return engine ? engine->e->read_records_ms() : 0.0; }
 ZraStatus ZraHipCompressFrames(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dBody, uint64_t* dSizes, size_t* bodySize, int8_t level,
                                uint32_t frameSize, bool checksum) {
   return mk(engine->e->compress_frames((const uint8_t*)dIn, inSize, (uint8_t*)dBody, dSizes, bodySize, level, frameSize, checksum));

@@ -131,9 +131,13 @@ class Engine {
   Status archive_view(const uint8_t* dArc, size_t arcSize, ArchiveView* a) {
     HeaderInfo h; const Status st = ra_header(dArc, arcSize, &h); if (!st.zra) *a = ArchiveView::over(h, dArc, arcSize); return st;
   }
-  Status ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces);
+  // endInclusive (internal, the record read alone): a query may end AT the content's end; every other caller keeps the reference's bound
+  Status ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces,
+                         bool endInclusive = false);
   Status ra_plan_fill(uint32_t* plan, size_t nq, const ArchiveView& a, uint32_t passSlots, bool fullFrames, const uint32_t* victim, uint32_t totals[2]);
-  Status ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
+  // *jobsOut (optional): the decode jobs the batch ran
+  Status ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool endInclusive = false,
+                       uint32_t* jobsOut = nullptr);
   // tuples [q0, q1) of pinQ_ (pinned_tuples) -> qmeta_, queued on the stream; the caller writes and sends them kTupleChunk at a time
   static constexpr size_t kTupleChunk = 1u << 17;
   Status upload_tuples(size_t q0, size_t q1) {
@@ -277,6 +281,33 @@ class Engine {
   void diff_signature_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = hstats_[i]; }
   double diff_signature_ms() const { return sigDiffMs_; }
 
+  // ---- record index (zra_records.hip): one 64-bit word per frame, bits 0..62 the delimiter bytes of the frame's content, bit 63 set iff
+  // its last content byte is not the delimiter. index_records writes the words of frames [first, first + count) into their places in
+  // dIndex; info6 = ZraHipRecordIndex's six words {content size, frame size, delimiter, frames, delimiters, records}, the totals from
+  // all F words as they lie in dIndex. Statuses and their order: zra_hip.h, ZraHipIndexRecords.
+  Status index_records(const uint8_t* dArc, size_t arcSize, uint32_t delimiter, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex,
+                       size_t indexCapWords, uint64_t info6[6]);
+  // the last index_records: {frames, frames indexed, content bytes scanned, delimiters in the range, passes, 0, 0, 0}; all zero unless it succeeded
+  void index_records_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = istats_[i]; }
+  // bring-up: HIP-event time of the last index's own launches (count, frame words, totals), summed over its passes
+  double index_records_ms() const { return indexMs_; }
+  // hRanges[i] = {start, size} of record hNumbers[i], in request order; only the frames that hold a boundary are decoded, and each is
+  // checked against its word. Statuses and their order: zra_hip.h, ZraHipLocateRecords.
+  Status locate_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
+                        size_t stagingBytes, uint64_t* hRanges);
+  // the last locate_records: {frames, records asked, boundaries looked up, frames decoded, content bytes regenerated, passes, 0, 0}
+  void locate_records_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = lstats_[i]; }
+  // bring-up: HIP-event time of the last locate's own launches (prefix, bounds, jobs, count, frame check, select), summed over its passes
+  double locate_records_ms() const { return locateMs_; }
+  // locate_records, then the records' bytes packed at dData in request order, each followed by one delimiter byte (the packing of
+  // extract_records); hRanges is optional. Statuses and their order: zra_hip.h, ZraHipReadRecords.
+  Status read_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
+                      size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+  // the last read_records: {frames, records, packed bytes, frames decoded by the locate sweep, decode jobs of the read sweep, locate passes, 0, 0}
+  void read_records_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = rstats_[i]; }
+  // bring-up: HIP-event time of the last read's locate-sweep launches, summed over its passes (its read sweep: kernel_stats)
+  double read_records_ms() const { return readMs_; }
+
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
@@ -387,6 +418,11 @@ class Engine {
   struct SignScratch { DevBuf flags, dirty, tables, list; } sig_;
   uint64_t gstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double signMs_ = 0, sigDiffMs_ = 0;
+  // record index (zra_records.hip): the header words + frame counts, prefix, slots and tile prefixes of a call; the record numbers,
+  // boundaries and positions of a locate. The three calls' counters stay apart
+  struct RecScratch { DevBuf tables, ranges; } rec_;
+  uint64_t istats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double indexMs_ = 0, locateMs_ = 0, readMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
@@ -394,6 +430,7 @@ class Engine {
   friend struct CompareImpl;      // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
   friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
   friend struct SignImpl;          // the signature calls drive the decoder's job arrays of one archive (zra_sign.hip)
+  friend struct RecordsImpl;       // the record index drives the decoder's job arrays of one archive (zra_records.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

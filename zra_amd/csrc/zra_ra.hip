@@ -150,7 +150,8 @@ uint64_t* Engine::pinned_tuples(size_t nTuples) {
 // overflow-safe), the slices (one per frame a query touches) and the (offset, size, destination, first slice) tuples the device
 // kernels read — written straight into page-locked memory, so that their copy (into qmeta_) runs at bus speed beside the launches that
 // follow. *maxPieces = the slices; 0 when there is nothing to decode (the copies may still be in flight: the caller synchronises).
-Status Engine::ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces) {
+Status Engine::ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint64_t* maxPieces,
+                               bool endInclusive) {
   const uint32_t nFrames = a.frames;
   const uint64_t fs = a.fs, U = a.U;
   *maxPieces = 0;
@@ -158,10 +159,11 @@ Status Engine::ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const
   uint64_t* const hq = pinned_tuples(nq);
   if (!hq) return zerr(64);
   uint64_t pieces = 0;
+  const uint64_t slack = endInclusive ? 1 : 0;                  // (the record read: offset + size == U is inside)
   const bool pow2 = fs && !(fs & (fs - 1));
   const unsigned fsLog = pow2 ? (unsigned)__builtin_ctzll(fs) : 0u;
   if (fs == 0 || nFrames == 0) {
-    for (size_t q = 0; q < nq; q++) if (hSize[q] >= U || hOff[q] >= U - hSize[q]) return {kOutOfBounds, 0};
+    for (size_t q = 0; q < nq; q++) if (hSize[q] >= U + slack || hOff[q] >= U - hSize[q] + slack) return {kOutOfBounds, 0};
     return ok();
   }
   if (!qmeta_.reserve(4 * nq * 8 + 64)) return zerr(64);
@@ -169,7 +171,7 @@ Status Engine::ra_walk_queries(const ArchiveView& a, const uint64_t* hOff, const
     const size_t q1 = std::min(nq, q0 + kTupleChunk);
     for (size_t q = q0; q < q1; q++) {
       const uint64_t o = hOff[q], z = hSize[q];
-      if (z >= U || o >= U - z) { (void)hipStreamSynchronize(stream_); return {kOutOfBounds, 0}; }
+      if (z >= U + slack || o >= U - z + slack) { (void)hipStreamSynchronize(stream_); return {kOutOfBounds, 0}; }
       hq[4 * q] = o; hq[4 * q + 1] = z; hq[4 * q + 2] = hOutOff[q]; hq[4 * q + 3] = pieces;
       if (z) pieces += pow2 ? ((o + z - 1) >> fsLog) - (o >> fsLog) + 1 : (o + z - 1) / fs - o / fs + 1;
     }
@@ -208,7 +210,9 @@ Status Engine::decompress_ra_batch_shard(const uint8_t* dArc, size_t arcSize, co
 }
 
 // the batch behind a header that has been read and checked (ra_header): the archive handle without slots comes here directly
-Status Engine::ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+Status Engine::ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool endInclusive,
+                             uint32_t* jobsOut) {
+  if (jobsOut) *jobsOut = 0;
   RaTrace trace{"  ra", 14};
   HIPCHK(hipSetDevice(device_));
   reset_decode_stats();
@@ -217,7 +221,7 @@ Status Engine::ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t
   const uint64_t fs = a.fs, U = a.U;
   if (nq == 0) return ok();
   uint64_t maxPieces = 0;
-  { Status st = ra_walk_queries(a, hOff, hSize, hOutOff, nq, &maxPieces); if (st.zra) return st; }
+  { Status st = ra_walk_queries(a, hOff, hSize, hOutOff, nq, &maxPieces, endInclusive); if (st.zra) return st; }
   if (fs == 0 || nFrames == 0) return ok();
   if (maxPieces == 0) { HIPCHK(hipStreamSynchronize(stream_)); return ok(); }
   trace.mark("queries");
@@ -245,6 +249,7 @@ Status Engine::ra_batch_body(const ArchiveView& a, uint8_t* dOut, const uint64_t
     touched = totals[0];
     trace.mark("plan");
   }
+  if (jobsOut) *jobsOut = touched;
   if (!touched) return ok();
   // decode the touched frames, a scratch window of passSlots frames at a time (only frames that are decoded in full — or larger
   // than what the decoder needs as its match window — actually write there); slices leave for dOut as each frame finishes

@@ -437,6 +437,53 @@ int diff_signature(const char* pathSig, const char* pathB) {
   std::printf("%llu writes, %llu bytes written, %llu bytes of patch data\n", (unsigned long long)n, (unsigned long long)at, (unsigned long long)bytes);
   return n || app ? 1 : 0;
 }
+
+// modes ix and rr: index the whole archive on the device (a sizing call, then the call), then, for rr, read records
+// [first, first + count) (clipped to the records there are) and write their text, each with its delimiter, to stdout. Nothing goes
+// to stdout when a call fails.
+int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first, uint64_t count) {
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr; void* dIndex = nullptr; void* dData = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  ZraHipRecordIndex info;
+  st = ZraHipIndexRecords(eng, dArc, arc.size(), delimiter, 0, UINT64_MAX, 0, nullptr, 0, &info);
+  if (st.zra == OutputBufferTooSmall) {
+    if (hipMalloc(&dIndex, info.frames * 8) != hipSuccess) { dIndex = nullptr; st.zra = ZStdError; st.zstd = 64; }
+    else st = ZraHipIndexRecords(eng, dArc, arc.size(), delimiter, 0, UINT64_MAX, 0, (uint64_t*)dIndex, info.frames, &info);
+  }
+  std::string text;
+  uint64_t got = 0;
+  if (st.zra == Success && read && first < info.records) {
+    got = std::min<uint64_t>(count, info.records - first);
+    std::vector<uint64_t> numbers(got);
+    for (uint64_t i = 0; i < got; i++) numbers[i] = first + i;
+    uint64_t bytes = 0;
+    st = ZraHipReadRecords(eng, dArc, arc.size(), &info, (const uint64_t*)dIndex, info.frames, numbers.data(), numbers.size(), 0, nullptr, nullptr, 0, &bytes);
+    if (st.zra == OutputBufferTooSmall) {
+      text.resize(bytes);
+      if (hipMalloc(&dData, bytes) != hipSuccess) { dData = nullptr; st.zra = ZStdError; st.zstd = 64; }
+      else {
+        st = ZraHipReadRecords(eng, dArc, arc.size(), &info, (const uint64_t*)dIndex, info.frames, numbers.data(), numbers.size(), 0, nullptr, dData, bytes, &bytes);
+        if (st.zra == Success && hipMemcpy(&text[0], dData, bytes, hipMemcpyDeviceToHost) != hipSuccess) { st.zra = ZStdError; st.zstd = 1; }
+      }
+    }
+  }
+  if (dArc) (void)hipFree(dArc);
+  if (dIndex) (void)hipFree(dIndex);
+  if (dData) (void)hipFree(dData);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot %s: %s\n", path, read ? "read records" : "index", ZraGetErrorString(st)); return 2; }
+  if (!read) {
+    std::printf("%llu frames, %llu delimiters, %llu records\n", (unsigned long long)info.frames, (unsigned long long)info.delimiters, (unsigned long long)info.records);
+    return 0;
+  }
+  if (!got) return 1;
+  if (std::fwrite(text.data(), 1, text.size(), stdout) != text.size() || std::fflush(stdout) != 0) { std::fprintf(stderr, "cannot write to stdout\n"); return 2; }
+  return 0;
+}
 }  // namespace
 
 // argv of the reference tool, position by position (zratool.cpp:98-125,213-221):
@@ -454,6 +501,8 @@ int diff_signature(const char* pathSig, const char* pathB) {
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
 //       sigdiff {signature file of A} {file B}
+//       ix {file} {-d hex byte = 0a}
+//       rr {file} {-d hex byte = 0a} {first record} {count}
 int main(int argc, char** argv) {
   if (argc < 3) {
     std::printf("%s {mode} {file} ...\n"
@@ -470,7 +519,9 @@ int main(int argc, char** argv) {
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
-                "sigdiff {signature file of A} {file B} - diff with archive A given by its signature (output and exit status as diff)\n",
+                "sigdiff {signature file of A} {file B} - diff with archive A given by its signature (output and exit status as diff)\n"
+                "ix {file} {-d hex byte = 0a} - Index the records (lines) of an archive on the device: frames, delimiters and records\n"
+                "rr {file} {-d hex byte = 0a} {first record} {count} - Read records by their number through the record index: their text, each with its delimiter, to stdout (exit status 0 some, 1 none, 2 trouble)\n",
                 argv[0]);
     return 0;
   }
@@ -532,6 +583,26 @@ int main(int argc, char** argv) {
   if (mode == "sigdiff") {
     if (argc != 4) { std::fprintf(stderr, "sigdiff {signature file of A} {file B}\n"); return 2; }
     return diff_signature(argv[2], argv[3]);
+  }
+  if (mode == "ix" || mode == "rr") {
+    const bool read = mode == "rr";
+    unsigned long delimiter = 0x0A;
+    int i = 3;
+    if (i < argc && std::string(argv[i]) == "-d") {
+      char* end = nullptr;
+      if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
+      if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
+      i++;
+    }
+    unsigned long long first = 0, count = 0;
+    bool good = argc - i == (read ? 2 : 0);
+    if (good && read) {
+      char* e1 = nullptr; char* e2 = nullptr;
+      first = std::strtoull(argv[i], &e1, 0); count = std::strtoull(argv[i + 1], &e2, 0);
+      good = *argv[i] && !*e1 && *argv[i + 1] && !*e2;
+    }
+    if (!good) { std::fprintf(stderr, read ? "rr {file} {-d hex byte = 0a} {first record} {count}\n" : "ix {file} {-d hex byte = 0a}\n"); return 2; }
+    return index_records(argv[2], (uint8_t)delimiter, read, first, count);
   }
   const bool comp = mode == "c" || mode == "imc" || mode == "b";
   const zra::i8 level = comp && argc > 3 ? (zra::i8)std::atoi(argv[3]) : 0;
