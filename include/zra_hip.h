@@ -147,6 +147,79 @@ ZRA_EXPORT ZraStatus ZraHipArchiveUpdate(ZraHipArchive* archive,
  *  frame replaced whole is refreshed, not staged. archive NULL: all zero; out8 NULL: no-op. */
 ZRA_EXPORT void ZraHipArchiveGetUpdateStats(const ZraHipArchive* archive, uint64_t* out8);
 
+/* ---- the range scans through the handle: resident frames are staged from the cache, not decoded ----
+ * ZraHipSearchArchive, ZraHipSearchArchiveMulti, ZraHipGrepArchive and ZraHipExtractRecords (below) decode every frame of their range
+ * on every call. A server that keeps its hot frames resident and greps them again and again holds that plaintext already: through the
+ * handle a pass copies the resident frames of its range out of the arena, at HBM bandwidth, and decodes only the others. */
+struct ZraHipPatternMatch;   /* defined with ZraHipSearchArchiveMulti */
+struct ZraHipContentRange;   /* defined with ZraHipGrepArchive */
+
+/** ZraHipSearchArchive on the archive the handle is bound to: its arguments without engine, dArchive and archiveSize. Synchronous; stream
+ *  ordering as the other compute calls (ZraHipWaitStream). What is said here holds for the three calls behind it as well, each against
+ *  its engine-level counterpart.
+ *  - Result: hMatches and *nMatches are byte for byte what ZraHipSearchArchive(the handle's engine, the bytes the handle is bound to, the
+ *    same arguments) gives, on every status: nothing reaches the host before the last pass, the early returns (the empty range, a
+ *    range shorter than the shortest pattern) decode nothing, and the extract's OutputBufferTooSmall sizes as it does there.
+ *  - Statuses: the plain call's, in its order, with three differences. archive NULL -> {ZStdError, 42} in front of everything. Header
+ *    problems cannot occur beyond those a handle can be opened with (a frame size of 0: HeaderInvalid): the handle holds a checked
+ *    header, which is not read from the device again; that is the one saving a handle with 0 slots still has. And the extract's rule 2
+ *    additionally refuses [dData, dData + dataCapacity) overlapping the handle's arena with {ZStdError, 42}, the arena check of
+ *    ZraHipArchiveUpdate.
+ *  - Where the plaintext of a pass comes from (at least 1 slot): a frame of the pass that is resident is copied from its arena slot
+ *    into its slot of the staging window, min(frameSize, U - f * frameSize) bytes, and is not decoded (this launders no damage: a frame
+ *    is resident only after a whole decode with status 0, checksum verified, exact size); one that is not resident is decoded whole,
+ *    its checksum verified, exactly as by the plain call. The window a pass scans holds the same bytes either way, and the scan
+ *    kernels are the plain call's.
+ *  - A scan is not a read: it inserts, evicts and refreshes nothing, sets no reference bit and moves no hand, and never writes the
+ *    arena. reads, hits, misses, evictions and resident of ZraHipArchiveGetStats do not change, on success or on failure: a scan of a
+ *    whole archive cannot flush the hot set. A caller who wants frames resident reads them (ZraHipArchiveRead).
+ *  - A frame that fails is by construction not resident; the status is the plain call's rule 5: the lowest failing frame of the first
+ *    failing pass. On failure the handle and its cache are exactly as before the call.
+ *  - 0 slots: the plain call minus the header read; the same kernels are launched.
+ *  - Stats: the call is a ZraHipSearchArchive on the handle's engine: it overwrites ZraHipGetSearchStats and ZraHipDebugSearchScanMs
+ *    (the other three: their own kind's) under their rules, zero on every outcome other than Success. Through a handle word [1]
+ *    counts decode jobs ("frames decoded") and word [2] the bytes the decoder regenerated: both leave out the frames staged from the
+ *    arena; every other word is the plain call's. ZraHipGetKernelStats reports 0 decode launches for a scan whose frames were all
+ *    resident.
+ *  - Scratch: the plain call's rule 4, plus, with at least 1 slot, 16 bytes per frame of a pass for the copy entries and the pass's two
+ *    counts, which come to the host through a page-locked word of the handle, one small read-back per pass.
+ *  Not covered: populating or refreshing the cache from a scan, scan kernels that read the arena in place, and handle variants of
+ *  ZraHipVerifyArchive, ZraHipCompareArchives, ZraHipDiffArchives, ZraHipSignArchive and the record index (the follow-up: the same
+ *  view of the cache will serve them), shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipArchiveSearch(ZraHipArchive* archive,
+    const void* hPattern, size_t patternSize,
+    uint64_t offset, uint64_t size,
+    size_t stagingBytes,
+    uint64_t* hMatches, size_t matchCapacity, uint64_t* nMatches);
+/** ZraHipSearchArchiveMulti through the handle: see ZraHipArchiveSearch. Overwrites ZraHipGetSearchMultiStats. */
+ZRA_EXPORT ZraStatus ZraHipArchiveSearchMulti(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint64_t offset, uint64_t size,
+    size_t stagingBytes,
+    struct ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern);
+/** ZraHipGrepArchive through the handle: see ZraHipArchiveSearch. Overwrites ZraHipGetGrepStats. */
+ZRA_EXPORT ZraStatus ZraHipArchiveGrep(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    struct ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+/** ZraHipExtractRecords through the handle: see ZraHipArchiveSearch. dData must overlap neither the archive nor the handle's arena
+ *  ({ZStdError, 42}, joined to rule 2). Overwrites ZraHipGetExtractStats. */
+ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecords(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    struct ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** out8 = {scans accepted, frames staged from the cache in the last accepted scan, frames decoded in it, passes of it, frames staged
+ *  (cumulative), frames decoded (cumulative), 0, 0}, over the four calls above. A scan is accepted when it returns Success; the early
+ *  returns that decode nothing count, with zeros for the three last-scan words. A scan that is not accepted changes none of the words.
+ *  archive NULL: all zero; out8 NULL: no-op. */
+ZRA_EXPORT void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugUpdateStageMs: HIP-event time of the last accepted scan's job-split and stage-from-cache launches,
+ *  summed over its passes; 0 when none ran. archive NULL: 0. */
+ZRA_EXPORT double ZraHipDebugArchiveScanStageMs(const ZraHipArchive* archive);
+
 /* ---- update: a new archive from an old one, on the device ----
  * The reference's Compressor only ever starts from nothing. Frames are independent zstd frames tied together by the seek table alone,
  * so a change re-encodes the frames it lands in and carries every other frame over byte for byte. */
@@ -298,7 +371,8 @@ ZRA_EXPORT void ZraHipGetVerifyStats(ZraHipEngine* engine, uint64_t* out8);
  *  the pattern's costs one word compare. The worst case is a pattern that matches everywhere (zeros in zeros): every position then runs
  *  the full m-byte compare, and every listed match is compared twice. That is accepted; there is no machinery for it.
  *  Several patterns per call: ZraHipSearchArchiveMulti, below.
- *  Not covered: a handle variant that scans resident frames from the cache of a ZraHipArchive, regular
+ *  Resident frames of a ZraHipArchive are staged from its cache, not decoded, by the handle's call: ZraHipArchiveSearch, above.
+ *  Not covered: regular
  *  expressions, the shards of a distributed archive (ZraHipShard), the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipSearchArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPattern, size_t patternSize,
@@ -350,8 +424,8 @@ typedef struct ZraHipPatternMatch { uint64_t offset; uint32_t pattern; uint32_t 
  *  first two bytes (a 1-byte pattern sets all 256 bits of its byte); only a position whose bit is set, a "filter survivor", is compared
  *  against the patterns that begin with its first byte. The worst case is patterns that match everywhere (64 patterns of zeros in
  *  zeros): every position then runs 64 full compares, and every listed match is compared twice. That is accepted.
- *  Not covered: regular expressions and case folding, patterns in device memory, a handle variant on resident frames, shards, the
- *  host-pointer API. */
+ *  Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveSearchMulti, above.
+ *  Not covered: regular expressions and case folding, patterns in device memory, shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipSearchArchiveMulti(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
     uint64_t offset, uint64_t size,
@@ -408,8 +482,8 @@ typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipCont
  *  Cost: one decode of the range and the multi search's filter; on top of it one byte compare per position and a segmented reduction
  *  over the positions between delimiters (profiles/grep_scan.md).
  *  Not covered: the BYTES of the records (ZraHipExtractRecords below keeps them from the same pass; with this call alone, fetch them
- *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), regular expressions and case folding, multi-byte delimiters, a handle variant, shards, the
- *  host-pointer API. */
+ *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), regular expressions and case folding, multi-byte delimiters, shards, the
+ *  host-pointer API. Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveGrep, above. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
     uint8_t delimiter, uint32_t mode,
@@ -452,6 +526,7 @@ ZRA_EXPORT double ZraHipDebugGrepScanMs(ZraHipEngine* engine);
  *      when nothing is selected). Nothing is written to hRecords; the first dataCapacity bytes of dData are undefined.
  *  On every status other than Success the stats are zero and hRecords is untouched; apart from rule 7, *nRecords = *dataSize = 0.
  *  Cost: the grep's, plus one byte store per copied position (profiles/extract_scan.md).
+ *  Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveExtractRecords, above.
  *  Not covered: context lines, output without the delimiter bytes, and what ZraHipGrepArchive does not cover. Records BY NUMBER are
  *  the record index's: ZraHipIndexRecords, ZraHipLocateRecords and ZraHipReadRecords below. */
 ZRA_EXPORT ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,

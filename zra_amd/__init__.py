@@ -156,6 +156,13 @@ def load():
         "ZraHipArchiveGetStats": (None, [vp, u64p]),
         "ZraHipArchiveUpdate": (S, [vp, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
         "ZraHipArchiveGetUpdateStats": (None, [vp, u64p]),
+        # the range scans through the handle: the engine calls' arguments without (engine, dArchive, archiveSize)
+        "ZraHipArchiveSearch": (S, [vp, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipArchiveSearchMulti": (S, [vp, vp, ctypes.POINTER(u32), sz, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipPatternMatch), sz, u64p, u64p]),
+        "ZraHipArchiveGrep": (S, [vp, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipArchiveExtractRecords": (S, [vp, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz, u64p]),
+        "ZraHipArchiveGetScanStats": (None, [vp, u64p]),
+        "ZraHipDebugArchiveScanStageMs": (ctypes.c_double, [vp]),
         # update
         "ZraHipUpdateArchive": (S, [vp, vp, sz, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
         "ZraHipGetUpdateStats": (None, [vp, u64p]),
@@ -251,6 +258,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCommGatherArchive", "ZraHipCommUseOwnStream", "ZraHipCommGatherArchiveBegin", "ZraHipCommGatherArchiveEnd", "ZraHipCommServe",
                    "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
                    "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
+                   "ZraHipArchiveSearch", "ZraHipArchiveSearchMulti", "ZraHipArchiveGrep", "ZraHipArchiveExtractRecords", "ZraHipArchiveGetScanStats",
+                   "ZraHipDebugArchiveScanStageMs",
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
@@ -787,6 +796,8 @@ ARCHIVE_STATS = ("slots", "resident", "reads", "hits", "misses", "evictions", "u
 
 ARCHIVE_UPDATE_STATS = ("updates", "frames", "archive_bytes", "staged", "refreshed", "staged_total", "refreshed_total")
 
+ARCHIVE_SCAN_STATS = ("scans", "staged", "decoded", "passes", "staged_total", "decoded_total")
+
 
 UPDATE_STATS = ("frames", "touched", "decoded", "compressed", "carried_bytes", "encoded_bytes", "content_bytes", "passes")
 
@@ -878,6 +889,72 @@ class Archive:
         a = (ctypes.c_uint64 * 8)()
         self.L.ZraHipArchiveGetUpdateStats(self.h, a)
         return dict(zip(ARCHIVE_UPDATE_STATS, (int(v) for v in a[:7])))
+
+    # ---- the range scans through the handle: Engine.search / search_multi / grep / extract of the archive the handle serves, with their
+    # keyword arguments and results. A pass copies its resident frames out of the cache and decodes only the others; a scan is not a
+    # read: the cache and stats() do not change. The call overwrites the engine's counters of its kind (engine.search_stats() ...).
+    def search(self, pattern, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20):
+        """ZraHipArchiveSearch: Engine.search through the handle. Returns (n_matches, [offsets])."""
+        pattern = bytes(pattern)
+        arr = (ctypes.c_uint64 * max_matches)() if max_matches else None
+        n = ctypes.c_uint64(0)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveSearch(self.h, _cbuf(pattern), len(pattern), offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                                        max_matches, ctypes.byref(n)), "ZraHipArchiveSearch")
+        return n.value, [int(v) for v in arr[:min(n.value, max_matches)]] if arr is not None else []
+
+    def search_multi(self, patterns, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20):
+        """ZraHipArchiveSearchMulti: Engine.search_multi through the handle. Returns (n_matches, [(offset, pattern index)], per_pattern)."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ZraHipPatternMatch * max_matches)() if max_matches else None
+        per = (ctypes.c_uint64 * max(len(patterns), 1))()
+        n = ctypes.c_uint64(0)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveSearchMulti(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), offset, (1 << 64) - 1 if length is None else length,
+                                             staging_bytes, arr, max_matches, ctypes.byref(n), per), "ZraHipArchiveSearchMulti")
+        listed = [(int(arr[i].offset), int(arr[i].pattern)) for i in range(min(n.value, max_matches))] if arr is not None else []
+        return n.value, listed, [int(v) for v in per[:len(patterns)]]
+
+    def grep(self, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20):
+        """ZraHipArchiveGrep: Engine.grep through the handle. Returns (n_records, [(offset, size)])."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n = ctypes.c_uint64(0)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveGrep(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter, GREP_INVERT if invert else 0, offset,
+                                      (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n)), "ZraHipArchiveGrep")
+        k = min(n.value, max_records)
+        return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def extract(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0):
+        """ZraHipArchiveExtractRecords: Engine.extract through the handle; d_data must overlap neither the archive nor the cache. Returns
+        (n_records, data_size, [(offset, size)]); OutputBufferTooSmall carries ZraError.needed_records and ZraError.needed_data."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._order()
+        st = self.L.ZraHipArchiveExtractRecords(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter, GREP_INVERT if invert else 0, offset,
+                                                (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n),
+                                                d_data or None, data_cap, ctypes.byref(ds))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipArchiveExtractRecords")
+            e.needed_records, e.needed_data = n.value, ds.value
+            raise e
+        k = n.value if max_records else 0
+        return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def scan_stats(self):
+        """Counters of the scans through this handle, keyed by ARCHIVE_SCAN_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipArchiveGetScanStats(self.h, a)
+        return dict(zip(ARCHIVE_SCAN_STATS, (int(v) for v in a[:6])))
+
+    def scan_stage_ms(self):
+        """bring-up: HIP-event time of the last accepted scan's job-split and stage-from-cache launches, summed over its passes."""
+        return self.L.ZraHipDebugArchiveScanStageMs(self.h)
 
     def drop_cache(self):
         _chk(self.L.ZraHipArchiveDropCache(self.h), "ZraHipArchiveDropCache")

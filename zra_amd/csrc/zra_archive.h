@@ -26,11 +26,28 @@ class ArchiveCache {
   // {updates accepted, frames now, archive size now, staged from the cache (last update), resident frames refreshed (last), staged
   // (cumulative), refreshed (cumulative), 0}
   void update_stats(uint64_t out[8]) const;
+  // The range scans of the engine (zra_scan.h) on the archive the handle is bound to: a pass copies its resident frames out of the
+  // arena and decodes the others (zra_hip.h: ZraHipArchiveSearch .. ZraHipArchiveExtractRecords). A scan is not a read: it changes
+  // nothing of the cache and none of stats()' words, on any status.
+  Status search(const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
+  Status search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset, uint64_t size, size_t stagingBytes, void* hMatches,
+                      size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
+  Status grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
+              size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
+  Status extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
+                 size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+  // {scans accepted, frames staged from the cache (last accepted scan), frames decoded (last), passes (last), staged (cumulative),
+  // decoded (cumulative), 0, 0}
+  void scan_stats(uint64_t out[8]) const;
+  // bring-up: HIP-event time of the last accepted scan's job-split and stage-from-cache launches, summed over its passes (0: none ran)
+  double scan_stage_ms() const { return scanStageMs_; }
 
  private:
   ArchiveCache() = default;
   static const uint32_t* update_table(void* ctx, uint32_t frames);   // UpdCacheView::table
   ArchiveView view() const { return ArchiveView::over(h_, dArc_, arcSize_); }   // the archive the handle serves now, its header checked at open / by the update
+  ScanCacheView scan_view() const;                  // what a scan borrows: header, arena, table, the pinned count words
+  Status scanned(Status st, const ScanCacheView& v); // the scan counters, kept when the scan was accepted
   Status read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
   Engine* e_ = nullptr;
   const uint8_t* dArc_ = nullptr;
@@ -53,6 +70,8 @@ class ArchiveCache {
   unsigned long long* dctr_ = nullptr;  // {evictions, resident}
   uint64_t* pin_ = nullptr;             // page-locked read-back words
   uint64_t reads_ = 0, hits_ = 0, misses_ = 0, evictions_ = 0, resident_ = 0;
+  uint64_t scans_ = 0, scanLast_[3] = {0, 0, 0}, scanStagedTotal_ = 0, scanDecodedTotal_ = 0;
+  double scanStageMs_ = 0;
   uint64_t updates_ = 0, stagedLast_ = 0, refreshedLast_ = 0, stagedTotal_ = 0, refreshedTotal_ = 0;
 };
 

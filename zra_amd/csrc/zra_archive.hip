@@ -13,6 +13,7 @@
 //      overwritten.
 //  (c) a frame is mapped (slotOf / frameOf) only by the commit kernel, after its decode pass: no lookup can find a half-decoded slot.
 #include "zra_archive.h"
+#include "zra_scan.h"
 #include "zra_host.h"
 #include "zra_dev.h"
 #include "zra_kernels.h"
@@ -122,8 +123,62 @@ extern "C" __global__ void __launch_bounds__(256) zra_cache_commit_kernel(const 
   if (t >= n && t < V) ref[victim[t]] = 0;
 }
 
+// A pass of a range scan through the handle (zra_scan.h): one workgroup walks the frames [first, first + n) of the pass, 1024 at a time
+// (zra_upd_plan_kernel's scheme: ballot + prefix counts over the chunk, a running base across chunks; no atomic decides a position).
+// A frame that is not resident gets a decode job, ranked in frame order: its seek-table span (whatever it says: the decoder refuses
+// a span that runs backwards or leaves the body), destination = its slot of the pass, expected size = its share of the content. A
+// resident frame gets a copy entry {window slot, arena slot, length, frame}, ranked the same way (zra_upd_stage_cached_kernel's
+// format). counts = {jobs, copies, bytes the jobs are to regenerate (low, high word)}. Nothing of the cache is written.
+extern "C" __global__ void __launch_bounds__(1024) zra_scan_split_kernel(const u32* slotOf, u32 nFrames, const u8* table, u64 fs, u64 total, u64 first, u32 n,
+                                                                      u64* frameOff, u64* outOff, u32* expect, u32* copies, u32* counts) {
+  __shared__ u32 sJ[16], sC[16];
+  __shared__ u64 sB[16];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  u32 jobBase = 0, copyBase = 0;
+  u64 bytes = 0;
+  for (u32 base = 0; base < n; base += 1024) {
+    const u32 k = base + tid;
+    const bool in = k < n;
+    const u64 f = first + k;
+    const u32 cs = in && f < nFrames ? slotOf[f] : kNone;
+    const u32 len = in ? (u32)frame_expect(f, fs, total) : 0u;
+    const bool cpy = in && cs != kNone, dec = in && !cpy;
+    const u64 mJ = __ballot(dec), mC = __ballot(cpy), below = (1ull << lane) - 1;
+    u64 wb = dec ? (u64)len : 0ull;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) wb += __shfl_xor(wb, d, 64);
+    if (lane == 0) { sJ[wave] = (u32)__popcll(mJ); sC[wave] = (u32)__popcll(mC); sB[wave] = wb; }
+    __syncthreads();
+    u32 beforeJ = 0, beforeC = 0, totalJ = 0, totalC = 0;
+    for (u32 w = 0; w < 16; w++) {
+      const u32 j = sJ[w], c = sC[w];
+      beforeJ += w < wave ? j : 0u; beforeC += w < wave ? c : 0u; totalJ += j; totalC += c;
+      bytes += sB[w];
+    }
+    if (cpy) {
+      u32* e = copies + 4 * (size_t)(copyBase + beforeC + (u32)__popcll(mC & below));
+      e[0] = k; e[1] = cs; e[2] = len; e[3] = (u32)f;
+    }
+    if (dec) {
+      const u32 job = jobBase + beforeJ + (u32)__popcll(mJ & below);
+      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, f + 1);
+      outOff[job] = (u64)k * fs;
+      expect[job] = len;
+    }
+    jobBase += totalJ; copyBase += totalC;
+    __syncthreads();                                                  // (sJ, sC, sB of the next chunk)
+  }
+  if (tid == 0) { counts[0] = jobBase; counts[1] = copyBase; counts[2] = (u32)bytes; counts[3] = (u32)(bytes >> 32); }
+}
+
 // =================================================================================================
 namespace zra_eng {
+
+void scan_launch_split(hipStream_t s, const uint32_t* slotOf, uint32_t nFrames, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n,
+                       uint64_t* frameOff, uint64_t* outOff, uint32_t* expect, uint32_t* copies, uint32_t* counts) {
+  hipLaunchKernelGGL(zra_scan_split_kernel, dim3(1), dim3(1024), 0, s, slotOf, nFrames, table, (u64)fs, (u64)total, (u64)first, n, frameOff, outOff, expect, copies,
+                     counts);
+}
 
 Status ArchiveCache::open(Engine* e, const uint8_t* dArc, size_t arcSize, size_t cacheBytes, ArchiveCache** out) {
   HIPCHK_CLR(hipSetDevice(e->device_));
@@ -223,6 +278,69 @@ Status ArchiveCache::update(const uint8_t* dData, const uint64_t* hOff, const ui
   updates_++;
   stagedLast_ = v.staged; refreshedLast_ = v.refreshed; stagedTotal_ += v.staged; refreshedTotal_ += v.refreshed;
   return ok();
+}
+
+// ---- the range scans through the handle. A scan is not a read: it inserts, evicts and refreshes nothing, sets no reference bit and
+// moves no hand; the driver reads the arena and slotOf and writes neither, so reads / hits / misses / evictions / resident stay, on
+// success and on failure. The call is one of its kind on the handle's engine: it overwrites that kind's counters and timer.
+ScanCacheView ArchiveCache::scan_view() const {
+  ScanCacheView v;
+  v.h = h_; v.arena = arena_; v.slotOf = slotOf_; v.slots = slots_; v.frames = nFrames_; v.pin = (uint32_t*)(pin_ + 4);
+  return v;
+}
+
+Status ArchiveCache::scanned(Status st, const ScanCacheView& v) {
+  if (st.zra) return st;
+  scans_++;
+  scanLast_[0] = v.staged; scanLast_[1] = v.decoded; scanLast_[2] = v.passes;
+  scanStagedTotal_ += v.staged; scanDecodedTotal_ += v.decoded;
+  scanStageMs_ = v.stageMs;
+  return st;
+}
+
+void ArchiveCache::scan_stats(uint64_t out[8]) const {
+  const uint64_t v[8] = {scans_, scanLast_[0], scanLast_[1], scanLast_[2], scanStagedTotal_, scanDecodedTotal_, 0, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+
+Status ArchiveCache::search(const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hMatches, size_t matchCap,
+                            uint64_t* nMatches) {
+  Engine& E = *e_;
+  ScanCacheView v = scan_view();
+  return scanned(ScanImpl::call(E, kScanSearch, nMatches, nullptr, [&] {
+    return ScanImpl::search(E, dArc_, arcSize_, (const uint8_t*)hPattern, patternSize, offset, size, stagingBytes, hMatches, matchCap, nMatches, &v);
+  }), v);
+}
+
+Status ArchiveCache::search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset, uint64_t size, size_t stagingBytes,
+                                  void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
+  Engine& E = *e_;
+  ScanCacheView v = scan_view();
+  return scanned(ScanImpl::call(E, kScanMulti, nMatches, nullptr, [&] {
+    return ScanImpl::msearch(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCap, nMatches,
+                             hPerPattern, &v);
+  }), v);
+}
+
+Status ArchiveCache::grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
+                          size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
+  Engine& E = *e_;
+  ScanCacheView v = scan_view();
+  return scanned(ScanImpl::call(E, kScanGrep, nRecords, nullptr, [&] {
+    return ScanImpl::grep(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords, recordCap,
+                          nRecords, &v);
+  }), v);
+}
+
+Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset,
+                             uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
+                             uint64_t* dataSize) {
+  Engine& E = *e_;
+  ScanCacheView v = scan_view();
+  return scanned(ScanImpl::call(E, kScanExtract, nRecords, dataSize, [&] {
+    return ScanImpl::extract(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
+                             recordCap, nRecords, dData, dataCap, dataSize, &v);
+  }), v);
 }
 
 Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt) {

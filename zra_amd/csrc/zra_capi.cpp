@@ -744,6 +744,38 @@ void ZraHipArchiveGetUpdateStats(const ZraHipArchive* archive, uint64_t* out8) {
   if (!out8) return;
   if (archive) archive->c->update_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
+ZraStatus ZraHipArchiveSearch(ZraHipArchive* archive, const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size, size_t stagingBytes,
+                              uint64_t* hMatches, size_t matchCapacity, uint64_t* nMatches) {
+  if (nMatches) *nMatches = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->search(hPattern, patternSize, offset, size, stagingBytes, hMatches, matchCapacity, nMatches));
+}
+ZraStatus ZraHipArchiveSearchMulti(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset, uint64_t size,
+                                   size_t stagingBytes, ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern) {
+  if (nMatches) *nMatches = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->search_multi(hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCapacity, nMatches, hPerPattern));
+}
+ZraStatus ZraHipArchiveGrep(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode,
+                            uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->grep(hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+}
+ZraStatus ZraHipArchiveExtractRecords(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+                                      uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity,
+                                      uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords,
+                                (uint8_t*)dData, dataCapacity, dataSize));
+}
+void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t* out8) {
+  if (!out8) return;
+  if (archive) archive->c->scan_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugArchiveScanStageMs(const ZraHipArchive* archive) { return archive ? archive->c->scan_stage_ms() : 0.0; }
 ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* dData, const uint64_t* hOffsets,
                               const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites, const void* dAppend, size_t appendSize, void* dOut,
                               size_t outCapacity, size_t* outSize, int8_t level, bool checksum) {

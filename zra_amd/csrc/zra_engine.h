@@ -69,6 +69,19 @@ struct UpdCacheView {
   HeaderInfo newHeader{};
   uint32_t staged = 0, refreshed = 0;
 };
+// A range scan through an archive handle (zra_archive.hip, ZraHipArchiveSearch .. ZraHipArchiveExtractRecords): what the handle lends to
+// the scans' driver (zra_scan.h) and what comes back. The driver only READS the arena and the table: a scan is not a read.
+struct ScanCacheView {
+  HeaderInfo h{};                    // the handle's checked header, taken in place of a read from the device
+  const uint8_t* arena = nullptr;    // slots x frameSize: the plaintext of the resident frames
+  const uint32_t* slotOf = nullptr;  // device: frame -> arena slot (0xFFFFFFFF: not resident), `frames` entries
+  uint32_t slots = 0, frames = 0;    // slots 0: a handle without a cache (the plain call's passes, minus the header read)
+  uint32_t* pin = nullptr;           // four page-locked words: the counts of a pass come back here (zra_scan_split_kernel)
+  // what the call did, on any status: frames staged from the arena, decode jobs, bytes those regenerated, passes; HIP-event time of
+  // the job-split and stage-from-cache launches, summed over the passes
+  uint64_t staged = 0, decoded = 0, decodedBytes = 0, passes = 0;
+  double stageMs = 0;
+};
 // chunk length of the pipelined host-pointer calls (zra_hostpipe.hip); ZRA_HOST_CHUNK_MIB, default 1024
 size_t host_chunk_bytes();
 
@@ -394,8 +407,9 @@ class Engine {
   // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
   struct UpdScratch { DevBuf plan, packed, encSizes, frames, table, copies; } upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // around a pass's stage-from-cache kernel (update through a handle), own launches (the range scans, compare, diff, sign); they never run inside each other
-  hipEvent_t evCall_[2] = {nullptr, nullptr};
+  // around a pass's stage-from-cache kernel (update through a handle), own launches (the range scans, compare, diff, sign); they never run inside each other.
+  // [2] .. [3] and [4] .. [5]: a range scan through a handle, around a pass's job split and around its stage-from-cache kernel (zra_scan.h)
+  hipEvent_t evCall_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list
   struct VerifyScratch { DevBuf plan, faults; } vfy_;
@@ -440,6 +454,13 @@ class Engine {
 // t, *cntOut = *cntIn + all of them; the last n bytes of the run win[.., L) moved to win[-n, 0), n <= 255.
 void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,
                         uint32_t* expect);
+// A pass of a range scan through a handle (zra_scan.h): frames [first, first + n) split by residency (zra_archive.hip,
+// zra_scan_split_kernel) into decode jobs and copy entries of 4 words, counts = {jobs, copies, bytes the jobs regenerate (2 words)};
+// and the copy entries [0, n) staged from the arena, entry slot e[0] to stage + (e[0] - s0) * fs (zra_update.hip, the update's
+// zra_upd_stage_cached_kernel).
+void scan_launch_split(hipStream_t s, const uint32_t* slotOf, uint32_t nFrames, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n,
+                       uint64_t* frameOff, uint64_t* outOff, uint32_t* expect, uint32_t* copies, uint32_t* counts);
+void upd_launch_stage_cached(hipStream_t s, const uint32_t* copies, uint32_t n, uint32_t s0, uint64_t fs, const uint8_t* arena, uint8_t* stage);
 void search_launch_scan(hipStream_t s, const uint32_t* counts, uint32_t nItems, uint64_t* bases, const uint64_t* cntIn, uint64_t* cntOut);
 void search_launch_carry(hipStream_t s, uint8_t* win, uint64_t L, uint32_t n);
 // The diff's steps that do not depend on how a grain became dirty (zra_compare.hip; the signature diff shares them): the three-column

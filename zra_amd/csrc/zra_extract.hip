@@ -333,20 +333,22 @@ Status Engine::extract_records(const uint8_t* dArc, size_t arcSize, const void* 
 
 Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
                          uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                         uint64_t* dataSize) {
+                         uint64_t* dataSize, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nRecords || !dataSize || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (!dData && dataCap) || (mode & ~1u)) return zerr(42);
   uint32_t M = 0, mMin = kMaxPattern;
   if (!record_patterns_ok(hPat, hSizes, nPat, delimiter, &M, &mMin)) return zerr(42);
-  // ---- 2. overlap
+  // ---- 2. overlap (with the archive, and with the arena of the handle the call goes through)
   if (dataCap && arcSize && (uintptr_t)dData < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dData + dataCap) return zerr(42);
+  if (cv && cv->slots && dataCap && (uintptr_t)dData < (uintptr_t)cv->arena + (size_t)cv->slots * cv->h.frameSize && (uintptr_t)cv->arena < (uintptr_t)dData + dataCap)
+    return zerr(42);
   const uint32_t inv = mode & 1u;
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   E.reset_decode_stats();
   // ---- 3. header: the statuses of ZraHipArchiveOpen, as the grep
   ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
   // ---- 4. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
@@ -377,7 +379,7 @@ Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const u
     if (listCap || dataCap)
       hipLaunchKernelGGL(zra_extract_copy_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums,
                          heads, list, (u64)listCap, dData, (u64)dataCap);
-  }, &launches);
+  }, &launches, cv);
   if (st.zra) return st;
   // ---- 6. the totals (they came back with the last synchronisation), then the list, once
   const XTotals& h = *(const XTotals*)(head.data() + kTotals);
@@ -390,7 +392,7 @@ Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const u
     HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, (size_t)total * sizeof(Range), hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
-  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, h.delims + fin.tail, total, packed, P.passes, h.matches};
+  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, packed, P.passes, h.matches};
   std::copy(st8, st8 + 8, stats);
   return ok();
 }

@@ -245,7 +245,7 @@ Status Engine::grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPa
 }
 
 Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                      uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
+                      uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nRecords || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (mode & ~1u)) return zerr(42);
   uint32_t M = 0, mMin = kMaxPattern;
@@ -256,7 +256,7 @@ Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint
   E.reset_decode_stats();
   // ---- 2. header: the statuses of ZraHipArchiveOpen, as the search
   ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
   // ---- 3. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
@@ -287,7 +287,7 @@ Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint
     if (listCap)
       hipLaunchKernelGGL(zra_grep_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, heads,
                          list, (u64)listCap);
-  }, &launches);
+  }, &launches, cv);
   if (st.zra) return st;
   // ---- 5. the totals (they came back with the last synchronisation), then the list, once
   const Totals& h = *(const Totals*)(head.data() + kTotals);
@@ -299,7 +299,7 @@ Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
   *nRecords = total;
-  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, h.delims + fin.tail, total, nOut, P.passes, h.matches};
+  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, nOut, P.passes, h.matches};
   std::copy(st8, st8 + 8, stats);
   return ok();
 }

@@ -113,7 +113,7 @@ Status Engine::search_archive_multi(const uint8_t* dArc, size_t arcSize, const v
 }
 
 Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
-                         size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
+                         size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nMatches || !hPat || !hSizes || (!dArc && arcSize) || (!hMatches && matchCap)) return zerr(42);
   uint32_t M = 0, mMin = kMaxPattern;
@@ -123,7 +123,7 @@ Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   E.reset_decode_stats();
   // ---- 2. header: the statuses of ZraHipArchiveOpen, as the search
   ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
   // ---- 3. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
@@ -157,7 +157,7 @@ Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const u
     if (listCap)
       hipLaunchKernelGGL(zra_msearch_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, counts, waveCnt, bases, (u64)ps.p0,
                          E.scan_.list.as<Match>(), (u64)listCap);
-  }, &launches);
+  }, &launches, cv);
   if (st.zra) return st;
   // ---- 5. the totals (they came back with the last synchronisation), then the list, once
   const Totals& h = *(const Totals*)(head.data() + kTotals);
@@ -169,7 +169,7 @@ Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   }
   if (hPerPattern) std::copy(h.per, h.per + nPat, hPerPattern);
   *nMatches = total;
-  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, total, nOut, P.passes, nPat, h.survivors};
+  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), total, nOut, P.passes, nPat, h.survivors};
   std::copy(st8, st8 + 8, stats);
   return ok();
 }

@@ -8,6 +8,15 @@
 //   4. the call's own launches over the start positions the pass owns                                    the per-pass callback
 //   5. the last M - 1 bytes seen so far move in front of slot 0 for the next pass                         zra_search_carry_kernel
 //   6. the call's totals come to the host with the last synchronisation; the call reads its list, once
+// Through an archive handle with a cache (ScanCacheView) steps 2 and 3 of a pass become
+//   2'. the frames are split by residency, one launch: the missing ones become decode jobs, compacted in frame order,   zra_scan_split_kernel
+//       the resident ones copy entries; the two counts come to the host through a pinned word (the pass's one read-back)
+//   2". the resident frames are copied from their arena slots into their window slots, when there are any          zra_upd_stage_cached_kernel
+//   3'. the missing frames are decoded whole, checksums verified, when there are any                              Engine::staged_pass
+// on the engine's stream, in that order. Copies and jobs write different slots, each frame its own; a resident frame was decoded whole
+// with status 0, a verified checksum and its exact size, so (contiguity) holds as before and the scan kernels see the same window.
+// The jobs are in frame order: the first failing job is the lowest failing frame, which is by construction a missing one. The driver
+// only reads the arena and the handle's table: a scan is not a read.
 // The staging window (Engine::stage_, reserved kScanMaxPattern bytes larger) is  [ carry area | slot 0 | slot 1 | ... ]: slot s lies at
 // s * frameSize behind the carry area. The arithmetic of a pass is zra_scan_plan.h's (host only, checked exhaustively on the CPU).
 //
@@ -30,20 +39,21 @@
 //  (d) nothing goes to the caller's arrays before the last pass is done: a call that fails midway writes nothing.
 #pragma once
 #include "zra_host.h"
+#include <algorithm>
 
 namespace zra_eng {
 
 struct ScanImpl {
   // the four calls behind Engine's entry points, each in its own file
   static Status search(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, size_t m, uint64_t offset, uint64_t size, size_t stagingBytes,
-                       uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
+                       uint64_t* hMatches, size_t matchCap, uint64_t* nMatches, ScanCacheView* cv = nullptr);
   static Status msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
-                        size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
+                        size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv = nullptr);
   static Status grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                     uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
+                     uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv = nullptr);
   static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
                         uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                        uint64_t* dataSize);
+                        uint64_t* dataSize, ScanCacheView* cv = nullptr);
 
   // What a call of the family leaves behind, decided here for all four. `which`: kScanSearch .. kScanExtract; out0 / out1: the call's
   // output words (either may be nullptr). The counters, the milliseconds and the words are zero before `run`; on any failure the
@@ -72,31 +82,67 @@ struct ScanImpl {
   // ownedOnly, for the passes that own a start position; *ran counts its invocations, (c). *ms gains the HIP-event time from in
   // front of a pass's callback to behind its carry move. Returns synchronised; a frame that does not decode ends the call with the
   // lowest failing frame's code of the first failing pass.
+  // cv (a call through an archive handle): with slots, a pass takes its plaintext from two places (through a handle, above); without,
+  // the passes are the plain call's. Either way cv's counters say what the passes did, as far as they came.
   template <class PerPass>
   static Status passes(Engine& E, const ArchiveView& arc, const ScanPlan& P, double* ms, void* head, size_t headBytes, size_t backOff, size_t backBytes,
-                       size_t tableBytes, size_t listBytes, bool ownedOnly, PerPass&& perPass, uint32_t* ran) {
+                       size_t tableBytes, size_t listBytes, bool ownedOnly, PerPass&& perPass, uint32_t* ran, ScanCacheView* cv = nullptr) {
     const size_t jobs = (size_t)P.nSlots + 1;
+    const bool cached = cv && cv->slots;
     if (!E.stage_.reserve(kScanMaxPattern + (size_t)P.window + 64) || !E.scan_.tables.reserve(tableBytes) || !E.scan_.list.reserve(listBytes) ||
-        !E.frameOff_.reserve(jobs * 16) || !E.outOff_.reserve(jobs * 8) || !E.expect_.reserve(jobs * 4))
+        !E.frameOff_.reserve(jobs * 16) || !E.outOff_.reserve(jobs * 8) || !E.expect_.reserve(jobs * 4) || (cached && !E.upd_.copies.reserve(jobs * 16)))
       return zerr(64);
     if (!E.call_events()) return zerr(1);
     hipStream_t s = E.stream_;
     HIPCHK_CLR(hipMemcpyAsync(E.scan_.tables.p, head, headBytes, hipMemcpyHostToDevice, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
     uint8_t* const win = window(E);
+    // (through a handle) the pass's count words, then its copy entries, 4 words each: jobs * 16 bytes
+    uint32_t* const counts = cached ? E.upd_.copies.as<uint32_t>() : nullptr, * const copies = cached ? counts + 4 : nullptr;
     uint32_t carry = 0;
-    bool timed = false;
+    bool timed = false, stageTimed = false;
     // (behind a synchronisation of the stream)
-    auto take_time = [&]() { if (timed) *ms += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); timed = false; };
+    auto take_time = [&]() {
+      if (timed) *ms += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]);
+      if (stageTimed) cv->stageMs += Engine::elapsed_ms(E.evCall_[4], E.evCall_[5]);
+      timed = stageTimed = false;
+    };
     *ran = 0;
     for (uint64_t p = 0; p < P.passes; p++) {
       const ScanPass ps = scan_pass(P, p, carry);
-      search_launch_jobs(s, arc.table, P.fs, P.U, ps.first, ps.nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-      unsigned long long firstError;
-      const Status st = E.staged_pass(arc, 0, ps.nj, win, &firstError);
-      take_time();
-      if (st.zra) return st;
-      if (firstError != ~0ull) return zerr(reported_code(firstError));
+      uint32_t nDec = ps.nj;
+      uint64_t decBytes = ps.L;
+      if (cached) {
+        HIPCHK_CLR(hipEventRecord(E.evCall_[2], s));
+        scan_launch_split(s, cv->slotOf, cv->frames, arc.table, P.fs, P.U, ps.first, ps.nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(),
+                          E.expect_.as<uint32_t>(), copies, counts);
+        HIPCHK_CLR(hipEventRecord(E.evCall_[3], s));
+        HIPCHK_CLR(hipMemcpyAsync(cv->pin, counts, 16, hipMemcpyDeviceToHost, s));
+        HIPCHK_CLR(hipStreamSynchronize(s));
+        HIPCHK_CLR(hipGetLastError());
+        take_time();
+        cv->stageMs += Engine::elapsed_ms(E.evCall_[2], E.evCall_[3]);
+        nDec = cv->pin[0];
+        const uint32_t nCopy = cv->pin[1];
+        decBytes = (uint64_t)cv->pin[2] | (uint64_t)cv->pin[3] << 32;
+        if (nCopy) {
+          HIPCHK_CLR(hipEventRecord(E.evCall_[4], s));
+          upd_launch_stage_cached(s, copies, nCopy, 0, P.fs, cv->arena, win);
+          HIPCHK_CLR(hipEventRecord(E.evCall_[5], s));
+          stageTimed = true;
+          cv->staged += nCopy;
+        }
+      }
+      if (nDec) {                                                      // (always, without a handle's cache: a pass has a frame)
+        if (!cached)
+          search_launch_jobs(s, arc.table, P.fs, P.U, ps.first, ps.nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
+        unsigned long long firstError;
+        const Status st = E.staged_pass(arc, 0, nDec, win, &firstError);
+        take_time();
+        if (st.zra) return st;
+        if (firstError != ~0ull) return zerr(reported_code(firstError));
+      }
+      if (cv) { cv->decoded += nDec; cv->decodedBytes += decBytes; cv->passes++; }
       HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
       if (!ownedOnly || ps.nPos) { perPass(ps); ++*ran; }
       if (!ps.lastPass && P.M > 1) search_launch_carry(s, win, ps.L, ps.carry);
@@ -109,6 +155,18 @@ struct ScanImpl {
     HIPCHK_CLR(hipGetLastError());
     take_time();
     return ok();
+  }
+
+  // words [1] and [2] of a call's counters: the decode jobs and the bytes they regenerated. Without a handle every frame of the
+  // range is one; through a handle the frames staged from its arena are left out
+  static uint64_t decoded_frames(const ScanPlan& P, const ScanCacheView* cv) { return cv ? cv->decoded : P.n; }
+  static uint64_t decoded_bytes(const ScanPlan& P, const ScanCacheView* cv) {
+    return cv ? cv->decodedBytes : std::min<uint64_t>(P.U, (P.f1 + 1) * P.fs) - P.f0 * P.fs;
+  }
+  // the header step of a call: read and checked (the statuses of ZraHipArchiveOpen), or, through a handle, the one it checked at open
+  static Status view(Engine& E, const uint8_t* dArc, size_t arcSize, const ScanCacheView* cv, ArchiveView* arc) {
+    if (cv) { *arc = ArchiveView::over(cv->h, dArc, arcSize); return ok(); }
+    return E.archive_view(dArc, arcSize, arc);
   }
 };
 

@@ -152,15 +152,15 @@ Status Engine::search_archive(const uint8_t* dArc, size_t arcSize, const void* h
 }
 
 Status ScanImpl::search(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, size_t m, uint64_t offset, uint64_t size, size_t stagingBytes,
-                        uint64_t* hMatches, size_t matchCap, uint64_t* nMatches) {
+                        uint64_t* hMatches, size_t matchCap, uint64_t* nMatches, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nMatches || !hPat || (!dArc && arcSize) || (!hMatches && matchCap) || m == 0 || m > kMaxPattern) return zerr(42);
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   E.reset_decode_stats();
-  // ---- 2. header: the statuses of ZraHipArchiveOpen. (The header's CRC-32 is not looked at: that is the verifier's job.)
+  // ---- 2. header: the statuses of ZraHipArchiveOpen; a handle's was checked at open. (The header's CRC-32 is not looked at: that is the verifier's job.)
   ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
   // ---- 3. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
@@ -186,7 +186,7 @@ Status ScanImpl::search(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
     if (listCap)
       hipLaunchKernelGGL(zra_search_fill_kernel, dim3(tiles), dim3(256), 0, s, win, ps.xLo, (u64)ps.nPos, pat, (u32)m, counts, bases, (u64)ps.p0,
                          E.scan_.list.as<uint64_t>(), (u64)listCap);
-  }, &launches);
+  }, &launches, cv);
   if (st.zra) return st;
   // ---- 5. the count (it came back with the last synchronisation), then the list, once
   const uint64_t total = ((const uint64_t*)(padded + kMaxPattern))[launches & 1];
@@ -196,7 +196,7 @@ Status ScanImpl::search(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
   *nMatches = total;
-  const uint64_t st8[8] = {arc.frames, P.n, std::min<uint64_t>(arc.U, (P.f1 + 1) * arc.fs) - P.f0 * arc.fs, total, nOut, P.passes, 0, 0};
+  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), total, nOut, P.passes, 0, 0};
   std::copy(st8, st8 + 8, stats);
   return ok();
 }

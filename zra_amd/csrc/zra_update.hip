@@ -267,6 +267,13 @@ extern "C" __global__ void __launch_bounds__(256) zra_upd_gather_kernel(const u6
 // =================================================================================================
 namespace zra_eng {
 
+// the stage-from-cache launch of a pass: the update's own, and the one a range scan through a handle makes (zra_engine.h, zra_scan.h)
+void upd_launch_stage_cached(hipStream_t s, const uint32_t* copies, uint32_t n, uint32_t s0, uint64_t fs, const uint8_t* arena, uint8_t* stage) {
+  const uint64_t nWork = (uint64_t)n * ((fs + kGatherChunk - 1) / kGatherChunk);
+  hipLaunchKernelGGL(zra_upd_stage_cached_kernel, dim3((uint32_t)std::min<uint64_t>((nWork + 3) / 4, kGatherGrid)), dim3(256), 0, s, copies, n, s0, (u64)fs,
+                     arena, stage);
+}
+
 struct UpdateImpl {
   static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* dData, const uint64_t* hOff, const uint64_t* hSize,
                     const uint64_t* hDataOff, size_t nw, const uint8_t* dAppend, size_t appendSize, uint8_t* dOut, size_t outCap,
@@ -393,10 +400,8 @@ Status UpdateImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, const uin
       const uint32_t s0 = p * passSlots, n = std::min(passSlots, touched - s0);
       const uint32_t j0 = hPassJob[p], j1 = hPassJob[p + 1], c0 = hPassCopy[p], c1 = hPassCopy[p + 1];
       if (c1 > c0) {                                                  // (other staging slots than the decode jobs': no order between the two)
-        const uint64_t nWork = (uint64_t)(c1 - c0) * ((fs + kGatherChunk - 1) / kGatherChunk);
         HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-        hipLaunchKernelGGL(zra_upd_stage_cached_kernel, dim3((uint32_t)std::min<uint64_t>((nWork + 3) / 4, kGatherGrid)), dim3(256), 0, s,
-                           copies + 4 * (size_t)c0, c1 - c0, s0, (u64)fs, cache->arena, stage);
+        upd_launch_stage_cached(s, copies + 4 * (size_t)c0, c1 - c0, s0, fs, cache->arena, stage);
         HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
       }
       if (j1 > j0) {
