@@ -381,6 +381,29 @@ def test_interleaved_with_the_other_archive_calls(zra, gpu_engine):
         f(*p)
 
 
+# ---- 10b
+def test_a_refused_sign_call_leaves_the_diff_counters_alone(zra, gpu_engine):
+    """Every call's counters and milliseconds are a row of one table: a row belongs to one call. After a sign call that succeeded and a
+    diff that succeeded, a sign call refused for its grain (3: not a power of two) zeroes the sign's row and leaves the diff's row,
+    counters and milliseconds, as it was."""
+    from test_gpu_sign import SIGN_ZERO, _sign_raw
+    fs = 1000
+    a = _data(np.random.RandomState(5), 5 * fs + 17)
+    b = bytearray(a + _data(np.random.RandomState(6), fs))
+    b[fs + 3] ^= 1
+    b[4 * fs] ^= 1
+    b = bytes(b)
+    A, B = _pair(gpu_engine, zra, a, b, fs)
+    assert _sign_raw(gpu_engine, zra, A, 64)["st"] == (0, 0) and gpu_engine.sign_stats()["signed"] == 6
+    _diff(gpu_engine, zra, A, B, a, b, fs, 64, staging=2 * 2 * fs)
+    stats, ms = gpu_engine.diff_stats(), zra.load().ZraHipDebugDiffMs(gpu_engine.h)
+    assert stats == M.stats(a, b, fs, 64, decoded=_changed(a, b, fs), slots=2, tail_slots=4) and ms > 0, (stats, ms)
+    r = _sign_raw(gpu_engine, zra, A, 3, cap=64)
+    assert r["st"] == (1, 42) and r["info"] == (0,) * 6, r["st"]
+    assert gpu_engine.sign_stats() == SIGN_ZERO and gpu_engine.sign_ms() == 0
+    assert gpu_engine.diff_stats() == stats and zra.load().ZraHipDebugDiffMs(gpu_engine.h) == ms
+
+
 # ---- 11
 def test_cli_mode_diff(zra, gpu_engine, tmp_path):
     fs = 1024

@@ -565,6 +565,39 @@ def test_interleaved_with_the_other_archive_calls(zra, gpu_engine):
         f(p)
 
 
+# ---- 11b
+def test_compare_and_signature_diff_share_one_scratch_group(zra, gpu_engine):
+    """The compare and the signature diff keep their flags, tables and lists in ONE scratch group of the engine. At frame size 4 with
+    four staging bytes (250 passes of one slot): a compare, a signature diff whose tables are larger (all 250 slots in one pass, a dirty
+    flag per grain), the compare again: the group is reserved again at a larger size between two uses, and the third call's ranges
+    and counters are the first call's. Then from empty scratch in the reverse order, the signature diff first."""
+    a = b"abcdefghij" * 100
+    b = bytearray(a)
+    for off, n in RUNS4:
+        b[off:off + n] = a[off:off + n].upper()
+    b = bytes(b)
+    xa, A, xb, B = _arcs(gpu_engine, zra, a, b, 4)
+    sig, buf, _ = _signed(gpu_engine, zra, A, xa, a, 4, 64)
+
+    def compare():
+        r = gpu_engine.compare(A[0].data_ptr(), A[1], B[0].data_ptr(), B[1], staging_bytes=4)
+        assert r == (len(RUNS4), sum(n for _, n in RUNS4), RUNS4), r
+        s = gpu_engine.compare_stats()
+        assert s["passes"] == 250, s
+        return r, s
+
+    def sigdiff():
+        want, r = _sigdiff(gpu_engine, zra, sig, buf, B, a, b, 4, staging=0)
+        s = gpu_engine.diff_signature_stats()
+        assert s["passes"] == 1, s
+        return want, {k: v for k, v in r.items()}, s
+
+    for order in ((compare, sigdiff, compare), (sigdiff, compare, sigdiff)):
+        gpu_engine.release_scratch()
+        got = [f() for f in order]
+        assert got[2] == got[0], (got[0], got[2])
+
+
 # ---- 12
 def test_cli_modes_sign_and_sigdiff(zra, gpu_engine, tmp_path):
     fs = 1024

@@ -14,7 +14,8 @@
 // The staging window (Engine::stage_) is [ half A | half B ], a half = the pass's slots rounded up to 16 bytes: slot s of either half
 // lies at s * frameSize of it, so the two plaintexts of a frame share their alignment modulo 16.
 //
-// Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
+// The passes run through the one frame-pass driver, flagged and with two sides: their order on the stream, the timed span and which
+// failing frame ends the call are stated there (zra_framepass.h). What the kernels of this file rely on:
 //  (slots) slot = frame - first frame of the pass, on both sides, whether the frame is decoded or not. A decoded frame that is not the
 //      last of the range regenerates frameSize bytes on both sides (anything else is a failing frame and ends the call), so the byte in
 //      front of a decoded frame's first byte is the last byte of the slot in front: the window is addressed by arithmetic alone. The
@@ -33,7 +34,7 @@
 //      list position is a sum of counts and lane prefixes, never the result of an atomic, and no workgroup waits for another one.
 //  (d) nothing goes to the caller's array before the last pass is done: a call that fails midway writes nothing.
 // The diff of two archives (zra_hip.h: ZraHipDiffArchives) is the second half of this file: the same passes with the plaintext kept.
-#include "zra_host.h"
+#include "zra_framepass.h"
 #include "zra_dev.h"
 #include <algorithm>
 
@@ -528,283 +529,192 @@ void diff_launch_tail(hipStream_t s, const uint8_t* src, uint64_t n, const uint6
   hipLaunchKernelGGL(zra_diff_tail_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, src, (u64)n, (const u64*)dirtyBytes, (u64)tailOff, dData, (u64)dataCap);
 }
 
-struct CompareImpl {
-  static Status run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
-                    size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes);
-};
+namespace {
+constexpr uint32_t kDecodeAll = 1u;                                           // ZRA_HIP_COMPARE_DECODE_ALL, ZRA_HIP_DIFF_DECODE_ALL
 
-Status Engine::compare_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
-                                size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes) {
-  for (auto& v : cstats_) v = 0;
-  cmpSizes_[0] = cmpSizes_[1] = 0;
-  compareMs_ = 0;
-  if (nRanges) *nRanges = 0;
-  if (differingBytes) *differingBytes = 0;
-  const Status st = CompareImpl::run(*this, dA, sizeA, dB, sizeB, mode, offset, size, stagingBytes, hRanges, rangeCap, nRanges, differingBytes);
-  if (st.zra) compareMs_ = 0;
-  return st;
+// The pair passes of compare and diff over the frames of [lo, hi): the passes run through the one driver (zra_framepass.h), flagged,
+// two sides. `before` is the same for both calls (steps 2 and 3 of the file head), `after` the call's own tile launches.
+struct PairPasses {
+  FramePasses& F;
+  const ArchiveView& A; const ArchiveView& B;
+  uint64_t fs, lo, hi;
+  PassPlan P;
+  uint64_t half;
+  uint32_t tpf;
+  uint8_t* winB() const { return F.win + half; }
+  uint32_t* carry() const { return (uint32_t*)(F.tables + kOffCarry); }
+  const uint32_t* job_count() const { return (const uint32_t*)(F.tables + kOffJobs); }
+  size_t items_max() const { return 1 + (size_t)P.nSlots * tpf; }
+
+  Status before(uint32_t mode, const FramePass& ps) const {
+    if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(F.flags, 1, ps.nj, F.s));
+    else
+      hipLaunchKernelGGL(zra_cmp_spans_kernel, dim3((ps.nj + 3) / 4), dim3(256), 0, F.s, A.table, A.body, (u64)A.bodyBytes, B.table, B.body, (u64)B.bodyBytes,
+                         (u64)ps.first, ps.nj, F.flags);
+    hipLaunchKernelGGL(zra_cmp_jobs_kernel, dim3(1), dim3(1024), 0, F.s, F.flags, ps.nj, A.table, (u64)A.U, B.table, (u64)B.U, (u64)fs, (u64)ps.first, (u64)lo, (u64)hi,
+                       F.frameOff, F.outOff, F.expect, P.nSlots, F.tables);
+    return ok();
+  }
+  // (look-behind) the tiles of a pass: item 0 and tpf tiles per decoded frame; the carry word the pass writes is zeroed first
+  Status tiles(const FramePass& ps, TileArgs* T) const {
+    T->winA = F.win; T->winB = winB(); T->outOff = F.outOff; T->flags = F.flags; T->fs = fs; T->first = ps.first; T->lo = lo; T->hi = hi; T->nj = ps.nj; T->tpf = tpf;
+    T->carryIn = carry() + ps.parity;
+    HIPCHK_CLR(hipMemsetAsync(carry() + (ps.parity ^ 1), 0, 4, F.s));
+    return ok();
+  }
+  template <class After>
+  Status run(uint32_t mode, uint64_t* decoded, After&& after) {
+    const FramePasses::Side a{&A, 0, F.win}, b{&B, P.nSlots, winB()};
+    return F.run(P, a, &b, job_count(), decoded, [&](const FramePass& ps) { return before(mode, ps); }, after);
+  }
+};
+PairPasses pair_passes(FramePasses& F, const ArchiveView& A, const ArchiveView& B, uint64_t lo, uint64_t hi, size_t stagingBytes) {
+  const uint64_t fs = A.fs, f0 = lo / fs, n = hi > lo ? (hi - 1) / fs - f0 + 1 : 0;   // (frames of both archives: hi <= C, and ra_header ties frames to U)
+  const PassPlan P = pass_plan(f0, n, pair_pass_slots(fs, stagingBytes));
+  return PairPasses{F, A, B, fs, lo, hi, P, pair_half(P.nSlots, fs), (uint32_t)((fs + kTile - 1) / kTile)};
+}
+// 2. headers, A then B: the statuses of ZraHipArchiveOpen. (The headers' CRC-32 is not looked at: that is the verifier's job.) 3. one frame size
+Status pair_views(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, ArchiveView* A, ArchiveView* B) {
+  STCHK(E.archive_view(dA, sizeA, A));
+  if (A->fs == 0) return {kHeaderInvalid, 0};
+  STCHK(E.archive_view(dB, sizeB, B));
+  if (B->fs == 0) return {kHeaderInvalid, 0};
+  return A->fs != B->fs ? zerr(40) : ok();
 }
 
-Status CompareImpl::run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
-                        size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes) {
-  constexpr uint32_t kDecodeAll = 1u;                                         // ZRA_HIP_COMPARE_DECODE_ALL
+Status compare_run(Engine& E, uint64_t (&stats)[8], double* ms, uint64_t sizes[2], const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode,
+                   uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes) {
   // ---- 1. arguments
   if (!nRanges || (!dA && sizeA) || (!dB && sizeB) || (!hRanges && rangeCap) || (mode & ~kDecodeAll)) return zerr(42);
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 2. headers, A then B: the statuses of ZraHipArchiveOpen. (The headers' CRC-32 is not looked at: that is the verifier's job.)
+  FramePasses F(E, ms);
+  STCHK(F.start());
+  // ---- 2. headers, 3. one frame size
   ArchiveView A, B;
-  { Status st = E.archive_view(dA, sizeA, &A); if (st.zra) return st; }
-  if (A.fs == 0) return {kHeaderInvalid, 0};
-  { Status st = E.archive_view(dB, sizeB, &B); if (st.zra) return st; }
-  if (B.fs == 0) return {kHeaderInvalid, 0};
-  // ---- 3. one frame size
-  if (A.fs != B.fs) return zerr(40);
-  const uint64_t fs = A.fs, C = std::min(A.U, B.U);
-  // ---- 4. the range [lo, hi) of the common content, inclusive bound
-  if (offset > C || (size != ~0ull && (offset + size < offset || offset + size > C))) return {kOutOfBounds, 0};
-  const uint64_t lo = offset, hi = size == ~0ull ? C : offset + size;
-  if (hi == lo) { E.cmpSizes_[0] = A.U; E.cmpSizes_[1] = B.U; return ok(); }
-  const uint64_t f0 = lo / fs, f1 = (hi - 1) / fs, n = f1 - f0 + 1;           // (frames of both archives: hi <= C, and ra_header ties frames to U)
+  STCHK(pair_views(E, dA, sizeA, dB, sizeB, &A, &B));
+  // ---- 4. the range [lo, hi) of the common content, inclusive bound (the range rule of the scans)
+  uint64_t lo, hi;
+  if (!scan_range(std::min(A.U, B.U), offset, size, &lo, &hi)) return {kOutOfBounds, 0};
+  if (hi == lo) { sizes[0] = A.U; sizes[1] = B.U; return ok(); }
   // ---- 5. scratch
-  const uint32_t passSlots = pass_slots(2 * fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
-  const uint64_t passes = (n + passSlots - 1) / passSlots;
-  const uint64_t half = ((uint64_t)nSlots * fs + 15) & ~15ull;
-  const uint32_t tpf = (uint32_t)((fs + kTile - 1) / kTile);
-  const size_t itemsMax = 1 + (size_t)nSlots * tpf;
+  PairPasses X = pair_passes(F, A, B, lo, hi, stagingBytes);
+  const PassPlan& P = X.P;
   const size_t listCap = (size_t)std::min<uint64_t>(rangeCap, (hi - lo + 1) / 2);   // (runs are at least one byte long and one byte apart)
-  if (!E.stage_.reserve((size_t)(2 * half) + 64) || !E.cmp_.flags.reserve((size_t)nSlots + 64) || !E.cmp_.tables.reserve(kHdrBytes + (itemsMax + 1) * 16 + 64) ||
-      !E.cmp_.list.reserve(listCap * 16 + 64) || !E.frameOff_.reserve((2 * (size_t)nSlots + 1) * 16) || !E.outOff_.reserve(((size_t)nSlots + 1) * 8) ||
-      !E.expect_.reserve((2 * (size_t)nSlots + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const winA = E.stage_.as<uint8_t>();
-  uint8_t* const winB = winA + half;
-  uint8_t* const flags = E.cmp_.flags.as<uint8_t>();
-  uint8_t* const hdr = E.cmp_.tables.as<uint8_t>();
+  STCHK(F.open({(size_t)(2 * X.half) + 64, (size_t)P.nSlots + 64, 0, kHdrBytes + (X.items_max() + 1) * 16 + 64, listCap * 16 + 64, 2 * (size_t)P.nSlots, P.nSlots}));
+  uint8_t* const hdr = F.tables;
   uint64_t* const tot = (uint64_t*)hdr;
-  uint32_t* const carry = (uint32_t*)(hdr + kOffCarry);
   uint64_t* const tab = (uint64_t*)(hdr + kHdrBytes);
-  uint64_t* const starts = E.cmp_.list.as<uint64_t>();
+  uint64_t* const starts = F.list;
   uint64_t* const ends = starts + listCap;
-  HIPCHK_CLR(hipMemsetAsync(hdr, 0, kHdrBytes, s));
   // ---- passes
   uint64_t decoded = 0;
-  // evCall_[0] .. evCall_[1] spans the compare's own launches between two decodes: the tiles of a pass and the spans and jobs of the
-  // next one follow each other on the stream. Taken behind a synchronisation of the stream.
-  auto take_time = [&]() { E.compareMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
-  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t first = f0 + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(flags, 1, nj, s));
-    else
-      hipLaunchKernelGGL(zra_cmp_spans_kernel, dim3((nj + 3) / 4), dim3(256), 0, s, A.table, A.body, (u64)A.bodyBytes, B.table, B.body, (u64)B.bodyBytes, (u64)first,
-                         nj, flags);
-    hipLaunchKernelGGL(zra_cmp_jobs_kernel, dim3(1), dim3(1024), 0, s, flags, nj, A.table, (u64)A.U, B.table, (u64)B.U, (u64)fs, (u64)first, (u64)lo, (u64)hi,
-                       E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), nSlots, hdr);
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    uint32_t nDec = 0;
-    HIPCHK_CLR(hipMemcpyAsync(&nDec, hdr + kOffJobs, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-    HIPCHK_CLR(hipGetLastError());
-    take_time();
-    if (nDec > nj) return zerr(1);                                            // (cannot happen)
-    if (nDec) {
-      unsigned long long errA, errB;
-      { Status st = E.staged_pass(A, 0, nDec, winA, &errA); if (st.zra) return st; }
-      { Status st = E.staged_pass(B, nSlots, nDec, winB, &errB); if (st.zra) return st; }
-      // the lowest failing frame of the first failing pass (jobs are in frame order, the same on both sides), A before B
-      if (errA != ~0ull || errB != ~0ull) return zerr(reported_code((errB >> 8) < (errA >> 8) ? errB : errA));
-      decoded += nDec;
-    }
-    // (look-behind) item 0 and the tiles of the decoded frames
-    const uint32_t items = 1 + nDec * tpf;
-    TileArgs T;
-    T.winA = winA; T.winB = winB; T.outOff = E.outOff_.as<uint64_t>(); T.flags = flags; T.fs = fs; T.first = first; T.lo = lo; T.hi = hi; T.nj = nj; T.tpf = tpf;
-    T.carryIn = carry + (p & 1);
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    HIPCHK_CLR(hipMemsetAsync(carry + ((p + 1) & 1), 0, 4, s));
-    hipLaunchKernelGGL(zra_cmp_count_kernel, dim3(items), dim3(256), 0, s, T, tab, (u64*)(hdr + kOffDiff), carry + ((p + 1) & 1));
-    hipLaunchKernelGGL(zra_cmp_scan_kernel, dim3(1), dim3(1024), 0, s, tab, items, tot + 2 * (p & 1), tot + 2 * ((p + 1) & 1));
-    if (listCap) hipLaunchKernelGGL(zra_cmp_fill_kernel, dim3(items), dim3(256), 0, s, T, tab, starts, ends, (u64)listCap);
-  }
+  STCHK(F.begin(hdr, kHdrBytes));
+  STCHK(X.run(mode, &decoded, [&](const FramePass& ps, uint32_t nDec) {
+      const uint32_t items = 1 + nDec * X.tpf;
+      TileArgs T;
+      STCHK(X.tiles(ps, &T));
+      hipLaunchKernelGGL(zra_cmp_count_kernel, dim3(items), dim3(256), 0, F.s, T, tab, (u64*)(hdr + kOffDiff), X.carry() + (ps.parity ^ 1));
+      hipLaunchKernelGGL(zra_cmp_scan_kernel, dim3(1), dim3(1024), 0, F.s, tab, items, tot + 2 * ps.parity, tot + 2 * (ps.parity ^ 1));
+      if (listCap) hipLaunchKernelGGL(zra_cmp_fill_kernel, dim3(items), dim3(256), 0, F.s, T, tab, starts, ends, (u64)listCap);
+      return ok();
+    }));
   // ---- the counts, then the lists, once
   uint64_t h8[8] = {0};
-  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-  HIPCHK_CLR(hipMemcpyAsync(h8, hdr, kHdrBytes, hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
-  const uint64_t total = h8[2 * (passes & 1)];
-  if (h8[2 * (passes & 1) + 1] != total) return zerr(1);                      // (cannot happen: every run has one start and one end)
+  STCHK(F.finish(h8, hdr, kHdrBytes));
+  const uint64_t total = h8[2 * (P.passes & 1)];
+  if (h8[2 * (P.passes & 1) + 1] != total) return zerr(1);                    // (cannot happen: every run has one start and one end)
   const size_t nOut = (size_t)std::min<uint64_t>(total, listCap);
   if (nOut) {
     std::vector<uint64_t> se(2 * nOut);
-    HIPCHK_CLR(hipMemcpyAsync(se.data(), starts, nOut * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipMemcpyAsync(se.data() + nOut, ends, nOut * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
+    HIPCHK_CLR(hipMemcpyAsync(se.data(), starts, nOut * 8, hipMemcpyDeviceToHost, F.s));
+    HIPCHK_CLR(hipMemcpyAsync(se.data() + nOut, ends, nOut * 8, hipMemcpyDeviceToHost, F.s));
+    HIPCHK_CLR(hipStreamSynchronize(F.s));
     for (size_t i = 0; i < nOut; i++) { hRanges[2 * i] = se[i]; hRanges[2 * i + 1] = se[nOut + i] - se[i]; }
   }
   *nRanges = total;
   if (differingBytes) *differingBytes = h8[kOffDiff / 8];
-  const uint64_t st8[8] = {n, n - decoded, decoded, h8[kOffBytes / 8], total, nOut, passes, 0};
-  for (int i = 0; i < 8; i++) E.cstats_[i] = st8[i];
-  E.cmpSizes_[0] = A.U; E.cmpSizes_[1] = B.U;
+  const uint64_t st8[8] = {P.n, P.n - decoded, decoded, h8[kOffBytes / 8], total, nOut, P.passes, 0};
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
+  sizes[0] = A.U; sizes[1] = B.U;
   return ok();
 }
 
-// ---- diff
-struct DiffImpl {
-  static Status run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
-                    uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
-                    uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
-};
+Status diff_run(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain,
+                size_t stagingBytes, const PatchOut& out) {
+  // ---- 1. arguments, 2. overlap
+  if (!out.args_ok() || (!dA && sizeA) || (!dB && sizeB) || (mode & ~kDecodeAll) || grain == 0 || grain > kTile || (grain & (grain - 1))) return zerr(42);
+  if (out.data_overlaps(dA, sizeA) || out.data_overlaps(dB, sizeB)) return zerr(42);
+  FramePasses F(E, ms);
+  STCHK(F.start());
+  // ---- 3. headers, A then B, 4. one frame size, 5. an update cannot shorten content
+  ArchiveView A, B;
+  STCHK(pair_views(E, dA, sizeA, dB, sizeB, &A, &B));
+  if (B.U < A.U) return zerr(40);
+  const uint64_t fs = A.fs, C = A.U;
+  const TailPlan tail = tail_plan(C, B.U, fs);                                 // B's frames that hold content behind C
+  const uint64_t tailBytes = B.U - C;
+  // ---- 6. scratch
+  PairPasses X = pair_passes(F, A, B, 0, C, stagingBytes);
+  const PassPlan& P = X.P;
+  const PassPlan PT = pass_plan(tail.fT0, tail.nTail, pass_slots(fs, stagingBytes));
+  const size_t listCap = (size_t)std::min<uint64_t>(out.writeCap, (C + 1) / 2);   // (writes are at least one byte long and one byte apart)
+  STCHK(F.open({(size_t)std::max<uint64_t>(2 * X.half, (uint64_t)PT.nSlots * fs) + 64, (size_t)P.nSlots + 64, 0, kDiffHdrBytes + (X.items_max() + 1) * 24 + 64,
+                        listCap * 16 + 64, std::max<size_t>(2 * (size_t)P.nSlots, PT.nSlots), std::max<size_t>(P.nSlots, PT.nSlots)}));
+  uint8_t* const hdr = F.tables;
+  uint64_t* const tot = (uint64_t*)(hdr + kOffTot3);
+  uint64_t* const tab = (uint64_t*)(hdr + kDiffHdrBytes);
+  uint64_t* const starts = F.list;
+  uint64_t* const ends = starts + listCap;
+  uint8_t* const dData = out.dData;
+  const uint64_t dataCap = out.dataCap;
+  // ---- pair passes: the compare's, with the grain kernels
+  uint64_t decoded = 0;
+  STCHK(F.begin(hdr, kDiffHdrBytes));
+  STCHK(X.run(mode, &decoded, [&](const FramePass& ps, uint32_t nDec) {
+      const uint32_t items = 1 + nDec * X.tpf;
+      TileArgs T;
+      STCHK(X.tiles(ps, &T));
+      hipLaunchKernelGGL(zra_diff_count_kernel, dim3(items), dim3(256), 0, F.s, T, grain, tab, (u64*)(hdr + kOffDiff), X.carry() + (ps.parity ^ 1));
+      hipLaunchKernelGGL(zra_diff_scan_kernel, dim3(1), dim3(1024), 0, F.s, tab, items, tot + 3 * ps.parity, tot + 3 * (ps.parity ^ 1));
+      if (listCap || dataCap) hipLaunchKernelGGL(zra_diff_fill_kernel, dim3(items), dim3(256), 0, F.s, T, grain, tab, starts, ends, (u64)listCap, dData, (u64)dataCap);
+      return ok();
+    }));
+  // ---- tail passes: B's frames from the one that holds C on, decoded on their own; their bytes behind C follow the dirty bytes
+  const uint64_t* const totEnd = tot + 3 * (P.passes & 1);                     // {writes, ends, dirty bytes} behind the last pair pass
+  STCHK(F.run(PT, FramePasses::Side{&B, 0, F.win}, nullptr, nullptr, nullptr, nullptr, [&](const FramePass& ps, uint32_t) {
+      const TailRun r = tail_run(tail, ps);
+      if (dataCap) diff_launch_tail(F.s, F.win + (r.pLo - ps.first * fs), r.len, totEnd + 2, r.pLo - C, dData, dataCap);
+      return ok();
+    }));
+  // ---- the counts, then the lists, once
+  uint64_t h16[kDiffHdrBytes / 8] = {0};
+  STCHK(F.finish(h16, hdr, kDiffHdrBytes));
+  const uint64_t* const t3 = h16 + kOffTot3 / 8 + 3 * (P.passes & 1);
+  const uint64_t total = t3[0], dirty = t3[2];
+  if (t3[1] != total) return zerr(1);                                         // (cannot happen: every write has one start and one end)
+  STCHK(F.patch(out, starts, ends, total, total, C, dirty, tailBytes));
+  const uint64_t st8[8] = {P.n, P.n - decoded, decoded, tail.nTail, total, dirty, P.passes + PT.passes, h16[kOffDiff / 8]};
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
+  return ok();
+}
+}  // namespace
+
+Status Engine::compare_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
+                                size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes) {
+  // (no status of the compare leaves a word behind: rangeCapacity cuts the list, it refuses nothing; the two sizes are words of the call too)
+  return entry_call(callStats_[kCallCompare], &callMs_[kCallCompare], {{nRanges, 1}, {differingBytes, 1}, {cmpSizes_, 2}}, false, [&] {
+    return compare_run(*this, callStats_[kCallCompare], &callMs_[kCallCompare], cmpSizes_, dA, sizeA, dB, sizeB, mode, offset, size, stagingBytes, hRanges, rangeCap,
+                       nRanges, differingBytes);
+  });
+}
 
 Status Engine::diff_archives(const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
                              uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
                              uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
-  for (auto& v : fstats_) v = 0;
-  diffMs_ = 0;
-  for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;
-  const Status st = DiffImpl::run(*this, dA, sizeA, dB, sizeB, mode, grain, stagingBytes, hOff, hSize, hDataOff, writeCap, nWrites, dData, dataCap, dataSize,
-                                  appendOffset, appendSize);
-  if (st.zra) {
-    diffMs_ = 0;
-    if (st.zra != kOutputTooSmall) for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;   // (rule 8 alone leaves what is needed)
-  }
-  return st;
-}
-
-Status DiffImpl::run(Engine& E, const uint8_t* dA, size_t sizeA, const uint8_t* dB, size_t sizeB, uint32_t mode, uint32_t grain, size_t stagingBytes,
-                     uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
-                     uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
-  constexpr uint32_t kDecodeAll = 1u;                                         // ZRA_HIP_DIFF_DECODE_ALL
-  // ---- 1. arguments, 2. overlap
-  if (!nWrites || !dataSize || !appendOffset || !appendSize || (!dA && sizeA) || (!dB && sizeB) || (writeCap && (!hOff || !hSize || !hDataOff)) ||
-      (!dData && dataCap) || (mode & ~kDecodeAll) || grain == 0 || grain > kTile || (grain & (grain - 1)))
-    return zerr(42);
-  auto overlaps = [&](const uint8_t* p, size_t n) { return dataCap && n && (uintptr_t)dData < (uintptr_t)p + n && (uintptr_t)p < (uintptr_t)dData + dataCap; };
-  if (overlaps(dA, sizeA) || overlaps(dB, sizeB)) return zerr(42);
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 3. headers, A then B, 4. one frame size, 5. an update cannot shorten content
-  ArchiveView A, B;
-  { Status st = E.archive_view(dA, sizeA, &A); if (st.zra) return st; }
-  if (A.fs == 0) return {kHeaderInvalid, 0};
-  { Status st = E.archive_view(dB, sizeB, &B); if (st.zra) return st; }
-  if (B.fs == 0) return {kHeaderInvalid, 0};
-  if (A.fs != B.fs) return zerr(40);
-  if (B.U < A.U) return zerr(40);
-  const uint64_t fs = A.fs, C = A.U, tailBytes = B.U - A.U;
-  const uint64_t n = (C + fs - 1) / fs;                                       // frames of [0, C), of both archives
-  const uint64_t fT0 = C / fs, nTail = tailBytes ? (B.U + fs - 1) / fs - fT0 : 0;   // B's frames that hold content behind C
-  // ---- 6. scratch
-  const uint32_t passSlots = pass_slots(2 * fs, stagingBytes), tailSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n), nTSlots = (uint32_t)std::min<uint64_t>(tailSlots, nTail);
-  const uint64_t passes = (n + passSlots - 1) / passSlots, tailPasses = (nTail + tailSlots - 1) / tailSlots;
-  const uint64_t half = ((uint64_t)nSlots * fs + 15) & ~15ull;
-  const uint32_t tpf = (uint32_t)((fs + kTile - 1) / kTile);
-  const size_t itemsMax = 1 + (size_t)nSlots * tpf;
-  const size_t listCap = (size_t)std::min<uint64_t>(writeCap, (C + 1) / 2);   // (writes are at least one byte long and one byte apart)
-  const size_t jobsMax = std::max<size_t>(2 * (size_t)nSlots, nTSlots), slotsMax = std::max<size_t>(nSlots, nTSlots);
-  if (!E.stage_.reserve((size_t)std::max<uint64_t>(2 * half, (uint64_t)nTSlots * fs) + 64) || !E.cmp_.flags.reserve((size_t)nSlots + 64) ||
-      !E.cmp_.tables.reserve(kDiffHdrBytes + (itemsMax + 1) * 24 + 64) || !E.cmp_.list.reserve(listCap * 16 + 64) ||
-      !E.frameOff_.reserve((jobsMax + 1) * 16) || !E.outOff_.reserve((slotsMax + 1) * 8) || !E.expect_.reserve((jobsMax + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const winA = E.stage_.as<uint8_t>();
-  uint8_t* const winB = winA + half;
-  uint8_t* const flags = E.cmp_.flags.as<uint8_t>();
-  uint8_t* const hdr = E.cmp_.tables.as<uint8_t>();
-  uint64_t* const tot = (uint64_t*)(hdr + kOffTot3);
-  uint32_t* const carry = (uint32_t*)(hdr + kOffCarry);
-  uint64_t* const tab = (uint64_t*)(hdr + kDiffHdrBytes);
-  uint64_t* const starts = E.cmp_.list.as<uint64_t>();
-  uint64_t* const ends = starts + listCap;
-  HIPCHK_CLR(hipMemsetAsync(hdr, 0, kDiffHdrBytes, s));
-  // ---- pair passes: the compare's, with the grain kernels
-  uint64_t decoded = 0;
-  // evCall_[0] .. evCall_[1] spans the diff's own launches between two decodes, as in the compare
-  auto take_time = [&]() { E.diffMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
-  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t first = p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(flags, 1, nj, s));
-    else
-      hipLaunchKernelGGL(zra_cmp_spans_kernel, dim3((nj + 3) / 4), dim3(256), 0, s, A.table, A.body, (u64)A.bodyBytes, B.table, B.body, (u64)B.bodyBytes, (u64)first,
-                         nj, flags);
-    hipLaunchKernelGGL(zra_cmp_jobs_kernel, dim3(1), dim3(1024), 0, s, flags, nj, A.table, (u64)A.U, B.table, (u64)B.U, (u64)fs, (u64)first, (u64)0, (u64)C,
-                       E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), nSlots, hdr);
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    uint32_t nDec = 0;
-    HIPCHK_CLR(hipMemcpyAsync(&nDec, hdr + kOffJobs, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-    HIPCHK_CLR(hipGetLastError());
-    take_time();
-    if (nDec > nj) return zerr(1);                                            // (cannot happen)
-    if (nDec) {
-      unsigned long long errA, errB;
-      { Status st = E.staged_pass(A, 0, nDec, winA, &errA); if (st.zra) return st; }
-      { Status st = E.staged_pass(B, nSlots, nDec, winB, &errB); if (st.zra) return st; }
-      if (errA != ~0ull || errB != ~0ull) return zerr(reported_code((errB >> 8) < (errA >> 8) ? errB : errA));
-      decoded += nDec;
-    }
-    const uint32_t items = 1 + nDec * tpf;
-    TileArgs T;
-    T.winA = winA; T.winB = winB; T.outOff = E.outOff_.as<uint64_t>(); T.flags = flags; T.fs = fs; T.first = first; T.lo = 0; T.hi = C; T.nj = nj; T.tpf = tpf;
-    T.carryIn = carry + (p & 1);
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    HIPCHK_CLR(hipMemsetAsync(carry + ((p + 1) & 1), 0, 4, s));
-    hipLaunchKernelGGL(zra_diff_count_kernel, dim3(items), dim3(256), 0, s, T, grain, tab, (u64*)(hdr + kOffDiff), carry + ((p + 1) & 1));
-    hipLaunchKernelGGL(zra_diff_scan_kernel, dim3(1), dim3(1024), 0, s, tab, items, tot + 3 * (p & 1), tot + 3 * ((p + 1) & 1));
-    if (listCap || dataCap)
-      hipLaunchKernelGGL(zra_diff_fill_kernel, dim3(items), dim3(256), 0, s, T, grain, tab, starts, ends, (u64)listCap, dData, (u64)dataCap);
-  }
-  // ---- tail passes: B's frames from the one that holds C on, decoded on their own; their bytes behind C follow the dirty bytes
-  const uint64_t* const totEnd = tot + 3 * (passes & 1);                       // {writes, ends, dirty bytes} behind the last pair pass
-  for (uint64_t p = 0; p < tailPasses; p++) {
-    const uint64_t first = fT0 + p * tailSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(tailSlots, nTail - p * tailSlots);
-    search_launch_jobs(s, B.table, fs, B.U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    unsigned long long errB;
-    { Status st = E.staged_pass(B, 0, nj, winA, &errB); if (st.zra) return st; }
-    take_time();
-    if (errB != ~0ull) return zerr(reported_code(errB));
-    const uint64_t pLo = std::max<uint64_t>(C, first * fs), pHi = std::min<uint64_t>(B.U, (first + nj) * fs), len = pHi - pLo;
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    if (dataCap)
-      hipLaunchKernelGGL(zra_diff_tail_kernel, dim3((unsigned)((len + 4095) / 4096)), dim3(256), 0, s, winA + (pLo - first * fs), (u64)len, totEnd + 2, (u64)(pLo - C),
-                         dData, (u64)dataCap);
-  }
-  // ---- the counts, then the lists, once
-  uint64_t h16[kDiffHdrBytes / 8] = {0};
-  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-  HIPCHK_CLR(hipMemcpyAsync(h16, hdr, kDiffHdrBytes, hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
-  const uint64_t* const t3 = h16 + kOffTot3 / 8 + 3 * (passes & 1);
-  const uint64_t total = t3[0], dirty = t3[2];
-  if (t3[1] != total) return zerr(1);                                         // (cannot happen: every write has one start and one end)
-  *nWrites = total; *dataSize = dirty + tailBytes; *appendOffset = dirty; *appendSize = tailBytes;
-  if (total > writeCap || dirty + tailBytes > dataCap) return {kOutputTooSmall, 0};
-  if (total) {
-    std::vector<uint64_t> se(2 * (size_t)total);
-    HIPCHK_CLR(hipMemcpyAsync(se.data(), starts, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipMemcpyAsync(se.data() + total, ends, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-    uint64_t at = 0;
-    for (size_t i = 0; i < total; i++) { hOff[i] = se[i]; hSize[i] = se[total + i] - se[i]; hDataOff[i] = at; at += hSize[i]; }
-  }
-  const uint64_t st8[8] = {n, n - decoded, decoded, nTail, total, dirty, passes + tailPasses, h16[kOffDiff / 8]};
-  for (int i = 0; i < 8; i++) E.fstats_[i] = st8[i];
-  return ok();
+  const PatchOut out{hOff, hSize, hDataOff, writeCap, nWrites, dData, dataCap, dataSize, appendOffset, appendSize};
+  // (rule 8, OutputTooSmall, alone leaves what is needed in the four words)
+  return entry_call(callStats_[kCallDiff], &callMs_[kCallDiff], {{nWrites, 1}, {dataSize, 1}, {appendOffset, 1}, {appendSize, 1}}, true, [&] {
+    return diff_run(*this, callStats_[kCallDiff], &callMs_[kCallDiff], dA, sizeA, dB, sizeB, mode, grain, stagingBytes, out);
+  });
 }
 
 }  // namespace zra_eng

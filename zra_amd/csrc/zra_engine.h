@@ -6,7 +6,7 @@
 #include <cstddef>
 #include <vector>
 #include "zra_kernels.h"
-#include "zra_scan_plan.h"   // pass_slots and the pass geometry of the range scans (host only)
+#include "zra_pass_plan.h"   // pass_slots, the pass geometry of the range scans (zra_scan_plan.h) and of the frame passes (host only)
 
 namespace zra_eng {
 
@@ -49,8 +49,10 @@ struct ArchiveView {
     return a;
   }
 };
-// The range scans (search, multi-pattern search, grep, extract; one host driver, zra_scan.h): the index of a call's counters
-enum : int { kScanSearch = 0, kScanMulti, kScanGrep, kScanExtract, kScanCalls };
+// The index of a device-archive call's counters and milliseconds (Engine::callStats_, callMs_): the range scans (search, multi-pattern
+// search, grep, extract; one host driver, zra_scan.h) first, then the calls on whole frames (zra_framepass.h, zra_verify.hip)
+enum : int { kScanSearch = 0, kScanMulti, kScanGrep, kScanExtract, kScanCalls,
+             kCallCompare = kScanCalls, kCallDiff, kCallSign, kCallSigDiff, kCallIndex, kCallLocate, kCallRead, kCallVerify, kCalls };
 // the code a failing frame is reported with: 255 (the decoder's own "regenerated another size than its slot") is corruption_detected
 __host__ __device__ inline int reported_code(unsigned long long firstError) { const int c = (int)(firstError & 0xFF); return c == 255 ? 20 : c; }
 // An update through an archive handle (zra_archive.hip, ZraHipArchiveUpdate): what the handle lends to Engine::update_archive and what
@@ -199,7 +201,7 @@ class Engine {
                         void* hFaults, size_t faultCap, size_t* nFaults);
   // the last verify_archive: {frames, checked, structure faults, content faults, decoded, content bytes regenerated, passes, 0}; all zero
   // unless it succeeded
-  void verify_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = vstats_[i]; }
+  void verify_stats(uint64_t out[8]) const { call_stats(kCallVerify, out); }
 
   // ---- search (zra_search.hip): every content offset p of [offset, offset + size) (size ~0: to the end) at which the patternSize host
   // bytes at hPattern occur whole inside the range, ascending. Only the frames of the range are decoded, whole, a staging window at a
@@ -207,9 +209,9 @@ class Engine {
   Status search_archive(const uint8_t* dArc, size_t arcSize, const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size,
                         size_t stagingBytes, uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
   // the last search_archive: {frames, decoded, content bytes regenerated, matches, matches listed, passes, 0, 0}; all zero unless it succeeded
-  void search_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanSearch][i]; }
+  void search_stats(uint64_t out[8]) const { call_stats(kScanSearch, out); }
   // bring-up: HIP-event time of the last search's scan launches (count, scan, fill, carry), summed over its passes
-  double search_scan_ms() const { return scanMs_[kScanSearch]; }
+  double search_scan_ms() const { return callMs_[kScanSearch]; }
 
   // ---- search for several patterns (zra_msearch.hip): every (content offset, pattern index) at which one of the nPatterns host
   // patterns (laid end to end at hPatterns, pattern i of hPatternSizes[i] bytes) occurs whole inside the range, ascending, in ONE
@@ -219,9 +221,9 @@ class Engine {
                               uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
   // the last search_archive_multi: {frames, decoded, content bytes regenerated, matches, matches listed, passes, patterns, filter
   // survivors}; all zero unless it succeeded. The single-pattern search and this one leave each other's counters alone
-  void search_multi_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanMulti][i]; }
+  void search_multi_stats(uint64_t out[8]) const { call_stats(kScanMulti, out); }
   // bring-up: HIP-event time of the last multi search's scan launches (count, scan, fill, carry), summed over its passes
-  double search_multi_scan_ms() const { return scanMs_[kScanMulti]; }
+  double search_multi_scan_ms() const { return callMs_[kScanMulti]; }
 
   // ---- grep (zra_grep.hip): the records of [offset, offset + size) (size ~0: to the end), cut at `delimiter`, in which a match of one
   // of the nPatterns host patterns starts (mode 1: in which none does), ascending, as {offset, size} pairs in hRecords, in ONE decode of
@@ -230,9 +232,9 @@ class Engine {
                       uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
   // the last grep_archive: {frames, decoded, content bytes regenerated, records of the range, records selected, records listed, passes,
   // matches}; all zero unless it succeeded. The searches and the grep leave each other's counters alone
-  void grep_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanGrep][i]; }
+  void grep_stats(uint64_t out[8]) const { call_stats(kScanGrep, out); }
   // bring-up: HIP-event time of the last grep's scan launches (count, scan, fill, carry), summed over its passes
-  double grep_scan_ms() const { return scanMs_[kScanGrep]; }
+  double grep_scan_ms() const { return callMs_[kScanGrep]; }
 
   // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
   // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:
@@ -242,9 +244,9 @@ class Engine {
                          uint8_t* dData, size_t dataCap, uint64_t* dataSize);
   // the last extract_records: {frames, decoded, content bytes regenerated, records of the range, records selected, packed bytes,
   // passes, matches}; all zero unless it succeeded. The searches, the grep and the extract leave each other's counters alone
-  void extract_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = scanStats_[kScanExtract][i]; }
+  void extract_stats(uint64_t out[8]) const { call_stats(kScanExtract, out); }
   // bring-up: HIP-event time of the last extract's own launches (count, scan, copy, carry), summed over its passes
-  double extract_ms() const { return scanMs_[kScanExtract]; }
+  double extract_ms() const { return callMs_[kScanExtract]; }
 
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
@@ -254,10 +256,10 @@ class Engine {
                           size_t stagingBytes, uint64_t* hRanges, size_t rangeCap, uint64_t* nRanges, uint64_t* differingBytes);
   // the last compare_archives: {frames of the range, equal by compressed bytes, frame pairs decoded, content bytes compared after decode,
   // ranges, ranges listed, passes, 0}; all zero unless it succeeded. compare_sizes: the two content sizes, likewise
-  void compare_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = cstats_[i]; }
+  void compare_stats(uint64_t out[8]) const { call_stats(kCallCompare, out); }
   void compare_sizes(uint64_t out[2]) const { out[0] = cmpSizes_[0]; out[1] = cmpSizes_[1]; }
   // bring-up: HIP-event time of the last compare's own launches (spans, jobs, count, scan, fill), summed over its passes
-  double compare_ms() const { return compareMs_; }
+  double compare_ms() const { return callMs_[kCallCompare]; }
 
   // ---- diff (zra_compare.hip): the patch that turns the content of the archive at dA into that of the archive at dB, in the shape
   // update_archive takes: the maximal runs of dirty grains of [0, UA) as writes in three host arrays, B's bytes of those runs packed
@@ -268,9 +270,9 @@ class Engine {
                        uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
   // the last diff_archives: {frames of [0, C), equal by compressed bytes, frame pairs decoded, tail frames of B decoded, writes, dirty
   // bytes, passes (pair + tail), dirty grains}; all zero unless it succeeded
-  void diff_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = fstats_[i]; }
+  void diff_stats(uint64_t out[8]) const { call_stats(kCallDiff, out); }
   // bring-up: HIP-event time of the last diff's own launches (spans, jobs, count, scan, fill, tail jobs, tail copy), summed over its passes
-  double diff_ms() const { return diffMs_; }
+  double diff_ms() const { return callMs_[kCallDiff]; }
 
   // ---- content signatures (zra_sign.hip): XXH64 words of the archive at dArc, a record of 1 + ceil(frameSize / grain) words per frame
   // (the frame's compressed span, then its grains as the diff cuts them), written into the records of frames [first, first + count) of
@@ -280,9 +282,9 @@ class Engine {
                       uint64_t* dSig, size_t sigCapWords, uint64_t info6[6]);
   // the last sign_archive: {frames of the archive, frames signed, grain words written, content bytes hashed, compressed bytes hashed,
   // passes, 0, 0}; all zero unless it succeeded
-  void sign_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = gstats_[i]; }
+  void sign_stats(uint64_t out[8]) const { call_stats(kCallSign, out); }
   // bring-up: HIP-event time of the last sign's own launches (span hash, grain hash), summed over its passes
-  double sign_ms() const { return signMs_; }
+  double sign_ms() const { return callMs_[kCallSign]; }
   // The diff of archive B against the SIGNATURE of an archive A that lies elsewhere: diff_archives' outputs at grain sig6[2], a grain
   // dirty when its word differs. sig6: ZraHipSignature's six words; dSigA: its words. Statuses and their order: zra_hip.h,
   // ZraHipDiffSignature.
@@ -291,8 +293,8 @@ class Engine {
                         uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize);
   // the last diff_signature, in diff_stats' shape: {frames of [0, C), equal by their frame word, decoded, tail frames decoded, writes,
   // dirty bytes, passes, dirty grains}; all zero unless it succeeded
-  void diff_signature_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = hstats_[i]; }
-  double diff_signature_ms() const { return sigDiffMs_; }
+  void diff_signature_stats(uint64_t out[8]) const { call_stats(kCallSigDiff, out); }
+  double diff_signature_ms() const { return callMs_[kCallSigDiff]; }
 
   // ---- record index (zra_records.hip): one 64-bit word per frame, bits 0..62 the delimiter bytes of the frame's content, bit 63 set iff
   // its last content byte is not the delimiter. index_records writes the words of frames [first, first + count) into their places in
@@ -301,25 +303,25 @@ class Engine {
   Status index_records(const uint8_t* dArc, size_t arcSize, uint32_t delimiter, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex,
                        size_t indexCapWords, uint64_t info6[6]);
   // the last index_records: {frames, frames indexed, content bytes scanned, delimiters in the range, passes, 0, 0, 0}; all zero unless it succeeded
-  void index_records_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = istats_[i]; }
+  void index_records_stats(uint64_t out[8]) const { call_stats(kCallIndex, out); }
   // bring-up: HIP-event time of the last index's own launches (count, frame words, totals), summed over its passes
-  double index_records_ms() const { return indexMs_; }
+  double index_records_ms() const { return callMs_[kCallIndex]; }
   // hRanges[i] = {start, size} of record hNumbers[i], in request order; only the frames that hold a boundary are decoded, and each is
   // checked against its word. Statuses and their order: zra_hip.h, ZraHipLocateRecords.
   Status locate_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
                         size_t stagingBytes, uint64_t* hRanges);
   // the last locate_records: {frames, records asked, boundaries looked up, frames decoded, content bytes regenerated, passes, 0, 0}
-  void locate_records_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = lstats_[i]; }
+  void locate_records_stats(uint64_t out[8]) const { call_stats(kCallLocate, out); }
   // bring-up: HIP-event time of the last locate's own launches (prefix, bounds, jobs, count, frame check, select), summed over its passes
-  double locate_records_ms() const { return locateMs_; }
+  double locate_records_ms() const { return callMs_[kCallLocate]; }
   // locate_records, then the records' bytes packed at dData in request order, each followed by one delimiter byte (the packing of
   // extract_records); hRanges is optional. Statuses and their order: zra_hip.h, ZraHipReadRecords.
   Status read_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
                       size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
   // the last read_records: {frames, records, packed bytes, frames decoded by the locate sweep, decode jobs of the read sweep, locate passes, 0, 0}
-  void read_records_stats(uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = rstats_[i]; }
+  void read_records_stats(uint64_t out[8]) const { call_stats(kCallRead, out); }
   // bring-up: HIP-event time of the last read's locate-sweep launches, summed over its passes (its read sweep: kernel_stats)
-  double read_records_ms() const { return readMs_; }
+  double read_records_ms() const { return callMs_[kCallRead]; }
 
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
@@ -370,6 +372,7 @@ class Engine {
     return true;
   }
   void free_scratch();                       // every DevBuf of the engine handed back: release_scratch() and the destructor
+  void call_stats(int which, uint64_t out[8]) const { for (int i = 0; i < 8; i++) out[i] = callStats_[which][i]; }
   hipEvent_t evR_[17] = {nullptr};   // per-round events of one encode batch: e[2r] before mf, e[2r+1] between, e[2r+2] after entropy
   // decode scratch
   DevBuf decFrames_, decTables_, decLists_, decCounters_, decLits_, decSeqs_, roundN_;
@@ -382,10 +385,12 @@ class Engine {
   DevBuf status_, produced_, frameMeta_, frameOff_, outOff_, expect_, result_, qmeta_;
   // THE plaintext staging window of the device-archive calls (batch, update, verify, search, multi-pattern search, grep, extract, compare,
   // diff, sign, signature diff): whole frames of one decode pass, slot s at s * frameSize; the range scans keep their carry area in
-  // front of slot 0 (zra_scan.h), the compare and the diffs two halves of slots. Every engine call runs on stream_ and returns synchronised, so one
-  // window is live at a time. THE RULE: a call reserves the window once, before it takes a pointer into it (reserve may move the buffer),
-  // and from there to its last use calls nothing that reserves it. decode_jobs / decode_pass / staged_pass and compress_frames do not
-  // (decoder and encoder scratch). The handle's read and update call ra_batch_body / update_archive, which do, but hold no window then.
+  // front of slot 0 (zra_scan.h), the compare and the diff two halves of slots (zra_pass_plan.h: pair_half). Every engine call runs on
+  // stream_ and returns synchronised, so one window is live at a time. THE RULE: a call reserves the window once, before it takes a
+  // pointer into it (reserve may move the buffer), and from there to its last use calls nothing that reserves it. decode_jobs /
+  // decode_pass / staged_pass and compress_frames do not (decoder and encoder scratch). The handle's read and update call ra_batch_body
+  // / update_archive, which do, but hold no window then. The calls on whole frames reserve it, and their tables (fp_, under the same
+  // rule), in one place: FramePasses::open (zra_framepass.h).
   DevBuf stage_;
   // encode scratch (see zra_encode.hip)
   struct EncCtx { DevBuf tables, seqs, lits, work, slots, misc, ck, sizes, rec; };   // rec: the split entropy stage's per-frame records (ZraEntRec)
@@ -407,50 +412,41 @@ class Engine {
   // the per-frame sizes / offsets / source displacements, the new seek table, the frames staged from a handle's cache (4 words each)
   struct UpdScratch { DevBuf plan, packed, encSizes, frames, table, copies; } upd_;
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // around a pass's stage-from-cache kernel (update through a handle), own launches (the range scans, compare, diff, sign); they never run inside each other.
+  // around a pass's stage-from-cache kernel (update through a handle), own launches (the range scans; compare, diff, sign, signature diff
+  // and index: zra_framepass.h, (time); the locate sweep); they never run inside each other.
   // [2] .. [3] and [4] .. [5]: a range scan through a handle, around a pass's job split and around its stage-from-cache kernel (zra_scan.h)
   hipEvent_t evCall_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list
   struct VerifyScratch { DevBuf plan, faults; } vfy_;
-  uint64_t vstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // range-scan scratch (zra_scan.h: search, multi-pattern search, grep, extract): the call's pattern table + totals + per-tile tables
   // (each call its own layout, uploaded before its first launch), its list. One pair: a call returns synchronised, so one is live at a
-  // time. The counters and the HIP-event time of each call's own launches stay apart: the calls leave each other's alone
+  // time
   struct ScanScratch { DevBuf tables, list; } scan_;
-  uint64_t scanStats_[kScanCalls][8] = {};
-  double scanMs_[kScanCalls] = {};
-  // compare scratch (zra_compare.hip): a flag per slot, the totals + carry + per-item table, the starts and ends of the listed ranges
-  struct CompareScratch { DevBuf flags, tables, list; } cmp_;
-  uint64_t cstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cmpSizes_[2] = {0, 0};
-  double compareMs_ = 0;
-  // diff (zra_compare.hip): the compare's scratch (one of the two runs at a time), its own counters
-  uint64_t fstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double diffMs_ = 0;
-  // signatures (zra_sign.hip): a decode flag per slot, a dirty flag per grain of a pass, the totals + carry + per-item table, the
-  // starts and ends of the listed writes; the counters of the sign call and of the signature diff
-  struct SignScratch { DevBuf flags, dirty, tables, list; } sig_;
-  uint64_t gstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double signMs_ = 0, sigDiffMs_ = 0;
+  // The counters and the HIP-event time of the own launches of every device-archive call, a row per call (kScanSearch .. kCallVerify),
+  // written through entry_call (zra_host.h): a call touches its own row and no other. The verify has no milliseconds
+  uint64_t callStats_[kCalls][8] = {};
+  double callMs_[kCalls] = {};
+  uint64_t cmpSizes_[2] = {0, 0};          // the two content sizes of the last compare
+  // frame-pass scratch (zra_framepass.h: compare, diff, sign, signature diff): a decode flag per slot, a dirty flag per grain of a pass
+  // (signature diff), the call's header words + per-item table, the starts and ends of the listed ranges or writes. One group: a call
+  // returns synchronised, so one is live at a time (THE RULE of stage_)
+  struct FramePassScratch { DevBuf flags, dirty, tables, list; } fp_;
   // record index (zra_records.hip): the header words + frame counts, prefix, slots and tile prefixes of a call; the record numbers,
-  // boundaries and positions of a locate. The three calls' counters stay apart
+  // boundaries and positions of a locate
   struct RecScratch { DevBuf tables, ranges; } rec_;
-  uint64_t istats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rstats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double indexMs_ = 0, locateMs_ = 0, readMs_ = 0;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend struct ScanImpl;          // the range scans drive the decoder's job arrays as the verifier does (zra_scan.h and the four calls' files)
-  friend struct CompareImpl;      // the compare drives the decoder's job arrays for two archives (zra_compare.hip)
-  friend struct DiffImpl;          // the diff does the same, and B's frames behind the common content on their own (zra_compare.hip)
-  friend struct SignImpl;          // the signature calls drive the decoder's job arrays of one archive (zra_sign.hip)
-  friend struct RecordsImpl;       // the record index drives the decoder's job arrays of one archive (zra_records.hip)
+  friend struct FramePasses;       // the one pass driver of compare, diff, sign, signature diff and index: scratch, job arrays, call events (zra_framepass.h)
+  friend struct RecordsImpl;       // the locate sweep drives the decoder's job arrays of the needed frames on its own (zra_records.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 
 // The range scans' per-pass steps that do not depend on the pattern, launched on stream s (zra_search.hip; the driver in zra_scan.h
-// makes the first and the third for all four calls, the multi-pattern search shares the second; the diffs and the sign call use the
-// first for their own passes): the decode jobs of frames [first, first + n) into slots 0 .. n - 1; bases[t] = *cntIn + the counts in front of item
+// makes the first and the third for all four calls, the multi-pattern search shares the second; the frame-pass driver, zra_framepass.h,
+// makes the first for its plain passes): the decode jobs of frames [first, first + n) into slots 0 .. n - 1; bases[t] = *cntIn + the counts in front of item
 // t, *cntOut = *cntIn + all of them; the last n bytes of the run win[.., L) moved to win[-n, 0), n <= 255.
 void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,
                         uint32_t* expect);

@@ -352,7 +352,7 @@ Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   // ---- 4. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.scanStats_[kScanExtract];
+  uint64_t* const stats = E.callStats_[kScanExtract];
   if (hi == lo || (!inv && hi - lo < mMin)) { stats[0] = arc.frames; return ok(); }   // no record, or none that could hold a match
   if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
   // ---- 5. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | XTotals | sums[tiles] | heads[tiles]
@@ -364,7 +364,7 @@ Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   build_table(*(Table*)head.data(), hPat, hSizes, nPat);
   ((XTotals*)(head.data() + kTotals))->st[0].start = lo;
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
-  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanExtract], head.data(), kHead, kTotals, sizeof(XTotals), kHead + P.tilesMax * (sizeof(XSum) + sizeof(XHead)) + 64,
+  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanExtract], head.data(), kHead, kTotals, sizeof(XTotals), kHead + P.tilesMax * (sizeof(XSum) + sizeof(XHead)) + 64,
                                listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const Table* const tbl = (const Table*)tb;

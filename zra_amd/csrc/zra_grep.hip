@@ -260,7 +260,7 @@ Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint
   // ---- 3. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.scanStats_[kScanGrep];
+  uint64_t* const stats = E.callStats_[kScanGrep];
   if (hi == lo || (!inv && hi - lo < mMin)) { stats[0] = arc.frames; return ok(); }   // no record, or none that could hold a match
   if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
   // ---- 4. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | Totals | sums[tiles] | heads[tiles]
@@ -272,7 +272,7 @@ Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint
   build_table(*(Table*)head.data(), hPat, hSizes, nPat);
   ((Totals*)(head.data() + kTotals))->st[0].start = lo;
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
-  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanGrep], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * (sizeof(Sum) + sizeof(Head)) + 64,
+  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanGrep], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * (sizeof(Sum) + sizeof(Head)) + 64,
                                listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const Table* const tbl = (const Table*)tb;

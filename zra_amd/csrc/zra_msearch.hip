@@ -127,7 +127,7 @@ Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   // ---- 3. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.scanStats_[kScanMulti];
+  uint64_t* const stats = E.callStats_[kScanMulti];
   if (hi - lo < mMin) {
     if (hPerPattern) std::fill(hPerPattern, hPerPattern + nPat, 0ull);
     stats[0] = arc.frames; stats[6] = nPat;
@@ -143,7 +143,7 @@ Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros)
   build_table(*(Table*)head.data(), hPat, hSizes, nPat);
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
-  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanMulti], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * 28 + 64, listCap * sizeof(Match) + 64, true,
+  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanMulti], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * 28 + 64, listCap * sizeof(Match) + 64, true,
                                [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const Table* const tbl = (const Table*)tb;

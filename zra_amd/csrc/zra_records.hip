@@ -9,6 +9,7 @@
 //   3. the delimiters of every 8 KiB tile of every slot are counted                                               zra_rec_count_kernel
 //   4. a wave per slot: the tile counts become their exclusive prefix and the frame's word                        zra_rec_frames_kernel
 // then one reduction over all F words as they lie in dIndex: D, R and the delimiters of the range                 zra_rec_totals_kernel
+// (plain passes of the one frame-pass driver, zra_framepass.h: steps 1 and 2, the timed span and the failing frame's code are its)
 // Locate:
 //   1. the counts of the F words (32 bits each) and their exclusive prefix, D behind it                zra_rec_counts_kernel, search_launch_scan
 //   2. a lane per request: up to two boundaries, delimiter r - 1 and delimiter r; each one is searched in the prefix,
@@ -31,7 +32,7 @@
 //      ends with {ZStdError, 20} before a range leaves the device.
 //  (d) an index call writes the words of its range only; locate and read write nothing but engine scratch and, the read, dData in
 //      front of dataCapacity.
-#include "zra_host.h"
+#include "zra_framepass.h"
 #include "zra_dev.h"
 #include <algorithm>
 #include <vector>
@@ -254,13 +255,14 @@ extern "C" __global__ void __launch_bounds__(256) zra_rec_delim_kernel(const u64
 namespace zra_eng {
 
 struct RecordsImpl {
-  static Status index(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex, size_t cap,
-                      uint64_t info6[6]);
+  static Status index(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count,
+                      size_t stagingBytes, uint64_t* dIndex, size_t cap, uint64_t info6[6]);
   // the locate sweep: hPos[2 i], hPos[2 i + 1] = start and end of record hNumbers[i]; st6 = {frames, boundaries looked up, frames
-  // decoded, content bytes regenerated, passes, D}. *view: the archive's checked view, for the read that follows.
-  static Status sweep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers,
+  // decoded, content bytes regenerated, passes, D}. *view: the archive's checked view, for the read that follows. *ms gains the
+  // HIP-event time of the sweep's own launches.
+  static Status sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers,
                       size_t n, size_t stagingBytes, const uint8_t* dData, size_t dataCap, std::vector<uint64_t>& hPos, uint64_t st6[6], ArchiveView* view);
-  static Status read(Engine& E, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
+  static Status read(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
                      size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
 };
 
@@ -274,84 +276,58 @@ uint32_t delim4(uint32_t d) { return d * 0x01010101u; }
 
 Status Engine::index_records(const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex,
                              size_t indexCapWords, uint64_t info6[6]) {
-  for (auto& v : istats_) v = 0;
-  indexMs_ = 0;
-  if (info6) for (int i = 0; i < 6; i++) info6[i] = 0;
-  const Status st = RecordsImpl::index(*this, dArc, arcSize, delim, first, count, stagingBytes, dIndex, indexCapWords, info6);
-  if (st.zra) {
-    indexMs_ = 0;
-    for (auto& v : istats_) v = 0;
-    if (st.zra != kOutputTooSmall && info6) for (int i = 0; i < 6; i++) info6[i] = 0;
-  }
-  return st;
+  // (rule 5, OutputTooSmall, leaves the first four words: they say how many words the index needs)
+  return entry_call(callStats_[kCallIndex], &callMs_[kCallIndex], {{info6, 6}}, true, [&] {
+    return RecordsImpl::index(*this, callStats_[kCallIndex], &callMs_[kCallIndex], dArc, arcSize, delim, first, count, stagingBytes, dIndex, indexCapWords, info6);
+  });
 }
 
-Status RecordsImpl::index(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex,
-                          size_t cap, uint64_t info6[6]) {
+Status RecordsImpl::index(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count,
+                          size_t stagingBytes, uint64_t* dIndex, size_t cap, uint64_t info6[6]) {
   // ---- 1. arguments, 2. overlap
   if (!info6 || (!dArc && arcSize) || (!dIndex && cap) || delim > 255) return zerr(42);
   if (cap > (~(size_t)0) / 8 || ranges_overlap(dIndex, 8 * (uint64_t)cap, dArc, arcSize)) return zerr(42);
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
+  FramePasses F(E, ms);
+  STCHK(F.start());
   // ---- 3. header: the statuses of ZraHipArchiveOpen
   ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  STCHK(E.archive_view(dArc, arcSize, &arc));
   if (arc.fs == 0) return {kHeaderInvalid, 0};
   const uint64_t fs = arc.fs, U = arc.U;
-  const uint64_t F = (U + fs - 1) / fs;
+  const uint64_t Fr = (U + fs - 1) / fs;
   // ---- 4. the range, as the verifier's
-  if (first > F || (count != ~0ull && count > F - first)) return {kOutOfBounds, 0};
-  const uint64_t n = count == ~0ull ? F - first : count;
-  const uint64_t head[4] = {U, fs, delim, F};
+  uint64_t n;
+  if (!frame_range(Fr, first, count, &n)) return {kOutOfBounds, 0};
+  const uint64_t head[4] = {U, fs, delim, Fr};
   for (int i = 0; i < 4; i++) info6[i] = head[i];
   // ---- 5. capacity: header arithmetic alone. (An empty range over words the caller holds still gives their totals.)
-  if (n && cap < F) return {kOutputTooSmall, 0};
-  if (!F || cap < F) { E.istats_[0] = F; return ok(); }
-  // ---- 6. scratch
-  const uint32_t passSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n), tpf = tiles_per_frame(fs);
-  const uint64_t passes = (n + passSlots - 1) / passSlots;
-  if (!E.rec_.tables.reserve(kHdrBytes + ((size_t)nSlots * (tpf + 1) + 16) * 4)) return zerr(64);
-  if (n && (!E.stage_.reserve((size_t)((uint64_t)nSlots * fs) + 64) || !E.frameOff_.reserve(((size_t)nSlots + 1) * 16) || !E.outOff_.reserve(((size_t)nSlots + 1) * 8) ||
-            !E.expect_.reserve(((size_t)nSlots + 1) * 4)))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const win = E.stage_.as<uint8_t>();
+  if (n && cap < Fr) return {kOutputTooSmall, 0};
+  if (!Fr || cap < Fr) { stats[0] = Fr; return ok(); }
+  // ---- 6. scratch: the call's tables are the record index's own; an empty range has no pass and reserves nothing of the decoder's
+  const PassPlan P = pass_plan(first, n, pass_slots(fs, stagingBytes));
+  const uint32_t tpf = tiles_per_frame(fs);
+  if (!E.rec_.tables.reserve(kHdrBytes + ((size_t)P.nSlots * (tpf + 1) + 16) * 4)) return zerr(64);
+  STCHK(F.open({n ? (size_t)((uint64_t)P.nSlots * fs) + 64 : 0, 0, 0, 0, 0, P.nSlots, P.nSlots}));
   uint8_t* const hdr = E.rec_.tables.as<uint8_t>();
   uint32_t* const tc = (uint32_t*)(hdr + kHdrBytes);
-  // ---- passes. evCall_[0] .. evCall_[1] spans the call's own launches between two decodes, as the sign call's
-  auto take_time = [&]() { E.indexMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
-  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t f0 = first + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    search_launch_jobs(s, arc.table, fs, U, f0, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    unsigned long long firstError;
-    { Status st = E.staged_pass(arc, 0, nj, win, &firstError); if (st.zra) return st; }
-    take_time();
-    if (firstError != ~0ull) return zerr(reported_code(firstError));          // the lowest failing frame of the first failing pass
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    hipLaunchKernelGGL(zra_rec_count_kernel, dim3(nj * tpf), dim3(256), 0, s, win, (u64)fs, (u64)U, (const u32*)nullptr, (u64)f0, tpf, delim4(delim), tc);
-    hipLaunchKernelGGL(zra_rec_frames_kernel, dim3((nj + 3) / 4), dim3(256), 0, s, win, (u64)fs, (u64)U, (const u32*)nullptr, (u64)f0, nj, tpf, delim, tc, (u64*)dIndex, 0u,
-                       (u32*)nullptr);
-  }
+  // ---- passes: plain, one side (zra_framepass.h)
+  STCHK(F.begin(nullptr, 0));
+  STCHK(F.run(P, FramePasses::Side{&arc, 0, F.win}, nullptr, nullptr, nullptr, nullptr, [&](const FramePass& ps, uint32_t) {
+      hipLaunchKernelGGL(zra_rec_count_kernel, dim3(ps.nj * tpf), dim3(256), 0, F.s, F.win, (u64)fs, (u64)U, (const u32*)nullptr, (u64)ps.first, tpf, delim4(delim), tc);
+      hipLaunchKernelGGL(zra_rec_frames_kernel, dim3((ps.nj + 3) / 4), dim3(256), 0, F.s, F.win, (u64)fs, (u64)U, (const u32*)nullptr, (u64)ps.first, ps.nj, tpf, delim, tc,
+                         (u64*)dIndex, 0u, (u32*)nullptr);
+      return ok();
+    }));
   uint64_t tot[3] = {0, 0, 0};
-  hipLaunchKernelGGL(zra_rec_totals_kernel, dim3(1), dim3(1024), 0, s, (const u64*)dIndex, (u64)F, (u64)first, (u64)(first + n), (u64*)(hdr + kOffTot));
-  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-  HIPCHK_CLR(hipMemcpyAsync(tot, hdr + kOffTot, 24, hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
+  hipLaunchKernelGGL(zra_rec_totals_kernel, dim3(1), dim3(1024), 0, F.s, (const u64*)dIndex, (u64)Fr, (u64)first, (u64)(first + n), (u64*)(hdr + kOffTot));
+  STCHK(F.finish(tot, hdr + kOffTot, 24));
   info6[4] = tot[0]; info6[5] = tot[1];
-  const uint64_t bytes = n ? std::min<uint64_t>(U, (first + n) * fs) - first * fs : 0;
-  const uint64_t st8[8] = {F, n, bytes, tot[2], passes, 0, 0, 0};
-  for (int i = 0; i < 8; i++) E.istats_[i] = st8[i];
+  const uint64_t st8[8] = {Fr, n, content_bytes(U, fs, first, n), tot[2], P.passes, 0, 0, 0};
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
   return ok();
 }
 
-Status RecordsImpl::sweep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers,
+Status RecordsImpl::sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers,
                           size_t n, size_t stagingBytes, const uint8_t* dData, size_t dataCap, std::vector<uint64_t>& hPos, uint64_t st6[6], ArchiveView* view) {
   // ---- 1. arguments and the info's own consistency, the read's overlap
   if (!info6 || (!dArc && arcSize) || (!dIndex && indexWords) || (n && !hNumbers)) return zerr(42);
@@ -364,7 +340,7 @@ Status RecordsImpl::sweep(Engine& E, const uint8_t* dArc, size_t arcSize, const 
   E.reset_decode_stats();
   // ---- 2. header, 3. the archive the index was made of
   ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
+  STCHK(E.archive_view(dArc, arcSize, &arc));
   if (arc.fs == 0) return {kHeaderInvalid, 0};
   const uint64_t fs = arc.fs, U = arc.U;
   const uint64_t F64 = (U + fs - 1) / fs;
@@ -399,7 +375,7 @@ Status RecordsImpl::sweep(Engine& E, const uint8_t* dArc, size_t arcSize, const 
   uint64_t* const numbers = E.rec_.ranges.as<uint64_t>();
   uint64_t* const bnd = numbers + n;
   uint64_t* const pos = bnd + 2 * n;
-  auto take_time = [&]() { E.locateMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
+  auto take_time = [&]() { *ms += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
   // ---- the prefix, the boundaries, the jobs
   HIPCHK_CLR(hipMemsetAsync(hdr, 0, kHdrBytes, s));
   HIPCHK_CLR(hipMemsetAsync(need, 0, F, s));
@@ -425,12 +401,14 @@ Status RecordsImpl::sweep(Engine& E, const uint8_t* dArc, size_t arcSize, const 
   // ---- 4. a record number at or behind R
   if (*(const uint32_t*)(hb + kOffOob)) return {kOutOfBounds, 0};
   if (nJobs > jobsMax) return zerr(1);                                        // (cannot happen)
-  // ---- passes over the needed frames
+  // ---- passes over the needed frames. Not the frame-pass driver's (zra_framepass.h): the jobs of all passes were built once, above, so
+  // a pass has no job launch and decodes at job base j0; its span closes BEHIND its own launches (the first span is the prefix's, taken
+  // above, hence `if (p)`); and the frames are not consecutive. Each of the three would be a special case there.
   const uint64_t passes = ((uint64_t)nJobs + passSlots - 1) / passSlots;
   for (uint64_t p = 0; p < passes; p++) {
     const uint32_t j0 = (uint32_t)(p * passSlots), nj = std::min<uint32_t>(passSlots, nJobs - j0);
     unsigned long long firstError;
-    { Status st = E.staged_pass(arc, j0, nj, win, &firstError); if (st.zra) return st; }
+    STCHK(E.staged_pass(arc, j0, nj, win, &firstError));
     if (p) take_time();
     if (firstError != ~0ull) return zerr(reported_code(firstError));          // 6. the lowest failing frame of the first failing pass
     HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
@@ -465,46 +443,40 @@ Status RecordsImpl::sweep(Engine& E, const uint8_t* dArc, size_t arcSize, const 
 
 Status Engine::locate_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
                               size_t stagingBytes, uint64_t* hRanges) {
-  for (auto& v : lstats_) v = 0;
-  locateMs_ = 0;
-  if (n && !hRanges) return zerr(42);
-  std::vector<uint64_t> hPos;
-  uint64_t st6[6];
-  ArchiveView arc;
-  const Status st = RecordsImpl::sweep(*this, dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, nullptr, 0, hPos, st6, &arc);
-  if (st.zra) { locateMs_ = 0; return st; }
-  for (size_t i = 0; i < n && hPos.size() == 2 * n; i++) { hRanges[2 * i] = hPos[2 * i]; hRanges[2 * i + 1] = hPos[2 * i + 1] - hPos[2 * i]; }
-  const uint64_t st8[8] = {st6[0], n, st6[1], st6[2], st6[3], st6[4], 0, 0};
-  for (int i = 0; i < 8; i++) lstats_[i] = st8[i];
-  return ok();
+  uint64_t (&stats)[8] = callStats_[kCallLocate];
+  // (the locate has no output words, and no status that keeps any)
+  return entry_call(stats, &callMs_[kCallLocate], {}, false, [&]() -> Status {
+    if (n && !hRanges) return zerr(42);
+    std::vector<uint64_t> hPos;
+    uint64_t st6[6];
+    ArchiveView arc;
+    const Status st = RecordsImpl::sweep(*this, &callMs_[kCallLocate], dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, nullptr, 0, hPos, st6, &arc);
+    if (st.zra) return st;
+    for (size_t i = 0; i < n && hPos.size() == 2 * n; i++) { hRanges[2 * i] = hPos[2 * i]; hRanges[2 * i + 1] = hPos[2 * i + 1] - hPos[2 * i]; }
+    const uint64_t st8[8] = {st6[0], n, st6[1], st6[2], st6[3], st6[4], 0, 0};
+    for (int i = 0; i < 8; i++) stats[i] = st8[i];
+    return ok();
+  });
 }
 
 Status Engine::read_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
                             size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
-  for (auto& v : rstats_) v = 0;
-  readMs_ = 0;
-  if (dataSize) *dataSize = 0;
-  if (!dataSize || (!dData && dataCap)) return zerr(42);
-  const Status st = RecordsImpl::read(*this, dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, hRanges, dData, dataCap, dataSize);
-  if (st.zra) {
-    readMs_ = 0;
-    for (auto& v : rstats_) v = 0;
-    if (st.zra != kOutputTooSmall) *dataSize = 0;
-  }
-  return st;
+  // (rule OutputTooSmall leaves the packed size the read needs)
+  return entry_call(callStats_[kCallRead], &callMs_[kCallRead], {{dataSize, 1}}, true, [&]() -> Status {
+    if (!dataSize || (!dData && dataCap)) return zerr(42);
+    return RecordsImpl::read(*this, callStats_[kCallRead], &callMs_[kCallRead], dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, hRanges, dData, dataCap,
+                             dataSize);
+  });
 }
 
-Status RecordsImpl::read(Engine& E, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
-                         size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
-  // the locate sweep runs under a timer of its own and leaves the locate's counters and time alone
-  const double keepMs = E.locateMs_;
-  E.locateMs_ = 0;
+Status RecordsImpl::read(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords,
+                         const uint64_t* hNumbers, size_t n, size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
+  // the locate sweep runs under a timer of its own (the read's, once it has succeeded) and leaves the locate's counters and time alone
+  double sweepMs = 0;
   std::vector<uint64_t> hPos;
   uint64_t st6[6];
   ArchiveView arc;
-  const Status st = sweep(E, dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, dData, dataCap, hPos, st6, &arc);
-  const double sweepMs = E.locateMs_;
-  E.locateMs_ = keepMs;
+  const Status st = sweep(E, &sweepMs, dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, dData, dataCap, hPos, st6, &arc);
   if (st.zra) return st;
   if (!n || hPos.size() != 2 * n) return ok();
   // ---- the located ranges as one batch: record k < D with its delimiter, an open record D without (its byte is stored below)
@@ -537,8 +509,8 @@ Status RecordsImpl::read(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   if (rs.zra) return rs;
   if (hRanges) for (size_t i = 0; i < n; i++) { hRanges[2 * i] = hPos[2 * i]; hRanges[2 * i + 1] = hPos[2 * i + 1] - hPos[2 * i]; }
   const uint64_t st8[8] = {st6[0], n, at, st6[2], readJobs, st6[4], 0, 0};
-  for (int i = 0; i < 8; i++) E.rstats_[i] = st8[i];
-  E.readMs_ = sweepMs;
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
+  *ms = sweepMs;
   return ok();
 }
 

@@ -55,22 +55,11 @@ struct ScanImpl {
                         uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                         uint64_t* dataSize, ScanCacheView* cv = nullptr);
 
-  // What a call of the family leaves behind, decided here for all four. `which`: kScanSearch .. kScanExtract; out0 / out1: the call's
-  // output words (either may be nullptr). The counters, the milliseconds and the words are zero before `run`; on any failure the
-  // counters and the milliseconds are zero again, and so are the words unless the status is OutputTooSmall (the extract's rule 7,
-  // whose two words say what the call needs). A success keeps what `run` wrote, the early return with only `frames` set included.
+  // What a call of the family leaves behind: entry_call's rule (zra_host.h). `which`: kScanSearch .. kScanExtract; out0 / out1: the
+  // call's output words (either may be nullptr), kept on OutputTooSmall (the extract's rule 7, whose two words say what the call needs).
   template <class Run>
   static Status call(Engine& E, int which, uint64_t* out0, uint64_t* out1, Run&& run) {
-    auto clear = [&](bool words) {
-      for (auto& v : E.scanStats_[which]) v = 0;
-      E.scanMs_[which] = 0;
-      if (words && out0) *out0 = 0;
-      if (words && out1) *out1 = 0;
-    };
-    clear(true);
-    const Status st = run();
-    if (st.zra) clear(st.zra != kOutputTooSmall);
-    return st;
+    return entry_call(E.callStats_[which], &E.callMs_[which], {{out0, 1}, {out1, 1}}, true, run);
   }
 
   static uint8_t* window(Engine& E) { return E.stage_.as<uint8_t>() + kScanMaxPattern; }   // slot 0; the carry area lies in front of it

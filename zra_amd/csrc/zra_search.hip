@@ -164,7 +164,7 @@ Status ScanImpl::search(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
   // ---- 3. the range [lo, hi)
   uint64_t lo, hi;
   if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.scanStats_[kScanSearch];
+  uint64_t* const stats = E.callStats_[kScanSearch];
   if (hi - lo < m) { stats[0] = arc.frames; return ok(); }
   if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};            // (content without frames: ra_header lets a frame size of 0 through)
   // ---- 4. the passes. tables: pattern (kMaxPattern bytes) | the ping-pong match count (2 words of 8 bytes, padded to 64) | bases[tiles] | counts[tiles]
@@ -173,7 +173,7 @@ Status ScanImpl::search(Engine& E, const uint8_t* dArc, size_t arcSize, const ui
   alignas(8) uint8_t padded[kMaxPattern + 64] = {0};                         // (the pattern's words behind its end read as zero, and so does the count)
   std::copy(hPat, hPat + m, padded);
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
-  Status st = ScanImpl::passes(E, arc, P, &E.scanMs_[kScanSearch], padded, sizeof(padded), kMaxPattern, 16, sizeof(padded) + P.tilesMax * 12 + 64, listCap * 8 + 64, true,
+  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanSearch], padded, sizeof(padded), kMaxPattern, 16, sizeof(padded) + P.tilesMax * 12 + 64, listCap * 8 + 64, true,
                                [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const uint32_t* const pat = (const uint32_t*)tb;

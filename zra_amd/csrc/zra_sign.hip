@@ -21,7 +21,9 @@
 // then B's frames from the one that holds C on, as the diff takes them (search_launch_jobs, staged_pass, diff_launch_tail), and the
 // counts and lists come to the host, once.
 //
-// Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
+// The passes of both calls run through the one frame-pass driver (zra_framepass.h: the sign's plain, the signature diff's flagged, the
+// tail's plain again): their order on the stream, the timed span and which failing frame ends the call are stated there. What the
+// kernels of this file rely on:
 //  (slots) slot = frame - first frame of the pass whether the frame is decoded or not, slot s at s * frameSize of the window. Grain
 //      i = s * gpf + g of a pass is the bytes [g * grain, min((g + 1) * grain, frameSize)) of slot s, clipped to C by arithmetic. A
 //      decoded frame regenerates its share of B's content (anything else is a failing frame and ends the call), which covers its share
@@ -38,7 +40,7 @@
 //      position depends on; they are added up with atomics.)
 //  (d) the lists stay on the device until the last pass is done; dData alone is written while the passes run, never at or behind
 //      dataCapacity. A sign call writes the words of the range's records only, and none at or behind sigCapacityWords.
-#include "zra_host.h"
+#include "zra_framepass.h"
 #include "zra_dev.h"
 #include <algorithm>
 
@@ -217,245 +219,166 @@ extern "C" __global__ void __launch_bounds__(256) zra_sig_fill_kernel(GrainArgs 
 // =================================================================================================
 namespace zra_eng {
 
-struct SignImpl {
-  static Status sign(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t grain, uint64_t seed, uint64_t first, uint64_t count, size_t stagingBytes,
-                     uint64_t* dSig, size_t sigCap, uint64_t info6[6]);
-  static Status diff(Engine& E, const uint64_t sig6[6], const uint64_t* dSigA, size_t sigWords, const uint8_t* dB, size_t sizeB, uint32_t mode, size_t stagingBytes,
-                     uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap, uint64_t* dataSize,
-                     uint64_t* appendOffset, uint64_t* appendSize);
-};
-
 namespace {
 constexpr uint32_t kMinGrain = 64, kMaxGrain = 8192;                          // ZRA_HIP_SIGN_MIN_GRAIN, ZRA_HIP_SIGN_MAX_GRAIN
 bool grain_ok(uint64_t g) { return g >= kMinGrain && g <= kMaxGrain && (g & (g - 1)) == 0; }
 bool ranges_overlap(const void* p, uint64_t n, const void* q, uint64_t m) {
   return n && m && (uintptr_t)p < (uintptr_t)q + m && (uintptr_t)q < (uintptr_t)p + n;
 }
+// the grains of a pass: nj slots of gpf grains each, clipped to C
+GrainArgs grain_args(const uint8_t* win, const uint8_t* flags, uint64_t fs, uint64_t C, uint32_t gpf, uint32_t grain, const FramePass& ps) {
+  GrainArgs G;
+  G.win = win; G.flags = flags; G.fs = fs; G.first = ps.first; G.C = C; G.total = (uint64_t)ps.nj * gpf; G.gpf = gpf; G.grain = grain;
+  return G;
+}
+
+Status sign_run(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, uint32_t grain, uint64_t seed, uint64_t first, uint64_t count,
+                size_t stagingBytes, uint64_t* dSig, size_t sigCap, uint64_t info6[6]) {
+  // ---- 1. arguments, 2. overlap
+  if (!info6 || (!dArc && arcSize) || (!dSig && sigCap) || !grain_ok(grain)) return zerr(42);
+  if (sigCap > (~(size_t)0) / 8 || ranges_overlap(dSig, 8 * (uint64_t)sigCap, dArc, arcSize)) return zerr(42);
+  FramePasses F(E, ms);
+  STCHK(F.start());
+  // ---- 3. header: the statuses of ZraHipArchiveOpen. (The header's CRC-32 is not looked at: that is the verifier's job.)
+  ArchiveView arc;
+  STCHK(E.archive_view(dArc, arcSize, &arc));
+  if (arc.fs == 0) return {kHeaderInvalid, 0};
+  const uint64_t fs = arc.fs, U = arc.U;
+  const uint64_t Fr = (U + fs - 1) / fs;                                      // (ra_header ties the table's frames to U when there is content)
+  const uint32_t gpf = (uint32_t)((fs + grain - 1) / grain), stride = 1 + gpf;
+  const uint64_t words = Fr * stride;
+  // ---- 4. the range, as the verifier's
+  uint64_t n;
+  if (!frame_range(Fr, first, count, &n)) return {kOutOfBounds, 0};
+  const uint64_t info[6] = {U, fs, grain, seed, Fr, words};
+  for (int i = 0; i < 6; i++) info6[i] = info[i];
+  if (!n) { stats[0] = Fr; return ok(); }
+  // ---- 5. capacity: header arithmetic alone
+  if (sigCap < words) return {kOutputTooSmall, 0};
+  // ---- 6. scratch
+  const PassPlan P = pass_plan(first, n, pass_slots(fs, stagingBytes));
+  STCHK(F.open({(size_t)((uint64_t)P.nSlots * fs) + 64, 0, 0, kHdrBytes, 0, P.nSlots, P.nSlots}));
+  uint8_t* const hdr = F.tables;
+  // ---- passes: plain, one side. The spans of a pass are hashed in front of its decode, its grains behind it
+  STCHK(F.begin(hdr, kHdrBytes));
+  STCHK(F.run(P, FramePasses::Side{&arc, 0, F.win}, nullptr, nullptr, nullptr,
+      [&](const FramePass& ps) {
+        hipLaunchKernelGGL(zra_sig_spans_kernel, dim3((ps.nj + 63) / 64), dim3(256), 0, F.s, arc.table, arc.body, (u64)arc.bodyBytes, (u64)ps.first, ps.nj, (u64)seed, stride,
+                           (u64*)dSig, (u64*)(hdr + kOffSpan), (const u64*)nullptr, (u8*)nullptr);
+        return ok();
+      },
+      [&](const FramePass& ps, uint32_t) {
+        const GrainArgs G = grain_args(F.win, nullptr, fs, U, gpf, grain, ps);
+        hipLaunchKernelGGL(zra_sig_grains_kernel, dim3((unsigned)((G.total + 63) / 64)), dim3(256), 0, F.s, G, (u64)seed, stride, (u64*)dSig, (const u64*)nullptr, (u8*)nullptr);
+        return ok();
+      }));
+  uint64_t spanBytes = 0;
+  STCHK(F.finish(&spanBytes, hdr + kOffSpan, 8));
+  const uint64_t full = first + n == Fr && U % fs ? n - 1 : n;                // frames of the range that hold frameSize bytes
+  const uint64_t grains = full * gpf + (full < n ? (U % fs + grain - 1) / grain : 0);
+  const uint64_t st8[8] = {Fr, n, grains, content_bytes(U, fs, first, n), spanBytes, P.passes, 0, 0};
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
+  return ok();
+}
+
+Status sigdiff_run(Engine& E, uint64_t (&stats)[8], double* ms, const uint64_t sig6[6], const uint64_t* dSigA, size_t sigWords, const uint8_t* dB, size_t sizeB,
+                   uint32_t mode, size_t stagingBytes, const PatchOut& out) {
+  constexpr uint32_t kDecodeAll = 1u;                                         // ZRA_HIP_SIGDIFF_DECODE_ALL
+  // ---- 1. arguments, the signature's own consistency among them, 2. overlap
+  if (!out.args_ok() || !sig6 || (!dSigA && sigWords) || (!dB && sizeB) || (mode & ~kDecodeAll)) return zerr(42);
+  const uint64_t C = sig6[0], fs = sig6[1], grain = sig6[2], seed = sig6[3], n = sig6[4], words = sig6[5];
+  if (!grain_ok(grain) || fs == 0 || fs > 0xFFFFFFFFull) return zerr(42);
+  const uint32_t gpf = (uint32_t)((fs + grain - 1) / grain), stride = 1 + gpf;
+  if (n != C / fs + (C % fs != 0) || n > 0xFFFFFFFFull || words != n * stride || sigWords < words) return zerr(42);
+  if (sigWords > (~(size_t)0) / 8 || out.data_overlaps(dB, sizeB) || out.data_overlaps(dSigA, 8 * (uint64_t)sigWords)) return zerr(42);
+  FramePasses F(E, ms);
+  STCHK(F.start());
+  // ---- 3. B's header, 4. one frame size, 5. an update cannot shorten content
+  ArchiveView B;
+  STCHK(E.archive_view(dB, sizeB, &B));
+  if (B.fs == 0) return {kHeaderInvalid, 0};
+  if (B.fs != fs) return zerr(40);
+  if (B.U < C) return zerr(40);
+  const TailPlan tail = tail_plan(C, B.U, fs);                                 // B's frames that hold content behind C
+  const uint64_t tailBytes = B.U - C;
+  // ---- 6. scratch. Only B is decoded: the window is not halved, and the tail's passes are as long as the others
+  const uint32_t passSlots = pass_slots(fs, stagingBytes);
+  const PassPlan P = pass_plan(0, n, passSlots), PT = pass_plan(tail.fT0, tail.nTail, passSlots);
+  const uint64_t grainsMax = (uint64_t)P.nSlots * gpf;
+  const size_t itemsMax = (size_t)((grainsMax + kItem - 1) / kItem);
+  const size_t listCap = (size_t)std::min<uint64_t>(out.writeCap, (n * gpf + 1) / 2);   // (writes are at least one grain long and one grain apart)
+  const size_t slotsMax = std::max<size_t>(P.nSlots, PT.nSlots);
+  if (itemsMax > 0xFFFFFFFEull) return zerr(64);
+  STCHK(F.open({(size_t)(slotsMax * fs) + 64, (size_t)P.nSlots + 64, (size_t)grainsMax + 64, kHdrBytes + (itemsMax + 1) * 24 + 64, listCap * 16 + 64, slotsMax, slotsMax}));
+  uint8_t* const hdr = F.tables;
+  uint64_t* const tot = (uint64_t*)(hdr + kOffTot);
+  uint32_t* const carry = (uint32_t*)(hdr + kOffCarry);
+  uint64_t* const tab = (uint64_t*)(hdr + kHdrBytes);
+  uint64_t* const starts = F.list;
+  uint64_t* const ends = starts + listCap;
+  uint8_t* const dData = out.dData;
+  const uint64_t dataCap = out.dataCap;
+  // ---- passes over [0, C): flagged, one side
+  uint64_t decoded = 0;
+  STCHK(F.begin(hdr, kHdrBytes));
+  STCHK(F.run(P, FramePasses::Side{&B, 0, F.win}, nullptr, (const uint32_t*)(hdr + kOffJobs), &decoded,
+      [&](const FramePass& ps) {
+        if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(F.flags, 1, ps.nj, F.s));
+        else
+          hipLaunchKernelGGL(zra_sig_spans_kernel, dim3((ps.nj + 63) / 64), dim3(256), 0, F.s, B.table, B.body, (u64)B.bodyBytes, (u64)ps.first, ps.nj, (u64)seed, stride,
+                             (u64*)nullptr, (u64*)nullptr, (const u64*)dSigA, F.flags);
+        hipLaunchKernelGGL(zra_sig_jobs_kernel, dim3(1), dim3(1024), 0, F.s, F.flags, ps.nj, B.table, (u64)B.U, (u64)fs, (u64)ps.first, F.frameOff, F.outOff, F.expect,
+                           (u32*)(hdr + kOffJobs));
+        return ok();
+      },
+      [&](const FramePass& ps, uint32_t) {
+        const GrainArgs G = grain_args(F.win, F.flags, fs, C, gpf, (uint32_t)grain, ps);
+        const uint32_t items = (uint32_t)((G.total + kItem - 1) / kItem);
+        uint32_t* const cIn = carry + ps.parity; uint32_t* const cOut = carry + (ps.parity ^ 1);
+        hipLaunchKernelGGL(zra_sig_grains_kernel, dim3((unsigned)((G.total + 63) / 64)), dim3(256), 0, F.s, G, (u64)seed, stride, (u64*)nullptr, (const u64*)dSigA, F.dirty);
+        hipLaunchKernelGGL(zra_sig_count_kernel, dim3(items), dim3(256), 0, F.s, G, F.dirty, cIn, tab, (u64*)(hdr + kOffGrains), cOut);
+        diff_launch_scan(F.s, tab, items, tot + 3 * ps.parity, tot + 3 * (ps.parity ^ 1));
+        if (listCap || dataCap)
+          hipLaunchKernelGGL(zra_sig_fill_kernel, dim3(items), dim3(256), 0, F.s, G, F.dirty, cIn, tab, starts, ends, (u64)listCap, dData, (u64)dataCap);
+        return ok();
+      }));
+  // ---- tail passes: B's frames from the one that holds C on, decoded on their own; their bytes behind C follow the dirty bytes
+  const uint64_t* const totEnd = tot + 3 * (P.passes & 1);                     // {writes, ends, dirty bytes} behind the last pass over [0, C)
+  STCHK(F.run(PT, FramePasses::Side{&B, 0, F.win}, nullptr, nullptr, nullptr, nullptr, [&](const FramePass& ps, uint32_t) {
+      const TailRun r = tail_run(tail, ps);
+      if (dataCap) diff_launch_tail(F.s, F.win + (r.pLo - ps.first * fs), r.len, totEnd + 2, r.pLo - C, dData, dataCap);
+      return ok();
+    }));
+  // ---- the counts, then the lists, once
+  uint64_t h16[kHdrBytes / 8] = {0};
+  STCHK(F.finish(h16, hdr, kHdrBytes));
+  const uint64_t* const t3 = h16 + kOffTot / 8 + 3 * (P.passes & 1);
+  const uint64_t total = t3[0], dirtyBytes = t3[2];
+  const bool open = ((const uint32_t*)((const uint8_t*)h16 + kOffCarry))[P.passes & 1] != 0;   // (runs) the last run ends at C
+  if (t3[1] + (open ? 1 : 0) != total) return zerr(1);                        // (cannot happen: every write has one start and one end)
+  STCHK(F.patch(out, starts, ends, total, t3[1], C, dirtyBytes, tailBytes));
+  const uint64_t st8[8] = {n, n - decoded, decoded, tail.nTail, total, dirtyBytes, P.passes + PT.passes, h16[kOffGrains / 8]};
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
+  return ok();
+}
 }  // namespace
 
 Status Engine::sign_archive(const uint8_t* dArc, size_t arcSize, uint32_t grain, uint64_t seed, uint64_t first, uint64_t count, size_t stagingBytes,
                             uint64_t* dSig, size_t sigCapWords, uint64_t info6[6]) {
-  for (auto& v : gstats_) v = 0;
-  signMs_ = 0;
-  if (info6) for (int i = 0; i < 6; i++) info6[i] = 0;
-  const Status st = SignImpl::sign(*this, dArc, arcSize, grain, seed, first, count, stagingBytes, dSig, sigCapWords, info6);
-  if (st.zra) {
-    signMs_ = 0;
-    for (auto& v : gstats_) v = 0;
-    if (st.zra != kOutputTooSmall && info6) for (int i = 0; i < 6; i++) info6[i] = 0;
-  }
-  return st;
-}
-
-Status SignImpl::sign(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t grain, uint64_t seed, uint64_t first, uint64_t count, size_t stagingBytes,
-                      uint64_t* dSig, size_t sigCap, uint64_t info6[6]) {
-  // ---- 1. arguments, 2. overlap
-  if (!info6 || (!dArc && arcSize) || (!dSig && sigCap) || !grain_ok(grain)) return zerr(42);
-  if (sigCap > (~(size_t)0) / 8 || ranges_overlap(dSig, 8 * (uint64_t)sigCap, dArc, arcSize)) return zerr(42);
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 3. header: the statuses of ZraHipArchiveOpen. (The header's CRC-32 is not looked at: that is the verifier's job.)
-  ArchiveView arc;
-  { Status st = E.archive_view(dArc, arcSize, &arc); if (st.zra) return st; }
-  if (arc.fs == 0) return {kHeaderInvalid, 0};
-  const uint64_t fs = arc.fs, U = arc.U;
-  const uint64_t F = (U + fs - 1) / fs;                                       // (ra_header ties the table's frames to U when there is content)
-  const uint32_t gpf = (uint32_t)((fs + grain - 1) / grain), stride = 1 + gpf;
-  const uint64_t words = F * stride;
-  // ---- 4. the range, as the verifier's
-  if (first > F || (count != ~0ull && count > F - first)) return {kOutOfBounds, 0};
-  const uint64_t n = count == ~0ull ? F - first : count;
-  const uint64_t info[6] = {U, fs, grain, seed, F, words};
-  if (!n) { for (int i = 0; i < 6; i++) info6[i] = info[i]; E.gstats_[0] = F; return ok(); }
-  // ---- 5. capacity: header arithmetic alone
-  for (int i = 0; i < 6; i++) info6[i] = info[i];
-  if (sigCap < words) return {kOutputTooSmall, 0};
-  // ---- 6. scratch
-  const uint32_t passSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n);
-  const uint64_t passes = (n + passSlots - 1) / passSlots;
-  if (!E.stage_.reserve((size_t)((uint64_t)nSlots * fs) + 64) || !E.sig_.tables.reserve(kHdrBytes) || !E.frameOff_.reserve(((size_t)nSlots + 1) * 16) ||
-      !E.outOff_.reserve(((size_t)nSlots + 1) * 8) || !E.expect_.reserve(((size_t)nSlots + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const win = E.stage_.as<uint8_t>();
-  uint8_t* const hdr = E.sig_.tables.as<uint8_t>();
-  HIPCHK_CLR(hipMemsetAsync(hdr, 0, kHdrBytes, s));
-  // ---- passes. evCall_[0] .. evCall_[1] spans the call's own launches between two decodes: the grains of a pass and the spans of the
-  // next one follow each other on the stream. Taken behind a synchronisation of the stream.
-  auto take_time = [&]() { E.signMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
-  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t f0 = first + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    hipLaunchKernelGGL(zra_sig_spans_kernel, dim3((nj + 63) / 64), dim3(256), 0, s, arc.table, arc.body, (u64)arc.bodyBytes, (u64)f0, nj, (u64)seed, stride, (u64*)dSig,
-                       (u64*)(hdr + kOffSpan), (const u64*)nullptr, (u8*)nullptr);
-    search_launch_jobs(s, arc.table, fs, U, f0, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    unsigned long long firstError;
-    { Status st = E.staged_pass(arc, 0, nj, win, &firstError); if (st.zra) return st; }
-    take_time();
-    if (firstError != ~0ull) return zerr(reported_code(firstError));          // the lowest failing frame of the first failing pass
-    GrainArgs G;
-    G.win = win; G.flags = nullptr; G.fs = fs; G.first = f0; G.C = U; G.total = (uint64_t)nj * gpf; G.gpf = gpf; G.grain = grain;
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    hipLaunchKernelGGL(zra_sig_grains_kernel, dim3((unsigned)((G.total + 63) / 64)), dim3(256), 0, s, G, (u64)seed, stride, (u64*)dSig, (const u64*)nullptr, (u8*)nullptr);
-  }
-  uint64_t spanBytes = 0;
-  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-  HIPCHK_CLR(hipMemcpyAsync(&spanBytes, hdr + kOffSpan, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
-  const uint64_t end = first + n, bytes = std::min<uint64_t>(U, end * fs) - first * fs;
-  const uint64_t full = end == F && U % fs ? n - 1 : n;                       // frames of the range that hold frameSize bytes
-  const uint64_t grains = full * gpf + (full < n ? (U % fs + grain - 1) / grain : 0);
-  const uint64_t st8[8] = {F, n, grains, bytes, spanBytes, passes, 0, 0};
-  for (int i = 0; i < 8; i++) E.gstats_[i] = st8[i];
-  return ok();
+  // (rule 5, OutputTooSmall, leaves the six words: they say how many words the signature needs)
+  return entry_call(callStats_[kCallSign], &callMs_[kCallSign], {{info6, 6}}, true, [&] {
+    return sign_run(*this, callStats_[kCallSign], &callMs_[kCallSign], dArc, arcSize, grain, seed, first, count, stagingBytes, dSig, sigCapWords, info6);
+  });
 }
 
 Status Engine::diff_signature(const uint64_t sig6[6], const uint64_t* dSigA, size_t sigWords, const uint8_t* dB, size_t sizeB, uint32_t mode, size_t stagingBytes,
                               uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap,
                               uint64_t* dataSize, uint64_t* appendOffset, uint64_t* appendSize) {
-  for (auto& v : hstats_) v = 0;
-  sigDiffMs_ = 0;
-  for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;
-  const Status st = SignImpl::diff(*this, sig6, dSigA, sigWords, dB, sizeB, mode, stagingBytes, hOff, hSize, hDataOff, writeCap, nWrites, dData, dataCap, dataSize,
-                                   appendOffset, appendSize);
-  if (st.zra) {
-    sigDiffMs_ = 0;
-    if (st.zra != kOutputTooSmall) for (uint64_t* w : {nWrites, dataSize, appendOffset, appendSize}) if (w) *w = 0;   // (rule 8 alone leaves what is needed)
-  }
-  return st;
-}
-
-Status SignImpl::diff(Engine& E, const uint64_t sig6[6], const uint64_t* dSigA, size_t sigWords, const uint8_t* dB, size_t sizeB, uint32_t mode, size_t stagingBytes,
-                      uint64_t* hOff, uint64_t* hSize, uint64_t* hDataOff, size_t writeCap, uint64_t* nWrites, uint8_t* dData, size_t dataCap, uint64_t* dataSize,
-                      uint64_t* appendOffset, uint64_t* appendSize) {
-  constexpr uint32_t kDecodeAll = 1u;                                         // ZRA_HIP_SIGDIFF_DECODE_ALL
-  // ---- 1. arguments, the signature's own consistency among them, 2. overlap
-  if (!nWrites || !dataSize || !appendOffset || !appendSize || !sig6 || (!dSigA && sigWords) || (!dB && sizeB) || (writeCap && (!hOff || !hSize || !hDataOff)) ||
-      (!dData && dataCap) || (mode & ~kDecodeAll))
-    return zerr(42);
-  const uint64_t C = sig6[0], fs = sig6[1], grain = sig6[2], seed = sig6[3], n = sig6[4], words = sig6[5];
-  if (!grain_ok(grain) || fs == 0 || fs > 0xFFFFFFFFull) return zerr(42);
-  const uint32_t gpf = (uint32_t)((fs + grain - 1) / grain), stride = 1 + gpf;
-  if (n != C / fs + (C % fs != 0) || n > 0xFFFFFFFFull || words != n * stride || sigWords < words) return zerr(42);
-  if (sigWords > (~(size_t)0) / 8 || ranges_overlap(dData, dataCap, dB, sizeB) || ranges_overlap(dData, dataCap, dSigA, 8 * (uint64_t)sigWords)) return zerr(42);
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 3. B's header, 4. one frame size, 5. an update cannot shorten content
-  ArchiveView B;
-  { Status st = E.archive_view(dB, sizeB, &B); if (st.zra) return st; }
-  if (B.fs == 0) return {kHeaderInvalid, 0};
-  if (B.fs != fs) return zerr(40);
-  if (B.U < C) return zerr(40);
-  const uint64_t tailBytes = B.U - C;
-  const uint64_t fT0 = C / fs, nTail = tailBytes ? (B.U + fs - 1) / fs - fT0 : 0;   // B's frames that hold content behind C
-  // ---- 6. scratch. Only B is decoded: the window is not halved
-  const uint32_t passSlots = pass_slots(fs, stagingBytes);
-  const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, n), nTSlots = (uint32_t)std::min<uint64_t>(passSlots, nTail);
-  const uint64_t passes = (n + passSlots - 1) / passSlots, tailPasses = (nTail + passSlots - 1) / passSlots;
-  const uint64_t grainsMax = (uint64_t)nSlots * gpf;
-  const size_t itemsMax = (size_t)((grainsMax + kItem - 1) / kItem);
-  const size_t listCap = (size_t)std::min<uint64_t>(writeCap, (n * gpf + 1) / 2);   // (writes are at least one grain long and one grain apart)
-  const size_t slotsMax = std::max<size_t>(nSlots, nTSlots);
-  if (itemsMax > 0xFFFFFFFEull) return zerr(64);
-  if (!E.stage_.reserve((size_t)(slotsMax * fs) + 64) || !E.sig_.flags.reserve((size_t)nSlots + 64) || !E.sig_.dirty.reserve((size_t)grainsMax + 64) ||
-      !E.sig_.tables.reserve(kHdrBytes + (itemsMax + 1) * 24 + 64) || !E.sig_.list.reserve(listCap * 16 + 64) || !E.frameOff_.reserve((slotsMax + 1) * 16) ||
-      !E.outOff_.reserve((slotsMax + 1) * 8) || !E.expect_.reserve((slotsMax + 1) * 4))
-    return zerr(64);
-  if (!E.call_events()) return zerr(1);
-  uint8_t* const win = E.stage_.as<uint8_t>();
-  uint8_t* const flags = E.sig_.flags.as<uint8_t>();
-  uint8_t* const dirty = E.sig_.dirty.as<uint8_t>();
-  uint8_t* const hdr = E.sig_.tables.as<uint8_t>();
-  uint64_t* const tot = (uint64_t*)(hdr + kOffTot);
-  uint32_t* const carry = (uint32_t*)(hdr + kOffCarry);
-  uint64_t* const tab = (uint64_t*)(hdr + kHdrBytes);
-  uint64_t* const starts = E.sig_.list.as<uint64_t>();
-  uint64_t* const ends = starts + listCap;
-  HIPCHK_CLR(hipMemsetAsync(hdr, 0, kHdrBytes, s));
-  // ---- passes over [0, C). evCall_[0] .. evCall_[1] spans the call's own launches between two decodes, as in the diff
-  uint64_t decoded = 0;
-  auto take_time = [&]() { E.sigDiffMs_ += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
-  HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-  for (uint64_t p = 0; p < passes; p++) {
-    const uint64_t first = p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, n - p * passSlots);
-    if (mode & kDecodeAll) HIPCHK_CLR(hipMemsetAsync(flags, 1, nj, s));
-    else
-      hipLaunchKernelGGL(zra_sig_spans_kernel, dim3((nj + 63) / 64), dim3(256), 0, s, B.table, B.body, (u64)B.bodyBytes, (u64)first, nj, (u64)seed, stride, (u64*)nullptr,
-                         (u64*)nullptr, (const u64*)dSigA, flags);
-    hipLaunchKernelGGL(zra_sig_jobs_kernel, dim3(1), dim3(1024), 0, s, flags, nj, B.table, (u64)B.U, (u64)fs, (u64)first, E.frameOff_.as<uint64_t>(),
-                       E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>(), (u32*)(hdr + kOffJobs));
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    uint32_t nDec = 0;
-    HIPCHK_CLR(hipMemcpyAsync(&nDec, hdr + kOffJobs, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-    HIPCHK_CLR(hipGetLastError());
-    take_time();
-    if (nDec > nj) return zerr(1);                                            // (cannot happen)
-    if (nDec) {
-      unsigned long long errB;
-      { Status st = E.staged_pass(B, 0, nDec, win, &errB); if (st.zra) return st; }
-      if (errB != ~0ull) return zerr(reported_code(errB));                    // the lowest failing frame of the first failing pass
-      decoded += nDec;
-    }
-    GrainArgs G;
-    G.win = win; G.flags = flags; G.fs = fs; G.first = first; G.C = C; G.total = (uint64_t)nj * gpf; G.gpf = gpf; G.grain = (uint32_t)grain;
-    const uint32_t items = (uint32_t)((G.total + kItem - 1) / kItem);
-    uint32_t* const cIn = carry + (p & 1); uint32_t* const cOut = carry + ((p + 1) & 1);
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    hipLaunchKernelGGL(zra_sig_grains_kernel, dim3((unsigned)((G.total + 63) / 64)), dim3(256), 0, s, G, (u64)seed, stride, (u64*)nullptr, (const u64*)dSigA, dirty);
-    hipLaunchKernelGGL(zra_sig_count_kernel, dim3(items), dim3(256), 0, s, G, dirty, cIn, tab, (u64*)(hdr + kOffGrains), cOut);
-    diff_launch_scan(s, tab, items, tot + 3 * (p & 1), tot + 3 * ((p + 1) & 1));
-    if (listCap || dataCap)
-      hipLaunchKernelGGL(zra_sig_fill_kernel, dim3(items), dim3(256), 0, s, G, dirty, cIn, tab, starts, ends, (u64)listCap, dData, (u64)dataCap);
-  }
-  // ---- tail passes: B's frames from the one that holds C on, decoded on their own; their bytes behind C follow the dirty bytes
-  const uint64_t* const totEnd = tot + 3 * (passes & 1);                       // {writes, ends, dirty bytes} behind the last pass over [0, C)
-  for (uint64_t p = 0; p < tailPasses; p++) {
-    const uint64_t first = fT0 + p * passSlots;
-    const uint32_t nj = (uint32_t)std::min<uint64_t>(passSlots, nTail - p * passSlots);
-    search_launch_jobs(s, B.table, fs, B.U, first, nj, E.frameOff_.as<uint64_t>(), E.outOff_.as<uint64_t>(), E.expect_.as<uint32_t>());
-    HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-    unsigned long long errB;
-    { Status st = E.staged_pass(B, 0, nj, win, &errB); if (st.zra) return st; }
-    take_time();
-    if (errB != ~0ull) return zerr(reported_code(errB));
-    const uint64_t pLo = std::max<uint64_t>(C, first * fs), pHi = std::min<uint64_t>(B.U, (first + nj) * fs), len = pHi - pLo;
-    HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
-    if (dataCap) diff_launch_tail(s, win + (pLo - first * fs), len, totEnd + 2, pLo - C, dData, dataCap);
-  }
-  // ---- the counts, then the lists, once
-  uint64_t h16[kHdrBytes / 8] = {0};
-  HIPCHK_CLR(hipEventRecord(E.evCall_[1], s));
-  HIPCHK_CLR(hipMemcpyAsync(h16, hdr, kHdrBytes, hipMemcpyDeviceToHost, s));
-  HIPCHK_CLR(hipStreamSynchronize(s));
-  HIPCHK_CLR(hipGetLastError());
-  take_time();
-  const uint64_t* const t3 = h16 + kOffTot / 8 + 3 * (passes & 1);
-  const uint64_t total = t3[0], dirtyBytes = t3[2];
-  const bool open = ((const uint32_t*)((const uint8_t*)h16 + kOffCarry))[passes & 1] != 0;   // (runs) the last run ends at C
-  if (t3[1] + (open ? 1 : 0) != total) return zerr(1);                        // (cannot happen: every write has one start and one end)
-  *nWrites = total; *dataSize = dirtyBytes + tailBytes; *appendOffset = dirtyBytes; *appendSize = tailBytes;
-  if (total > writeCap || dirtyBytes + tailBytes > dataCap) return {kOutputTooSmall, 0};
-  if (total) {
-    std::vector<uint64_t> se(2 * (size_t)total);
-    HIPCHK_CLR(hipMemcpyAsync(se.data(), starts, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    if (t3[1]) HIPCHK_CLR(hipMemcpyAsync(se.data() + total, ends, (size_t)t3[1] * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-    if (open) se[2 * (size_t)total - 1] = C;
-    uint64_t at = 0;
-    for (size_t i = 0; i < total; i++) { hOff[i] = se[i]; hSize[i] = se[total + i] - se[i]; hDataOff[i] = at; at += hSize[i]; }
-  }
-  const uint64_t st8[8] = {n, n - decoded, decoded, nTail, total, dirtyBytes, passes + tailPasses, h16[kOffGrains / 8]};
-  for (int i = 0; i < 8; i++) E.hstats_[i] = st8[i];
-  return ok();
+  const PatchOut out{hOff, hSize, hDataOff, writeCap, nWrites, dData, dataCap, dataSize, appendOffset, appendSize};
+  // (rule 8, OutputTooSmall, alone leaves what is needed in the four words)
+  return entry_call(callStats_[kCallSigDiff], &callMs_[kCallSigDiff], {{nWrites, 1}, {dataSize, 1}, {appendOffset, 1}, {appendSize, 1}}, true, [&] {
+    return sigdiff_run(*this, callStats_[kCallSigDiff], &callMs_[kCallSigDiff], sig6, dSigA, sigWords, dB, sizeB, mode, stagingBytes, out);
+  });
 }
 
 }  // namespace zra_eng

@@ -165,18 +165,20 @@ extern "C" __global__ void __launch_bounds__(256) zra_vfy_collect_kernel(const u
 namespace zra_eng {
 
 struct VerifyImpl {
-  static Status run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t mode, uint64_t first, uint64_t count, size_t stagingBytes,
+  static Status run(Engine& E, uint64_t (&stats)[8], const uint8_t* dArc, size_t arcSize, uint32_t mode, uint64_t first, uint64_t count, size_t stagingBytes,
                     void* hFaults, size_t faultCap, size_t* nFaults);
 };
 
 Status Engine::verify_archive(const uint8_t* dArc, size_t arcSize, uint32_t mode, uint64_t first, uint64_t count, size_t stagingBytes,
                               void* hFaults, size_t faultCap, size_t* nFaults) {
-  for (auto& v : vstats_) v = 0;
-  if (nFaults) *nFaults = 0;
-  return VerifyImpl::run(*this, dArc, arcSize, mode, first, count, stagingBytes, hFaults, faultCap, nFaults);
+  static_assert(sizeof(size_t) == sizeof(uint64_t), "the fault count is one output word");
+  // (the verify has no milliseconds, and no status that keeps the count: faultCapacity cuts the list, it refuses nothing)
+  return entry_call(callStats_[kCallVerify], nullptr, {{reinterpret_cast<uint64_t*>(nFaults), 1}}, false, [&] {
+    return VerifyImpl::run(*this, callStats_[kCallVerify], dArc, arcSize, mode, first, count, stagingBytes, hFaults, faultCap, nFaults);
+  });
 }
 
-Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t mode, uint64_t first, uint64_t count, size_t stagingBytes,
+Status VerifyImpl::run(Engine& E, uint64_t (&stats)[8], const uint8_t* dArc, size_t arcSize, uint32_t mode, uint64_t first, uint64_t count, size_t stagingBytes,
                        void* hFaults, size_t faultCap, size_t* nFaults) {
   // ---- 1. arguments
   if (!nFaults || (!dArc && arcSize) || (!hFaults && faultCap) || !mode || (mode & ~(kStageStructure | kStageContent))) return zerr(42);
@@ -196,9 +198,10 @@ Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t 
   // ---- 4. the range
   const uint32_t F = arc.frames;
   const uint64_t fs = arc.fs, U = arc.U;
-  if (first > F || (count != ~0ull && count > F - first)) return {kOutOfBounds, 0};
-  const uint32_t f0 = (uint32_t)first, n = count == ~0ull ? F - f0 : (uint32_t)count;
-  if (!n) { E.vstats_[0] = F; return ok(); }
+  uint64_t n64;
+  if (!frame_range(F, first, count, &n64)) return {kOutOfBounds, 0};
+  const uint32_t f0 = (uint32_t)first, n = (uint32_t)n64;
+  if (!n) { stats[0] = F; return ok(); }
   // ---- 5. scratch
   const bool content = (mode & kStageContent) != 0;
   const uint32_t passSlots = pass_slots(fs, stagingBytes);
@@ -266,7 +269,7 @@ Status VerifyImpl::run(Engine& E, const uint8_t* dArc, size_t arcSize, uint32_t 
   *nFaults = nf;
   const uint64_t structural = content ? (uint64_t)n - jobs : nf;
   const uint64_t st8[8] = {F, n, structural, nf - structural, jobs, regenerated, passes, 0};
-  for (int i = 0; i < 8; i++) E.vstats_[i] = st8[i];
+  for (int i = 0; i < 8; i++) stats[i] = st8[i];
   return ok();
 }
 
