@@ -184,8 +184,8 @@ struct ZraHipContentRange;   /* defined with ZraHipGrepArchive */
  *  - Scratch: the plain call's rule 4, plus, with at least 1 slot, 16 bytes per frame of a pass for the copy entries and the pass's two
  *    counts, which come to the host through a page-locked word of the handle, one small read-back per pass.
  *  Not covered: populating or refreshing the cache from a scan, scan kernels that read the arena in place, and handle variants of
- *  ZraHipVerifyArchive, ZraHipCompareArchives, ZraHipDiffArchives, ZraHipSignArchive and the record index (the follow-up: the same
- *  view of the cache will serve them), shards, the host-pointer API. */
+ *  ZraHipVerifyArchive, ZraHipCompareArchives, ZraHipDiffArchives and ZraHipSignArchive (the record index has them: below), shards,
+ *  the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipArchiveSearch(ZraHipArchive* archive,
     const void* hPattern, size_t patternSize,
     uint64_t offset, uint64_t size,
@@ -219,6 +219,73 @@ ZRA_EXPORT void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t
 /** Bring-up aid, like ZraHipDebugUpdateStageMs: HIP-event time of the last accepted scan's job-split and stage-from-cache launches,
  *  summed over its passes; 0 when none ran. archive NULL: 0. */
 ZRA_EXPORT double ZraHipDebugArchiveScanStageMs(const ZraHipArchive* archive);
+
+/* ---- the record index through the handle: index, locate and read records from the frame cache ----
+ * ZraHipIndexRecords, ZraHipLocateRecords and ZraHipReadRecords (below) are the one read path whose caller comes back to the same frames
+ * again and again: a server that hands out records by number draws its batches from a hot set, and every plain call decodes every frame
+ * that holds a boundary, the read a second time for the bytes. Through the handle the resident ones are not decoded. It also closes the
+ * handle's own workflow: after ZraHipArchiveUpdate the touched resident frames hold their new plaintext, and the sub-range call that
+ * refreshes their index words takes it from there. */
+struct ZraHipRecordIndex;    /* defined with ZraHipIndexRecords */
+
+/** ZraHipIndexRecords on the archive the handle is bound to: its arguments without engine, dArchive and archiveSize. Synchronous; stream
+ *  ordering as the other compute calls (ZraHipWaitStream). What is said here holds for ZraHipArchiveLocateRecords and
+ *  ZraHipArchiveReadRecords as well, each against its engine-level counterpart, run on the handle's engine, on the bytes the handle is
+ *  bound to, with the same arguments.
+ *  - Result: the words at dIndex, *info, hRanges, dData and *dataSize are byte for byte the plain call's, and so is what stays
+ *    untouched on failure.
+ *  - Statuses: the plain call's, in its order, with four differences. archive NULL -> {ZStdError, 42} in front of everything; the
+ *    output words are zeroed as the plain call zeroes them. The header is the handle's checked one and is not read from the device: a
+ *    frame size of 0 -> HeaderInvalid is the only header status left. Locate and read check the archive against *info (rule 3,
+ *    {ZStdError, 40}) by the handle's header. And the overlap rule (rule 2 of the index, the read's dData rule) additionally refuses a
+ *    dIndex or dData range that overlaps the handle's arena with {ZStdError, 42}, the arena check of ZraHipArchiveUpdate.
+ *  - Where the plaintext of a whole-frame sweep comes from (at least 1 slot): the sweep needs the frames of the index range, or the
+ *    boundary frames of the locate sweep. One that is resident is copied from its arena slot into its slot of the staging window,
+ *    min(frameSize, U - f * frameSize) bytes, and is not decoded (no damage is laundered by this: a frame is resident only after a whole
+ *    decode with status 0, checksum verified, exact size); one that is not resident is decoded whole, its checksum verified, exactly as
+ *    by the plain call. The tile-count, frame-word, stale-word and select kernels run over the same window and are the plain call's: a
+ *    stale word of a staged resident frame is found like any other ({ZStdError, 20}).
+ *  - Index and locate are not reads: they insert, evict and refresh nothing, set no reference bit and move no hand, and never write
+ *    the arena. Every word of ZraHipArchiveGetStats stays as it was, on success and on failure. A frame that fails is by construction
+ *    not resident; the status is the plain rule: the lowest failing frame of the first failing pass.
+ *  - 0 slots: the plain call minus the header read; the same kernels are launched.
+ *  - Stats: the call is one of its kind on the handle's engine: it overwrites ZraHipGetIndexRecordsStats and ZraHipDebugIndexRecordsMs
+ *    (locate, read: their own kind's) under their rules. The index's words are the plain call's. Through a handle the locate's words
+ *    [3] and [4] and the read's word [3] count decode jobs and the bytes those regenerated: they leave out the frames staged from the
+ *    arena; the read's word [4] is the frames its byte fetch decoded. ZraHipGetKernelStats reports 0 decode launches for a call
+ *    whose frames were all resident.
+ *  - Scratch: the plain call's, plus, with at least 1 slot, 16 bytes per frame of a pass for the copy entries and the pass's counts,
+ *    which come to the host through a page-locked word of the handle, one small read-back per pass.
+ *  Not covered: populating the cache from the index or the locate, sweep kernels that read the arena in place (they address frames
+ *  slot by slot, so they could), fusing the two sweeps of the read, shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipArchiveIndexRecords(ZraHipArchive* archive, uint32_t delimiter, uint64_t firstFrame, uint64_t frameCount,
+    size_t stagingBytes, uint64_t* dIndex, size_t indexCapacityWords, struct ZraHipRecordIndex* info);
+/** ZraHipLocateRecords through the handle: see ZraHipArchiveIndexRecords. Overwrites ZraHipGetLocateRecordsStats. */
+ZRA_EXPORT ZraStatus ZraHipArchiveLocateRecords(ZraHipArchive* archive, const struct ZraHipRecordIndex* info, const uint64_t* dIndex,
+    size_t indexWords, const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes, struct ZraHipContentRange* hRanges);
+/** ZraHipReadRecords through the handle: a composition, as the plain call is. The locate sweep runs as described with
+ *  ZraHipArchiveIndexRecords; then the located ranges are fetched with the semantics of ZraHipArchiveRead on this handle (record k < D
+ *  as [s_k, t_k + 1), the end bound inclusive; an open last record gets its delimiter byte stored separately).
+ *  THE BYTE FETCH IS A READ: it counts one read, hits plus misses are the distinct frames the located ranges touch, misses are
+ *  decoded whole, checksums verified, into CLOCK victims, more misses than slots go in passes, and a failing fetch leaves its
+ *  claimed slots empty.
+ *  Statuses: the locate sweep's, then OutputBufferTooSmall, then those of ZraHipArchiveRead for the located ranges. On a damaged
+ *  archive the one difference from the plain call is the one ZraHipArchiveRead has: with at least 1 slot a frame that only the fetch
+ *  decodes (an interior frame of a record longer than a frame) is decoded whole and its checksum looked at.
+ *  The sizing call (dataCapacity 0) runs the locate sweep only and changes no word of ZraHipArchiveGetStats. A second identical call
+ *  with every touched frame resident launches the decoder in neither sweep. dData must overlap neither the archive, the index nor the
+ *  handle's arena. Overwrites ZraHipGetReadRecordsStats. */
+ZRA_EXPORT ZraStatus ZraHipArchiveReadRecords(ZraHipArchive* archive, const struct ZraHipRecordIndex* info, const uint64_t* dIndex,
+    size_t indexWords, const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes, struct ZraHipContentRange* hRanges,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** out8 = {record calls accepted, frames staged from the cache in the last accepted call's whole-frame sweep, frames decoded by that
+ *  sweep, its passes, frames staged (cumulative), frames decoded (cumulative), 0, 0}, over the three calls above; the read's byte fetch
+ *  is in ZraHipArchiveGetStats. A call is accepted when it returns Success; the early returns that decode nothing count, with zeros
+ *  for the three last-call words. A call that is not accepted changes none of the words. archive NULL: all zero; out8 NULL: no-op. */
+ZRA_EXPORT void ZraHipArchiveGetRecordStats(const ZraHipArchive* archive, uint64_t* out8);
+/** Bring-up aid, like ZraHipDebugArchiveScanStageMs: HIP-event time of the last accepted record call's job-split and stage-from-cache
+ *  launches, summed over its passes; 0 when none ran. archive NULL: 0. */
+ZRA_EXPORT double ZraHipDebugArchiveRecordStageMs(const ZraHipArchive* archive);
 
 /* ---- update: a new archive from an old one, on the device ----
  * The reference's Compressor only ever starts from nothing. Frames are independent zstd frames tied together by the seek table alone,
@@ -806,7 +873,8 @@ typedef struct ZraHipRecordIndex { uint64_t contentSize; uint32_t frameSize; uin
  *  On Success info->delimiters and info->records are computed on the device from ALL F words as they lie in dIndex after the call
  *  (the empty range included, when indexCapacityWords >= frames): THEY ARE MEANINGFUL ONCE EVERY FRAME HAS BEEN INDEXED, by this call
  *  or by earlier ones into the same buffer. *info is zeroed on every status other than Success and OutputBufferTooSmall.
- *  Not covered: delimiters of more than one byte, a variant on ZraHipArchive handles, shards, the host-pointer API. */
+ *  Through an archive handle, ZraHipArchiveIndexRecords takes the resident frames of the range out of the cache.
+ *  Not covered: delimiters of more than one byte, shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipIndexRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, uint32_t delimiter,
     uint64_t firstFrame, uint64_t frameCount, size_t stagingBytes, uint64_t* dIndex, size_t indexCapacityWords, ZraHipRecordIndex* info);
 /** The last ZraHipIndexRecords on the engine (all zero after any outcome other than Success; engine NULL: all zero; out8 NULL: no-op):
@@ -840,7 +908,8 @@ ZRA_EXPORT double ZraHipDebugIndexRecordsMs(ZraHipEngine* engine);
  *  max(1, min(65,536, stagingBytes / frameSize)) NEEDED frames; per pass the delimiters of each 8 KiB tile are counted, the tiles of a
  *  frame prefixed, total and last byte compared with the word, and every boundary whose frame is in the pass is resolved by reading one
  *  tile. The cost follows the records asked for, not the archive: 100 records in 3 frames decode 3 frames. Every pass launches one wave
- *  per boundary of the call (those of other passes leave at once). */
+ *  per boundary of the call (those of other passes leave at once).
+ *  Through an archive handle, ZraHipArchiveLocateRecords decodes only the boundary frames that are not resident. */
 ZRA_EXPORT ZraStatus ZraHipLocateRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const ZraHipRecordIndex* info,
     const uint64_t* dIndex, size_t indexWords, const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes,
     ZraHipContentRange* hRanges);
@@ -866,7 +935,8 @@ ZRA_EXPORT double ZraHipDebugLocateRecordsMs(ZraHipEngine* engine);
  *  [s_k, t_k + 1), so its delimiter comes from the content; only an open last record gets its delimiter byte stored separately).
  *  THE KNOWN COST: a frame that holds a boundary is decoded by both sweeps. The read sweep decodes up to the last byte a record
  *  needs, whatever ZRA_HIP_OPT_RA_WHOLE_FRAMES says (the boundary frames were decoded whole, checksums verified, by the locate sweep).
- *  Fusing the two sweeps when all needed frames fit one window is not done. */
+ *  Fusing the two sweeps when all needed frames fit one window is not done. Through an archive handle, ZraHipArchiveReadRecords serves
+ *  both sweeps from the resident frames and keeps the frames it had to decode. */
 ZRA_EXPORT ZraStatus ZraHipReadRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const ZraHipRecordIndex* info,
     const uint64_t* dIndex, size_t indexWords, const uint64_t* hRecordNumbers, size_t nRecords, size_t stagingBytes,
     ZraHipContentRange* hRanges, void* dData, size_t dataCapacity, uint64_t* dataSize);

@@ -163,6 +163,12 @@ def load():
         "ZraHipArchiveExtractRecords": (S, [vp, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz, u64p]),
         "ZraHipArchiveGetScanStats": (None, [vp, u64p]),
         "ZraHipDebugArchiveScanStageMs": (ctypes.c_double, [vp]),
+        # the record index through the handle: likewise
+        "ZraHipArchiveIndexRecords": (S, [vp, u32, ctypes.c_uint64, ctypes.c_uint64, sz, vp, sz, ctypes.POINTER(ZraHipRecordIndex)]),
+        "ZraHipArchiveLocateRecords": (S, [vp, ctypes.POINTER(ZraHipRecordIndex), vp, sz, u64p, sz, sz, u64p]),
+        "ZraHipArchiveReadRecords": (S, [vp, ctypes.POINTER(ZraHipRecordIndex), vp, sz, u64p, sz, sz, u64p, vp, sz, u64p]),
+        "ZraHipArchiveGetRecordStats": (None, [vp, u64p]),
+        "ZraHipDebugArchiveRecordStageMs": (ctypes.c_double, [vp]),
         # update
         "ZraHipUpdateArchive": (S, [vp, vp, sz, vp, u64p, u64p, u64p, sz, vp, sz, vp, sz, szp, ctypes.c_int8, ctypes.c_bool]),
         "ZraHipGetUpdateStats": (None, [vp, u64p]),
@@ -260,6 +266,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
                    "ZraHipArchiveSearch", "ZraHipArchiveSearchMulti", "ZraHipArchiveGrep", "ZraHipArchiveExtractRecords", "ZraHipArchiveGetScanStats",
                    "ZraHipDebugArchiveScanStageMs",
+                   "ZraHipArchiveIndexRecords", "ZraHipArchiveLocateRecords", "ZraHipArchiveReadRecords", "ZraHipArchiveGetRecordStats",
+                   "ZraHipDebugArchiveRecordStageMs",
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
                    "ZraHipSearchArchive", "ZraHipGetSearchStats", "ZraHipDebugSearchScanMs",
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
@@ -798,6 +806,8 @@ ARCHIVE_UPDATE_STATS = ("updates", "frames", "archive_bytes", "staged", "refresh
 
 ARCHIVE_SCAN_STATS = ("scans", "staged", "decoded", "passes", "staged_total", "decoded_total")
 
+ARCHIVE_RECORD_STATS = ("calls", "staged", "decoded", "passes", "staged_total", "decoded_total")
+
 
 UPDATE_STATS = ("frames", "touched", "decoded", "compressed", "carried_bytes", "encoded_bytes", "content_bytes", "passes")
 
@@ -955,6 +965,65 @@ class Archive:
     def scan_stage_ms(self):
         """bring-up: HIP-event time of the last accepted scan's job-split and stage-from-cache launches, summed over its passes."""
         return self.L.ZraHipDebugArchiveScanStageMs(self.h)
+
+    # ---- the record index through the handle: Engine.index_records / locate_records / read_records of the archive the handle serves,
+    # without d_archive and size. A whole-frame sweep copies the resident frames it needs out of the cache and decodes only the others.
+    # Index and locate are not reads: the cache and stats() do not change. The read's byte fetch is a read of the handle: it counts in
+    # stats() and keeps the frames it decoded. The call overwrites the engine's counters of its kind (engine.index_records_stats() ...).
+    def index_records(self, d_index, index_cap_words, *, delimiter=0x0A, first_frame=0, frame_count=None, staging_bytes=0):
+        """ZraHipArchiveIndexRecords: Engine.index_records through the handle; d_index must overlap neither the archive nor the cache.
+        Returns the RecordIndex of the whole archive; OutputBufferTooSmall carries the words needed in ZraError.needed_words."""
+        info = ZraHipRecordIndex()
+        self.engine._order()
+        st = self.L.ZraHipArchiveIndexRecords(self.h, delimiter, first_frame, 0xFFFFFFFFFFFFFFFF if frame_count is None else frame_count, staging_bytes,
+                                              d_index or None, index_cap_words, ctypes.byref(info))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipArchiveIndexRecords")
+            e.needed_words = info.frames
+            raise e
+        return RecordIndex(info.contentSize, info.frameSize, info.delimiter, info.frames, info.delimiters, info.records)
+
+    def locate_records(self, index, d_index, index_words, numbers, *, staging_bytes=0):
+        """ZraHipArchiveLocateRecords: Engine.locate_records through the handle. Returns [(offset, size)] in request order."""
+        import numpy as np
+        nums = np.ascontiguousarray(np.asarray(numbers, dtype=np.uint64))
+        n = int(nums.size)
+        out = np.zeros(2 * max(n, 1), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        info = ZraHipRecordIndex(*index)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveLocateRecords(self.h, ctypes.byref(info), d_index or None, index_words, p(nums) if n else None, n, staging_bytes,
+                                               p(out) if n else None), "ZraHipArchiveLocateRecords")
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)]
+
+    def read_records(self, index, d_index, index_words, numbers, d_data, data_cap, *, staging_bytes=0, ranges=True):
+        """ZraHipArchiveReadRecords: Engine.read_records through the handle; d_data must overlap neither the archive, the index nor the
+        cache. Returns (data_size, [(offset, size)] or None without `ranges`); OutputBufferTooSmall carries ZraError.needed_data."""
+        import numpy as np
+        nums = np.ascontiguousarray(np.asarray(numbers, dtype=np.uint64))
+        n = int(nums.size)
+        out = np.zeros(2 * max(n, 1), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        info = ZraHipRecordIndex(*index)
+        ds = ctypes.c_uint64(0)
+        self.engine._order()
+        st = self.L.ZraHipArchiveReadRecords(self.h, ctypes.byref(info), d_index or None, index_words, p(nums) if n else None, n, staging_bytes,
+                                             p(out) if ranges and n else None, d_data or None, data_cap, ctypes.byref(ds))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipArchiveReadRecords")
+            e.needed_data = ds.value
+            raise e
+        return ds.value, ([(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n)] if ranges else None)
+
+    def record_stats(self):
+        """Counters of the record calls through this handle, keyed by ARCHIVE_RECORD_STATS."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipArchiveGetRecordStats(self.h, a)
+        return dict(zip(ARCHIVE_RECORD_STATS, (int(v) for v in a[:6])))
+
+    def record_stage_ms(self):
+        """bring-up: HIP-event time of the last accepted record call's job-split and stage-from-cache launches, summed over its passes."""
+        return self.L.ZraHipDebugArchiveRecordStageMs(self.h)
 
     def drop_cache(self):
         _chk(self.L.ZraHipArchiveDropCache(self.h), "ZraHipArchiveDropCache")

@@ -13,7 +13,9 @@ class ArchiveCache {
   ~ArchiveCache();
   // query i: bytes [hOff[i], hOff[i] + hSize[i]) of the content at dOut + hOutOff[i]; wholeFramesOpt: the process-wide
   // ZRA_HIP_OPT_RA_WHOLE_FRAMES (what a handle without slots follows, like the batch call)
-  Status read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt);
+  // endInclusive (internal, the record read alone): a query may end AT the content's end; *jobsOut (optional): the frames the read decoded
+  Status read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt, bool endInclusive = false,
+              uint32_t* jobsOut = nullptr);
   // forget every resident frame (the cumulative counters stay)
   Status drop();
   // {slots, resident, reads, hits, misses, evictions, uncompressed size, frame size}
@@ -41,6 +43,19 @@ class ArchiveCache {
   void scan_stats(uint64_t out[8]) const;
   // bring-up: HIP-event time of the last accepted scan's job-split and stage-from-cache launches, summed over its passes (0: none ran)
   double scan_stage_ms() const { return scanStageMs_; }
+  // The record calls of the engine (zra_records.hip) on the archive the handle is bound to (zra_hip.h: ZraHipArchiveIndexRecords,
+  // ZraHipArchiveLocateRecords, ZraHipArchiveReadRecords): a whole-frame sweep copies the resident frames it needs out of the arena and
+  // decodes the others. Index and locate are not reads: they change nothing of the cache and none of stats()' words, on any status. The
+  // read's byte fetch is one: read() of the located ranges, with the inclusive end bound.
+  Status index_records(uint32_t delimiter, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex, size_t indexCapWords, uint64_t info6[6]);
+  Status locate_records(const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n, size_t stagingBytes, uint64_t* hRanges);
+  Status read_records(const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n, size_t stagingBytes, uint64_t* hRanges,
+                      uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+  // {record calls accepted, frames staged from the cache by the last accepted call's whole-frame sweep, frames decoded by it, its passes,
+  // staged (cumulative), decoded (cumulative), 0, 0}
+  void record_stats(uint64_t out[8]) const;
+  // bring-up: HIP-event time of the last accepted record call's job-split and stage-from-cache launches, summed over its passes (0: none ran)
+  double record_stage_ms() const { return recStageMs_; }
 
  private:
   ArchiveCache() = default;
@@ -48,7 +63,8 @@ class ArchiveCache {
   ArchiveView view() const { return ArchiveView::over(h_, dArc_, arcSize_); }   // the archive the handle serves now, its header checked at open / by the update
   ScanCacheView scan_view() const;                  // what a scan borrows: header, arena, table, the pinned count words
   Status scanned(Status st, const ScanCacheView& v); // the scan counters, kept when the scan was accepted
-  Status read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq);
+  Status recorded(Status st, const ScanCacheView& v); // the record counters, kept when the call was accepted
+  Status read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool endInclusive, uint32_t* jobsOut);
   Engine* e_ = nullptr;
   const uint8_t* dArc_ = nullptr;
   size_t arcSize_ = 0;
@@ -72,6 +88,8 @@ class ArchiveCache {
   uint64_t reads_ = 0, hits_ = 0, misses_ = 0, evictions_ = 0, resident_ = 0;
   uint64_t scans_ = 0, scanLast_[3] = {0, 0, 0}, scanStagedTotal_ = 0, scanDecodedTotal_ = 0;
   double scanStageMs_ = 0;
+  uint64_t recCalls_ = 0, recLast_[3] = {0, 0, 0}, recStagedTotal_ = 0, recDecodedTotal_ = 0;
+  double recStageMs_ = 0;
   uint64_t updates_ = 0, stagedLast_ = 0, refreshedLast_ = 0, stagedTotal_ = 0, refreshedTotal_ = 0;
 };
 

@@ -343,13 +343,56 @@ Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSize
   }), v);
 }
 
-Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt) {
+// ---- the record calls through the handle. Index and locate are not reads, like the scans above: their sweeps read the arena and slotOf
+// and write neither. The read's byte fetch is a read of the handle, through read() itself: reads / hits / misses / evictions / resident
+// move exactly as for ZraHipArchiveRead of the located ranges. The call is one of its kind on the handle's engine.
+Status ArchiveCache::recorded(Status st, const ScanCacheView& v) {
+  if (st.zra) return st;
+  recCalls_++;
+  recLast_[0] = v.staged; recLast_[1] = v.decoded; recLast_[2] = v.passes;
+  recStagedTotal_ += v.staged; recDecodedTotal_ += v.decoded;
+  recStageMs_ = v.stageMs;
+  return st;
+}
+
+void ArchiveCache::record_stats(uint64_t out[8]) const {
+  const uint64_t v[8] = {recCalls_, recLast_[0], recLast_[1], recLast_[2], recStagedTotal_, recDecodedTotal_, 0, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+
+Status ArchiveCache::index_records(uint32_t delimiter, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex, size_t indexCapWords, uint64_t info6[6]) {
+  ScanCacheView v = scan_view();
+  return recorded(e_->index_records(dArc_, arcSize_, delimiter, first, count, stagingBytes, dIndex, indexCapWords, info6, &v), v);
+}
+
+Status ArchiveCache::locate_records(const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n, size_t stagingBytes,
+                                    uint64_t* hRanges) {
+  ScanCacheView v = scan_view();
+  return recorded(e_->locate_records(dArc_, arcSize_, info6, dIndex, indexWords, hNumbers, n, stagingBytes, hRanges, &v), v);
+}
+
+Status ArchiveCache::read_records(const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n, size_t stagingBytes,
+                                  uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
+  ScanCacheView v = scan_view();
+  RecordFetch fetch;
+  fetch.ctx = this;
+  // (the read sweep decodes up to the last byte a record needs whatever the process option says, as the plain call's: what a handle
+  // without slots follows; with slots a miss is decoded whole either way)
+  fetch.fn = [](void* ctx, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint32_t* jobs) {
+    return ((ArchiveCache*)ctx)->read(dOut, hOff, hSize, hOutOff, nq, false, true, jobs);
+  };
+  return recorded(e_->read_records(dArc_, arcSize_, info6, dIndex, indexWords, hNumbers, n, stagingBytes, hRanges, dData, dataCap, dataSize, &v, &fetch), v);
+}
+
+Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool wholeFramesOpt, bool endInclusive,
+                          uint32_t* jobsOut) {
   Engine& E = *e_;
+  if (jobsOut) *jobsOut = 0;
   HIPCHK_CLR(hipSetDevice(E.device_));
   if (!slots_) {
     // no cache: the batch call itself, header read and checked at open
     E.set_ra_verify_whole_frames(wholeFramesOpt);
-    Status st = E.ra_batch_body(view(), dOut, hOff, hSize, hOutOff, nq);
+    Status st = E.ra_batch_body(view(), dOut, hOff, hSize, hOutOff, nq, endInclusive, jobsOut);
     if (st.zra == kOutOfBounds) return st;
     reads_++;
     const uint64_t fs = h_.frameSize;
@@ -366,10 +409,10 @@ Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* h
     return st;
   }
   E.reset_decode_stats();
-  return read_cached(dOut, hOff, hSize, hOutOff, nq);
+  return read_cached(dOut, hOff, hSize, hOutOff, nq, endInclusive, jobsOut);
 }
 
-Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq) {
+Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, bool endInclusive, uint32_t* jobsOut) {
   Engine& E = *e_;
   hipStream_t s = E.stream_;
   const ArchiveView a = view();
@@ -377,7 +420,7 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
   const uint32_t nF = a.frames;
   if (nq == 0) { reads_++; return ok(); }
   uint64_t nSlices = 0;
-  { Status st = E.ra_walk_queries(a, hOff, hSize, hOutOff, nq, &nSlices); if (st.zra) return st; }
+  { Status st = E.ra_walk_queries(a, hOff, hSize, hOutOff, nq, &nSlices, endInclusive); if (st.zra) return st; }
   reads_++;
   if (nSlices == 0) { HIPCHK_CLR(hipStreamSynchronize(s)); return ok(); }
   // the batch's planner scratch (the lookup's two result words inside its totals), then seen[nFrames]: one memset
@@ -406,6 +449,7 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
   uint32_t totals[2];
   Status fail = E.ra_plan_fill(plan, nq, a, V, true, victim_, totals);
   const uint32_t jobs = fail.zra ? 0u : totals[0];
+  if (jobsOut) *jobsOut = jobs;
   ZraDecodeArgs ra{};
   ra.pieces = E.raPieces_.as<ZraRaPiece>(); ra.raOut = dOut;
   const uint32_t commitGrid = (std::max(nF, V) + 255) / 256;
@@ -431,7 +475,7 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
     // itself is asked; the frames it decodes are the same, whole.
     const bool was = E.ra_verify_whole_frames();
     E.set_ra_verify_whole_frames(true);
-    const Status st2 = E.ra_batch_body(a, dOut, hOff, hSize, hOutOff, nq);
+    const Status st2 = E.ra_batch_body(a, dOut, hOff, hSize, hOutOff, nq, endInclusive);
     E.set_ra_verify_whole_frames(was);
     if (st2.zra) return st2;
   }

@@ -776,6 +776,33 @@ void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t* out8) {
   if (archive) archive->c->scan_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugArchiveScanStageMs(const ZraHipArchive* archive) { return archive ? archive->c->scan_stage_ms() : 0.0; }
+ZraStatus ZraHipArchiveIndexRecords(ZraHipArchive* archive, uint32_t delimiter, uint64_t firstFrame, uint64_t frameCount, size_t stagingBytes, uint64_t* dIndex,
+                                    size_t indexCapacityWords, ZraHipRecordIndex* info) {
+  if (info) *info = ZraHipRecordIndex{0, 0, 0, 0, 0, 0};
+  if (!archive || !info) return mk(ZStdError, 42);
+  uint64_t w[6] = {0, 0, 0, 0, 0, 0};
+  const ZraStatus st = mk(archive->c->index_records(delimiter, firstFrame, frameCount, stagingBytes, dIndex, indexCapacityWords, w));
+  *info = ZraHipRecordIndex{w[0], (uint32_t)w[1], (uint32_t)w[2], w[3], w[4], w[5]};
+  return st;
+}
+ZraStatus ZraHipArchiveLocateRecords(ZraHipArchive* archive, const ZraHipRecordIndex* info, const uint64_t* dIndex, size_t indexWords, const uint64_t* hRecordNumbers,
+                                     size_t nRecords, size_t stagingBytes, ZraHipContentRange* hRanges) {
+  if (!archive || !info) return mk(ZStdError, 42);
+  const uint64_t w[6] = {info->contentSize, info->frameSize, info->delimiter, info->frames, info->delimiters, info->records};
+  return mk(archive->c->locate_records(w, dIndex, indexWords, hRecordNumbers, nRecords, stagingBytes, (uint64_t*)hRanges));
+}
+ZraStatus ZraHipArchiveReadRecords(ZraHipArchive* archive, const ZraHipRecordIndex* info, const uint64_t* dIndex, size_t indexWords, const uint64_t* hRecordNumbers,
+                                   size_t nRecords, size_t stagingBytes, ZraHipContentRange* hRanges, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (dataSize) *dataSize = 0;
+  if (!archive || !info) return mk(ZStdError, 42);
+  const uint64_t w[6] = {info->contentSize, info->frameSize, info->delimiter, info->frames, info->delimiters, info->records};
+  return mk(archive->c->read_records(w, dIndex, indexWords, hRecordNumbers, nRecords, stagingBytes, (uint64_t*)hRanges, (uint8_t*)dData, dataCapacity, dataSize));
+}
+void ZraHipArchiveGetRecordStats(const ZraHipArchive* archive, uint64_t* out8) {
+  if (!out8) return;
+  if (archive) archive->c->record_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugArchiveRecordStageMs(const ZraHipArchive* archive) { return archive ? archive->c->record_stage_ms() : 0.0; }
 ZraStatus ZraHipUpdateArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* dData, const uint64_t* hOffsets,
                               const uint64_t* hSizes, const uint64_t* hDataOffsets, size_t nWrites, const void* dAppend, size_t appendSize, void* dOut,
                               size_t outCapacity, size_t* outSize, int8_t level, bool checksum) {

@@ -71,8 +71,10 @@ struct UpdCacheView {
   HeaderInfo newHeader{};
   uint32_t staged = 0, refreshed = 0;
 };
-// A range scan through an archive handle (zra_archive.hip, ZraHipArchiveSearch .. ZraHipArchiveExtractRecords): what the handle lends to
-// the scans' driver (zra_scan.h) and what comes back. The driver only READS the arena and the table: a scan is not a read.
+// A range scan or a record call through an archive handle (zra_archive.hip, ZraHipArchiveSearch .. ZraHipArchiveExtractRecords,
+// ZraHipArchiveIndexRecords .. ZraHipArchiveReadRecords): what the handle lends to the scans' driver (zra_scan.h), to the frame-pass
+// driver (zra_framepass.h) and to the locate sweep (zra_records.hip), and what comes back. They only READ the arena and the table: a
+// scan, an index and a locate are not reads.
 struct ScanCacheView {
   HeaderInfo h{};                    // the handle's checked header, taken in place of a read from the device
   const uint8_t* arena = nullptr;    // slots x frameSize: the plaintext of the resident frames
@@ -83,6 +85,12 @@ struct ScanCacheView {
   // the job-split and stage-from-cache launches, summed over the passes
   uint64_t staged = 0, decoded = 0, decodedBytes = 0, passes = 0;
   double stageMs = 0;
+};
+// The byte fetch of a record read through an archive handle (zra_records.hip): the located ranges as one read of the handle, a query
+// allowed to end AT the content's end. *jobs: the frames the fetch decoded.
+struct RecordFetch {
+  Status (*fn)(void* ctx, uint8_t* dOut, const uint64_t* hOff, const uint64_t* hSize, const uint64_t* hOutOff, size_t nq, uint32_t* jobs) = nullptr;
+  void* ctx = nullptr;
 };
 // chunk length of the pipelined host-pointer calls (zra_hostpipe.hip); ZRA_HOST_CHUNK_MIB, default 1024
 size_t host_chunk_bytes();
@@ -300,8 +308,10 @@ class Engine {
   // its last content byte is not the delimiter. index_records writes the words of frames [first, first + count) into their places in
   // dIndex; info6 = ZraHipRecordIndex's six words {content size, frame size, delimiter, frames, delimiters, records}, the totals from
   // all F words as they lie in dIndex. Statuses and their order: zra_hip.h, ZraHipIndexRecords.
+  // cv (here and in the two calls below; a call through an archive handle, zra_archive.hip): the handle's header, and, with slots, the
+  // resident frames a whole-frame sweep needs are staged from the arena; dIndex / dData must not overlap the arena either
   Status index_records(const uint8_t* dArc, size_t arcSize, uint32_t delimiter, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex,
-                       size_t indexCapWords, uint64_t info6[6]);
+                       size_t indexCapWords, uint64_t info6[6], ScanCacheView* cv = nullptr);
   // the last index_records: {frames, frames indexed, content bytes scanned, delimiters in the range, passes, 0, 0, 0}; all zero unless it succeeded
   void index_records_stats(uint64_t out[8]) const { call_stats(kCallIndex, out); }
   // bring-up: HIP-event time of the last index's own launches (count, frame words, totals), summed over its passes
@@ -309,15 +319,17 @@ class Engine {
   // hRanges[i] = {start, size} of record hNumbers[i], in request order; only the frames that hold a boundary are decoded, and each is
   // checked against its word. Statuses and their order: zra_hip.h, ZraHipLocateRecords.
   Status locate_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
-                        size_t stagingBytes, uint64_t* hRanges);
-  // the last locate_records: {frames, records asked, boundaries looked up, frames decoded, content bytes regenerated, passes, 0, 0}
+                        size_t stagingBytes, uint64_t* hRanges, ScanCacheView* cv = nullptr);
+  // the last locate_records: {frames, records asked, boundaries looked up, frames decoded, content bytes regenerated, passes, 0, 0};
+  // through a handle "decoded" and "regenerated" count the decode jobs and leave out the frames staged from its arena
   void locate_records_stats(uint64_t out[8]) const { call_stats(kCallLocate, out); }
   // bring-up: HIP-event time of the last locate's own launches (prefix, bounds, jobs, count, frame check, select), summed over its passes
   double locate_records_ms() const { return callMs_[kCallLocate]; }
   // locate_records, then the records' bytes packed at dData in request order, each followed by one delimiter byte (the packing of
   // extract_records); hRanges is optional. Statuses and their order: zra_hip.h, ZraHipReadRecords.
   Status read_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
-                      size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+                      size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize, ScanCacheView* cv = nullptr,
+                      const RecordFetch* fetch = nullptr);
   // the last read_records: {frames, records, packed bytes, frames decoded by the locate sweep, decode jobs of the read sweep, locate passes, 0, 0}
   void read_records_stats(uint64_t out[8]) const { call_stats(kCallRead, out); }
   // bring-up: HIP-event time of the last read's locate-sweep launches, summed over its passes (its read sweep: kernel_stats)
@@ -414,7 +426,8 @@ class Engine {
   uint64_t ustats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // around a pass's stage-from-cache kernel (update through a handle), own launches (the range scans; compare, diff, sign, signature diff
   // and index: zra_framepass.h, (time); the locate sweep); they never run inside each other.
-  // [2] .. [3] and [4] .. [5]: a range scan through a handle, around a pass's job split and around its stage-from-cache kernel (zra_scan.h)
+  // [2] .. [3] and [4] .. [5]: a range scan or a record call through a handle, around a pass's job split and around its stage-from-cache
+  // kernel (zra_scan.h, zra_framepass.h, zra_records.hip)
   hipEvent_t evCall_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double updStageMs_ = 0;
   // verify scratch (zra_verify.hip): per-frame structure codes and job numbers + totals, the fault list

@@ -21,6 +21,17 @@
 //   5. the positions come to the host, once, behind the last pass.
 // Read: the locate sweep, then one batched read of the located ranges through Engine::ra_batch_body (a record k < D is read with its
 // delimiter, so a read may end at U: the walk's inclusive bound); the delimiter behind an open last record is stored on its own.
+// Through an archive handle with a cache (ScanCacheView, zra_hip.h: ZraHipArchiveIndexRecords .. ZraHipArchiveReadRecords) the header is
+// the handle's, and a resident frame that a whole-frame sweep needs is copied out of the arena, not decoded. The index: the frame-pass
+// driver's steps 2a .. 2c. The locate sweep, per pass, in front of step 4's launches:
+//   4a. the needed frames of the pass, slotFrame[j0 .. j0 + nj), are split by residency, one launch: a missing one becomes a decode job,
+//       compacted in frame order from job 0 of the pass, into its slot of the pass; a resident one a copy entry      zra_rec_split_kernel
+//   4b. the pass's four count words come to the host through the handle's pinned words (the pass's one read-back)
+//   4c. the resident frames are copied from their arena slots into their window slots, when there are any             zra_upd_stage_cached_kernel
+//   4d. the missing frames are decoded whole, checksums verified, when there are any                                  Engine::staged_pass
+// The count, frame-word and select launches run over the same window and are the plain call's: a stale word in a staged frame is found
+// like any other. Index and locate only read the arena and the handle's table: they are not reads. The read's byte fetch IS one: it
+// goes through the handle's own read path (RecordFetch), hits copied out of the arena, misses decoded whole into CLOCK victims.
 //
 // Ordering conditions (all launches on the engine's stream, staged_pass returns synchronised):
 //  (slots) job k of a locate is the k-th needed frame, ascending; pass p holds the jobs [p * passSlots, ...), job k in slot
@@ -30,9 +41,13 @@
 //  (stale) a boundary is resolved only inside a frame that was decoded in this call, and its ordinal is checked against the decoded
 //      frame's own count before a byte is read. A frame whose count or bit 63 differs from its word raises the flag, and the call
 //      ends with {ZStdError, 20} before a range leaves the device.
+//  (split) through a handle the jobs of pass p are rebuilt by 4a over frameOff_ / outOff_ / expect_ [0, nj): what the jobs launch left
+//      there is not read again (slotFrame / slotOf, which the passes do read, lie in the call's tables). Positions are prefix counts in
+//      frame order, so the first failing job is the lowest failing needed frame of the pass, by construction a missing one.
 //  (d) an index call writes the words of its range only; locate and read write nothing but engine scratch and, the read, dData in
 //      front of dataCapacity.
 #include "zra_framepass.h"
+#include "zra_scan.h"
 #include "zra_dev.h"
 #include <algorithm>
 #include <vector>
@@ -46,6 +61,7 @@ constexpr u32 kTile = zra_eng::kScanTile;
 constexpr u32 kHdrBytes = 128, kOffD = 0, kOffZero = 8, kOffTot = 16, kOffJobs = 40, kOffStale = 44, kOffOob = 48;
 constexpr u64 kCountMask = ~(1ull << 63);
 constexpr u64 kDirect = ~0ull;               // a boundary that needs no lookup: its position is written by the bounds launch
+constexpr u32 kNotResident = 0xFFFFFFFFu;    // a handle's frame -> arena slot table: the frame is not in the cache
 
 // bit 7 of every byte of w that equals the delimiter (d4: the delimiter in all four bytes); exact, no carry between bytes
 __device__ __forceinline__ u32 eq_bytes(u32 w, u32 d4) {
@@ -201,6 +217,55 @@ extern "C" __global__ void __launch_bounds__(1024) zra_rec_jobs_kernel(const u8*
   if (tid == 1023) *nJobs = sS[1023];
 }
 
+// A pass of the locate sweep through a handle: one workgroup walks the frame LIST slotFrame[0 .. n) of the pass (ascending; the caller
+// passes slotFrame + j0), 1024 at a time (zra_scan_split_kernel's scheme, zra_archive.hip: ballot + popcount per wave, a wave table in LDS,
+// a running base across chunks; no atomic decides a position). Entry k is frame f in slot k of the window. cacheSlotOf[f] ==
+// kNotResident: a decode job, ranked in list order from job 0: its seek-table span (whatever it says: the decoder refuses a span that
+// runs backwards or leaves the body), destination k * fs, expected size = its share of the content. Otherwise a copy entry {k, arena
+// slot, length, frame}, ranked the same way (zra_upd_stage_cached_kernel's format). counts = {jobs, copies, bytes the jobs are to
+// regenerate (low, high word)}. Nothing of the cache is written.
+extern "C" __global__ void __launch_bounds__(1024) zra_rec_split_kernel(const u32* slotFrame, u32 n, const u32* cacheSlotOf, u32 nFrames, const u8* table, u64 fs, u64 U,
+                                                                        u64* frameOff, u64* outOff, u32* expect, u32* copies, u32* counts) {
+  __shared__ u32 sJ[16], sC[16];
+  __shared__ u64 sB[16];
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  u32 jobBase = 0, copyBase = 0;
+  u64 bytes = 0;
+  for (u32 base = 0; base < n; base += 1024) {
+    const u32 k = base + tid;
+    const bool in = k < n;
+    const u32 f = in ? slotFrame[k] : 0u;
+    const u32 cs = in && f < nFrames ? cacheSlotOf[f] : kNotResident;
+    const u32 len = in ? (u32)frame_expect(f, fs, U) : 0u;
+    const bool cpy = in && cs != kNotResident, dec = in && !cpy;
+    const u64 mJ = __ballot(dec), mC = __ballot(cpy), below = (1ull << lane) - 1;
+    u64 wb = dec ? (u64)len : 0ull;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) wb += __shfl_xor(wb, d, 64);
+    if (lane == 0) { sJ[wave] = (u32)__popcll(mJ); sC[wave] = (u32)__popcll(mC); sB[wave] = wb; }
+    __syncthreads();
+    u32 beforeJ = 0, beforeC = 0, totalJ = 0, totalC = 0;
+    for (u32 w = 0; w < 16; w++) {
+      const u32 j = sJ[w], c = sC[w];
+      beforeJ += w < wave ? j : 0u; beforeC += w < wave ? c : 0u; totalJ += j; totalC += c;
+      bytes += sB[w];
+    }
+    if (cpy) {
+      u32* e = copies + 4 * (size_t)(copyBase + beforeC + (u32)__popcll(mC & below));
+      e[0] = k; e[1] = cs; e[2] = len; e[3] = f;
+    }
+    if (dec) {
+      const u32 job = jobBase + beforeJ + (u32)__popcll(mJ & below);
+      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, (u64)f + 1);
+      outOff[job] = (u64)k * fs;
+      expect[job] = len;
+    }
+    jobBase += totalJ; copyBase += totalC;
+    __syncthreads();                                                  // (sJ, sC, sB of the next chunk)
+  }
+  if (tid == 0) { counts[0] = jobBase; counts[1] = copyBase; counts[2] = (u32)bytes; counts[3] = (u32)(bytes >> 32); }
+}
+
 // A wave per boundary x whose frame is one of the jobs [j0, j0 + nj) of this pass: ordinal j of the frame. A binary search over the
 // frame's tile prefix finds the tile, then the wave reads that one tile, 1 KiB per trip: per-lane masks, their popcounts, a wave
 // prefix, and the lane that holds the delimiter writes its content position (+ 1 for a start boundary). It leaves with the trip
@@ -256,42 +321,47 @@ namespace zra_eng {
 
 struct RecordsImpl {
   static Status index(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count,
-                      size_t stagingBytes, uint64_t* dIndex, size_t cap, uint64_t info6[6]);
+                      size_t stagingBytes, uint64_t* dIndex, size_t cap, uint64_t info6[6], ScanCacheView* cv);
   // the locate sweep: hPos[2 i], hPos[2 i + 1] = start and end of record hNumbers[i]; st6 = {frames, boundaries looked up, frames
   // decoded, content bytes regenerated, passes, D}. *view: the archive's checked view, for the read that follows. *ms gains the
-  // HIP-event time of the sweep's own launches.
+  // HIP-event time of the sweep's own launches. cv (every call below; a call through an archive handle): the header step is the
+  // handle's; with slots a needed frame that is resident is staged from the arena, and st6[2], st6[3] count the decode jobs alone.
   static Status sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers,
-                      size_t n, size_t stagingBytes, const uint8_t* dData, size_t dataCap, std::vector<uint64_t>& hPos, uint64_t st6[6], ArchiveView* view);
+                      size_t n, size_t stagingBytes, const uint8_t* dData, size_t dataCap, std::vector<uint64_t>& hPos, uint64_t st6[6], ArchiveView* view, ScanCacheView* cv);
   static Status read(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
-                     size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+                     size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize, ScanCacheView* cv, const RecordFetch* fetch);
 };
 
 namespace {
 bool ranges_overlap(const void* p, uint64_t n, const void* q, uint64_t m) {
   return n && m && (uintptr_t)p < (uintptr_t)q + m && (uintptr_t)q < (uintptr_t)p + n;
 }
+// the arena check of the update through a handle: a buffer the call writes must not lie over the handle's decoded frames
+bool overlaps_arena(const ScanCacheView* cv, const void* p, uint64_t n) {
+  return cv && cv->slots && ranges_overlap(p, n, cv->arena, (uint64_t)cv->slots * cv->h.frameSize);
+}
 uint32_t tiles_per_frame(uint64_t fs) { return (uint32_t)((fs + kTile - 1) / kTile); }
 uint32_t delim4(uint32_t d) { return d * 0x01010101u; }
 }  // namespace
 
 Status Engine::index_records(const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count, size_t stagingBytes, uint64_t* dIndex,
-                             size_t indexCapWords, uint64_t info6[6]) {
+                             size_t indexCapWords, uint64_t info6[6], ScanCacheView* cv) {
   // (rule 5, OutputTooSmall, leaves the first four words: they say how many words the index needs)
   return entry_call(callStats_[kCallIndex], &callMs_[kCallIndex], {{info6, 6}}, true, [&] {
-    return RecordsImpl::index(*this, callStats_[kCallIndex], &callMs_[kCallIndex], dArc, arcSize, delim, first, count, stagingBytes, dIndex, indexCapWords, info6);
+    return RecordsImpl::index(*this, callStats_[kCallIndex], &callMs_[kCallIndex], dArc, arcSize, delim, first, count, stagingBytes, dIndex, indexCapWords, info6, cv);
   });
 }
 
 Status RecordsImpl::index(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, uint32_t delim, uint64_t first, uint64_t count,
-                          size_t stagingBytes, uint64_t* dIndex, size_t cap, uint64_t info6[6]) {
-  // ---- 1. arguments, 2. overlap
+                          size_t stagingBytes, uint64_t* dIndex, size_t cap, uint64_t info6[6], ScanCacheView* cv) {
+  // ---- 1. arguments, 2. overlap (with the archive, and with the arena of the handle the call goes through)
   if (!info6 || (!dArc && arcSize) || (!dIndex && cap) || delim > 255) return zerr(42);
-  if (cap > (~(size_t)0) / 8 || ranges_overlap(dIndex, 8 * (uint64_t)cap, dArc, arcSize)) return zerr(42);
+  if (cap > (~(size_t)0) / 8 || ranges_overlap(dIndex, 8 * (uint64_t)cap, dArc, arcSize) || overlaps_arena(cv, dIndex, 8 * (uint64_t)cap)) return zerr(42);
   FramePasses F(E, ms);
   STCHK(F.start());
-  // ---- 3. header: the statuses of ZraHipArchiveOpen
+  // ---- 3. header: the statuses of ZraHipArchiveOpen, or the header a handle checked when it was opened
   ArchiveView arc;
-  STCHK(E.archive_view(dArc, arcSize, &arc));
+  STCHK(ScanImpl::view(E, dArc, arcSize, cv, &arc));
   if (arc.fs == 0) return {kHeaderInvalid, 0};
   const uint64_t fs = arc.fs, U = arc.U;
   const uint64_t Fr = (U + fs - 1) / fs;
@@ -307,12 +377,12 @@ Status RecordsImpl::index(Engine& E, uint64_t (&stats)[8], double* ms, const uin
   const PassPlan P = pass_plan(first, n, pass_slots(fs, stagingBytes));
   const uint32_t tpf = tiles_per_frame(fs);
   if (!E.rec_.tables.reserve(kHdrBytes + ((size_t)P.nSlots * (tpf + 1) + 16) * 4)) return zerr(64);
-  STCHK(F.open({n ? (size_t)((uint64_t)P.nSlots * fs) + 64 : 0, 0, 0, 0, 0, P.nSlots, P.nSlots}));
+  STCHK(F.open({n ? (size_t)((uint64_t)P.nSlots * fs) + 64 : 0, 0, 0, 0, 0, P.nSlots, P.nSlots, cv && cv->slots ? (size_t)P.nSlots : 0}));
   uint8_t* const hdr = E.rec_.tables.as<uint8_t>();
   uint32_t* const tc = (uint32_t*)(hdr + kHdrBytes);
-  // ---- passes: plain, one side (zra_framepass.h)
+  // ---- passes: plain, one side (zra_framepass.h); through a handle the resident frames of a pass are staged, steps 2a .. 2c there
   STCHK(F.begin(nullptr, 0));
-  STCHK(F.run(P, FramePasses::Side{&arc, 0, F.win}, nullptr, nullptr, nullptr, nullptr, [&](const FramePass& ps, uint32_t) {
+  STCHK(F.run(P, FramePasses::Side{&arc, 0, F.win, cv}, nullptr, nullptr, nullptr, nullptr, [&](const FramePass& ps, uint32_t) {
       hipLaunchKernelGGL(zra_rec_count_kernel, dim3(ps.nj * tpf), dim3(256), 0, F.s, F.win, (u64)fs, (u64)U, (const u32*)nullptr, (u64)ps.first, tpf, delim4(delim), tc);
       hipLaunchKernelGGL(zra_rec_frames_kernel, dim3((ps.nj + 3) / 4), dim3(256), 0, F.s, F.win, (u64)fs, (u64)U, (const u32*)nullptr, (u64)ps.first, ps.nj, tpf, delim, tc,
                          (u64*)dIndex, 0u, (u32*)nullptr);
@@ -328,19 +398,21 @@ Status RecordsImpl::index(Engine& E, uint64_t (&stats)[8], double* ms, const uin
 }
 
 Status RecordsImpl::sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers,
-                          size_t n, size_t stagingBytes, const uint8_t* dData, size_t dataCap, std::vector<uint64_t>& hPos, uint64_t st6[6], ArchiveView* view) {
+                          size_t n, size_t stagingBytes, const uint8_t* dData, size_t dataCap, std::vector<uint64_t>& hPos, uint64_t st6[6], ArchiveView* view,
+                          ScanCacheView* cv) {
   // ---- 1. arguments and the info's own consistency, the read's overlap
   if (!info6 || (!dArc && arcSize) || (!dIndex && indexWords) || (n && !hNumbers)) return zerr(42);
   const uint64_t iU = info6[0], ifs = info6[1], delim = info6[2], iF = info6[3];
   if (ifs == 0 || ifs > 0xFFFFFFFFull || delim > 255 || iF != iU / ifs + (iU % ifs != 0) || indexWords < iF || indexWords > (~(size_t)0) / 8) return zerr(42);
   if (n > 0xFFFFFFF0ull) return zerr(64);
-  if (ranges_overlap(dData, dataCap, dArc, arcSize) || ranges_overlap(dData, dataCap, dIndex, 8 * (uint64_t)indexWords)) return zerr(42);
+  if (ranges_overlap(dData, dataCap, dArc, arcSize) || ranges_overlap(dData, dataCap, dIndex, 8 * (uint64_t)indexWords) || overlaps_arena(cv, dData, dataCap))
+    return zerr(42);
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   E.reset_decode_stats();
-  // ---- 2. header, 3. the archive the index was made of
+  // ---- 2. header (a handle's: the one it checked), 3. the archive the index was made of
   ArchiveView arc;
-  STCHK(E.archive_view(dArc, arcSize, &arc));
+  STCHK(ScanImpl::view(E, dArc, arcSize, cv, &arc));
   if (arc.fs == 0) return {kHeaderInvalid, 0};
   const uint64_t fs = arc.fs, U = arc.U;
   const uint64_t F64 = (U + fs - 1) / fs;
@@ -355,12 +427,13 @@ Status RecordsImpl::sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arc
   const uint32_t passSlots = pass_slots(fs, stagingBytes), tpf = tiles_per_frame(fs);
   const size_t jobsMax = (size_t)std::min<uint64_t>(F, 2 * (uint64_t)n);
   const uint32_t nSlots = (uint32_t)std::min<uint64_t>(passSlots, jobsMax);
+  const bool cached = cv && cv->slots;
   // tables: header | cnt[F] (u32) | slotOf[F] (u32) | slotFrame[F] (u32) | tile prefixes | pre[F + 1] (u64) | need[F] (u8)
   const size_t offCnt = kHdrBytes, offSlotOf = offCnt + (size_t)F * 4, offSlotFrame = offSlotOf + (size_t)F * 4, offTc = offSlotFrame + (size_t)F * 4;
   const size_t offPre = (offTc + ((size_t)nSlots * (tpf + 1) + 1) * 4 + 15) & ~(size_t)15, offNeed = offPre + ((size_t)F + 1) * 8;
   // ranges: numbers[n] | bnd[2 n] | pos[2 n]
   if (!E.rec_.tables.reserve(offNeed + F + 64) || !E.rec_.ranges.reserve(((size_t)n * 5 + 8) * 8) || !E.frameOff_.reserve((jobsMax + 1) * 16) ||
-      !E.outOff_.reserve(((size_t)nSlots + 1) * 8) || !E.expect_.reserve((jobsMax + 1) * 4))
+      !E.outOff_.reserve(((size_t)nSlots + 1) * 8) || !E.expect_.reserve((jobsMax + 1) * 4) || (cached && !E.upd_.copies.reserve(((size_t)nSlots + 1) * 16)))
     return zerr(64);
   if (nSlots && !E.stage_.reserve((size_t)((uint64_t)nSlots * fs) + 64)) return zerr(64);
   if (!E.call_events()) return zerr(1);
@@ -375,7 +448,15 @@ Status RecordsImpl::sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arc
   uint64_t* const numbers = E.rec_.ranges.as<uint64_t>();
   uint64_t* const bnd = numbers + n;
   uint64_t* const pos = bnd + 2 * n;
-  auto take_time = [&]() { *ms += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]); };
+  // (through a handle's cache) the pass's count words, then its copy entries, 4 words each
+  uint32_t* const counts = cached ? E.upd_.copies.as<uint32_t>() : nullptr, * const copies = cached ? counts + 4 : nullptr;
+  bool stageTimed = false;
+  // (behind a synchronisation of the stream)
+  auto take_time = [&]() {
+    *ms += Engine::elapsed_ms(E.evCall_[0], E.evCall_[1]);
+    if (stageTimed) cv->stageMs += Engine::elapsed_ms(E.evCall_[4], E.evCall_[5]);
+    stageTimed = false;
+  };
   // ---- the prefix, the boundaries, the jobs
   HIPCHK_CLR(hipMemsetAsync(hdr, 0, kHdrBytes, s));
   HIPCHK_CLR(hipMemsetAsync(need, 0, F, s));
@@ -403,14 +484,47 @@ Status RecordsImpl::sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arc
   if (nJobs > jobsMax) return zerr(1);                                        // (cannot happen)
   // ---- passes over the needed frames. Not the frame-pass driver's (zra_framepass.h): the jobs of all passes were built once, above, so
   // a pass has no job launch and decodes at job base j0; its span closes BEHIND its own launches (the first span is the prefix's, taken
-  // above, hence `if (p)`); and the frames are not consecutive. Each of the three would be a special case there.
+  // above, hence `if (p)`); and the frames are not consecutive. Each of the three would be a special case there. A fourth through a
+  // handle's cache: the driver splits a RANGE of frames by residency (scan_launch_split), this sweep a LIST (slotFrame), with its own
+  // kernel, and a pass's jobs are rebuilt from job 0, (split), where the driver's plain pass had none to rebuild. The previous pass's
+  // span is read behind the first synchronisation of the pass: the read-back's of 4b through a cache, staged_pass's without.
   const uint64_t passes = ((uint64_t)nJobs + passSlots - 1) / passSlots;
+  uint64_t decJobs = 0, decBytes = 0;
   for (uint64_t p = 0; p < passes; p++) {
     const uint32_t j0 = (uint32_t)(p * passSlots), nj = std::min<uint32_t>(passSlots, nJobs - j0);
-    unsigned long long firstError;
-    STCHK(E.staged_pass(arc, j0, nj, win, &firstError));
-    if (p) take_time();
-    if (firstError != ~0ull) return zerr(reported_code(firstError));          // 6. the lowest failing frame of the first failing pass
+    uint32_t nDec = nj;
+    bool taken = false;
+    if (cached) {                                                             // 4a .. 4c
+      HIPCHK_CLR(hipEventRecord(E.evCall_[2], s));
+      hipLaunchKernelGGL(zra_rec_split_kernel, dim3(1), dim3(1024), 0, s, (const u32*)(slotFrame + j0), nj, (const u32*)cv->slotOf, cv->frames, arc.table, (u64)fs, (u64)U,
+                         E.frameOff_.as<u64>(), E.outOff_.as<u64>(), E.expect_.as<u32>(), copies, counts);
+      HIPCHK_CLR(hipEventRecord(E.evCall_[3], s));
+      HIPCHK_CLR(hipMemcpyAsync(cv->pin, counts, 16, hipMemcpyDeviceToHost, s));
+      HIPCHK_CLR(hipStreamSynchronize(s));
+      HIPCHK_CLR(hipGetLastError());
+      if (p) take_time();
+      taken = true;
+      cv->stageMs += Engine::elapsed_ms(E.evCall_[2], E.evCall_[3]);
+      nDec = cv->pin[0];
+      const uint32_t nCopy = cv->pin[1];
+      if (nDec > nj || nCopy != nj - nDec) return zerr(1);                    // (cannot happen)
+      decBytes += (uint64_t)cv->pin[2] | (uint64_t)cv->pin[3] << 32;
+      if (nCopy) {
+        HIPCHK_CLR(hipEventRecord(E.evCall_[4], s));
+        upd_launch_stage_cached(s, copies, nCopy, 0, fs, cv->arena, win);
+        HIPCHK_CLR(hipEventRecord(E.evCall_[5], s));
+        stageTimed = true;
+        cv->staged += nCopy;
+      }
+    }
+    if (nDec) {                                                               // (always, without a handle's cache: a pass has a frame)
+      unsigned long long firstError;
+      STCHK(E.staged_pass(arc, cached ? 0 : j0, nDec, win, &firstError));
+      if (p && !taken) take_time();
+      if (firstError != ~0ull) return zerr(reported_code(firstError));        // 6. the lowest failing frame of the first failing pass
+    }
+    decJobs += nDec;
+    if (cv) { cv->decoded += nDec; cv->passes++; }
     HIPCHK_CLR(hipEventRecord(E.evCall_[0], s));
     hipLaunchKernelGGL(zra_rec_count_kernel, dim3(nj * tpf), dim3(256), 0, s, (const u8*)win, (u64)fs, (u64)U, (const u32*)(slotFrame + j0), (u64)0, tpf,
                        delim4((uint32_t)delim), tc);
@@ -431,18 +545,20 @@ Status RecordsImpl::sweep(Engine& E, double* ms, const uint8_t* dArc, size_t arc
   if (stale) return zerr(20);                                                 // 7. a decoded frame contradicts its word
   uint64_t lookups = 0, bytes = 0;
   for (size_t i = 0; i < n; i++) lookups += (hNumbers[i] != 0) + (hNumbers[i] != D);
-  if (nJobs) {
+  if (cached) bytes = decBytes;
+  else if (nJobs) {
     std::vector<uint32_t> ex(nJobs);
     HIPCHK_CLR(hipMemcpyAsync(ex.data(), E.expect_.p, (size_t)nJobs * 4, hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
     for (uint32_t e : ex) bytes += e;
   }
-  st6[1] = lookups; st6[2] = nJobs; st6[3] = bytes; st6[4] = passes; st6[5] = D;
+  if (cv) cv->decodedBytes += bytes;
+  st6[1] = lookups; st6[2] = decJobs; st6[3] = bytes; st6[4] = passes; st6[5] = D;
   return ok();
 }
 
 Status Engine::locate_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
-                              size_t stagingBytes, uint64_t* hRanges) {
+                              size_t stagingBytes, uint64_t* hRanges, ScanCacheView* cv) {
   uint64_t (&stats)[8] = callStats_[kCallLocate];
   // (the locate has no output words, and no status that keeps any)
   return entry_call(stats, &callMs_[kCallLocate], {}, false, [&]() -> Status {
@@ -450,7 +566,7 @@ Status Engine::locate_records(const uint8_t* dArc, size_t arcSize, const uint64_
     std::vector<uint64_t> hPos;
     uint64_t st6[6];
     ArchiveView arc;
-    const Status st = RecordsImpl::sweep(*this, &callMs_[kCallLocate], dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, nullptr, 0, hPos, st6, &arc);
+    const Status st = RecordsImpl::sweep(*this, &callMs_[kCallLocate], dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, nullptr, 0, hPos, st6, &arc, cv);
     if (st.zra) return st;
     for (size_t i = 0; i < n && hPos.size() == 2 * n; i++) { hRanges[2 * i] = hPos[2 * i]; hRanges[2 * i + 1] = hPos[2 * i + 1] - hPos[2 * i]; }
     const uint64_t st8[8] = {st6[0], n, st6[1], st6[2], st6[3], st6[4], 0, 0};
@@ -460,23 +576,24 @@ Status Engine::locate_records(const uint8_t* dArc, size_t arcSize, const uint64_
 }
 
 Status Engine::read_records(const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords, const uint64_t* hNumbers, size_t n,
-                            size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
+                            size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize, ScanCacheView* cv, const RecordFetch* fetch) {
   // (rule OutputTooSmall leaves the packed size the read needs)
   return entry_call(callStats_[kCallRead], &callMs_[kCallRead], {{dataSize, 1}}, true, [&]() -> Status {
     if (!dataSize || (!dData && dataCap)) return zerr(42);
     return RecordsImpl::read(*this, callStats_[kCallRead], &callMs_[kCallRead], dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, hRanges, dData, dataCap,
-                             dataSize);
+                             dataSize, cv, fetch);
   });
 }
 
 Status RecordsImpl::read(Engine& E, uint64_t (&stats)[8], double* ms, const uint8_t* dArc, size_t arcSize, const uint64_t info6[6], const uint64_t* dIndex, size_t indexWords,
-                         const uint64_t* hNumbers, size_t n, size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
+                         const uint64_t* hNumbers, size_t n, size_t stagingBytes, uint64_t* hRanges, uint8_t* dData, size_t dataCap, uint64_t* dataSize, ScanCacheView* cv,
+                         const RecordFetch* fetch) {
   // the locate sweep runs under a timer of its own (the read's, once it has succeeded) and leaves the locate's counters and time alone
   double sweepMs = 0;
   std::vector<uint64_t> hPos;
   uint64_t st6[6];
   ArchiveView arc;
-  const Status st = sweep(E, &sweepMs, dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, dData, dataCap, hPos, st6, &arc);
+  const Status st = sweep(E, &sweepMs, dArc, arcSize, info6, dIndex, indexWords, hNumbers, n, stagingBytes, dData, dataCap, hPos, st6, &arc, cv);
   if (st.zra) return st;
   if (!n || hPos.size() != 2 * n) return ok();
   // ---- the located ranges as one batch: record k < D with its delimiter, an open record D without (its byte is stored below)
@@ -504,7 +621,9 @@ Status RecordsImpl::read(Engine& E, uint64_t (&stats)[8], double* ms, const uint
   const bool whole = E.raVerifyWholeFrames_;
   E.raVerifyWholeFrames_ = false;
   uint32_t readJobs = 0;
-  const Status rs = E.ra_batch_body(arc, dData, q.data(), q.data() + n, q.data() + 2 * n, n, true, &readJobs);
+  // (through a handle the fetch is a read of the handle: hits out of the arena, misses decoded whole into CLOCK victims)
+  const Status rs = fetch ? fetch->fn(fetch->ctx, dData, q.data(), q.data() + n, q.data() + 2 * n, n, &readJobs)
+                          : E.ra_batch_body(arc, dData, q.data(), q.data() + n, q.data() + 2 * n, n, true, &readJobs);
   E.raVerifyWholeFrames_ = whole;
   if (rs.zra) return rs;
   if (hRanges) for (size_t i = 0; i < n; i++) { hRanges[2 * i] = hPos[2 * i]; hRanges[2 * i + 1] = hPos[2 * i + 1] - hPos[2 * i]; }
