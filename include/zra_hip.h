@@ -191,7 +191,9 @@ ZRA_EXPORT ZraStatus ZraHipArchiveSearch(ZraHipArchive* archive,
     uint64_t offset, uint64_t size,
     size_t stagingBytes,
     uint64_t* hMatches, size_t matchCapacity, uint64_t* nMatches);
-/** ZraHipSearchArchiveMulti through the handle: see ZraHipArchiveSearch. Overwrites ZraHipGetSearchMultiStats. */
+/** ZraHipSearchArchiveMulti through the handle: see ZraHipArchiveSearch. Overwrites ZraHipGetSearchMultiStats. This call and the two
+ *  below take their patterns literally; with case folding and byte classes: the ZraHipArchive...Expr calls, further below. Not
+ *  covered by either: quantifiers, alternation, anchors. */
 ZRA_EXPORT ZraStatus ZraHipArchiveSearchMulti(ZraHipArchive* archive,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
     uint64_t offset, uint64_t size,
@@ -492,7 +494,8 @@ typedef struct ZraHipPatternMatch { uint64_t offset; uint32_t pattern; uint32_t 
  *  against the patterns that begin with its first byte. The worst case is patterns that match everywhere (64 patterns of zeros in
  *  zeros): every position then runs 64 full compares, and every listed match is compared twice. That is accepted.
  *  Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveSearchMulti, above.
- *  Not covered: regular expressions and case folding, patterns in device memory, shards, the host-pointer API. */
+ *  Case folding and byte classes: ZraHipSearchArchiveMultiExpr, below.
+ *  Not covered: quantifiers, alternation, anchors, patterns in device memory, shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipSearchArchiveMulti(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
     uint64_t offset, uint64_t size,
@@ -549,7 +552,7 @@ typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipCont
  *  Cost: one decode of the range and the multi search's filter; on top of it one byte compare per position and a segmented reduction
  *  over the positions between delimiters (profiles/grep_scan.md).
  *  Not covered: the BYTES of the records (ZraHipExtractRecords below keeps them from the same pass; with this call alone, fetch them
- *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), regular expressions and case folding, multi-byte delimiters, shards, the
+ *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), quantifiers, alternation, anchors (case folding and byte classes: ZraHipGrepArchiveExpr, below), multi-byte delimiters, shards, the
  *  host-pointer API. Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveGrep, above. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
@@ -594,7 +597,8 @@ ZRA_EXPORT double ZraHipDebugGrepScanMs(ZraHipEngine* engine);
  *  On every status other than Success the stats are zero and hRecords is untouched; apart from rule 7, *nRecords = *dataSize = 0.
  *  Cost: the grep's, plus one byte store per copied position (profiles/extract_scan.md).
  *  Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveExtractRecords, above.
- *  Not covered: context lines, output without the delimiter bytes, and what ZraHipGrepArchive does not cover. Records BY NUMBER are
+ *  Not covered: context lines, output without the delimiter bytes, and what ZraHipGrepArchive does not cover (case folding and byte
+ *  classes: ZraHipExtractRecordsExpr, below). Records BY NUMBER are
  *  the record index's: ZraHipIndexRecords, ZraHipLocateRecords and ZraHipReadRecords below. */
 ZRA_EXPORT ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
@@ -608,6 +612,96 @@ ZRA_EXPORT ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArc
 ZRA_EXPORT void ZraHipGetExtractStats(ZraHipEngine* engine, uint64_t* out8);
 /** Bring-up aid, like ZraHipDebugGrepScanMs: HIP-event time of the last extract's own launches, summed over its passes. engine NULL: 0. */
 ZRA_EXPORT double ZraHipDebugExtractMs(ZraHipEngine* engine);
+
+/* ---- pattern expressions for the multi-pattern scans: case folding and byte classes ----
+ * The six calls above that take several patterns (ZraHipSearchArchiveMulti, ZraHipGrepArchive, ZraHipExtractRecords and their
+ * ZraHipArchive... twins) have a twin with one more word, `syntax`, behind nPatterns. Every ELEMENT of a pattern matches exactly one
+ * byte: a literal, a case-folded letter or a byte set. A pattern therefore keeps a fixed length, counted in elements, and everything
+ * the literal calls say about lengths, ranges, passes, ownership, records, capacities, statuses and stats holds word for word with
+ * m_i = the number of elements of pattern i. Quantifiers, alternation and anchors need another scan and are not part of this; their
+ * characters are reserved, so that adding them later changes the meaning of no expression accepted now. */
+#define ZRA_HIP_PATTERN_FOLD_CASE 1u   /* ASCII letters match either case (grep -i) */
+#define ZRA_HIP_PATTERN_CLASSES   2u   /* patterns are expressions: . [set] [^set] \escape */
+#define ZRA_HIP_PATTERN_MAX_SETS        32u     /* distinct byte sets per call, see below */
+#define ZRA_HIP_PATTERN_MAX_EXPR_BYTES  16384u  /* sum of the expression sizes */
+
+/** Rule 1's pattern checks of the ...Expr calls, on the host alone: no engine, no device. hPatterns / hPatternSizes / nPatterns as
+ *  for the calls; delimiter: the grep's and the extract's byte, or -1 for the multi search, which has none. On Success hLengths[i]
+ *  (may be NULL) is pattern i's length in elements and *nSets (may be NULL) the number of counted sets. Any refusal -> {ZStdError, 42},
+ *  the outputs untouched.
+ *
+ *  syntax == 0: literal bytes, as the literal calls take them. The two bits combine; any other bit is refused.
+ *  Without ZRA_HIP_PATTERN_CLASSES the pattern bytes are literals and hPatternSizes[i] = m_i; FOLD_CASE still applies to them.
+ *  With ZRA_HIP_PATTERN_CLASSES hPatternSizes[i] is the size of expression i in bytes (1 and up, ZRA_HIP_PATTERN_MAX_EXPR_BYTES in
+ *  all); the limits of the literal calls apply to elements: 1 .. ZRA_HIP_SEARCH_MAX_PATTERN per pattern, _MAX_PATTERN_BYTES in all.
+ *   .            any byte
+ *   [items]      a byte set; [^items] its complement. An item is a byte, an escape, or a range a-b of two single bytes, a <= b.
+ *                ] directly behind [ or [^ is a literal; - first or last is a literal; [ followed by : is refused, at the head of
+ *                a set and inside one (POSIX classes are reserved). An unterminated set is refused.
+ *   \xHH         the byte HH (hex digits of either case); \n \t \r
+ *   \d \w \s     [0-9], [0-9A-Za-z_], space and \t \n \v \f \r; allowed inside a set, but not as either end of a range
+ *   \c           the byte c, for c one of . [ ] \ * + ? { } ( ) | ^ $ -
+ *                Any other byte behind \, and a \ at the end, is refused.
+ *   ] * + ? { } ( ) | ^ $ unescaped outside a set are refused: reserved.
+ *   Every other byte, NUL and bytes >= 0x80 included, is a literal. Bytes are bytes: nothing is UTF-8 aware.
+ *  An element whose final set is empty is refused.
+ *  ZRA_HIP_PATTERN_FOLD_CASE: a literal A-Z or a-z matches both cases; a set is closed under the case swap of its ASCII letters
+ *  BEFORE a ^ complements it (grep -i '[^a]'). No other byte folds: not @ [ ` {, not 0xC0 .. 0xFF.
+ *  The delimiter (grep and extract): no element may match it, so that an occurrence stays inside one record. `.` and [^...] lose it
+ *  silently, as . never matches a newline in grep; a literal, a positive set or a fold that contains it is refused.
+ *  ZRA_HIP_PATTERN_MAX_SETS bounds the distinct final sets of a call. A set of one byte does not count, nor does a set that is one
+ *  letter in its two cases; equal sets count once. */
+ZRA_EXPORT ZraStatus ZraHipCheckPatternExpr(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint32_t syntax, int delimiter, uint32_t* hLengths, uint32_t* nSets);
+
+/** ZraHipSearchArchiveMulti with a syntax word: a match is (p, i) with lo <= p, p + m_i <= hi and element q of pattern i admitting
+ *  content[p + q] for every q < m_i. Rule 1 gains ZraHipCheckPatternExpr's refusals (delimiter -1: `.` matches all 256 bytes).
+ *  Everything else is the literal call's definition with m_i counted in elements, the shortcut "range shorter than the shortest
+ *  pattern" included. Writes ZraHipGetSearchMultiStats and ZraHipDebugSearchMultiScanMs; "filter survivors" are the positions whose
+ *  first two elements admit their bytes for some pattern. With syntax == 0 the call IS the literal one: the same kernels.
+ *  Cost: a position is tested against the patterns whose first two elements admit its first two bytes, element by element from the
+ *  third. A pattern that begins `..` makes every position a candidate (as 64 patterns of zeros in a content of zeros do for the
+ *  literal call); the work per position is bounded by 64 patterns x 256 elements (profiles/pattern_expr.md).
+ *  Not covered: quantifiers, alternation, anchors, POSIX classes, UTF-8 awareness, patterns in device memory, shards, the host-pointer
+ *  API, the single-pattern ZraHipSearchArchive (one expression goes through this call). */
+ZRA_EXPORT ZraStatus ZraHipSearchArchiveMultiExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint64_t offset, uint64_t size,
+    size_t stagingBytes,
+    ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern);
+/** ZraHipGrepArchive with a syntax word, as ZraHipSearchArchiveMultiExpr is to its twin; `delimiter` enters the pattern checks as
+ *  described at ZraHipCheckPatternExpr. `mode` is the literal call's (ZRA_HIP_GREP_INVERT only). Writes ZraHipGetGrepStats and
+ *  ZraHipDebugGrepScanMs. */
+ZRA_EXPORT ZraStatus ZraHipGrepArchiveExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+/** ZraHipExtractRecords with a syntax word: see ZraHipGrepArchiveExpr. Writes ZraHipGetExtractStats and ZraHipDebugExtractMs. */
+ZRA_EXPORT ZraStatus ZraHipExtractRecordsExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** The three through a ZraHipArchive handle: ZraHipArchiveSearchMulti, ZraHipArchiveGrep and ZraHipArchiveExtractRecords with the
+ *  syntax word; resident frames are staged from the cache as for their twins, and the handle's counters move as for them. */
+ZRA_EXPORT ZraStatus ZraHipArchiveSearchMultiExpr(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint64_t offset, uint64_t size,
+    size_t stagingBytes,
+    ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern);
+ZRA_EXPORT ZraStatus ZraHipArchiveGrepExpr(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecordsExpr(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
 
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte

@@ -193,6 +193,18 @@ def load():
                                      u64p]),
         "ZraHipGetExtractStats": (None, [vp, u64p]),
         "ZraHipDebugExtractMs": (ctypes.c_double, [vp]),
+        # pattern expressions: the six multi-pattern scans with a syntax word behind nPatterns, and the host-only checker
+        "ZraHipCheckPatternExpr": (S, [vp, ctypes.POINTER(u32), sz, u32, ctypes.c_int, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "ZraHipSearchArchiveMultiExpr": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipPatternMatch),
+                                             sz, u64p, u64p]),
+        "ZraHipGrepArchiveExpr": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipExtractRecordsExpr": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp,
+                                         sz, u64p]),
+        "ZraHipArchiveSearchMultiExpr": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, ctypes.POINTER(ZraHipPatternMatch), sz, u64p,
+                                             u64p]),
+        "ZraHipArchiveGrepExpr": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipArchiveExtractRecordsExpr": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz,
+                                                u64p]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -273,6 +285,8 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipSearchArchiveMulti", "ZraHipGetSearchMultiStats", "ZraHipDebugSearchMultiScanMs",
                    "ZraHipGrepArchive", "ZraHipGetGrepStats", "ZraHipDebugGrepScanMs",
                    "ZraHipExtractRecords", "ZraHipGetExtractStats", "ZraHipDebugExtractMs",
+                   "ZraHipCheckPatternExpr", "ZraHipSearchArchiveMultiExpr", "ZraHipGrepArchiveExpr", "ZraHipExtractRecordsExpr",
+                   "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -511,21 +525,22 @@ class Engine:
         """bring-up: HIP-event time of the last search()'s scan launches, summed over its passes (its decode: kernel_stats()['dec_ms'])."""
         return self.L.ZraHipDebugSearchScanMs(self.h)
 
-    def search_multi(self, d_archive, size, patterns, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20):
+    def search_multi(self, d_archive, size, patterns, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20, syntax=0):
         """ZraHipSearchArchiveMulti: where each of `patterns` (1 .. SEARCH_MAX_PATTERNS byte strings of 1 .. SEARCH_MAX_PATTERN bytes,
         SEARCH_MAX_PATTERN_BYTES in all, literal) occurs whole inside [offset, offset + length) (None: to the end) of the content of
         the archive at d_archive, in one decode of the range. Returns (n_matches, [(offset, pattern index)], per_pattern): every match
         is counted, the first max_matches are listed in ascending (offset, pattern index) order, and per_pattern[i] counts the matches
-        of patterns[i], listed or not. ZraError is a call that could not search."""
+        of patterns[i], listed or not. syntax: PATTERN_FOLD_CASE | PATTERN_CLASSES (ZraHipSearchArchiveMultiExpr; lengths are then
+        counted in elements). ZraError is a call that could not search."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ZraHipPatternMatch * max_matches)() if max_matches else None
         per = (ctypes.c_uint64 * max(len(patterns), 1))()
         n = ctypes.c_uint64(0)
         self._order()
-        _chk(self.L.ZraHipSearchArchiveMulti(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), offset,
-                                             (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_matches, ctypes.byref(n), per),
-             "ZraHipSearchArchiveMulti")
+        fn, sx = _scan_call(self.L, "ZraHipSearchArchiveMulti", syntax)
+        _chk(fn(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, offset,
+                (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_matches, ctypes.byref(n), per), fn.__name__)
         listed = [(int(arr[i].offset), int(arr[i].pattern)) for i in range(min(n.value, max_matches))] if arr is not None else []
         return n.value, listed, [int(v) for v in per[:len(patterns)]]
 
@@ -539,19 +554,21 @@ class Engine:
         """bring-up: HIP-event time of the last search_multi()'s scan launches, summed over its passes."""
         return self.L.ZraHipDebugSearchMultiScanMs(self.h)
 
-    def grep(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20):
+    def grep(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0):
         """ZraHipGrepArchive: the records of [offset, offset + length) (None: to the end) of the content of the archive at d_archive,
         cut at the byte `delimiter`, in which one of `patterns` (search_multi's, none holding the delimiter) occurs; invert: those in
         which none does. Returns (n_records, [(offset, size)]): every selected record is counted and the first max_records are listed
-        in ascending order, without their delimiter. max_records=0 is `grep -c`. ZraError is a call that could not grep."""
+        in ascending order, without their delimiter. max_records=0 is `grep -c`. syntax: search_multi's (ZraHipGrepArchiveExpr).
+        ZraError is a call that could not grep."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n = ctypes.c_uint64(0)
         self._order()
-        _chk(self.L.ZraHipGrepArchive(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter,
-                                      GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
-                                      max_records, ctypes.byref(n)), "ZraHipGrepArchive")
+        fn, sx = _scan_call(self.L, "ZraHipGrepArchive", syntax)
+        _chk(fn(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter,
+                GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                max_records, ctypes.byref(n)), fn.__name__)
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
 
@@ -565,22 +582,25 @@ class Engine:
         """bring-up: HIP-event time of the last grep()'s scan launches, summed over its passes."""
         return self.L.ZraHipDebugGrepScanMs(self.h)
 
-    def extract(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0):
+    def extract(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0,
+                syntax=0):
         """ZraHipExtractRecords: grep()'s selected records with their bytes, from one decode pass. For each selected record, in ascending
         order, its content and then one `delimiter` byte lie packed at d_data (data_cap bytes, device memory): the text `grep` prints.
         Returns (n_records, data_size, [(offset, size)]); the list is filled iff max_records != 0. OutputBufferTooSmall (more than
         max_records records when a list is wanted, or more than data_cap bytes) carries what the call needs in ZraError.needed_records
-        and ZraError.needed_data; d_data=0, data_cap=0 is the sizing call. ZraError otherwise is a call that could not extract."""
+        and ZraError.needed_data; d_data=0, data_cap=0 is the sizing call. syntax: search_multi's (ZraHipExtractRecordsExpr). ZraError
+        otherwise is a call that could not extract."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._order()
-        st = self.L.ZraHipExtractRecords(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter,
-                                         GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
-                                         max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
+        fn, sx = _scan_call(self.L, "ZraHipExtractRecords", syntax)
+        st = fn(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter,
+                GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
         if st.zra != 0:
-            e = ZraError(st.tup(), "ZraHipExtractRecords")
+            e = ZraError(st.tup(), fn.__name__)
             e.needed_records, e.needed_data = n.value, ds.value
             raise e
         k = n.value if max_records else 0
@@ -819,6 +839,28 @@ SEARCH_MAX_PATTERNS = 64                     # ZRA_HIP_SEARCH_MAX_PATTERNS
 SEARCH_MAX_PATTERN_BYTES = 4096              # ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
 SEARCH_MULTI_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes", "patterns", "survivors")
 GREP_INVERT = 1                              # ZRA_HIP_GREP_INVERT
+PATTERN_FOLD_CASE = 1                        # ZRA_HIP_PATTERN_FOLD_CASE: ASCII letters match either case
+PATTERN_CLASSES = 2                          # ZRA_HIP_PATTERN_CLASSES: patterns are expressions: . [set] [^set] \escape
+PATTERN_MAX_SETS = 32                        # ZRA_HIP_PATTERN_MAX_SETS
+PATTERN_MAX_EXPR_BYTES = 16384               # ZRA_HIP_PATTERN_MAX_EXPR_BYTES
+
+
+def _scan_call(L, name, syntax):
+    """the entry point of a multi-pattern scan and what goes behind nPatterns: the literal call for syntax 0, else its ...Expr twin"""
+    return (getattr(L, name), ()) if not syntax else (getattr(L, name + "Expr"), (syntax,))
+
+
+def check_pattern_expr(patterns, syntax=PATTERN_CLASSES, delimiter=None):
+    """ZraHipCheckPatternExpr: the pattern checks of the scans' `syntax` keyword, on the host alone (no engine, no device).
+    delimiter: the grep's and the extract's byte, None for the multi search. Returns (lengths in elements, counted sets); ZraError is
+    a refused pattern list."""
+    patterns = [bytes(p) for p in patterns]
+    sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+    lens = (ctypes.c_uint32 * max(len(patterns), 1))()
+    ns = ctypes.c_uint32(0)
+    _chk(load().ZraHipCheckPatternExpr(_cbuf(b"".join(patterns)), sizes, len(patterns), syntax, -1 if delimiter is None else delimiter, lens, ctypes.byref(ns)),
+         "ZraHipCheckPatternExpr")
+    return [int(v) for v in lens[:len(patterns)]], int(ns.value)
 GREP_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "listed", "passes", "matches")
 EXTRACT_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "packed_bytes", "passes", "matches")
 
@@ -913,44 +955,47 @@ class Archive:
                                         max_matches, ctypes.byref(n)), "ZraHipArchiveSearch")
         return n.value, [int(v) for v in arr[:min(n.value, max_matches)]] if arr is not None else []
 
-    def search_multi(self, patterns, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20):
-        """ZraHipArchiveSearchMulti: Engine.search_multi through the handle. Returns (n_matches, [(offset, pattern index)], per_pattern)."""
+    def search_multi(self, patterns, *, offset=0, length=None, staging_bytes=0, max_matches=1 << 20, syntax=0):
+        """ZraHipArchiveSearchMulti (syntax != 0: ...Expr): Engine.search_multi through the handle. Returns (n_matches, [(offset, pattern index)], per_pattern)."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ZraHipPatternMatch * max_matches)() if max_matches else None
         per = (ctypes.c_uint64 * max(len(patterns), 1))()
         n = ctypes.c_uint64(0)
         self.engine._order()
-        _chk(self.L.ZraHipArchiveSearchMulti(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), offset, (1 << 64) - 1 if length is None else length,
-                                             staging_bytes, arr, max_matches, ctypes.byref(n), per), "ZraHipArchiveSearchMulti")
+        fn, sx = _scan_call(self.L, "ZraHipArchiveSearchMulti", syntax)
+        _chk(fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, offset, (1 << 64) - 1 if length is None else length,
+                staging_bytes, arr, max_matches, ctypes.byref(n), per), fn.__name__)
         listed = [(int(arr[i].offset), int(arr[i].pattern)) for i in range(min(n.value, max_matches))] if arr is not None else []
         return n.value, listed, [int(v) for v in per[:len(patterns)]]
 
-    def grep(self, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20):
-        """ZraHipArchiveGrep: Engine.grep through the handle. Returns (n_records, [(offset, size)])."""
+    def grep(self, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0):
+        """ZraHipArchiveGrep (syntax != 0: ...Expr): Engine.grep through the handle. Returns (n_records, [(offset, size)])."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n = ctypes.c_uint64(0)
         self.engine._order()
-        _chk(self.L.ZraHipArchiveGrep(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter, GREP_INVERT if invert else 0, offset,
-                                      (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n)), "ZraHipArchiveGrep")
+        fn, sx = _scan_call(self.L, "ZraHipArchiveGrep", syntax)
+        _chk(fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, offset,
+                (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n)), fn.__name__)
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
 
-    def extract(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0):
-        """ZraHipArchiveExtractRecords: Engine.extract through the handle; d_data must overlap neither the archive nor the cache. Returns
+    def extract(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0, syntax=0):
+        """ZraHipArchiveExtractRecords (syntax != 0: ...Expr): Engine.extract through the handle; d_data must overlap neither the archive nor the cache. Returns
         (n_records, data_size, [(offset, size)]); OutputBufferTooSmall carries ZraError.needed_records and ZraError.needed_data."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self.engine._order()
-        st = self.L.ZraHipArchiveExtractRecords(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), delimiter, GREP_INVERT if invert else 0, offset,
-                                                (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n),
-                                                d_data or None, data_cap, ctypes.byref(ds))
+        fn, sx = _scan_call(self.L, "ZraHipArchiveExtractRecords", syntax)
+        st = fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, offset,
+                (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n),
+                d_data or None, data_cap, ctypes.byref(ds))
         if st.zra != 0:
-            e = ZraError(st.tup(), "ZraHipArchiveExtractRecords")
+            e = ZraError(st.tup(), fn.__name__)
             e.needed_records, e.needed_data = n.value, ds.value
             raise e
         k = n.value if max_records else 0

@@ -32,11 +32,11 @@ class ArchiveCache {
   // arena and decodes the others (zra_hip.h: ZraHipArchiveSearch .. ZraHipArchiveExtractRecords). A scan is not a read: it changes
   // nothing of the cache and none of stats()' words, on any status.
   Status search(const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
-  Status search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset, uint64_t size, size_t stagingBytes, void* hMatches,
+  Status search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset, uint64_t size, size_t stagingBytes, void* hMatches,
                       size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
-  Status grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
+  Status grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
               size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-  Status extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
+  Status extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
                  size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
   // {scans accepted, frames staged from the cache (last accepted scan), frames decoded (last), passes (last), staged (cumulative),
   // decoded (cumulative), 0, 0}

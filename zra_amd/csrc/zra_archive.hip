@@ -312,33 +312,33 @@ Status ArchiveCache::search(const void* hPattern, size_t patternSize, uint64_t o
   }), v);
 }
 
-Status ArchiveCache::search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset, uint64_t size, size_t stagingBytes,
+Status ArchiveCache::search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset, uint64_t size, size_t stagingBytes,
                                   void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
   Engine& E = *e_;
   ScanCacheView v = scan_view();
   return scanned(ScanImpl::call(E, kScanMulti, nMatches, nullptr, [&] {
-    return ScanImpl::msearch(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCap, nMatches,
+    return ScanImpl::msearch(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, offset, size, stagingBytes, hMatches, matchCap, nMatches,
                              hPerPattern, &v);
   }), v);
 }
 
-Status ArchiveCache::grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
+Status ArchiveCache::grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
                           size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
   Engine& E = *e_;
   ScanCacheView v = scan_view();
   return scanned(ScanImpl::call(E, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords, recordCap,
+    return ScanImpl::grep(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords, recordCap,
                           nRecords, &v);
   }), v);
 }
 
-Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode, uint64_t offset,
+Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
                              uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                              uint64_t* dataSize) {
   Engine& E = *e_;
   ScanCacheView v = scan_view();
   return scanned(ScanImpl::call(E, kScanExtract, nRecords, dataSize, [&] {
-    return ScanImpl::extract(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
+    return ScanImpl::extract(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords,
                              recordCap, nRecords, dData, dataCap, dataSize, &v);
   }), v);
 }

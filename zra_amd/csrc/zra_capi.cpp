@@ -8,6 +8,7 @@
 #include "zra_archive.h"
 #include "zra_format.h"
 #include "zra_env.h"
+#include "zra_pattern_expr.h"
 
 #include <atomic>
 #include <algorithm>
@@ -754,13 +755,13 @@ ZraStatus ZraHipArchiveSearchMulti(ZraHipArchive* archive, const void* hPatterns
                                    size_t stagingBytes, ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern) {
   if (nMatches) *nMatches = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->search_multi(hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCapacity, nMatches, hPerPattern));
+  return mk(archive->c->search_multi(hPatterns, hPatternSizes, nPatterns, 0, offset, size, stagingBytes, hMatches, matchCapacity, nMatches, hPerPattern));
 }
 ZraStatus ZraHipArchiveGrep(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter, uint32_t mode,
                             uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->grep(hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(archive->c->grep(hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
 }
 ZraStatus ZraHipArchiveExtractRecords(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
                                       uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity,
@@ -768,7 +769,7 @@ ZraStatus ZraHipArchiveExtractRecords(ZraHipArchive* archive, const void* hPatte
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords,
+  return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords,
                                 (uint8_t*)dData, dataCapacity, dataSize));
 }
 void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t* out8) {
@@ -843,7 +844,7 @@ ZraStatus ZraHipSearchArchiveMulti(ZraHipEngine* engine, const void* dArchive, s
   static_assert(sizeof(ZraHipPatternMatch) == 16, "a 64-bit offset and two 32-bit words per match");
   if (nMatches) *nMatches = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->search_archive_multi((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches,
+  return mk(engine->e->search_archive_multi((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, 0, offset, size, stagingBytes, hMatches,
                                             matchCapacity, nMatches, hPerPattern));
 }
 void ZraHipGetSearchMultiStats(ZraHipEngine* engine, uint64_t* out8) {
@@ -856,7 +857,7 @@ ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t a
                             size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->grep_archive((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes,
+  return mk(engine->e->grep_archive((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
                                     (uint64_t*)hRecords, recordCapacity, nRecords));
 }
 void ZraHipGetGrepStats(ZraHipEngine* engine, uint64_t* out8) {
@@ -870,7 +871,7 @@ ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->extract_records((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes,
+  return mk(engine->e->extract_records((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
                                        (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
 }
 void ZraHipGetExtractStats(ZraHipEngine* engine, uint64_t* out8) {
@@ -878,6 +879,65 @@ void ZraHipGetExtractStats(ZraHipEngine* engine, uint64_t* out8) {
   if (engine) engine->e->extract_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugExtractMs(ZraHipEngine* engine) { return engine ? engine->e->extract_ms() : 0.0; }
+
+// ---- the scans with a pattern syntax word: the literal calls above through the same ScanImpl functions, `syntax` behind
+// nPatterns. They write their literal twins' stats rows and millisecond words.
+ZraStatus ZraHipCheckPatternExpr(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, int delimiter, uint32_t* hLengths,
+                                 uint32_t* nSets) {
+  zra_expr::Compiled C;
+  if (!zra_expr::compile((const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, &C)) return mk(ZStdError, 42);
+  if (hLengths) for (size_t i = 0; i < nPatterns; i++) hLengths[i] = C.len[i];
+  if (nSets) *nSets = (uint32_t)C.sets.size();
+  return mk(Success, 0);
+}
+ZraStatus ZraHipSearchArchiveMultiExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes,
+                                       size_t nPatterns, uint32_t syntax, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipPatternMatch* hMatches,
+                                       size_t matchCapacity, uint64_t* nMatches, uint64_t* hPerPattern) {
+  if (nMatches) *nMatches = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->search_archive_multi((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, offset, size, stagingBytes, hMatches,
+                                            matchCapacity, nMatches, hPerPattern));
+}
+ZraStatus ZraHipGrepArchiveExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                                uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
+                                size_t recordCapacity, uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->grep_archive((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords));
+}
+ZraStatus ZraHipExtractRecordsExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes,
+                                   size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes,
+                                   ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->extract_records((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size,
+                                       stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+}
+ZraStatus ZraHipArchiveSearchMultiExpr(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset,
+                                       uint64_t size, size_t stagingBytes, ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches,
+                                       uint64_t* hPerPattern) {
+  if (nMatches) *nMatches = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->search_multi(hPatterns, hPatternSizes, nPatterns, syntax, offset, size, stagingBytes, hMatches, matchCapacity, nMatches, hPerPattern));
+}
+ZraStatus ZraHipArchiveGrepExpr(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity,
+                                uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->grep(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+}
+ZraStatus ZraHipArchiveExtractRecordsExpr(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+                                          uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
+                                          size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
+                                nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+}
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {
   static_assert(sizeof(ZraHipContentRange) == 16, "two 64-bit words per range");

@@ -224,8 +224,9 @@ class Engine {
   // ---- search for several patterns (zra_msearch.hip): every (content offset, pattern index) at which one of the nPatterns host
   // patterns (laid end to end at hPatterns, pattern i of hPatternSizes[i] bytes) occurs whole inside the range, ascending, in ONE
   // decode of the range's frames. hMatches: ZraHipPatternMatch's layout; hPerPattern (optional): the matches of each pattern.
-  // Statuses and their order: zra_hip.h, ZraHipSearchArchiveMulti.
-  Status search_archive_multi(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset,
+  // Statuses and their order: zra_hip.h, ZraHipSearchArchiveMulti. syntax (here and in the two calls below): the pattern syntax word of
+  // the ...Expr entry points (zra_pattern_expr.h; lengths then count elements), 0 for the literal ones.
+  Status search_archive_multi(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset,
                               uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
   // the last search_archive_multi: {frames, decoded, content bytes regenerated, matches, matches listed, passes, patterns, filter
   // survivors}; all zero unless it succeeded. The single-pattern search and this one leave each other's counters alone
@@ -236,7 +237,7 @@ class Engine {
   // ---- grep (zra_grep.hip): the records of [offset, offset + size) (size ~0: to the end), cut at `delimiter`, in which a match of one
   // of the nPatterns host patterns starts (mode 1: in which none does), ascending, as {offset, size} pairs in hRecords, in ONE decode of
   // the range's frames. Patterns, range and passes are search_archive_multi's. Statuses and their order: zra_hip.h, ZraHipGrepArchive.
-  Status grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+  Status grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
                       uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
   // the last grep_archive: {frames, decoded, content bytes regenerated, records of the range, records selected, records listed, passes,
   // matches}; all zero unless it succeeded. The searches and the grep leave each other's counters alone
@@ -247,7 +248,7 @@ class Engine {
   // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
   // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:
   // the packed bytes. Statuses and their order: zra_hip.h, ZraHipExtractRecords.
-  Status extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+  Status extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
                          uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
                          uint8_t* dData, size_t dataCap, uint64_t* dataSize);
   // the last extract_records: {frames, decoded, content bytes regenerated, records of the range, records selected, packed bytes,

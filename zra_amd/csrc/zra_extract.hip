@@ -84,8 +84,8 @@ __device__ __forceinline__ Run trip_run(u64 dm, u64 hm, u32 lane, u32 inv, u64 p
 
 // One tile's first walk, the same in the count and in the copy: per trip the two ballots (kept in sMask when kKeep), per wave its
 // summary -> sW[wave]. Returns the delimiters the wave saw.
-template <bool kKeep>
-__device__ __forceinline__ u32 tile_runs(const Table* sT, const u32* sTile, u32 d, u32 n, long long toHi, u32 delim, u32 inv, u64 tilePos, Run* sW,
+template <bool kKeep, class TB>
+__device__ __forceinline__ u32 tile_runs(const TB* sT, const u32* sTile, u32 d, u32 n, long long toHi, u32 delim, u32 inv, u64 tilePos, Run* sW,
                                          u64 (*sMask)[kWaveIters][2], u32* pairs) {
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w0 = wave * kWavePos;
   Run w = {0, 0, 0, 0, 0};
@@ -105,10 +105,11 @@ __device__ __forceinline__ u32 tile_runs(const Table* sT, const u32* sTile, u32 
 // The run of a pass as the grep sees it: win = slot 0, position x is the byte win[x]; the positions of the pass are xLo + [0, nPos), xHi
 // is the position of the range's end (hi - passBase), M the longest pattern, p0 the content offset of position xLo. Workgroup g takes
 // the tiles [g * kGroup, (g + 1) * kGroup): per tile its summary -> sums[tile]; per call the totals.
-extern "C" __global__ void __launch_bounds__(256) zra_extract_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+template <class TB>
+__device__ __forceinline__ void extract_count(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 delim,
                                                                            u32 inv, u64 p0, XSum* sums, XTotals* tot) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
-  __shared__ Table sT;
+  __shared__ TB sT;
   __shared__ Run sW[4];
   const u32 tid = threadIdx.x, lane = tid & 63;
   const u32 tiles = (u32)((nPos + kTile - 1) / kTile);
@@ -133,6 +134,14 @@ extern "C" __global__ void __launch_bounds__(256) zra_extract_count_kernel(const
   pairs = wave_sum(pairs);
   if (lane == 0 && pairs) atomicAdd((unsigned long long*)&tot->matches, (unsigned long long)pairs);
   if (lane == 0 && delims) atomicAdd((unsigned long long*)&tot->delims, (unsigned long long)delims);   // (a ballot's count: the same in every lane)
+}
+extern "C" __global__ void __launch_bounds__(256) zra_extract_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+                                                                           u32 inv, u64 p0, XSum* sums, XTotals* tot) {
+  extract_count<Table>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, tot);
+}
+extern "C" __global__ void __launch_bounds__(256) zra_extract_count_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl, u32 delim,
+                                                                           u32 inv, u64 p0, XSum* sums, XTotals* tot) {
+  extract_count<ClassTable>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, tot);
 }
 
 // One workgroup. Forward, as the grep's scan: every lane reduces a run of consecutive tiles, the 1,024 summaries are scanned in LDS
@@ -218,11 +227,12 @@ extern "C" __global__ void __launch_bounds__(1024) zra_extract_scan_kernel(XSum*
 // others are skipped; a workgroup without such a tile leaves at once). First walk: the ballots of every trip go to LDS with the waves'
 // summaries. Second walk: a wave takes what lies in front of it from the tile's head and the waves in front, what lies behind it from
 // the waves behind and the head's look-ahead bit, and every lane stores its position's byte where (compaction) puts it.
-extern "C" __global__ void __launch_bounds__(256) zra_extract_copy_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+template <class TB>
+__device__ __forceinline__ void extract_copy(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 delim,
                                                                           u32 inv, u64 p0, const XSum* sums, const XHead* heads, Range* list, u64 cap, u8* dData,
                                                                           u64 dataCap) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
-  __shared__ Table sT;
+  __shared__ TB sT;
   __shared__ Run sW[4];
   __shared__ u64 sMask[4][kWaveIters][2];
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w0 = wave * kWavePos;
@@ -318,26 +328,37 @@ extern "C" __global__ void __launch_bounds__(256) zra_extract_copy_kernel(const 
     }
   }
 }
+extern "C" __global__ void __launch_bounds__(256) zra_extract_copy_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+                                                                          u32 inv, u64 p0, const XSum* sums, const XHead* heads, Range* list, u64 cap, u8* dData,
+                                                                          u64 dataCap) {
+  extract_copy<Table>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, heads, list, cap, dData, dataCap);
+}
+extern "C" __global__ void __launch_bounds__(256) zra_extract_copy_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl, u32 delim,
+                                                                          u32 inv, u64 p0, const XSum* sums, const XHead* heads, Range* list, u64 cap, u8* dData,
+                                                                          u64 dataCap) {
+  extract_copy<ClassTable>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, heads, list, cap, dData, dataCap);
+}
 
 // =================================================================================================
 namespace zra_eng {
 
-Status Engine::extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+Status Engine::extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
                                uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
                                uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
   return ScanImpl::call(*this, kScanExtract, nRecords, dataSize, [&] {
-    return ScanImpl::extract(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
-                             recordCap, nRecords, dData, dataCap, dataSize);
+    return ScanImpl::extract(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                             hRecords, recordCap, nRecords, dData, dataCap, dataSize);
   });
 }
 
-Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                         uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
+Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
+                         uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                          uint64_t* dataSize, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nRecords || !dataSize || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (!dData && dataCap) || (mode & ~1u)) return zerr(42);
-  uint32_t M = 0, mMin = kMaxPattern;
-  if (!record_patterns_ok(hPat, hSizes, nPat, delimiter, &M, &mMin)) return zerr(42);
+  PatternSet pset;
+  if (!patterns_ok(hPat, hSizes, nPat, syntax, delimiter, &pset)) return zerr(42);
+  const uint32_t M = pset.M, mMin = pset.mMin;
   // ---- 2. overlap (with the archive, and with the arena of the handle the call goes through)
   if (dataCap && arcSize && (uintptr_t)dData < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dData + dataCap) return zerr(42);
   if (cv && cv->slots && dataCap && (uintptr_t)dData < (uintptr_t)cv->arena + (size_t)cv->slots * cv->h.frameSize && (uintptr_t)cv->arena < (uintptr_t)dData + dataCap)
@@ -358,25 +379,32 @@ Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   // ---- 5. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | XTotals | sums[tiles] | heads[tiles]
   const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
   const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  constexpr size_t kTotals = sizeof(Table) + 64, kHead = kTotals + sizeof(XTotals);
-  static_assert(kHead % 16 == 0 && sizeof(XSum) == 32 && sizeof(XHead) == 32 && sizeof(Range) == 16 && sizeof(XState) == 64, "16-byte entries behind a 16-byte head");
+  const size_t kTotals = pset.table_bytes() + 64, kHead = kTotals + sizeof(XTotals);
+  static_assert((sizeof(Table) + 64 + sizeof(XTotals)) % 16 == 0 && (sizeof(ClassTable) + 64 + sizeof(XTotals)) % 16 == 0 && sizeof(XSum) == 32 && sizeof(XHead) == 32 && sizeof(Range) == 16 && sizeof(XState) == 64, "16-byte entries behind a 16-byte head");
   std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo")
-  build_table(*(Table*)head.data(), hPat, hSizes, nPat);
+  build_pattern_table(head.data(), pset, hPat, hSizes, nPat);
   ((XTotals*)(head.data() + kTotals))->st[0].start = lo;
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
   Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanExtract], head.data(), kHead, kTotals, sizeof(XTotals), kHead + P.tilesMax * (sizeof(XSum) + sizeof(XHead)) + 64,
                                listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const Table* const tbl = (const Table*)tb;
+    const ClassTable* const ctbl = (const ClassTable*)tb;                    // (one of the two, by the syntax word)
     XTotals* const tot = (XTotals*)(tb + kTotals);
     XSum* const sums = (XSum*)(tb + kHead);
     XHead* const heads = (XHead*)(sums + P.tilesMax);
     Range* const list = E.scan_.list.as<Range>();
     const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    hipLaunchKernelGGL(zra_extract_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+    if (pset.classes)
+      hipLaunchKernelGGL(zra_extract_count_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+    else
+      hipLaunchKernelGGL(zra_extract_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
     hipLaunchKernelGGL(zra_extract_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
                        (u32)ps.lastPass, (u64)hi, (u64)ps.p0, (u64)ps.nPos, list, (u64)listCap, dData, (u64)dataCap, (u32)delimiter);
-    if (listCap || dataCap)
+    if ((listCap || dataCap) && pset.classes)
+      hipLaunchKernelGGL(zra_extract_copy_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums,
+                         heads, list, (u64)listCap, dData, (u64)dataCap);
+    else if (listCap || dataCap)
       hipLaunchKernelGGL(zra_extract_copy_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums,
                          heads, list, (u64)listCap, dData, (u64)dataCap);
   }, &launches, cv);

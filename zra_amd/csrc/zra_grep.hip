@@ -90,10 +90,11 @@ __device__ __forceinline__ Sum walk_sum(const Walk& s) {
 // The run of a pass as the multi search sees it: win = slot 0, position x is the byte win[x]; the positions of the pass are xLo + [0,
 // nPos), xHi is the position of the range's end (hi - passBase), M the longest pattern, p0 the content offset of position xLo.
 // Workgroup g takes the tiles [g * kGroup, (g + 1) * kGroup): per tile its summary -> sums[tile]; per call the totals.
-extern "C" __global__ void __launch_bounds__(256) zra_grep_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+template <class TB>
+__device__ __forceinline__ void grep_count(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 delim,
                                                                         u32 inv, u64 p0, Sum* sums, Totals* tot) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
-  __shared__ Table sT;
+  __shared__ TB sT;
   __shared__ Sum sW[4];
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w0 = wave * kWavePos;
   const u32 tiles = (u32)((nPos + kTile - 1) / kTile);
@@ -126,6 +127,14 @@ extern "C" __global__ void __launch_bounds__(256) zra_grep_count_kernel(const u8
   pairs = wave_sum(pairs);
   if (lane == 0 && pairs) atomicAdd((unsigned long long*)&tot->matches, (unsigned long long)pairs);
   if (lane == 0 && delims) atomicAdd((unsigned long long*)&tot->delims, (unsigned long long)delims);   // (a ballot's count: the same in every lane)
+}
+extern "C" __global__ void __launch_bounds__(256) zra_grep_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+                                                                        u32 inv, u64 p0, Sum* sums, Totals* tot) {
+  grep_count<Table>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, tot);
+}
+extern "C" __global__ void __launch_bounds__(256) zra_grep_count_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl, u32 delim,
+                                                                        u32 inv, u64 p0, Sum* sums, Totals* tot) {
+  grep_count<ClassTable>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, tot);
 }
 
 // One workgroup: (launches). Every lane reduces a run of consecutive tiles, the 1024 summaries are scanned in LDS (Hillis-Steele over
@@ -184,10 +193,11 @@ extern "C" __global__ void __launch_bounds__(1024) zra_grep_scan_kernel(Sum* sum
 // The count's workgroups redo the tiles that hold a listed record (a tile without a selected record, or behind the list's capacity, is
 // skipped; a workgroup without such a tile leaves at once): the ballots of every trip go to LDS with the waves' summaries, a wave takes
 // what lies in front of it from the tile's head and the waves in front, and walks its trips again, writing.
-extern "C" __global__ void __launch_bounds__(256) zra_grep_fill_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+template <class TB>
+__device__ __forceinline__ void grep_fill(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 delim,
                                                                        u32 inv, u64 p0, const Sum* sums, const Head* heads, Range* list, u64 cap) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
-  __shared__ Table sT;
+  __shared__ TB sT;
   __shared__ Sum sW[4];
   __shared__ u64 sMask[4][kWaveIters][2];
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w0 = wave * kWavePos;
@@ -232,24 +242,33 @@ extern "C" __global__ void __launch_bounds__(256) zra_grep_fill_kernel(const u8*
       walk_trip<true>(e, sMask[wave][t][0], sMask[wave][t][1], lane, inv, p0 + t0 + w0 + t * 64, at, list, cap);
   }
 }
+extern "C" __global__ void __launch_bounds__(256) zra_grep_fill_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
+                                                                       u32 inv, u64 p0, const Sum* sums, const Head* heads, Range* list, u64 cap) {
+  grep_fill<Table>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, heads, list, cap);
+}
+extern "C" __global__ void __launch_bounds__(256) zra_grep_fill_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl, u32 delim,
+                                                                       u32 inv, u64 p0, const Sum* sums, const Head* heads, Range* list, u64 cap) {
+  grep_fill<ClassTable>(win, xLo, xHi, nPos, M, tbl, delim, inv, p0, sums, heads, list, cap);
+}
 
 // =================================================================================================
 namespace zra_eng {
 
-Status Engine::grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
+Status Engine::grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
                             uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
   return ScanImpl::call(*this, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, delimiter, mode, offset, size, stagingBytes, hRecords,
-                          recordCap, nRecords);
+    return ScanImpl::grep(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                          hRecords, recordCap, nRecords);
   });
 }
 
-Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                      uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv) {
+Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
+                      uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nRecords || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (mode & ~1u)) return zerr(42);
-  uint32_t M = 0, mMin = kMaxPattern;
-  if (!record_patterns_ok(hPat, hSizes, nPat, delimiter, &M, &mMin)) return zerr(42);
+  PatternSet pset;
+  if (!patterns_ok(hPat, hSizes, nPat, syntax, delimiter, &pset)) return zerr(42);
+  const uint32_t M = pset.M, mMin = pset.mMin;
   const uint32_t inv = mode & 1u;
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
@@ -266,25 +285,32 @@ Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint
   // ---- 4. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | Totals | sums[tiles] | heads[tiles]
   const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
   const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  constexpr size_t kTotals = sizeof(Table) + 64, kHead = kTotals + sizeof(Totals);
-  static_assert(kHead % 16 == 0 && sizeof(Sum) == 16 && sizeof(Head) == 16 && sizeof(Range) == 16, "16-byte entries behind a 16-byte head");
+  const size_t kTotals = pset.table_bytes() + 64, kHead = kTotals + sizeof(Totals);
+  static_assert((sizeof(Table) + 64 + sizeof(Totals)) % 16 == 0 && (sizeof(ClassTable) + 64 + sizeof(Totals)) % 16 == 0 && sizeof(Sum) == 16 && sizeof(Head) == 16 && sizeof(Range) == 16, "16-byte entries behind a 16-byte head");
   std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo")
-  build_table(*(Table*)head.data(), hPat, hSizes, nPat);
+  build_pattern_table(head.data(), pset, hPat, hSizes, nPat);
   ((Totals*)(head.data() + kTotals))->st[0].start = lo;
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
   Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanGrep], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * (sizeof(Sum) + sizeof(Head)) + 64,
                                listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const Table* const tbl = (const Table*)tb;
+    const ClassTable* const ctbl = (const ClassTable*)tb;                    // (one of the two, by the syntax word)
     Totals* const tot = (Totals*)(tb + kTotals);
     Sum* const sums = (Sum*)(tb + kHead);
     Head* const heads = (Head*)(sums + P.tilesMax);
     Range* const list = E.scan_.list.as<Range>();
     const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    hipLaunchKernelGGL(zra_grep_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+    if (pset.classes)
+      hipLaunchKernelGGL(zra_grep_count_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+    else
+      hipLaunchKernelGGL(zra_grep_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
     hipLaunchKernelGGL(zra_grep_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
                        (u32)ps.lastPass, (u64)hi, list, (u64)listCap);
-    if (listCap)
+    if (listCap && pset.classes)
+      hipLaunchKernelGGL(zra_grep_fill_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums,
+                         heads, list, (u64)listCap);
+    else if (listCap)
       hipLaunchKernelGGL(zra_grep_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, heads,
                          list, (u64)listCap);
   }, &launches, cv);

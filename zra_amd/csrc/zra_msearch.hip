@@ -23,10 +23,11 @@ struct __attribute__((aligned(16))) Match { u64 offset; u32 pattern, reserved; }
 // The run of a pass: win = slot 0, position x is the byte win[x]; the start positions of the pass are xLo + [0, nPos), xHi is the
 // position of the range's end (hi - passBase), M the longest pattern. Workgroup g takes the tiles [g * kGroup, (g + 1) * kGroup): per
 // tile the matches -> counts[tile], those of its four waves -> waveCnt[4 * tile + wave]; per call the totals.
-extern "C" __global__ void __launch_bounds__(256) zra_msearch_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 nPat,
+template <class TB>
+__device__ __forceinline__ void msearch_count(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 nPat,
                                                                            u32* counts, u32* waveCnt, Totals* tot) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
-  __shared__ Table sT;
+  __shared__ TB sT;
   __shared__ u32 sPer[kMaxPatterns], sCnt[4];
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w0 = wave * kWavePos;
   const u32 tiles = (u32)((nPos + kTile - 1) / kTile);
@@ -60,13 +61,22 @@ extern "C" __global__ void __launch_bounds__(256) zra_msearch_count_kernel(const
   __syncthreads();
   if (tid < nPat && sPer[tid]) atomicAdd((unsigned long long*)&tot->per[tid], (unsigned long long)sPer[tid]);
 }
+extern "C" __global__ void __launch_bounds__(256) zra_msearch_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 nPat,
+                                                                           u32* counts, u32* waveCnt, Totals* tot) {
+  msearch_count<Table>(win, xLo, xHi, nPos, M, tbl, nPat, counts, waveCnt, tot);
+}
+extern "C" __global__ void __launch_bounds__(256) zra_msearch_count_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl, u32 nPat,
+                                                                           u32* counts, u32* waveCnt, Totals* tot) {
+  msearch_count<ClassTable>(win, xLo, xHi, nPos, M, tbl, nPat, counts, waveCnt, tot);
+}
 
 // The same workgroups redo the tiles that hold a listed match (a tile without matches, or behind the list's capacity, is skipped; a
 // workgroup without such a tile leaves at once) and write the pairs, (order). p0 = the content offset of position xLo.
-extern "C" __global__ void __launch_bounds__(256) zra_msearch_fill_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl,
+template <class TB>
+__device__ __forceinline__ void msearch_fill(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl,
                                                                           const u32* counts, const u32* waveCnt, const u64* bases, u64 p0, Match* list, u64 cap) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
-  __shared__ Table sT;
+  __shared__ TB sT;
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w0 = wave * kWavePos;
   const u32 tiles = (u32)((nPos + kTile - 1) / kTile);
   const u32 bBegin = blockIdx.x * kGroup, bEnd = min(tiles, bBegin + kGroup);
@@ -100,24 +110,33 @@ extern "C" __global__ void __launch_bounds__(256) zra_msearch_fill_kernel(const 
     }
   }
 }
+extern "C" __global__ void __launch_bounds__(256) zra_msearch_fill_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl,
+                                                                          const u32* counts, const u32* waveCnt, const u64* bases, u64 p0, Match* list, u64 cap) {
+  msearch_fill<Table>(win, xLo, xHi, nPos, M, tbl, counts, waveCnt, bases, p0, list, cap);
+}
+extern "C" __global__ void __launch_bounds__(256) zra_msearch_fill_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl,
+                                                                          const u32* counts, const u32* waveCnt, const u64* bases, u64 p0, Match* list, u64 cap) {
+  msearch_fill<ClassTable>(win, xLo, xHi, nPos, M, tbl, counts, waveCnt, bases, p0, list, cap);
+}
 
 // =================================================================================================
 namespace zra_eng {
 
-Status Engine::search_archive_multi(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint64_t offset,
+Status Engine::search_archive_multi(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset,
                                     uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern) {
   return ScanImpl::call(*this, kScanMulti, nMatches, nullptr, [&] {
-    return ScanImpl::msearch(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, offset, size, stagingBytes, hMatches, matchCap, nMatches,
-                             hPerPattern);
+    return ScanImpl::msearch(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, offset, size, stagingBytes, hMatches, matchCap,
+                             nMatches, hPerPattern);
   });
 }
 
-Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
-                         size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv) {
+Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint64_t offset,
+                         uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv) {
   // ---- 1. arguments
   if (!nMatches || !hPat || !hSizes || (!dArc && arcSize) || (!hMatches && matchCap)) return zerr(42);
-  uint32_t M = 0, mMin = kMaxPattern;
-  if (!pattern_sizes_ok(hSizes, nPat, &M, &mMin)) return zerr(42);
+  PatternSet pset;
+  if (!patterns_ok(hPat, hSizes, nPat, syntax, -1, &pset)) return zerr(42);
+  const uint32_t M = pset.M, mMin = pset.mMin;
   HIPCHK_CLR(hipSetDevice(E.device_));
   hipStream_t s = E.stream_;
   E.reset_decode_stats();
@@ -137,24 +156,31 @@ Status ScanImpl::msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const u
   // ---- 4. the passes. tables: Table | Totals | bases[tiles] | counts[tiles] | waveCnt[4 * tiles]
   const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
   uint64_t possible = 0;                                                     // no list is longer: a start per pattern that fits the range
-  for (size_t i = 0; i < nPat && possible < matchCap; i++) possible += hi - lo >= hSizes[i] ? hi - lo - hSizes[i] + 1 : 0;
+  for (size_t i = 0; i < nPat && possible < matchCap; i++) possible += hi - lo >= pset.len[i] ? hi - lo - pset.len[i] + 1 : 0;
   const size_t listCap = (size_t)std::min<uint64_t>(matchCap, possible);
-  constexpr size_t kTotals = sizeof(Table) + 64, kHead = kTotals + sizeof(Totals);
+  const size_t kTotals = pset.table_bytes() + 64, kHead = kTotals + sizeof(Totals);
   std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros)
-  build_table(*(Table*)head.data(), hPat, hSizes, nPat);
+  build_pattern_table(head.data(), pset, hPat, hSizes, nPat);
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
   Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanMulti], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * 28 + 64, listCap * sizeof(Match) + 64, true,
                                [&](const ScanPass& ps) {
     uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
     const Table* const tbl = (const Table*)tb;
+    const ClassTable* const ctbl = (const ClassTable*)tb;                    // (one of the two, by the syntax word)
     Totals* const tot = (Totals*)(tb + kTotals);
     uint64_t* const bases = (uint64_t*)(tb + kHead);
     uint32_t* const counts = (uint32_t*)(bases + P.tilesMax);
     uint32_t* const waveCnt = counts + P.tilesMax;
     const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    hipLaunchKernelGGL(zra_msearch_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)nPat, counts, waveCnt, tot);
+    if (pset.classes)
+      hipLaunchKernelGGL(zra_msearch_count_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)nPat, counts, waveCnt, tot);
+    else
+      hipLaunchKernelGGL(zra_msearch_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)nPat, counts, waveCnt, tot);
     search_launch_scan(s, counts, tiles, bases, tot->cnt + (launches & 1), tot->cnt + ((launches + 1) & 1));
-    if (listCap)
+    if (listCap && pset.classes)
+      hipLaunchKernelGGL(zra_msearch_fill_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, counts, waveCnt, bases, (u64)ps.p0,
+                         E.scan_.list.as<Match>(), (u64)listCap);
+    else if (listCap)
       hipLaunchKernelGGL(zra_msearch_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, counts, waveCnt, bases, (u64)ps.p0,
                          E.scan_.list.as<Match>(), (u64)listCap);
   }, &launches, cv);

@@ -7,9 +7,13 @@
 //      b1. A position whose byte pair has no bit costs that one bit test; only a survivor is compared, against the patterns that begin
 //      with its first byte (bucketed on the host). The position hi - 1 has no second byte: it is a survivor iff a 1-byte pattern
 //      matches it. A survivor's hits are a 64-bit mask over the pattern indices.
+//  (classes) the calls with a syntax word (zra_pattern_expr.h: every element of a pattern is a byte set) use ClassTable and
+//      position_mask's overload for it, through the same kernel bodies: two 256-entry tables of 64-bit pattern masks, indexed by the position's
+//      first and second byte, are exact on two elements; their AND is the candidates, each verified element by element from the third.
 #pragma once
 #include "zra_scan.h"
 #include "zra_scan_tile.h"
+#include "zra_pattern_expr.h"
 #include <algorithm>
 #include <cstring>
 
@@ -71,8 +75,61 @@ inline void build_table(Table& T, const uint8_t* hPat, const uint32_t* hSizes, s
   for (size_t i = 0; i < nPat; i++) { T.order[first[src[0]]++] = (u8)i; src += hSizes[i]; }
 }
 
-__device__ __forceinline__ void stage_table(const Table* tbl, Table* sT) {
-  for (u32 c = threadIdx.x; c < sizeof(Table) / 16; c += 256) lds_st128((u8*)sT + 16 * (size_t)c, ((const uint4*)tbl)[c]);
+// (classes) What the host makes of compiled expressions, as it lies in device memory and in LDS (13,584 bytes).
+struct __attribute__((aligned(16))) ClassTable {
+  u64 first[256];                 // byte b: the patterns whose element 0 admits b
+  u64 second[256];                // byte b: the patterns whose element 1 admits b; a one-element pattern has its bit set everywhere
+  u32 member[256];                // byte b: bit c is set iff b is in counted set c (ZRA_HIP_PATTERN_MAX_SETS = 32)
+  u16 elem[kMaxPatternBytes];     // zra_expr's codes: a byte, a letter in either case, or a counted set's number
+  u16 off[kMaxPatterns];          // pattern i: elem[off .. off + len)
+  u16 len[kMaxPatterns];
+  u64 one, pad;                   // the one-element patterns
+};
+static_assert(sizeof(ClassTable) % 16 == 0 && sizeof(ClassTable) == 13584 && zra_expr::kMaxSets == 32 && zra_expr::kMaxElementsAll == kMaxPatternBytes, "staged 16 bytes at a time");
+
+inline void build_class_table(ClassTable& T, const zra_expr::Compiled& C) {
+  std::copy(C.codes.begin(), C.codes.end(), T.elem);
+  for (size_t i = 0; i < C.len.size(); i++) {
+    const zra_expr::ByteSet* const e = &C.elems[C.off[i]];
+    T.off[i] = (u16)C.off[i]; T.len[i] = (u16)C.len[i];
+    if (C.len[i] == 1) T.one |= 1ull << i;
+    for (uint32_t b = 0; b < 256; b++) {
+      if (e[0].has(b)) T.first[b] |= 1ull << i;
+      if (C.len[i] == 1 || e[1].has(b)) T.second[b] |= 1ull << i;
+    }
+  }
+  for (size_t c = 0; c < C.sets.size(); c++)
+    for (uint32_t b = 0; b < 256; b++) if (C.sets[c].has(b)) T.member[b] |= 1u << c;
+}
+
+// Rule 1 of the three calls as far as the patterns go, for every syntax word, and what the passes need of the patterns: their lengths
+// (in elements), the longest, the shortest, and the table that heads the call's device tables. syntax 0 is the literal calls' path,
+// byte for byte: Table and the literal kernels; any other accepted word compiles expressions and takes ClassTable and the class kernels.
+struct PatternSet {
+  bool classes = false;
+  uint32_t M = 0, mMin = kMaxPattern;
+  const uint32_t* len = nullptr;   // per pattern, in elements
+  zra_expr::Compiled C;
+  size_t table_bytes() const { return classes ? sizeof(ClassTable) : sizeof(Table); }
+};
+// delimiter: the grep's and the extract's, -1: none (the multi search). hPat and hSizes are not null.
+inline bool patterns_ok(const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, int delimiter, PatternSet* ps) {
+  if (syntax == 0) {
+    ps->len = hSizes;
+    return delimiter < 0 ? pattern_sizes_ok(hSizes, nPat, &ps->M, &ps->mMin) : record_patterns_ok(hPat, hSizes, nPat, (uint8_t)delimiter, &ps->M, &ps->mMin);
+  }
+  if (!zra_expr::compile(hPat, hSizes, nPat, syntax, delimiter, &ps->C)) return false;
+  ps->classes = true; ps->M = ps->C.M; ps->mMin = ps->C.mMin; ps->len = ps->C.len.data();
+  return true;
+}
+// the table into dst (table_bytes() zeroed bytes)
+inline void build_pattern_table(void* dst, const PatternSet& ps, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat) {
+  if (ps.classes) build_class_table(*(ClassTable*)dst, ps.C); else build_table(*(Table*)dst, hPat, hSizes, nPat);
+}
+
+template <class TB>
+__device__ __forceinline__ void stage_table(const TB* tbl, TB* sT) {
+  for (u32 c = threadIdx.x; c < sizeof(TB) / 16; c += 256) lds_st128((u8*)sT + 16 * (size_t)c, ((const uint4*)tbl)[c]);
 }
 
 // The patterns that occur at the position whose first byte is byte i of sTile, as a mask over their indices; avail = min(hi - p, 256)
@@ -99,6 +156,35 @@ __device__ __forceinline__ u64 position_mask(const Table* sT, const u32* sTile, 
   return mask;
 }
 
+// (classes) does the element with this code admit the byte b
+__device__ __forceinline__ bool admits(const ClassTable* sT, u32 code, u32 b) {
+  return code < zra_expr::kCodePair ? b == code : code < zra_expr::kCodeSet ? (b | 0x20) == (code & 0xFF) : ((sT->member[b] >> (code & 31)) & 1) != 0;
+}
+
+// (classes) position_mask over a ClassTable. The candidates are first[b0] & second[b1], exact on two elements (with avail < 2: first[b0]
+// of the one-element patterns); *surv: there is one. A candidate is verified from element 2 and leaves at the first miss; elements 2
+// and 3, where most candidates leave, take their bytes from the word the candidates came from. Only elements q < m <= avail are
+// tested, so no tile byte is read that the literal compare does not read.
+__device__ __forceinline__ u64 position_mask(const ClassTable* sT, const u32* sTile, u32 i, u32 avail, bool* surv) {
+  const u32 w = lds_word(sTile, i);
+  u64 cand = sT->first[w & 0xFF] & (avail >= 2 ? sT->second[(w >> 8) & 0xFF] : sT->one);
+  *surv = cand != 0;
+  u64 mask = 0;
+  for (; cand; cand &= cand - 1) {
+    const u32 pi = (u32)__builtin_ctzll(cand), m = sT->len[pi];
+    if (m > avail) continue;
+    const u16* const el = sT->elem + sT->off[pi];
+    bool hit = m < 3 || admits(sT, el[2], (w >> 16) & 0xFF);
+    if (hit && m > 3) hit = admits(sT, el[3], w >> 24);
+    for (u32 q = 4; q < m && hit; q++) {
+      const u32 at = i + q;
+      hit = admits(sT, el[q], (sTile[at >> 2] >> ((at & 3) * 8)) & 0xFF);
+    }
+    if (hit) mask |= 1ull << pi;
+  }
+  return mask;
+}
+
 // ---- the grep and the extract: a position's two flags, a list entry
 struct __attribute__((aligned(16))) Range { u64 offset, size; };   // ZraHipContentRange
 constexpr u64 kHitBit = 1ull << 63;                                // the hit bit of the record open at a tile's head, beside its start
@@ -106,7 +192,8 @@ constexpr u64 kHitBit = 1ull << 63;                                // the hit bi
 // The two ballots of trip t of a wave (tile position j = w0 + 64 t + lane; d = the index of the tile's first byte in sTile; toHi = the
 // bytes of the range at and behind the tile's first position): `delimiter` (its byte) and `hit` (a match starts here), and the lane's
 // matches as (position, pattern) pairs.
-__device__ __forceinline__ void trip_flags(const Table* sT, const u32* sTile, u32 d, u32 j, u32 n, long long toHi, u32 delim, u64* dm, u64* hm, u32* pairs) {
+template <class TB>
+__device__ __forceinline__ void trip_flags(const TB* sT, const u32* sTile, u32 d, u32 j, u32 n, long long toHi, u32 delim, u64* dm, u64* hm, u32* pairs) {
   bool isD = false, hit = false;
   if (j < n) {
     isD = (lds_word(sTile, d + j) & 0xFF) == delim;

@@ -44,15 +44,16 @@
 namespace zra_eng {
 
 struct ScanImpl {
-  // the four calls behind Engine's entry points, each in its own file
+  // the four calls behind Engine's entry points, each in its own file. syntax: the pattern syntax word of the ...Expr entry points
+  // (zra_pattern_expr.h), 0 for the literal ones
   static Status search(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, size_t m, uint64_t offset, uint64_t size, size_t stagingBytes,
                        uint64_t* hMatches, size_t matchCap, uint64_t* nMatches, ScanCacheView* cv = nullptr);
-  static Status msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint64_t offset, uint64_t size,
-                        size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv = nullptr);
-  static Status grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                     uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv = nullptr);
-  static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint8_t delimiter, uint32_t mode,
-                        uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
+  static Status msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint64_t offset,
+                        uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv = nullptr);
+  static Status grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
+                     uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv = nullptr);
+  static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
+                        uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                         uint64_t* dataSize, ScanCacheView* cv = nullptr);
 
   // What a call of the family leaves behind: entry_call's rule (zra_host.h). `which`: kScanSearch .. kScanExtract; out0 / out1: the

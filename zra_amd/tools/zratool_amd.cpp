@@ -17,6 +17,10 @@
 //         all) and a summary; exit status as grep: 0 some, 1 none, 2 trouble
 //   gx  : the text of those records, what `grep -F -f` prints (ZraHipExtractRecords): every selected record and its delimiter, packed on
 //         the device, to stdout or with -o {file} to a file; -v and -d as gl; exit status as grep, and no output when nothing is selected
+//   gme, gle, gxe: gm, gl and gx with pattern expressions (ZraHipSearchArchiveMultiExpr, ZraHipGrepArchiveExpr, ZraHipExtractRecordsExpr):
+//         a pattern is an expression of fixed length, . [set] [^set] \escape (zra_hip.h: ZraHipCheckPatternExpr); -i: ASCII letters
+//         match either case, -F: the patterns are literal after all; behind "hex:" a pattern is literal bytes either way. A refused
+//         expression is exit status 2 with a message that names the pattern's index; otherwise output and exit status of gm, gl, gx
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
@@ -169,6 +173,50 @@ bool parse_pattern(const char* text, std::string* out) {
   return true;
 }
 
+// The modes with pattern expressions (gme, gle, gxe): -i and -F. Null for gm, gl and gx.
+struct ExprOpt { bool fold, fixed; };
+
+// The patterns texts[0 .. n) of a multi-pattern mode laid end to end, their sizes and the calls' syntax word. delimiter: gl's and gx's,
+// -1 for gm. Without ex the patterns are literal (syntax 0). With ex a pattern is an expression unless -F was given; a "hex:" pattern
+// becomes \xHH escapes, so that it stays literal bytes. false: message printed, for an expression with the pattern's index.
+bool gather_patterns(char** texts, int n, int delimiter, const ExprOpt* ex, std::string* all, std::vector<uint32_t>* sizes, uint32_t* syntax) {
+  *syntax = !ex ? 0u : (ex->fold ? ZRA_HIP_PATTERN_FOLD_CASE : 0u) | (ex->fixed ? 0u : ZRA_HIP_PATTERN_CLASSES);
+  const bool expr = (*syntax & ZRA_HIP_PATTERN_CLASSES) != 0;
+  for (int i = 0; i < n; i++) {
+    std::string pat;
+    if (!expr || std::string(texts[i]).rfind("hex:", 0) == 0) {
+      if (!parse_pattern(texts[i], &pat)) return false;
+      if (expr) {
+        std::string esc;
+        char b[8];
+        for (unsigned char c : pat) { std::snprintf(b, sizeof b, "\\x%02x", c); esc += b; }
+        pat = esc;
+      }
+    } else pat = texts[i];
+    if (ex) {
+      const uint32_t size = (uint32_t)pat.size();
+      if (ZraHipCheckPatternExpr(pat.data(), &size, 1, *syntax, delimiter, nullptr, nullptr).zra != Success) {
+        std::fprintf(stderr, "pattern %d: not a pattern expression of 1 to %u elements%s\n", i, ZRA_HIP_SEARCH_MAX_PATTERN, delimiter >= 0 ? ", or it matches the delimiter" : "");
+        return false;
+      }
+    }
+    *all += pat;
+    sizes->push_back((uint32_t)pat.size());
+  }
+  if (ex) {
+    if (n >= 1 && ZraHipCheckPatternExpr(all->data(), sizes->data(), sizes->size(), *syntax, delimiter, nullptr, nullptr).zra == Success) return true;
+    std::fprintf(stderr, "1 to %u patterns of %u elements, %u expression bytes and %u byte sets in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES,
+                 ZRA_HIP_PATTERN_MAX_EXPR_BYTES, ZRA_HIP_PATTERN_MAX_SETS);
+    return false;
+  }
+  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all->size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
+    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
+    return false;
+  }
+  if (delimiter >= 0 && all->find((char)delimiter) != std::string::npos) { std::fprintf(stderr, "a pattern holds the delimiter %02x\n", delimiter); return false; }
+  return true;
+}
+
 // mode g
 int search_archive(const char* path, const char* text) {
   std::string pat;
@@ -191,20 +239,12 @@ int search_archive(const char* path, const char* text) {
   return n ? 0 : 1;
 }
 
-// mode gm: the patterns texts[0 .. n), their indices in that order
-int search_archive_multi(const char* path, char** texts, int n) {
+// modes gm and (ex) gme: the patterns texts[0 .. n), their indices in that order
+int search_archive_multi(const char* path, char** texts, int n, const ExprOpt* ex) {
   std::string all;
   std::vector<uint32_t> sizes;
-  for (int i = 0; i < n; i++) {
-    std::string pat;
-    if (!parse_pattern(texts[i], &pat)) return 2;
-    all += pat;
-    sizes.push_back((uint32_t)pat.size());
-  }
-  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all.size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
-    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
-    return 2;
-  }
+  uint32_t syntax = 0;
+  if (!gather_patterns(texts, n, -1, ex, &all, &sizes, &syntax)) return 2;
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -213,7 +253,8 @@ int search_archive_multi(const char* path, char** texts, int n) {
   if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
   std::vector<ZraHipPatternMatch> at(1u << 20);
   uint64_t total = 0;
-  st = ZraHipSearchArchiveMulti(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), 0, UINT64_MAX, 0, at.data(), at.size(), &total, nullptr);
+  st = ex ? ZraHipSearchArchiveMultiExpr(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, 0, UINT64_MAX, 0, at.data(), at.size(), &total, nullptr)
+          : ZraHipSearchArchiveMulti(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), 0, UINT64_MAX, 0, at.data(), at.size(), &total, nullptr);
   if (dArc) (void)hipFree(dArc);
   ZraHipDestroyEngine(eng);
   if (st.zra != Success) { std::fprintf(stderr, "%s: cannot search: %s\n", path, ZraGetErrorString(st)); return 2; }
@@ -223,21 +264,12 @@ int search_archive_multi(const char* path, char** texts, int n) {
   return total ? 0 : 1;
 }
 
-// mode gl: the patterns texts[0 .. n)
-int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts, int n) {
+// modes gl and (ex) gle: the patterns texts[0 .. n)
+int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts, int n, const ExprOpt* ex) {
   std::string all;
   std::vector<uint32_t> sizes;
-  for (int i = 0; i < n; i++) {
-    std::string pat;
-    if (!parse_pattern(texts[i], &pat)) return 2;
-    all += pat;
-    sizes.push_back((uint32_t)pat.size());
-  }
-  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all.size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
-    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
-    return 2;
-  }
-  if (all.find((char)delimiter) != std::string::npos) { std::fprintf(stderr, "a pattern holds the delimiter %02x\n", delimiter); return 2; }
+  uint32_t syntax = 0;
+  if (!gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -246,8 +278,9 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
   std::vector<ZraHipContentRange> at(1u << 20);
   uint64_t total = 0;
-  st = ZraHipGrepArchive(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, invert ? ZRA_HIP_GREP_INVERT : 0u, 0, UINT64_MAX, 0, at.data(),
-                         at.size(), &total);
+  const uint32_t mode = invert ? ZRA_HIP_GREP_INVERT : 0u;
+  st = ex ? ZraHipGrepArchiveExpr(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, at.data(), at.size(), &total)
+          : ZraHipGrepArchive(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, at.data(), at.size(), &total);
   if (dArc) (void)hipFree(dArc);
   ZraHipDestroyEngine(eng);
   if (st.zra != Success) { std::fprintf(stderr, "%s: cannot grep: %s\n", path, ZraGetErrorString(st)); return 2; }
@@ -257,22 +290,13 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   return total ? 0 : 1;
 }
 
-// mode gx: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to stdout when it is
+// modes gx and (ex) gxe: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to stdout when it is
 // null. Nothing is written when a call fails or when nothing is selected.
-int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n) {
+int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex) {
   std::string all;
   std::vector<uint32_t> sizes;
-  for (int i = 0; i < n; i++) {
-    std::string pat;
-    if (!parse_pattern(texts[i], &pat)) return 2;
-    all += pat;
-    sizes.push_back((uint32_t)pat.size());
-  }
-  if (n < 1 || n > (int)ZRA_HIP_SEARCH_MAX_PATTERNS || all.size() > ZRA_HIP_SEARCH_MAX_PATTERN_BYTES) {
-    std::fprintf(stderr, "1 to %u patterns of %u bytes in all\n", ZRA_HIP_SEARCH_MAX_PATTERNS, ZRA_HIP_SEARCH_MAX_PATTERN_BYTES);
-    return 2;
-  }
-  if (all.find((char)delimiter) != std::string::npos) { std::fprintf(stderr, "a pattern holds the delimiter %02x\n", delimiter); return 2; }
+  uint32_t syntax = 0;
+  if (!gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -282,13 +306,17 @@ int extract_records(const char* path, bool invert, uint8_t delimiter, const char
   const uint32_t mode = invert ? ZRA_HIP_GREP_INVERT : 0u;
   uint64_t total = 0, bytes = 0;
   std::string text;
-  st = ZraHipExtractRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, nullptr, 0, &bytes);
+  auto extract = [&](void* dOut, size_t cap) {
+    return ex ? ZraHipExtractRecordsExpr(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dOut,
+                                         cap, &bytes)
+              : ZraHipExtractRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dOut, cap, &bytes);
+  };
+  st = extract(nullptr, 0);
   if (st.zra == OutputBufferTooSmall) {
     text.resize(bytes);
     if (hipMalloc(&dData, bytes) != hipSuccess) { dData = nullptr; st.zra = ZStdError; st.zstd = 64; }
     else {
-      st = ZraHipExtractRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dData, bytes,
-                                &bytes);
+      st = extract(dData, bytes);
       if (st.zra == Success && hipMemcpy(&text[0], dData, bytes, hipMemcpyDeviceToHost) != hipSuccess) { st.zra = ZStdError; st.zstd = 1; }
     }
   }
@@ -497,6 +525,9 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gm {file} {pattern | hex:digits}...
 //       gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}...
 //       gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}...
+//       gme {file} {-i} {-F} {expression | hex:digits}...
+//       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
+//       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
@@ -516,6 +547,7 @@ int main(int argc, char** argv) {
                 "gm {file} {pattern | hex:digits}... - Search an archive on the device for 1 to 64 patterns in one pass: offset and pattern index of every match (exit status as g)\n"
                 "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}... - Grep an archive on the device: offset and size of every record (line) that holds a match, -v: that holds none (exit status 0 some, 1 none, 2 trouble)\n"
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
+                "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -533,10 +565,21 @@ int main(int argc, char** argv) {
   }
   if (mode == "gm") {
     if (argc < 4) { std::fprintf(stderr, "gm {file} {pattern | hex:digits}...\n"); return 2; }
-    return search_archive_multi(argv[2], argv + 3, argc - 3);
+    return search_archive_multi(argv[2], argv + 3, argc - 3, nullptr);
   }
-  if (mode == "gl" || mode == "gx") {
-    const bool text = mode == "gx";
+  if (mode == "gme") {
+    ExprOpt ex = {false, false};
+    int i = 3;
+    for (; i < argc; i++) {
+      const std::string opt = argv[i];
+      if (opt == "-i") ex.fold = true; else if (opt == "-F") ex.fixed = true; else break;
+    }
+    if (i >= argc) { std::fprintf(stderr, "gme {file} {-i} {-F} {expression | hex:digits}...\n"); return 2; }
+    return search_archive_multi(argv[2], argv + i, argc - i, &ex);
+  }
+  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe") {
+    const bool text = mode[1] == 'x', expr = mode.size() == 3;
+    ExprOpt ex = {false, false};
     bool invert = false;
     unsigned long delimiter = 0x0A;
     const char* outPath = nullptr;
@@ -544,6 +587,8 @@ int main(int argc, char** argv) {
     for (; i < argc; i++) {
       const std::string opt = argv[i];
       if (opt == "-v") invert = true;
+      else if (expr && opt == "-i") ex.fold = true;
+      else if (expr && opt == "-F") ex.fixed = true;
       else if (text && opt == "-o") {
         if (++i >= argc || !*argv[i]) { std::fprintf(stderr, "-o takes a file name\n"); return 2; }
         outPath = argv[i];
@@ -553,9 +598,13 @@ int main(int argc, char** argv) {
         if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
       } else break;
     }
-    if (i >= argc) { std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s{pattern | hex:digits}...\n", mode.c_str(), text ? "{-o file} " : ""); return 2; }
-    if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i);
-    return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i);
+    if (i >= argc) {
+      std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s%s{%s | hex:digits}...\n", mode.c_str(), expr ? "{-i} {-F} " : "", text ? "{-o file} " : "",
+                   expr ? "expression" : "pattern");
+      return 2;
+    }
+    if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, expr ? &ex : nullptr);
+    return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, expr ? &ex : nullptr);
   }
   if (mode == "cmp") {
     if (argc < 4) { std::fprintf(stderr, "cmp {file A} {file B}\n"); return 2; }
