@@ -81,6 +81,8 @@ def lib():
             f = getattr(L, p + "_zra_decompress_ra")
             f.restype = Status
             f.argtypes = [vp, sz, vp, sz, sz, sz]
+        L.zo_huf_select_decoder.restype = i                 # HUF_selectDecoder: 0 = single-symbol, 1 = double-symbol decoder
+        L.zo_huf_select_decoder.argtypes = [sz, sz]
         L.zo_libzstd_load.restype = i
         L.zo_libzstd_load.argtypes = [ctypes.c_char_p]
         L.zo_libzstd_version.restype = ctypes.c_char_p
