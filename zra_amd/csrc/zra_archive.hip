@@ -16,6 +16,7 @@
 #include "zra_scan.h"
 #include "zra_host.h"
 #include "zra_dev.h"
+#include "zra_joblist.h"
 #include "zra_kernels.h"
 #include <algorithm>
 #include <cstring>
@@ -123,52 +124,11 @@ extern "C" __global__ void __launch_bounds__(256) zra_cache_commit_kernel(const 
   if (t >= n && t < V) ref[victim[t]] = 0;
 }
 
-// A pass of a range scan through the handle (zra_scan.h): one workgroup walks the frames [first, first + n) of the pass, 1024 at a time
-// (zra_upd_plan_kernel's scheme: ballot + prefix counts over the chunk, a running base across chunks; no atomic decides a position).
-// A frame that is not resident gets a decode job, ranked in frame order: its seek-table span (whatever it says: the decoder refuses
-// a span that runs backwards or leaves the body), destination = its slot of the pass, expected size = its share of the content. A
-// resident frame gets a copy entry {window slot, arena slot, length, frame}, ranked the same way (zra_upd_stage_cached_kernel's
-// format). counts = {jobs, copies, bytes the jobs are to regenerate (low, high word)}. Nothing of the cache is written.
+// A pass of a range scan through the handle (zra_scan.h): the frames [first, first + n) of the pass, split by residency into decode
+// jobs and copy entries (zra_joblist.h, split_by_residency: entry k is frame first + k).
 extern "C" __global__ void __launch_bounds__(1024) zra_scan_split_kernel(const u32* slotOf, u32 nFrames, const u8* table, u64 fs, u64 total, u64 first, u32 n,
                                                                       u64* frameOff, u64* outOff, u32* expect, u32* copies, u32* counts) {
-  __shared__ u32 sJ[16], sC[16];
-  __shared__ u64 sB[16];
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  u32 jobBase = 0, copyBase = 0;
-  u64 bytes = 0;
-  for (u32 base = 0; base < n; base += 1024) {
-    const u32 k = base + tid;
-    const bool in = k < n;
-    const u64 f = first + k;
-    const u32 cs = in && f < nFrames ? slotOf[f] : kNone;
-    const u32 len = in ? (u32)frame_expect(f, fs, total) : 0u;
-    const bool cpy = in && cs != kNone, dec = in && !cpy;
-    const u64 mJ = __ballot(dec), mC = __ballot(cpy), below = (1ull << lane) - 1;
-    u64 wb = dec ? (u64)len : 0ull;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) wb += __shfl_xor(wb, d, 64);
-    if (lane == 0) { sJ[wave] = (u32)__popcll(mJ); sC[wave] = (u32)__popcll(mC); sB[wave] = wb; }
-    __syncthreads();
-    u32 beforeJ = 0, beforeC = 0, totalJ = 0, totalC = 0;
-    for (u32 w = 0; w < 16; w++) {
-      const u32 j = sJ[w], c = sC[w];
-      beforeJ += w < wave ? j : 0u; beforeC += w < wave ? c : 0u; totalJ += j; totalC += c;
-      bytes += sB[w];
-    }
-    if (cpy) {
-      u32* e = copies + 4 * (size_t)(copyBase + beforeC + (u32)__popcll(mC & below));
-      e[0] = k; e[1] = cs; e[2] = len; e[3] = (u32)f;
-    }
-    if (dec) {
-      const u32 job = jobBase + beforeJ + (u32)__popcll(mJ & below);
-      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, f + 1);
-      outOff[job] = (u64)k * fs;
-      expect[job] = len;
-    }
-    jobBase += totalJ; copyBase += totalC;
-    __syncthreads();                                                  // (sJ, sC, sB of the next chunk)
-  }
-  if (tid == 0) { counts[0] = jobBase; counts[1] = copyBase; counts[2] = (u32)bytes; counts[3] = (u32)(bytes >> 32); }
+  split_by_residency(n, [=](u32 k) { return first + k; }, slotOf, nFrames, table, fs, total, frameOff, outOff, expect, copies, counts);
 }
 
 // =================================================================================================

@@ -36,6 +36,7 @@
 // The diff of two archives (zra_hip.h: ZraHipDiffArchives) is the second half of this file: the same passes with the plaintext kept.
 #include "zra_framepass.h"
 #include "zra_dev.h"
+#include "zra_joblist.h"
 #include <algorithm>
 
 using namespace zra_dev;
@@ -196,43 +197,30 @@ extern "C" __global__ void __launch_bounds__(256) zra_cmp_spans_kernel(const u8*
   if (lane == 0) flags[j] = decode ? 1 : 0;
 }
 
-// One workgroup: the decode-flagged slots of the pass, in order, become jobs 0 .. nDec - 1 of archive A (frameOff / expect at job k)
-// and of archive B (at job jobsB + k); outOff[k] = the slot's place in its half, the same for both. A job decodes its frame's seek-table
-// span, whatever it says (the decoder refuses a span that runs backwards or leaves the body), and has to regenerate that frame's share
-// of its own archive's content. hdr: the job count for the host, and the content bytes of [lo, hi) inside the decoded frames, summed.
+// One workgroup walks the slots of the pass, 1024 at a time: the decode-flagged ones, in order, become jobs 0 .. nDec - 1 of archive A
+// (zra_joblist.h: block_rank, emit_job at job k) and of archive B (at job jobsB + k); outOff[k] = the slot's place in its half, the
+// same for both. A job has to regenerate its frame's share of its own archive's content. hdr: the job count for the host, and the
+// content bytes of [lo, hi) inside the decoded frames, summed.
 extern "C" __global__ void __launch_bounds__(1024) zra_cmp_jobs_kernel(const u8* flags, u32 nj, const u8* tableA, u64 UA, const u8* tableB, u64 UB, u64 fs,
                                                                        u64 first, u64 lo, u64 hi, u64* frameOff, u64* outOff, u32* expect, u32 jobsB, u8* hdr) {
-  __shared__ u32 sS[1024];
-  __shared__ u64 sBytes;
-  const u32 tid = threadIdx.x;
-  const u32 per = (nj + 1023) / 1024;
-  const u32 s0 = min(nj, tid * per), s1 = min(nj, s0 + per);
-  u32 own = 0;
-  for (u32 s = s0; s < s1; s++) own += flags[s] != 0;
-  sS[tid] = own;
-  if (tid == 0) sBytes = 0;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
-    const u32 x = tid >= d ? sS[tid - d] : 0;
-    __syncthreads();
-    sS[tid] += x;
-    __syncthreads();
+  u32 jobBase = 0;
+  u64 bytes[1] = {0}, allBytes[1];
+  for (u32 base = 0; base < nj; base += 1024) {
+    const u32 s = base + threadIdx.x;
+    const bool p[1] = {s < nj && flags[s] != 0};
+    u32 rank[1], total[1];
+    block_rank<1>(p, rank, total);
+    if (p[0]) {
+      const u64 f = first + s;
+      const size_t k = jobBase + rank[0];
+      emit_job(tableA, f, fs, UA, k, s, frameOff, outOff, expect);
+      emit_job(tableB, f, fs, UB, (size_t)jobsB + k, s, frameOff, nullptr, expect);
+      bytes[0] += min(hi, (f + 1) * fs) - max(lo, f * fs);
+    }
+    jobBase += total[0];
   }
-  u32 k = sS[tid] - own;
-  u64 bytes = 0;
-  for (u32 s = s0; s < s1; s++) {
-    if (!flags[s]) continue;
-    const u64 f = first + s;
-    frameOff[2 * (size_t)k] = seek_entry(tableA, f); frameOff[2 * (size_t)k + 1] = seek_entry(tableA, f + 1);
-    frameOff[2 * ((size_t)jobsB + k)] = seek_entry(tableB, f); frameOff[2 * ((size_t)jobsB + k) + 1] = seek_entry(tableB, f + 1);
-    expect[k] = (u32)frame_expect(f, fs, UA); expect[(size_t)jobsB + k] = (u32)frame_expect(f, fs, UB);
-    outOff[k] = (u64)s * fs;
-    bytes += min(hi, (f + 1) * fs) - max(lo, f * fs);
-    k++;
-  }
-  if (bytes) atomicAdd((unsigned long long*)&sBytes, (unsigned long long)bytes);
-  __syncthreads();
-  if (tid == 1023) { *(u32*)(hdr + kOffJobs) = sS[1023]; *(u64*)(hdr + kOffBytes) += sBytes; }
+  block_excl_scan<1>(bytes, allBytes);
+  if (threadIdx.x == 0) { *(u32*)(hdr + kOffJobs) = jobBase; *(u64*)(hdr + kOffBytes) += allBytes[0]; }
 }
 
 // Workgroup 0 is item 0 of the pass (the end at the pass's first byte, when the pass in front left a run open and the first frame is
@@ -254,33 +242,10 @@ extern "C" __global__ void __launch_bounds__(256) zra_cmp_count_kernel(TileArgs 
 }
 
 // One workgroup, in place: tab[2 i] / tab[2 i + 1] = totIn + the starts / ends of the items in front of item i, for i = 0 .. nItems
-// (entry nItems: behind all of them; an item's own counts are the difference to the next entry); totOut = that last entry.
+// (entry nItems: behind all of them; an item's own counts are the difference to the next entry); totOut = that last entry
+// (zra_joblist.h, scan_in_place).
 extern "C" __global__ void __launch_bounds__(1024) zra_cmp_scan_kernel(u64* tab, u32 nItems, const u64* totIn, u64* totOut) {
-  __shared__ u64 sS[1024], sE[1024];
-  const u32 tid = threadIdx.x;
-  const u32 per = (nItems + 1023) / 1024;
-  const u32 i0 = min(nItems, tid * per), i1 = min(nItems, i0 + per);
-  u64 ownS = 0, ownE = 0;
-  for (u32 i = i0; i < i1; i++) { ownS += tab[2 * (size_t)i]; ownE += tab[2 * (size_t)i + 1]; }
-  sS[tid] = ownS; sE[tid] = ownE;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
-    const u64 x = tid >= d ? sS[tid - d] : 0, y = tid >= d ? sE[tid - d] : 0;
-    __syncthreads();
-    sS[tid] += x; sE[tid] += y;
-    __syncthreads();
-  }
-  u64 atS = totIn[0] + sS[tid] - ownS, atE = totIn[1] + sE[tid] - ownE;
-  for (u32 i = i0; i < i1; i++) {
-    const u64 cS = tab[2 * (size_t)i], cE = tab[2 * (size_t)i + 1];
-    tab[2 * (size_t)i] = atS; tab[2 * (size_t)i + 1] = atE;
-    atS += cS; atE += cE;
-  }
-  if (tid == 1023) {
-    const u64 eS = totIn[0] + sS[1023], eE = totIn[1] + sE[1023];
-    tab[2 * (size_t)nItems] = eS; tab[2 * (size_t)nItems + 1] = eE;
-    totOut[0] = eS; totOut[1] = eE;
-  }
+  scan_in_place<2>(tab, nItems, totIn, totOut);
 }
 
 // Workgroup i redoes item i's compare when one of its starts or ends has a place in the lists (an item without any, or behind the
@@ -441,30 +406,10 @@ extern "C" __global__ void __launch_bounds__(256) zra_diff_count_kernel(TileArgs
   }
 }
 
-// zra_cmp_scan_kernel with three columns: tab[3 i + c] = totIn[c] + column c of the items in front of item i, for i = 0 .. nItems;
-// totOut = the last entry.
+// zra_cmp_scan_kernel's table with three columns: tab[3 i + c] = totIn[c] + column c of the items in front of item i, for
+// i = 0 .. nItems; totOut = the last entry.
 extern "C" __global__ void __launch_bounds__(1024) zra_diff_scan_kernel(u64* tab, u32 nItems, const u64* totIn, u64* totOut) {
-  __shared__ u64 sS[3][1024];
-  const u32 tid = threadIdx.x;
-  const u32 per = (nItems + 1023) / 1024;
-  const u32 i0 = min(nItems, tid * per), i1 = min(nItems, i0 + per);
-  u64 own[3] = {0, 0, 0};
-  for (u32 i = i0; i < i1; i++) for (u32 c = 0; c < 3; c++) own[c] += tab[3 * (size_t)i + c];
-  for (u32 c = 0; c < 3; c++) sS[c][tid] = own[c];
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
-    u64 x[3];
-    for (u32 c = 0; c < 3; c++) x[c] = tid >= d ? sS[c][tid - d] : 0;
-    __syncthreads();
-    for (u32 c = 0; c < 3; c++) sS[c][tid] += x[c];
-    __syncthreads();
-  }
-  u64 at[3];
-  for (u32 c = 0; c < 3; c++) at[c] = totIn[c] + sS[c][tid] - own[c];
-  for (u32 i = i0; i < i1; i++)
-    for (u32 c = 0; c < 3; c++) { const u64 n = tab[3 * (size_t)i + c]; tab[3 * (size_t)i + c] = at[c]; at[c] += n; }
-  if (tid == 1023)
-    for (u32 c = 0; c < 3; c++) { const u64 e = totIn[c] + sS[c][1023]; tab[3 * (size_t)nItems + c] = e; totOut[c] = e; }
+  scan_in_place<3>(tab, nItems, totIn, totOut);
 }
 
 // Workgroup i redoes item i's mask when it holds a listed start or end, or a dirty byte with a place in front of dataCap (an item

@@ -464,8 +464,8 @@ class Engine {
 // t, *cntOut = *cntIn + all of them; the last n bytes of the run win[.., L) moved to win[-n, 0), n <= 255.
 void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,
                         uint32_t* expect);
-// A pass of a range scan through a handle (zra_scan.h): frames [first, first + n) split by residency (zra_archive.hip,
-// zra_scan_split_kernel) into decode jobs and copy entries of 4 words, counts = {jobs, copies, bytes the jobs regenerate (2 words)};
+// A pass of a range scan through a handle (zra_scan.h): frames [first, first + n) split by residency (zra_joblist.h,
+// split_by_residency) into decode jobs and copy entries of 4 words, counts = {jobs, copies, bytes the jobs regenerate (2 words)};
 // and the copy entries [0, n) staged from the arena, entry slot e[0] to stage + (e[0] - s0) * fs (zra_update.hip, the update's
 // zra_upd_stage_cached_kernel).
 void scan_launch_split(hipStream_t s, const uint32_t* slotOf, uint32_t nFrames, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n,

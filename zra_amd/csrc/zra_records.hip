@@ -49,6 +49,7 @@
 #include "zra_framepass.h"
 #include "zra_scan.h"
 #include "zra_dev.h"
+#include "zra_joblist.h"
 #include <algorithm>
 #include <vector>
 
@@ -61,7 +62,6 @@ constexpr u32 kTile = zra_eng::kScanTile;
 constexpr u32 kHdrBytes = 128, kOffD = 0, kOffZero = 8, kOffTot = 16, kOffJobs = 40, kOffStale = 44, kOffOob = 48;
 constexpr u64 kCountMask = ~(1ull << 63);
 constexpr u64 kDirect = ~0ull;               // a boundary that needs no lookup: its position is written by the bounds launch
-constexpr u32 kNotResident = 0xFFFFFFFFu;    // a handle's frame -> arena slot table: the frame is not in the cache
 
 // bit 7 of every byte of w that equals the delimiter (d4: the delimiter in all four bytes); exact, no carry between bytes
 __device__ __forceinline__ u32 eq_bytes(u32 w, u32 d4) {
@@ -186,84 +186,32 @@ extern "C" __global__ void __launch_bounds__(256) zra_rec_bounds_kernel(const u6
   }
 }
 
-// One workgroup: the flagged frames, ascending, become jobs 0 .. nJobs - 1; a job decodes its frame's seek-table span, whatever it
-// says (the decoder refuses a span that runs backwards or leaves the body), and has to regenerate that frame's share of the content.
-// slotFrame[k] = the frame of job k, slotOf[frame] = k; outOff[j] = j * fs for the slots of one pass (the same every pass).
+// One workgroup walks the frames, 1024 at a time: the flagged ones, ascending, become jobs 0 .. nJobs - 1 (zra_joblist.h: block_rank,
+// emit_job). slotFrame[k] = the frame of job k, slotOf[frame] = k; outOff[j] = j * fs for the slots of one pass (the same every pass).
 extern "C" __global__ void __launch_bounds__(1024) zra_rec_jobs_kernel(const u8* need, u32 F, const u8* table, u64 U, u64 fs, u32 passSlots, u64* frameOff, u64* outOff,
                                                                        u32* expect, u32* slotFrame, u32* slotOf, u32* nJobs) {
-  __shared__ u32 sS[1024];
-  const u32 tid = threadIdx.x;
-  const u32 per = (u32)(((u64)F + 1023) / 1024);
-  const u32 f0 = (u32)min((u64)F, (u64)tid * per), f1 = (u32)min((u64)F, (u64)f0 + per);
-  u32 own = 0;
-  for (u32 f = f0; f < f1; f++) own += need[f] != 0;
-  sS[tid] = own;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
-    const u32 x = tid >= d ? sS[tid - d] : 0;
-    __syncthreads();
-    sS[tid] += x;
-    __syncthreads();
+  u32 jobBase = 0;
+  for (u64 base = 0; base < F; base += 1024) {                        // (64 bits: F may lie within 1024 of 2^32)
+    const u64 f = base + threadIdx.x;
+    const bool p[1] = {f < F && need[f] != 0};
+    u32 rank[1], total[1];
+    block_rank<1>(p, rank, total);
+    if (p[0]) {
+      const u32 k = jobBase + rank[0];
+      emit_job(table, f, fs, U, k, k, frameOff, k < passSlots ? outOff : nullptr, expect);
+      slotFrame[k] = (u32)f; slotOf[f] = k;
+    }
+    jobBase += total[0];
   }
-  u32 k = sS[tid] - own;
-  for (u32 f = f0; f < f1; f++) {
-    if (!need[f]) continue;
-    frameOff[2 * (size_t)k] = seek_entry(table, f); frameOff[2 * (size_t)k + 1] = seek_entry(table, (u64)f + 1);
-    expect[k] = (u32)frame_expect(f, fs, U);
-    if (k < passSlots) outOff[k] = (u64)k * fs;
-    slotFrame[k] = f; slotOf[f] = k;
-    k++;
-  }
-  if (tid == 1023) *nJobs = sS[1023];
+  if (threadIdx.x == 0) *nJobs = jobBase;
 }
 
-// A pass of the locate sweep through a handle: one workgroup walks the frame LIST slotFrame[0 .. n) of the pass (ascending; the caller
-// passes slotFrame + j0), 1024 at a time (zra_scan_split_kernel's scheme, zra_archive.hip: ballot + popcount per wave, a wave table in LDS,
-// a running base across chunks; no atomic decides a position). Entry k is frame f in slot k of the window. cacheSlotOf[f] ==
-// kNotResident: a decode job, ranked in list order from job 0: its seek-table span (whatever it says: the decoder refuses a span that
-// runs backwards or leaves the body), destination k * fs, expected size = its share of the content. Otherwise a copy entry {k, arena
-// slot, length, frame}, ranked the same way (zra_upd_stage_cached_kernel's format). counts = {jobs, copies, bytes the jobs are to
-// regenerate (low, high word)}. Nothing of the cache is written.
+// A pass of the locate sweep through a handle: the frame LIST slotFrame[0 .. n) of the pass (ascending; the caller passes
+// slotFrame + j0), split by residency into decode jobs and copy entries (zra_joblist.h, split_by_residency: entry k is frame
+// slotFrame[k] in slot k of the window).
 extern "C" __global__ void __launch_bounds__(1024) zra_rec_split_kernel(const u32* slotFrame, u32 n, const u32* cacheSlotOf, u32 nFrames, const u8* table, u64 fs, u64 U,
                                                                         u64* frameOff, u64* outOff, u32* expect, u32* copies, u32* counts) {
-  __shared__ u32 sJ[16], sC[16];
-  __shared__ u64 sB[16];
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  u32 jobBase = 0, copyBase = 0;
-  u64 bytes = 0;
-  for (u32 base = 0; base < n; base += 1024) {
-    const u32 k = base + tid;
-    const bool in = k < n;
-    const u32 f = in ? slotFrame[k] : 0u;
-    const u32 cs = in && f < nFrames ? cacheSlotOf[f] : kNotResident;
-    const u32 len = in ? (u32)frame_expect(f, fs, U) : 0u;
-    const bool cpy = in && cs != kNotResident, dec = in && !cpy;
-    const u64 mJ = __ballot(dec), mC = __ballot(cpy), below = (1ull << lane) - 1;
-    u64 wb = dec ? (u64)len : 0ull;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) wb += __shfl_xor(wb, d, 64);
-    if (lane == 0) { sJ[wave] = (u32)__popcll(mJ); sC[wave] = (u32)__popcll(mC); sB[wave] = wb; }
-    __syncthreads();
-    u32 beforeJ = 0, beforeC = 0, totalJ = 0, totalC = 0;
-    for (u32 w = 0; w < 16; w++) {
-      const u32 j = sJ[w], c = sC[w];
-      beforeJ += w < wave ? j : 0u; beforeC += w < wave ? c : 0u; totalJ += j; totalC += c;
-      bytes += sB[w];
-    }
-    if (cpy) {
-      u32* e = copies + 4 * (size_t)(copyBase + beforeC + (u32)__popcll(mC & below));
-      e[0] = k; e[1] = cs; e[2] = len; e[3] = f;
-    }
-    if (dec) {
-      const u32 job = jobBase + beforeJ + (u32)__popcll(mJ & below);
-      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, (u64)f + 1);
-      outOff[job] = (u64)k * fs;
-      expect[job] = len;
-    }
-    jobBase += totalJ; copyBase += totalC;
-    __syncthreads();                                                  // (sJ, sC, sB of the next chunk)
-  }
-  if (tid == 0) { counts[0] = jobBase; counts[1] = copyBase; counts[2] = (u32)bytes; counts[3] = (u32)(bytes >> 32); }
+  split_by_residency(n, [=](u32 k) { return slotFrame[k]; }, cacheSlotOf, nFrames, table, fs, U, frameOff, outOff, expect, copies, counts);
 }
 
 // A wave per boundary x whose frame is one of the jobs [j0, j0 + nj) of this pass: ordinal j of the frame. A binary search over the

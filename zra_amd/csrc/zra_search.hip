@@ -13,6 +13,7 @@
 //      come to the host, once.
 #include "zra_scan.h"
 #include "zra_scan_tile.h"
+#include "zra_joblist.h"
 #include <algorithm>
 
 namespace {
@@ -48,16 +49,11 @@ __device__ __forceinline__ u32 scan_tile(const u8* win, long long x0, u32 n, con
 }
 }  // namespace
 
-// Lane per frame of a pass: job j decodes frame first + j (its seek-table span, whatever it says: the decoder refuses a span that runs
-// backwards or leaves the body) into slot j, and has to regenerate that frame's share of the content.
+// Lane per frame of a pass: job j decodes frame first + j into slot j (zra_joblist.h, emit_job).
 extern "C" __global__ void __launch_bounds__(256) zra_search_jobs_kernel(const u8* table, u64 fs, u64 total, u64 first, u32 n, u64* frameOff, u64* outOff,
                                                                          u32* expect) {
   const u32 j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const u64 f = first + j;
-  frameOff[2 * (size_t)j] = seek_entry(table, f); frameOff[2 * (size_t)j + 1] = seek_entry(table, f + 1);
-  outOff[j] = (u64)j * fs;
-  expect[j] = (u32)frame_expect(f, fs, total);
+  if (j < n) emit_job(table, first + j, fs, total, j, j, frameOff, outOff, expect);
 }
 
 // Workgroup b: the matches among the start positions xLo + [b * kTile, min(nPos, (b + 1) * kTile)) of the run -> counts[b].
@@ -73,7 +69,8 @@ extern "C" __global__ void __launch_bounds__(256) zra_search_count_kernel(const 
 }
 
 // One workgroup: bases[t] = *cntIn + the matches of the tiles in front of tile t; *cntOut = *cntIn + all of them (condition (c)).
-// Every lane sums a run of consecutive tiles, the 1024 sums are scanned in LDS, then the lane walks its run again.
+// Every lane sums a run of consecutive tiles, the 1024 sums are scanned in LDS, then the lane walks its run again. (Not zra_joblist.h's
+// block_excl_scan like the other additive scans: tests/test_pattern_expr.py pins this kernel's registers where this body has them.)
 extern "C" __global__ void __launch_bounds__(1024) zra_search_scan_kernel(const u32* counts, u32 nTiles, u64* bases, const u64* cntIn, u64* cntOut) {
   __shared__ u64 sS[1024];
   const u32 tid = threadIdx.x;

@@ -42,6 +42,7 @@
 //      dataCapacity. A sign call writes the words of the range's records only, and none at or behind sigCapacityWords.
 #include "zra_framepass.h"
 #include "zra_dev.h"
+#include "zra_joblist.h"
 #include <algorithm>
 
 using namespace zra_dev;
@@ -104,35 +105,20 @@ extern "C" __global__ void __launch_bounds__(256) zra_sig_spans_kernel(const u8*
   }
 }
 
-// One workgroup: the decode-flagged slots of the pass, in order, become jobs 0 .. nDec - 1 of archive B; a job decodes its frame's
-// seek-table span, whatever it says (the decoder refuses a span that runs backwards or leaves the body), into the frame's OWN slot,
-// and has to regenerate that frame's share of B's content. *nJobs: the job count for the host.
+// One workgroup walks the slots of the pass, 1024 at a time: the decode-flagged ones, in order, become jobs 0 .. nDec - 1 of archive B
+// (zra_joblist.h: block_rank, emit_job), each into the frame's OWN slot. *nJobs: the job count for the host.
 extern "C" __global__ void __launch_bounds__(1024) zra_sig_jobs_kernel(const u8* flags, u32 nj, const u8* table, u64 U, u64 fs, u64 first, u64* frameOff, u64* outOff,
                                                                        u32* expect, u32* nJobs) {
-  __shared__ u32 sS[1024];
-  const u32 tid = threadIdx.x;
-  const u32 per = (nj + 1023) / 1024;
-  const u32 s0 = min(nj, tid * per), s1 = min(nj, s0 + per);
-  u32 own = 0;
-  for (u32 s = s0; s < s1; s++) own += flags[s] != 0;
-  sS[tid] = own;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                     // Hillis-Steele inclusive scan of the 1024 partials
-    const u32 x = tid >= d ? sS[tid - d] : 0;
-    __syncthreads();
-    sS[tid] += x;
-    __syncthreads();
+  u32 jobBase = 0;
+  for (u32 base = 0; base < nj; base += 1024) {
+    const u32 s = base + threadIdx.x;
+    const bool p[1] = {s < nj && flags[s] != 0};
+    u32 rank[1], total[1];
+    block_rank<1>(p, rank, total);
+    if (p[0]) emit_job(table, first + s, fs, U, jobBase + rank[0], s, frameOff, outOff, expect);
+    jobBase += total[0];
   }
-  u32 k = sS[tid] - own;
-  for (u32 s = s0; s < s1; s++) {
-    if (!flags[s]) continue;
-    const u64 f = first + s;
-    frameOff[2 * (size_t)k] = seek_entry(table, f); frameOff[2 * (size_t)k + 1] = seek_entry(table, f + 1);
-    expect[k] = (u32)frame_expect(f, fs, U);
-    outOff[k] = (u64)s * fs;
-    k++;
-  }
-  if (tid == 1023) *nJobs = sS[1023];
+  if (threadIdx.x == 0) *nJobs = jobBase;
 }
 
 // Four lanes per grain of a pass: XXH64 with `seed` of the grain's bytes in its slot, clipped (grain_len). The slots are not 8-byte

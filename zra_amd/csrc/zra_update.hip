@@ -24,6 +24,7 @@
 //      update changes nothing (a HIP runtime error behind that point leaves dOut and those frames undefined).
 #include "zra_host.h"
 #include "zra_dev.h"
+#include "zra_joblist.h"
 #include "zra_format.h"
 #include <algorithm>
 #include <vector>
@@ -52,12 +53,6 @@ __device__ __forceinline__ void copy_span(u8* dst, const u8* src, u64 n, u32 lan
   for (; i < n16; i += 64) { const uint4 v = s4[i]; st128(d16 + 16 * (size_t)i, v.x, v.y, v.z, v.w); }
   for (u64 k = head + ((u64)n16 << 4) + lane; k < n; k += 64) dst[k] = src[k];
 }
-
-__device__ __forceinline__ u64 wave_incl_scan64(u64 v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const u64 t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
-  return v;
-}
 }  // namespace
 
 // Thread per slice: the bytes the slice replaces are counted into its frame. Writes do not overlap and the append lies behind all
@@ -70,9 +65,10 @@ extern "C" __global__ void __launch_bounds__(256) zra_upd_mark_kernel(const u64*
 }
 
 // One workgroup walks the frames of the result, 1024 at a time. A frame is touched when cover != 0; its staging slot is its rank among
-// the touched frames (ballot + prefix counts over the chunk, a running base across chunks). A touched frame that keeps old bytes
-// (cover < its new length) gets a decode job, ranked the same way: compressed span from the old seek table, destination = its slot of
-// the pass, expected size = its old length. passJob[p] = jobs in front of pass p (slots [p * passSlots, ...)), passJob[passes] = all.
+// the touched frames (zra_joblist.h, block_rank: four predicates ranked at once, the running bases kept here). A touched frame that
+// keeps old bytes (cover < its new length) gets a decode job, ranked the same way (emit_job): compressed span from the old seek table,
+// destination = its slot of the pass, expected size = its old length.
+// passJob[p] = jobs in front of pass p (slots [p * passSlots, ...)), passJob[passes] = all.
 // An untouched frame is carried over by its table entries: they must not run backwards nor end beyond the body (flag).
 // With a handle's cache (cacheSlotOf != nullptr, readable for nNew frames) a frame that keeps old bytes and is resident gets no job but
 // a copy entry {staging slot, arena slot, old length, frame}, ranked in frame order like the jobs, passCopy[] like passJob[]; and
@@ -82,8 +78,8 @@ extern "C" __global__ void __launch_bounds__(1024) zra_upd_plan_kernel(const u32
                                                                     u64 oldTotal, u64 newTotal, u32 passSlots, const u32* cacheSlotOf, u32* slotOf,
                                                                     u64* frameOff, u64* outOff, u32* expect, u32* passJob, u32* copies,
                                                                     u32* passCopy, u32* totals) {
-  __shared__ u32 sT[16], sJ[16], sC[16], sF[16], sFlag;
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ u32 sFlag;
+  const u32 tid = threadIdx.x;
   if (tid == 0) sFlag = 0;
   u32 slotBase = 0, jobBase = 0, copyBase = 0, fresh = 0;
   for (u32 base = 0; base < nNew; base += 1024) {
@@ -95,37 +91,25 @@ extern "C" __global__ void __launch_bounds__(1024) zra_upd_plan_kernel(const u32
     const bool touched = c != 0;
     const u32 cs = touched && cacheSlotOf ? cacheSlotOf[f] : kNone;
     const bool keeps = touched && c != newLen, cpy = keeps && cs != kNone, dec = keeps && !cpy;
-    const u64 mT = __ballot(touched), mJ = __ballot(dec), mC = __ballot(cpy), mF = __ballot(cs != kNone);
-    const u64 below = (1ull << lane) - 1;
-    if (lane == 0) { sT[wave] = (u32)__popcll(mT); sJ[wave] = (u32)__popcll(mJ); sC[wave] = (u32)__popcll(mC); sF[wave] = (u32)__popcll(mF); }
-    __syncthreads();
-    u32 beforeT = 0, beforeJ = 0, beforeC = 0, totalT = 0, totalJ = 0, totalC = 0;
-    for (u32 w = 0; w < 16; w++) {
-      const u32 t = sT[w], j = sJ[w], k = sC[w];
-      beforeT += w < wave ? t : 0u; beforeJ += w < wave ? j : 0u; beforeC += w < wave ? k : 0u; totalT += t; totalJ += j; totalC += k;
-      fresh += sF[w];
-    }
-    const u32 slot = slotBase + beforeT + (u32)__popcll(mT & below), job = jobBase + beforeJ + (u32)__popcll(mJ & below);
-    const u32 copy = copyBase + beforeC + (u32)__popcll(mC & below);
+    const bool p[4] = {touched, dec, cpy, cs != kNone};
+    u32 rank[4], total[4];
+    block_rank<4>(p, rank, total);
+    const u32 slot = slotBase + rank[0], job = jobBase + rank[1], copy = copyBase + rank[2];
     if (in) slotOf[f] = touched ? slot : kNone;
     if (touched && slot % passSlots == 0) { passJob[slot / passSlots] = job; passCopy[slot / passSlots] = copy; }
     if (cpy) {
       u32* e = copies + 4 * (size_t)copy;
       e[0] = slot; e[1] = cs; e[2] = (u32)min<u64>(fs, oldTotal - o); e[3] = f;
     }
-    if (dec) {
-      // (dec implies f < nOld: a frame behind the old content is supplied whole by the append)
-      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, (u64)f + 1);
-      outOff[job] = (u64)(slot % passSlots) * fs;
-      expect[job] = (u32)min<u64>(fs, oldTotal - o);
-    }
+    // (dec implies f < nOld: a frame behind the old content is supplied whole by the append)
+    if (dec) emit_job(table, f, fs, oldTotal, job, slot % passSlots, frameOff, outOff, expect);
     if (in && !touched && f < nOld) {
       const u64 a = seek_entry(table, f), b = seek_entry(table, (u64)f + 1);
       if (b < a || b > bodyBytes) atomicOr(&sFlag, 1u);
     }
-    slotBase += totalT; jobBase += totalJ; copyBase += totalC;
-    __syncthreads();                                                  // (sT, sJ, sC, sF of the next chunk; sFlag)
+    slotBase += total[0]; jobBase += total[1]; copyBase += total[2]; fresh += total[3];
   }
+  __syncthreads();                                                    // (sFlag)
   if (tid == 0) {
     passJob[(slotBase + passSlots - 1) / passSlots] = jobBase; passCopy[(slotBase + passSlots - 1) / passSlots] = copyBase;
     totals[0] = slotBase; totals[1] = jobBase; totals[2] = sFlag; totals[3] = copyBase; totals[4] = fresh;
@@ -172,55 +156,32 @@ __device__ __forceinline__ void upd_frame_size(u32 f, u32 nNew, const u32* slotO
   if (slot != kNone) { *sz = *tsz = encSizes[slot]; return; }
   *sz = seek_entry(table, (u64)f + 1) - seek_entry(table, f);               // (not backwards: the plan kernel has checked the untouched frames)
 }
-// exclusive scan of (a, b) over the 1024 threads of a workgroup; *ta, *tb = the sums
-__device__ __forceinline__ void block_excl_scan2(u64& a, u64& b, u64* ta, u64* tb, u64* sA, u64* sB) {
-  const u32 tid = threadIdx.x, wave = tid >> 6; const int lane = (int)(tid & 63);
-  const u64 ia = wave_incl_scan64(a, lane), ib = wave_incl_scan64(b, lane);
-  if (lane == 63) { sA[wave] = ia; sB[wave] = ib; }
-  __syncthreads();
-  u64 ba = 0, bb = 0, sa = 0, sb = 0;
-  for (u32 w = 0; w < 16; w++) { const u64 x = sA[w], y = sB[w]; ba += w < wave ? x : 0; bb += w < wave ? y : 0; sa += x; sb += y; }
-  a = ba + ia - a; b = bb + ib - b; *ta = sa; *tb = sb;
-  __syncthreads();
-}
 }  // namespace
 
 // Workgroup b sums the sizes of frames [1024 b, 1024 b + 1024): sums[2b] all, sums[2b + 1] the newly encoded ones.
 extern "C" __global__ void __launch_bounds__(1024) zra_upd_sizes_kernel(u32 nNew, const u32* slotOf, const u64* encSizes, const u8* table, u64* sums) {
-  __shared__ u64 sA[16], sB[16];
-  u64 a, b, ta, tb;
-  upd_frame_size(blockIdx.x * 1024 + threadIdx.x, nNew, slotOf, encSizes, table, &a, &b);
-  block_excl_scan2(a, b, &ta, &tb, sA, sB);
-  if (threadIdx.x == 0) { sums[2 * (size_t)blockIdx.x] = ta; sums[2 * (size_t)blockIdx.x + 1] = tb; }
+  u64 v[2], tot[2];
+  upd_frame_size(blockIdx.x * 1024 + threadIdx.x, nNew, slotOf, encSizes, table, &v[0], &v[1]);
+  block_excl_scan<2>(v, tot);
+  if (threadIdx.x == 0) { sums[2 * (size_t)blockIdx.x] = tot[0]; sums[2 * (size_t)blockIdx.x + 1] = tot[1]; }
 }
 
-// One workgroup: the workgroup sums become exclusive prefixes in place; sums[2 nBlocks], [2 nBlocks + 1] = the totals.
-extern "C" __global__ void __launch_bounds__(1024) zra_upd_scan_kernel(u64* sums, u32 nBlocks) {
-  __shared__ u64 sA[16], sB[16];
-  u64 ca = 0, cb = 0;
-  for (u32 base = 0; base < nBlocks; base += 1024) {
-    const u32 i = base + threadIdx.x;
-    u64 a = i < nBlocks ? sums[2 * (size_t)i] : 0, b = i < nBlocks ? sums[2 * (size_t)i + 1] : 0, ta, tb;
-    block_excl_scan2(a, b, &ta, &tb, sA, sB);
-    if (i < nBlocks) { sums[2 * (size_t)i] = ca + a; sums[2 * (size_t)i + 1] = cb + b; }
-    ca += ta; cb += tb;
-  }
-  if (threadIdx.x == 0) { sums[2 * (size_t)nBlocks] = ca; sums[2 * (size_t)nBlocks + 1] = cb; }
-}
+// One workgroup: the workgroup sums become exclusive prefixes in place; sums[2 nBlocks], [2 nBlocks + 1] = the totals
+// (zra_joblist.h, scan_in_place).
+extern "C" __global__ void __launch_bounds__(1024) zra_upd_scan_kernel(u64* sums, u32 nBlocks) { scan_in_place<2>(sums, nBlocks, nullptr, nullptr); }
 
 // Thread per frame (and one for the end entry): newOff[f] = where the frame starts in the new body, its 5-byte entry of the new seek
 // table, and disp[f] = the address of its compressed bytes minus newOff[f] — in the old body for a frame carried over, in the packed
 // buffer for a newly encoded one. Neighbours that stay neighbours have the same displacement: the gather copies them as one span.
 extern "C" __global__ void __launch_bounds__(1024) zra_upd_offsets_kernel(u32 nNew, const u32* slotOf, const u64* encSizes, const u8* table, const u64* sums,
                                                                        const u8* oldBody, const u8* packed, u64* newOff, u64* disp, u8* entries) {
-  __shared__ u64 sA[16], sB[16];
   const u32 f = blockIdx.x * 1024 + threadIdx.x;
-  u64 a, b, ta, tb;
-  upd_frame_size(f, nNew, slotOf, encSizes, table, &a, &b);
-  const bool enc = b != 0 || (f < nNew && slotOf[f] != kNone);
-  block_excl_scan2(a, b, &ta, &tb, sA, sB);
+  u64 v[2], tot[2];
+  upd_frame_size(f, nNew, slotOf, encSizes, table, &v[0], &v[1]);
+  const bool enc = v[1] != 0 || (f < nNew && slotOf[f] != kNone);
+  block_excl_scan<2>(v, tot);
   if (f > nNew) return;
-  const u64 off = sums[2 * (size_t)blockIdx.x] + a, toff = sums[2 * (size_t)blockIdx.x + 1] + b;
+  const u64 off = sums[2 * (size_t)blockIdx.x] + v[0], toff = sums[2 * (size_t)blockIdx.x + 1] + v[1];
   newOff[f] = off;
   u8* e = entries + (size_t)f * 5;
   e[0] = (u8)off; e[1] = (u8)(off >> 8); e[2] = (u8)(off >> 16); e[3] = (u8)(off >> 24); e[4] = (u8)(off >> 32);

@@ -19,6 +19,7 @@
 //  (d) nothing goes to the caller's fault array before the last pass is done: a call that fails midway writes nothing.
 #include "zra_host.h"
 #include "zra_dev.h"
+#include "zra_joblist.h"
 #include "zra_format.h"
 #include <algorithm>
 #include <vector>
@@ -95,36 +96,28 @@ extern "C" __global__ void __launch_bounds__(256) zra_vfy_structure_kernel(const
   sstat[i] = structure_code(table, nFrames, body, bodyBytes, fs, total, first + i);
 }
 
-// One workgroup walks the range, 1024 frames at a time (zra_upd_plan_kernel's scheme): a sound frame's job is its rank among the sound
-// frames (ballot + prefix counts over the chunk, a running base across chunks); the job gets the frame's compressed span and the size
-// it has to regenerate. passFirst[p] = range index of the first frame of pass p (jobs [p * passSlots, ...)), passFirst[passes] = count.
+// One workgroup walks the range, 1024 frames at a time: a sound frame's job is its rank among the sound frames (zra_joblist.h:
+// block_rank, emit_job); the job gets the frame's compressed span and the size it has to regenerate.
+// passFirst[p] = range index of the first frame of pass p (jobs [p * passSlots, ...)), passFirst[passes] = count.
 // outOff[s] = where slot s of the staging window starts: every pass uses the same nSlots entries. totals[0] = jobs.
 extern "C" __global__ void __launch_bounds__(1024) zra_vfy_jobs_kernel(const u32* sstat, u32 first, u32 count, const u8* table, u64 fs, u64 total, u32 passSlots,
                                                                      u32 nSlots, u32* jobOf, u64* frameOff, u64* outOff, u32* expect, u32* passFirst, u32* totals) {
-  __shared__ u32 sJ[16];
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (u32 s = tid; s < nSlots; s += 1024) outOff[s] = (u64)s * fs;
+  for (u32 s = threadIdx.x; s < nSlots; s += 1024) outOff[s] = (u64)s * fs;
   u32 jobBase = 0;
   for (u32 base = 0; base < count; base += 1024) {
-    const u32 i = base + tid;
-    const bool in = i < count, sound = in && sstat[i] == 0;
-    const u64 m = __ballot(sound);
-    if (lane == 0) sJ[wave] = (u32)__popcll(m);
-    __syncthreads();
-    u32 before = 0, all = 0;
-    for (u32 w = 0; w < 16; w++) { const u32 c = sJ[w]; before += w < wave ? c : 0u; all += c; }
-    const u32 job = jobBase + before + (u32)__popcll(m & ((1ull << lane) - 1));
-    if (in) jobOf[i] = sound ? job : kNoJob;
-    if (sound) {
-      const u64 f = (u64)first + i;
-      frameOff[2 * (size_t)job] = seek_entry(table, f); frameOff[2 * (size_t)job + 1] = seek_entry(table, f + 1);
-      expect[job] = (u32)frame_expect(f, fs, total);
+    const u32 i = base + threadIdx.x;
+    const bool in = i < count, p[1] = {in && sstat[i] == 0};
+    u32 rank[1], all[1];
+    block_rank<1>(p, rank, all);
+    const u32 job = jobBase + rank[0];
+    if (in) jobOf[i] = p[0] ? job : kNoJob;
+    if (p[0]) {
+      emit_job(table, (u64)first + i, fs, total, job, 0, frameOff, nullptr, expect);
       if (job % passSlots == 0) passFirst[job / passSlots] = i;
     }
-    jobBase += all;
-    __syncthreads();                                                  // (sJ of the next chunk)
+    jobBase += all[0];
   }
-  if (tid == 0) { passFirst[(jobBase + passSlots - 1) / passSlots] = count; totals[0] = jobBase; }
+  if (threadIdx.x == 0) { passFirst[(jobBase + passSlots - 1) / passSlots] = count; totals[0] = jobBase; }
 }
 
 // Ordered compaction of the faults of range indices [i0, i0 + n) into the fault list, behind the *cntIn entries counted so far.
