@@ -7,6 +7,7 @@
 #include "zra_dev.h"
 #include "zra_format.h"
 #include "zra_env.h"
+#include "zra_enc_plan.h"
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -80,50 +81,6 @@ __global__ void zra_gather_frames_kernel(const u8* slots, u64 slotStride, const 
   }
 }
 
-// ---- zstd 1.4.9 parameter rows (dumped there from the dependency): [wlog clog hlog slog mml tlen strat]
-const uint16_t kCP16[23][7] = {{14,14,15,2,4,0,2},{14,14,15,1,5,0,1},{14,14,15,1,4,0,1},{14,14,15,2,4,0,2},{14,14,14,4,4,2,3},{14,14,14,3,4,4,4},
-  {14,14,14,4,4,8,5},{14,14,14,6,4,8,5},{14,14,14,8,4,8,5},{14,15,14,5,4,8,6},{14,15,14,9,4,8,6},{14,15,14,3,4,12,7},{14,15,14,4,3,24,7},
-  {14,15,14,5,3,32,8},{14,15,15,6,3,64,8},{14,15,15,7,3,256,8},{14,15,15,5,3,48,9},{14,15,15,6,3,128,9},{14,15,15,7,3,256,9},{14,15,15,8,3,256,9},{14,15,15,8,3,512,9},{14,15,15,9,3,512,9},{14,15,15,10,3,999,9}};
-const uint16_t kCP128[23][7] = {{17,15,16,2,5,0,2},{17,12,13,1,6,0,1},{17,13,15,1,5,0,1},{17,15,16,2,5,0,2},{17,17,17,2,4,0,2},{17,16,17,3,4,2,3},
-  {17,17,17,3,4,4,4},{17,17,17,3,4,8,5},{17,17,17,4,4,8,5},{17,17,17,5,4,8,5},{17,17,17,6,4,8,5},{17,17,17,5,4,8,6},{17,18,17,7,4,12,6},
-  {17,18,17,3,4,12,7},{17,18,17,4,3,32,7},{17,18,17,6,3,256,7},{17,18,17,6,3,128,8},{17,18,17,8,3,256,8},{17,18,17,10,3,512,8},{17,18,17,5,3,256,9},{17,18,17,7,3,512,9},{17,18,17,9,3,512,9},{17,18,17,11,3,999,9}};
-const uint16_t kCP256[23][7] = {{18,16,16,1,4,0,2},{18,13,14,1,6,0,1},{18,14,14,1,5,0,2},{18,16,16,1,4,0,2},{18,16,17,2,5,2,3},{18,18,18,3,5,2,3},
-  {18,18,19,3,5,4,4},{18,18,19,4,4,4,4},{18,18,19,4,4,8,5},{18,18,19,5,4,8,5},{18,18,19,6,4,8,5},{18,18,19,5,4,12,6},{18,19,19,7,4,12,6},
-  {18,18,19,4,4,16,7},{18,18,19,4,3,32,7},{18,18,19,6,3,128,7},{18,19,19,6,3,128,8},{18,19,19,8,3,256,8},{18,19,19,6,3,128,9},{18,19,19,8,3,256,9},{18,19,19,10,3,512,9},{18,19,19,12,3,512,9},{18,19,19,13,3,999,9}};
-
-inline uint32_t hbit(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
-
-// row 0 of ZSTD_getCParams_internal's level tables, "base for negative levels": strategy fast, the level becomes the acceleration
-// (targetLength = -level), and literals are then stored raw (ZSTD_compressLiterals' disableLiteralCompression)
-const uint16_t kCPNeg16[7] = {14, 12, 13, 1, 5, 1, 1}, kCPNeg128[7] = {17, 12, 12, 1, 5, 1, 1}, kCPNeg256[7] = {18, 12, 13, 1, 5, 1, 1};
-
-// the "default" table (srcSize > 256 KB), levels 0..15 (13-15: btlazy2)
-const uint16_t kCPDef[23][7] = {{21,16,17,1,5,0,2},{19,13,14,1,7,0,1},{20,15,16,1,6,0,1},{21,16,17,1,5,0,2},{21,18,18,1,5,0,2},{21,18,19,2,5,2,3},
-  {21,19,19,3,5,4,3},{21,19,19,3,5,8,4},{21,19,19,3,5,16,5},{21,19,20,4,5,16,5},{22,20,21,4,5,16,5},{22,21,22,4,5,16,5},{22,21,22,5,5,16,5},
-  {22,21,22,5,5,32,6},{22,22,23,5,5,32,6},{22,23,23,6,5,32,6},
-  {22,22,22,5,5,48,7},{23,23,22,5,4,64,7},{23,23,22,6,3,64,8},{23,24,22,7,3,256,9},{25,25,23,7,3,256,9},{26,26,24,7,3,512,9},{27,27,25,9,3,999,9}};
-const uint16_t kCPNegDef[7] = {19, 12, 13, 1, 6, 1, 1};
-
-// parameters of ZSTD_getCParams(level, S) for every level (-128..22); false only for S == 0
-bool get_params(int level, size_t S, ZraEncParams* p) {
-  if (level == 0) level = 3;
-  if (S == 0) return false;
-  if (level > 22) level = 22;                                                       // ZSTD_maxCLevel
-  const uint16_t* r = level < 0 ? (S <= (16u << 10) ? kCPNeg16 : S <= (128u << 10) ? kCPNeg128 : S <= (256u << 10) ? kCPNeg256 : kCPNegDef)
-                               : (S <= (16u << 10) ? kCP16[level] : S <= (128u << 10) ? kCP128[level] : S <= (256u << 10) ? kCP256[level] : kCPDef[level]);
-  // (a frame larger than 2^windowLog is parsed by the serial finders with the sliding-window rules: compress_impl_body, serialAll)
-  p->windowLog = r[0]; p->chainLog = r[1]; p->hashLog = r[2]; p->searchLog = r[3]; p->minMatch = r[4];
-  p->targetLength = level < 0 ? (uint32_t)(-level) : r[5]; p->strategy = r[6];
-  const uint32_t srcLog = S < 64 ? 6 : hbit((uint32_t)S - 1) + 1;
-  if (p->windowLog > srcLog) p->windowLog = srcLog;
-  if (p->hashLog > p->windowLog + 1) p->hashLog = p->windowLog + 1;
-  const uint32_t cycleLog = p->chainLog - (p->strategy >= 6);
-  if (cycleLog > p->windowLog) p->chainLog -= cycleLog - p->windowLog;
-  if (p->windowLog < 10) p->windowLog = 10;
-  p->blockSize = std::min<uint32_t>(128u << 10, 1u << p->windowLog);
-  return true;
-}
-
 }  // namespace
 
 namespace zra_eng {
@@ -175,24 +132,15 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
   // the generic (one lane per frame) finder exists with and without the optimal parsers: only levels 13-22 pay for their registers
   const auto mfGeneric = (full.strategy >= 7 || tail.strategy >= 7) ? zra_mf_opt_kernel : zra_mf_kernel;
 
-  // per-frame table slot: hash table + chain table / tree; the optimal parsers add a 3-byte hash table and their state (ZraOptState)
-  auto slotWords = [](const ZraEncParams& q) -> uint64_t {
-    uint64_t w = (1ull << q.hashLog) + (1ull << q.chainLog);
-    if (q.strategy >= 3 && q.strategy <= 5) w += 3ull << q.chainLog;   // the wave-cooperative hash-chain finder keeps four links per slot
-    if (q.strategy >= 7) w += (q.minMatch == 3 ? 1ull << std::min(17u, q.windowLog) : 0) + (sizeof(ZraOptState) + 3) / 4 + 16;
-    return w;
-  };
-  const uint64_t tableWords = (std::max(slotWords(full), slotWords(tail)) + 3) & ~3ull;   // 16-byte slots
-  const uint32_t maxBlock = std::max(full.blockSize, tail.blockSize);
-  const uint64_t seqStride = (maxBlock / 4 + 16 + 7) & ~7ull;   // (a multiple of 8: the entropy stage's u16 chain output sits behind 3 * seqStride code bytes, and the chain kernel moves 8 bytes at a time)
-  const uint64_t litStride = ((uint64_t)maxBlock + 64 + 15) & ~15ull;
   // blocks per frame, per size class (a short last frame has its own, smaller, block size but is still one block)
   const uint64_t fullFrame = std::min<uint64_t>(frameSize, inSize);
   const uint32_t maxBlocksPerFrame = (uint32_t)std::max<uint64_t>(
       (nFramesTotal > 1 || !tailSize) ? (fullFrame + full.blockSize - 1) / full.blockSize : 0,
       tailSize ? (tailSize + tail.blockSize - 1) / tail.blockSize : 0);
-  const uint64_t slotStride = (zra_fmt::compress_bound(frameSize) + 1024 + 4 * (uint64_t)maxBlocksPerFrame + 15) & ~15ull;
-  const uint64_t perFrame = tableWords * 4 + seqStride * 8 + litStride + slotStride + sizeof(ZraEncFrameState) + sizeof(ZraEncBlockOut) + 64;
+  // the per-frame scratch (zra_enc_plan.h): table slot, sequence store, literal buffer, work area of the entropy stage, encoded-frame slot
+  const EncPlan plan = enc_plan(full, tail, frameSize, maxBlocksPerFrame);
+  const uint64_t tableWords = plan.tableWords, seqStride = plan.seqStride, litStride = plan.litStride, slotStride = plan.slotStride;
+  const uint64_t entWorkStride = plan.entWorkStride, perFrame = plan.perFrame;
   // ---------------------------------------------------------------------------------------------------------------------
   // Persistent pipeline (dfast, single-block frames: levels 3-4 up to 128 KiB frames — the headline configuration).
   // ONE match-finder launch per super-batch: `nSlots` resident waves pull frames from a queue, each wave owns one hash-table
@@ -214,7 +162,7 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
     if (waitValueOk_ < 0) persist = false;
     if (persist)
       return compress_persistent(dIn, inSize, dBody, bodyBase0, dEntries, dSizes, bodySize, frameSize, checksum, full, tail,
-                                 tableWords, seqStride, litStride, slotStride);
+                                 plan);
   }
   // Two scratch contexts: the match finder of batch k+1 (stream A) overlaps the entropy stage + gather of batch k (stream B);
   // both kernels are latency-bound, so they share the CUs almost for free. 8 GiB of scratch per context.
@@ -244,7 +192,6 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
   // the entropy stage: workgroups that take the batch's frames from a queue — as many as the device holds at once (5 waves per SIMD by
   // registers), each with its own literal buffer and sequence work area
   const uint32_t entGridB = (uint32_t)std::min<uint64_t>(B, (uint64_t)numCUs_ * 5);
-  const uint64_t entWorkStride = (9 * seqStride + 255) & ~255ull;
   const int nCtx = nFramesTotal > B ? 2 : 1;
   for (int c = 0; c < nCtx; c++) {
     EncCtx& x = encCtx_[c];
@@ -401,7 +348,9 @@ Status Engine::compress_impl_body(const uint8_t* dIn, size_t inSize, uint8_t* dB
 
 Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* dBody, uint64_t bodyBase0, uint8_t* dEntries, uint64_t* dSizes,
                                    size_t* bodySize, uint32_t frameSize, bool checksum, const ZraEncParams& full, const ZraEncParams& tail,
-                                   uint64_t tableWords, uint64_t seqStride, uint64_t litStride, uint64_t slotStride) {
+                                   const EncPlan& plan) {
+  const uint64_t tableWords = plan.tableWords, seqStride = plan.seqStride, litStride = plan.litStride, slotStride = plan.slotStride;
+  const uint64_t entWorkStride = plan.entWorkStride;
   const uint64_t nFramesTotal = (inSize + frameSize - 1) / frameSize;
   const size_t tailSize = inSize % frameSize;
   const auto mfGeneric = (full.strategy >= 7 || tail.strategy >= 7) ? zra_mf_opt_kernel : zra_mf_kernel;
@@ -439,7 +388,6 @@ Status Engine::compress_persistent(const uint8_t* dIn, size_t inSize, uint8_t* d
   // entropy stage: queue-driven workgroups, launched per sub-batch; they sit where a CU has room beside the finder's waves
   static const uint32_t entPerCU = (uint32_t)std::max(1, env_int("ZRA_ENT_WGS", 8));
   const uint32_t entGrid = (uint32_t)std::min<uint64_t>((uint64_t)numCUs_ * entPerCU, nFramesTotal);
-  const uint64_t entWorkStride = (9 * seqStride + 255) & ~255ull;
   // round 6: the split entropy stage: per sub-batch a FRONT launch (literals, tables), zra_ent_chain_kernel (the state chains,
   // lane = (frame, stream)), a BACK launch (sequence bitstream, block / frame end). The work area and a record are then per FRAME of the
   // sub-batch. ZRA_ENT_SPLIT: 0 never, 1 (default) calls of at least 256 frames, 2 always.
