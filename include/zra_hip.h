@@ -1147,7 +1147,9 @@ ZRA_EXPORT double ZraHipLastKernelMs(ZraHipEngine* engine);
  *  out6 = {match-finder ms, launches, entropy-stage ms, launches, decode ms, launches}. */
 ZRA_EXPORT void ZraHipGetKernelStats(ZraHipEngine* engine, double* out6);
 /** Decode stages of the LAST decode / random-access call on this engine (HIP events on the engine's stream, summed over its rounds):
- *  out8 = {parse ms, Huffman ms, sequence-chain ms, execute ms, rounds, one-launch small-batch kernel ms, its launches, 0}. */
+ *  out8 = {parse ms, Huffman ms, sequence-chain ms, execute ms, rounds, one-launch small-batch kernel ms, its launches, 0}.
+ *  The parse span includes the literal streams its waves decode themselves (blocks whose literals come with a new Huffman tree);
+ *  the Huffman span is what is left to that stage's own launch. */
 ZRA_EXPORT void ZraHipGetDecodeStageStats(ZraHipEngine* engine, double* out8);
 /** Launch telemetry of the LAST persistent level-3/4 compress on this engine, written by every wave of the match-finder launch:
  *  u64 words [0] shader cycles summed over waves, [1] ticks of the constant 100 MHz clock summed over waves (cycles / ticks x 100 = the

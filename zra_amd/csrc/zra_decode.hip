@@ -9,8 +9,12 @@
 //   zra_dec_parse_kernel   wave per frame. Frame / block / literal / sequence headers and the bit-serial table descriptions (lane 0);
 //                          the Huffman weights (FSE table in a register, one cell per lane), the tree's rank arithmetic and the
 //                          three FSE decode tables wave-wide (built in LDS, stored as 4-byte cells to the frame's table scratch in
-//                          HBM). Raw and RLE blocks and the frame end are handled on the way; a compressed block is handed on.
-//   zra_dec_huf_kernel     the whole wave on one frame's literal streams: 16 self-synchronising runs per stream decoded side by side
+//                          HBM). Raw and RLE blocks and the frame end are handled on the way; a compressed block is handed on —
+//                          and when its Huffman-coded literals come with a new tree, the same wave decodes them right away (the
+//                          front end, huf_front: the body of the next stage, its decode table over LDS the parse is done with),
+//                          while the CU's other waves are in their serial parse phases.
+//   zra_dec_huf_kernel     (what the front end left: treeless blocks of later rounds, the block-parallel pass, ZRA_DEC_FRONT=0)
+//                          the whole wave on one frame's literal streams: 16 self-synchronising runs per stream decoded side by side
 //                          from guessed starts, restarted from the predecessor's hand-over point until nothing moves, placed by a
 //                          prefix sum of the counts (huf_decode_wave); damaged or unusual streams go to the serial X1 / X2 decoders
 //                          of libzstd, one lane per stream. Literals to a bump-allocated scratch, sixteen at a time.
@@ -667,7 +671,8 @@ __device__ __forceinline__ void frame_finish(const ZraDecodeArgs& a, u32 j, cons
 // stage 1: parse — one job (frame j, its next block) by one wave. FUSED (the one-launch path for small random-access batches,
 // zra_ra_small_kernel below): nothing is appended to the stage lists, the sequence tables are also left in LDS (ldsT), and the
 // outcome comes back as a code: 0 = the frame is finished (frame_finish has run), 1 = a compressed block was handed on,
-// 2 = no scratch for it in this round.
+// 2 = no scratch for it in this round. Not FUSED, the classic rounds: 3 = handed on, and its literal streams are this wave's to decode
+// (huf_front) — the block is not on the Huffman stage's list.
 namespace {
 // ALL (round 6, the block-parallel pass for frames of several blocks, zra_dec_parse_all_kernel): the wave walks ALL blocks of the frame in
 // one go instead of one per round. Every compressed block becomes a job of its own for the Huffman and chain stages (record and tables
@@ -947,7 +952,15 @@ __device__ __forceinline__ u32 parse_job(const ZraDecodeArgs& a, const u32 j, Pa
         }
       }
 
-      // ---- hand the block on: persistent state + the block record; Huffman-coded literals go through the Huffman kernel first
+      // ---- fused front end (a.decFront; the classic rounds): a block with Huffman-coded literals and a NEW tree — its description
+      //      is complete in S — has its literal streams decoded by this wave, with the body of the Huffman stage, as soon as the
+      //      job is parsed (huf_front, called by the kernel on outcome 3): the serial parse phases of the CU's other waves run
+      //      beside it, the record does not travel to the Huffman kernel and back, and the decode table is built once, from the
+      //      weights in LDS. A treeless block of a later round (its tree is in the frame's record, not here) goes to the Huffman
+      //      kernel as before.
+      const bool front = !FUSED && !ALL && a.decFront && S.litKind == 2 && S.litType == 2;
+      // ---- hand the block on: persistent state + the block record; Huffman-coded literals the wave has not decoded itself go
+      //      through the Huffman kernel first
       if (ALL) {
         ZraDecFrame* const D = &a.blkRecs[jb];
         if (lane == 0) {
@@ -988,13 +1001,15 @@ __device__ __forceinline__ u32 parse_job(const ZraDecodeArgs& a, const u32 j, Pa
         F->longMode = (S.bigWindow && nbSeq > 4 && S.ofShare >= 7) ? 1u : 0u;
         if (!FUSED) {
           a.pending[atomicAdd(&a.counters[ZRA_DC_NPENDING], 1u)] = j;
-          if (S.litKind == 2) a.hufJobs[atomicAdd(&a.counters[ZRA_DC_NHUF], 1u)] = j;
+          if (S.litKind == 2 && !front) a.hufJobs[atomicAdd(&a.counters[ZRA_DC_NHUF], 1u)] = j;
         }
       }
-      if (S.litType == 2) {                               // a new tree: its description stays with the frame (treeless blocks reuse it)
+      // a new tree: its description stays with the frame (treeless blocks of later rounds reuse it) — unless nothing reads it any
+      // more: the literals are decoded and this is the frame's last block
+      if (S.litType == 2 && !(front && S.blkLast)) {
         for (u32 i = lane; i < 256; i += DEC_THREADS) { F->weights[i] = S.weights[i]; F->hufStart[i] = S.hufStart[i]; }
       }
-      handed = true; outcome = 1;
+      handed = true; outcome = front ? 3u : 1u;
       wsync();
       PPROF(13)
       break;
@@ -1018,6 +1033,14 @@ __device__ __forceinline__ u32 parse_job(const ZraDecodeArgs& a, const u32 j, Pa
 }
 }  // namespace
 
+// the fused front end (behind the Huffman stage's helpers, below): the literal streams of the block the wave has just parsed
+namespace {
+typedef __attribute__((address_space(3))) ParseShared* ParseSharedLds;
+typedef __attribute__((address_space(1))) u8* GlobalBytes;
+typedef __attribute__((address_space(1))) const u8* GlobalCBytes;
+__device__ bool huf_front(ParseSharedLds Sl, GlobalBytes litsG, GlobalCBytes blkG, GlobalCBytes limG, int lane);
+}  // namespace
+
 // waves per SIMD the parse kernel is compiled for. The stage is one lane's serial work per frame (header fields, weight decode, table
 // spreads): what it needs is frames in flight. A/B on one box, 8 GiB decode, parse stage: 2 waves per SIMD (170 VGPRs, the compiler's
 // own choice) 22.5 ms, 3 (162) 15.2, 4 (128, 9 spilled) 11.9, 5 (96, 40 spilled, 164 B scratch) 10.7, 6 (80, 55 spilled) 10.9
@@ -1027,16 +1050,26 @@ __device__ __forceinline__ u32 parse_job(const ZraDecodeArgs& a, const u32 j, Pa
 extern "C" __global__ void __launch_bounds__(DEC_THREADS, ZRA_PARSE_WAVES)
 zra_dec_parse_kernel(ZraDecodeArgs a) {
   __shared__ ParseShared S;
-  const int lane = threadIdx.x;
+  const int lane0 = threadIdx.x;
   // a round enqueued behind the previous one without a host synchronisation learns its job count on the device
   const u32 nActive = a.nActivePtr ? __hip_atomic_load(a.nActivePtr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.nActive;
   for (;;) {
+    // (the lane number is opaque to the compiler once per job: what it derives from it — addresses in S, lane masks — is computed in
+    //  the job that needs it instead of being kept, mostly in spill slots, from job to job and across the call below. With it the
+    //  kernel needs 216 B of scratch per lane including the call; 296 without, 240 before there was a call.)
+    int lane = lane0; asm volatile("" : "+v"(lane));
     if (lane == 0) S.job = atomicAdd(&a.counters[ZRA_DC_QPARSE], 1u);
     wsync();
     const u32 qi = S.job;
     wsync();
     if (qi >= nActive) return;
-    (void)parse_job<false>(a, a.active ? a.active[qi] : qi, S, lane, nullptr);
+    const u32 j = a.active ? a.active[qi] : qi;
+    if (parse_job<false>(a, j, S, lane, nullptr) == 3) {
+      // the block's literal streams, by this wave (S.blkPos: the block's content)
+      const u8* const blk = a.body + a.frameOff[(size_t)j * a.offStride] + S.blkPos;
+      if (!huf_front((ParseSharedLds)&S, (GlobalBytes)a.lits, (GlobalCBytes)blk, (GlobalCBytes)(a.body + a.bodySize), lane) && lane == 0) a.frames[j].hufErr = 1;
+      wsync();
+    }
   }
 }
 
@@ -1056,9 +1089,9 @@ zra_dec_parse_all_kernel(ZraDecodeArgs a) {
 }
 
 // =================================================================================================
-// stage 1b: Huffman literal streams, lane = stream.
+// stage 1b: Huffman literal streams, lane = stream (the kernel; and the front end of stage 1, huf_front).
 // A stream is a serial chain (table lookup -> code length -> next bit position); the four streams of a frame gave a wave four busy
-// lanes. Here a wave takes 16 frames: their 16 decode tables are built in LDS (64 KiB) and the 64 streams advance together.
+// lanes. The whole wave works on one block at a time (huf_decode_wave); a workgroup of the Huffman kernel holds HUF_FRAMES tables.
 namespace {
 constexpr int HUF_FRAMES = ZRA_HUF_FRAMES;
 struct __attribute__((aligned(16))) HufShared {
@@ -1066,6 +1099,13 @@ struct __attribute__((aligned(16))) HufShared {
   u8 w1[HUF_FRAMES][256];      // weight-1 symbols in order (only tables of depth 12 need them)
   u32 base;
 };
+// The parse wave decodes the literals of a block it has just parsed (the fused front end of parse_job) with its decode table in LDS
+// that the parse no longer needs by then: the cells over `stage` (the last sequence table has been stored to the table scratch), the
+// weight-1 symbols over `spread` (scratch of the table builds). weights[] / hufStart[], which the table is built FROM, and the control
+// words stay where they are. Nothing of the aliased storage is read again before the next block's parse writes it.
+static_assert(sizeof(ParseShared::stage) >= sizeof(HufShared::tab[0]), "Huffman decode table over the FSE table staging area");
+static_assert(sizeof(ParseShared::spread) >= sizeof(HufShared::w1[0]), "weight-1 symbols over the spread scratch");
+static_assert(offsetof(ParseShared, stage) % 16 == 0 && offsetof(ParseShared, weights) % 8 == 0 && offsetof(ParseShared, hufStart) % 8 == 0, "huf_build_table reads 4 weights / 4 start cells per lane");
 // Huffman symbol lookup on 12 bits v (left-aligned code bits): symbol | nbBits<<8
 __device__ __forceinline__ u32 huf_lookup12(const u16* tab, const u8* w1, u32 v12, u32 mb) {
   if (mb < 12) return tab[v12 >> (12 - mb)] & 0x7FFFu;
@@ -1119,12 +1159,29 @@ __device__ __forceinline__ bool huf_stream_x2(const u16* tab, const u8* w1, u32 
 }  // namespace
 
 namespace {
-// decode table of one frame's kept Huffman description, by the whole wave: lane l owns symbols 4l .. 4l+3
-__device__ __forceinline__ void huf_build_table(const ZraDecFrame* const F, u16* const tab, u8* const w1, const int lane) {
-  const u32 maxBits = F->hufMaxBits, nSym = F->hufNSym;
+// One block's Huffman-coded literal section as the decoders below see it: filled from the block's record (Huffman kernel, one-launch
+// kernel) or from the parse wave's LDS (the fused front end) — the stream positions are read through the pointers, by the lane that
+// needs them.
+struct HufLit {
+  u32 streams, regen, maxBits, x2;
+  u8* out;                         // the block's literal scratch
+  const u8* blk;                   // the block's content
+  const u32* streamOff; const u32* streamLen;
+};
+__device__ __forceinline__ HufLit huf_lit_of(const ZraDecodeArgs& a, const ZraDecFrame* const F, const u32 j) {
+  HufLit d;
+  d.streams = F->litStreams; d.regen = F->litRegen; d.maxBits = F->hufMaxBits; d.x2 = F->hufX2;
+  d.out = a.lits + F->litBase;
+  d.blk = a.body + a.frameOff[frame_of(a, j) * a.offStride] + F->bpos;
+  d.streamOff = F->streamOff; d.streamLen = F->streamLen;
+  return d;
+}
+// decode table of a Huffman description (weight and first cell of every symbol, 8-byte aligned: a frame's record, or the parse wave's
+// LDS), by the whole wave: lane l owns symbols 4l .. 4l+3
+__device__ __forceinline__ void huf_build_table(const u8* const weights, const u16* const hufStart, const u32 maxBits, const u32 nSym, u16* const tab, u8* const w1, const int lane) {
   const u32 sh = maxBits == 12 ? 1u : 0u;          // depth 12: cells are indexed by the top 11 bits, the 12-bit codes come in pairs
-  const u32 w4 = *(const u32*)(F->weights + 4 * lane);
-  const u64 st4 = *(const u64*)(F->hufStart + 4 * lane);
+  const u32 w4 = *(const u32*)(weights + 4 * lane);
+  const u64 st4 = *(const u64*)(hufStart + 4 * lane);
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const u32 sy = 4 * (u32)lane + k;
@@ -1179,17 +1236,14 @@ __device__ __forceinline__ void huf_x1_emit(Reader& hb, const u16* const tab, co
   for (; i < count; i++) { hb.ensure(mb); u32 e = tab[hb.peek(mb)]; o[i] = (u8)e; hb.skip((int)(e >> 8)); }
 }
 
-// one literal stream of frame job j by ONE lane (strm < F->litStreams); returns false when libzstd would reject the stream.
-// stopAt: symbols of this stream that are needed (random access that stops early: the rest is not decoded; only without X2 fall-back)
-__device__ __forceinline__ bool huf_decode_stream(const ZraDecodeArgs& a, ZraDecFrame* const F, const u32 j, const u16* const tab, const u8* const w1,
-                                                  const u32 strm, const u8* const lim) {
-  const u32 nStreams = F->litStreams, regen = F->litRegen;
+// one literal stream of a block by ONE lane (strm < d.streams); returns false when libzstd would reject the stream.
+__device__ __forceinline__ bool huf_decode_stream(const HufLit& d, const u16* const tab, const u8* const w1, const u32 strm, const u8* const lim) {
+  const u32 nStreams = d.streams, regen = d.regen;
   const u32 seg = nStreams == 1 ? regen : (regen + 3) / 4;
   const u32 myLen = nStreams == 1 ? regen : (strm < 3 ? seg : regen - 3 * seg);
-  u8* o = a.lits + F->litBase + (size_t)strm * seg;
-  const u8* const blk = a.body + a.frameOff[frame_of(a, j) * a.offStride] + F->bpos;
-  const u8* const sb = blk + F->streamOff[strm]; const u32 sl = F->streamLen[strm];
-  const int mb = (int)F->hufMaxBits;
+  u8* o = d.out + (size_t)strm * seg;
+  const u8* const sb = d.blk + d.streamOff[strm]; const u32 sl = d.streamLen[strm];
+  const int mb = (int)d.maxBits;
 #ifndef ZRA_HUF_READER_AHEAD
 #define ZRA_HUF_READER_AHEAD 1
 #endif
@@ -1210,27 +1264,26 @@ __device__ __forceinline__ bool huf_decode_stream(const ZraDecodeArgs& a, ZraDec
     if (hb.pos != 0) bad = true;
   }
   // a stream the single-symbol rules reject may still pass libzstd's double-symbol decoder, if that is the one it would use
-  if (bad && F->hufX2) bad = !huf_stream_x2(tab, w1, (u32)mb, sb, sl, lim, o, myLen);
+  if (bad && d.x2) bad = !huf_stream_x2(tab, w1, (u32)mb, sb, sl, lim, o, myLen);
   return !bad;
 }
 
-// The literal streams of one frame by the WHOLE wave. A Huffman stream can only be decoded from its end, one code after the other — but
+// The literal streams of one block by the WHOLE wave. A Huffman stream can only be decoded from its end, one code after the other — but
 // a decoder that starts in the middle of a stream falls into step with the real code boundaries after a few codes (self-synchronisation).
 // So every stream is cut into 16 runs of bits (a lone stream: 64), every lane decodes its run from a guessed start, counts the codes
 // and notes where the first code of the NEXT run starts; the lanes then restart from their predecessor's hand-over point until nobody's
 // start moves — lane 0 of a stream starts at the true end mark, so the fixed point is the real decode — and a last pass writes the
 // symbols at the prefix sums of the counts. Returns false unless every stream regenerates exactly its share and ends on bit 0: the
 // caller then runs the serial decoders, which decide what a damaged stream returns (what was written here is overwritten or unused).
-__device__ __forceinline__ bool huf_decode_wave(const ZraDecodeArgs& a, const ZraDecFrame* const F, const u32 j, const u16* const tab, const int lane, const u8* const lim) {
-  const u32 nStreams = F->litStreams, regen = F->litRegen;
-  const int mb = (int)F->hufMaxBits;
+__device__ __forceinline__ bool huf_decode_wave(const HufLit& d, const u16* const tab, const int lane, const u8* const lim) {
+  const u32 nStreams = d.streams, regen = d.regen;
+  const int mb = (int)d.maxBits;
   if (mb >= 12 || regen < 64) return false;
   const u32 L = nStreams == 1 ? 64u : 16u;
   const u32 strm = nStreams == 1 ? 0u : (u32)lane >> 4, t = (u32)lane & (L - 1);
   const u32 seg = nStreams == 1 ? regen : (regen + 3) / 4;
   const u32 myLen = nStreams == 1 ? regen : (strm < 3 ? seg : regen - 3 * seg);
-  const u8* const blk = a.body + a.frameOff[frame_of(a, j) * a.offStride] + F->bpos;
-  const u8* const sb = blk + F->streamOff[strm]; const u32 sl = F->streamLen[strm];
+  const u8* const sb = d.blk + d.streamOff[strm]; const u32 sl = d.streamLen[strm];
   const u32 last = sl ? (u32)sb[sl - 1] : 0u;
   if (__ballot(last == 0)) return false;
   const u32 P = (sl - 1) * 8 + hb32(last);                            // unread bits under the end mark
@@ -1296,9 +1349,39 @@ __device__ __forceinline__ bool huf_decode_wave(const ZraDecodeArgs& a, const Zr
   if (__ballot(total != myLen || (active && lower == 0 && end != 0))) return false;
   if (active && n) {
     hb.init_at(sb, lim, start);
-    huf_x1_emit(hb, tab, mb, a.lits + F->litBase + (size_t)strm * seg + (incl - n), n);
+    huf_x1_emit(hb, tab, mb, d.out + (size_t)strm * seg + (incl - n), n);
   }
   return true;
+}
+// The body of the Huffman stage for one block whose decode table stands in tab / w1: the wave-wide decode, and for what that declines
+// (damaged or unusual streams) libzstd's serial decoders, one lane per stream. False: a literal stream libzstd rejects (hufErr).
+// Called by the Huffman kernel, by the parse wave for the blocks it finishes itself, and by the one-launch kernel's second wave.
+__device__ __forceinline__ bool huf_decode_job(const HufLit& d, const u16* const tab, const u8* const w1, const int lane, const u8* const lim, bool* const wide = nullptr) {
+  const bool w = huf_decode_wave(d, tab, lane, lim);
+  if (wide) *wide = w;
+  if (w) return true;
+  bool bad = false;
+  if ((u32)lane < d.streams) bad = !huf_decode_stream(d, tab, w1, (u32)lane, lim);
+  return __ballot(bad) == 0;
+}
+// The fused front end of the parse kernel: the literal streams of the block whose section and NEW tree the wave has just described
+// in S (parse_job returned 3), decoded by that wave. A real call, made by the kernel with nothing of the parse alive: the parse kernel
+// is compiled for five waves per SIMD and holds its spills to a budget (tests/test_kernel_budgets.py) that the Huffman stage's body,
+// inlined into parse_job, does not fit beside. The pointers are passed with their address spaces (S: LDS, the rest: global), so that
+// the table lookups stay LDS reads and the streams global loads. False: a literal stream libzstd rejects (the record's hufErr).
+__device__ __attribute__((noinline)) bool huf_front(ParseSharedLds const Sl, GlobalBytes const litsG, GlobalCBytes const blkG, GlobalCBytes const limG, const int lane) {
+  ParseShared& S = *(ParseShared*)Sl;
+  u8* const lits = (u8*)litsG;
+  const u8* const blk = (const u8*)blkG;
+  const u8* const lim = (const u8*)limG;
+  u16* const tab = (u16*)S.stage; u8* const w1 = S.spread;       // (aliases: see the static_asserts at HufShared)
+  HufLit d;
+  d.streams = S.litStreams; d.regen = S.litRegen; d.maxBits = S.hufMaxBits; d.x2 = S.hufX2;
+  d.out = lits + S.litBase; d.blk = blk;
+  d.streamOff = S.streamOff; d.streamLen = S.streamLen;
+  huf_build_table(S.weights, S.hufStart, d.maxBits, S.hufNSym, tab, w1, lane);
+  wsync();
+  return huf_decode_job(d, tab, w1, lane, lim);
 }
 }  // namespace
 
@@ -1316,19 +1399,17 @@ zra_dec_huf_kernel(ZraDecodeArgs a) {
     if (base >= nJobs) return;
     const u32 nHere = min((u32)HUF_FRAMES, nJobs - base);
     // ---- the tables of this batch, one frame after the other, all lanes on each
-    for (u32 s = 0; s < nHere; s++) huf_build_table(&a.frames[a.hufJobs[base + s]], S.tab[s], S.w1[s], lane);
+    for (u32 s = 0; s < nHere; s++) {
+      const ZraDecFrame* const F = &a.frames[a.hufJobs[base + s]];
+      huf_build_table(F->weights, F->hufStart, F->hufMaxBits, F->hufNSym, S.tab[s], S.w1[s], lane);
+    }
     wsync();
-    // ---- all lanes on one frame after the other; what that leaves (damaged or unusual streams): lane -> (frame slot, stream)
-    u32 doneMask = 0;
+    // ---- all lanes on one frame after the other
     for (u32 s = 0; s < nHere; s++) {
       const u32 j = a.hufJobs[base + s];
-      if (huf_decode_wave(a, &a.frames[j], j, S.tab[s], lane, lim)) doneMask |= 1u << s;
-    }
-    const u32 slot = (u32)lane >> 2, strm = (u32)lane & 3;
-    if (slot < nHere && !((doneMask >> slot) & 1u)) {
-      const u32 j = a.hufJobs[base + slot];
       ZraDecFrame* const F = &a.frames[j];
-      if (strm < F->litStreams && !huf_decode_stream(a, F, j, S.tab[slot], S.w1[slot], strm, lim)) F->hufErr = 1;
+      const HufLit d = huf_lit_of(a, F, j);
+      if (!huf_decode_job(d, S.tab[s], S.w1[s], lane, lim) && lane == 0) F->hufErr = 1;
     }
   }
 }
@@ -2349,16 +2430,16 @@ zra_ra_small_kernel(ZraDecodeArgs a0, u32* bail, const u32* expect, u32 jobBase,
     if (wave == 1) {
       u32 ok = 1;
       if (F->litKind == 2) {
-        huf_build_table(F, S.hufTab, S.hufW1, lane);
+        huf_build_table(F->weights, F->hufStart, F->hufMaxBits, F->hufNSym, S.hufTab, S.hufW1, lane);
         wsync();
-        const bool wide = huf_decode_wave(a, F, j, S.hufTab, lane, lim);
+        bool wide;
+        const HufLit d = huf_lit_of(a, F, j);
+        ok = huf_decode_job(d, S.hufTab, S.hufW1, lane, lim, &wide) ? 1u : 0u;
 #ifdef ZRA_SMALL_PROFILE
         if (lane == 0) atomicAdd(&zra_small_prof[wide ? 14 : 15], 1ull);
 #endif
-        if (!wide)
-          if ((u32)lane < F->litStreams && !huf_decode_stream(a, F, j, S.hufTab, S.hufW1, (u32)lane, lim)) S.ctl[1] = 1;
+        if (!ok && lane == 0) S.ctl[1] = 1;
         wsync();
-        ok = S.ctl[1] == 0;
       }
       __threadfence_block();
       if (lane == 0) ring_st(&S.ctl[3], ok ? 1u : 2u);             // the execute steps of the chain's consumer may read the literals

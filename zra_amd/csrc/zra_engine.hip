@@ -317,6 +317,10 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
   const uint32_t n = a.nFrames;
   { Status st = decode_scratch(a, maxFrameBytes); if (st.zra) return st; }
   decCountersClean_ = false;
+  // ZRA_DEC_FRONT=0: every block with Huffman-coded literals goes through the Huffman kernel (the two kernels as they were); default:
+  // the parse wave of the rounds below decodes the literals of a block with a new tree itself, the Huffman launch takes the rest
+  static const int decFront = zra_env::env_int("ZRA_DEC_FRONT", 1);
+  a.decFront = decFront != 0;
   uint32_t* listA = decLists_.as<uint32_t>(); uint32_t* listB = listA + n;
   if (!decOccParse_) {
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&decOccParse_, zra_dec_parse_kernel, 64, 0));

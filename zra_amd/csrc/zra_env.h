@@ -23,6 +23,7 @@
 //   ZRA_ENT_SPLIT           split entropy stage: 0 never, 1 calls of >= 256 frames, 2 always
 //   ZRA_DEC_FMB             0: no block-parallel decode pass
 //   ZRA_DEC_FMB_MIN         smallest pass that takes the block-parallel decode pass, in jobs
+//   ZRA_DEC_FRONT           0: the parse wave leaves every Huffman-coded literal section to the Huffman kernel
 //   ZRA_DEC_CHAIN_LDS       decoder's LDS-table chain kernel: 0 never, 1 beside the other one, 2 alone
 //   ZRA_DEC_CHAIN_LDS_MIN   smallest round that runs the LDS-table chain kernel, in jobs
 //   ZRA_COMM_CHUNK_BYTES    largest piece of one RCCL message, in bytes

@@ -6,8 +6,9 @@
 // ------------------------------------------------------------------------------------------------ decode
 // The decoder is four stages per ROUND (one compressed block of every unfinished frame per round; raw / RLE blocks and the frame
 // ends are consumed by the first kernel on the way); zra_decode.hip's header describes them:
-//   zra_dec_parse_kernel      wave per frame    headers, Huffman tree descriptions, FSE tables -> per-frame table scratch
-//   zra_dec_huf_kernel        wave per frame    Huffman literal streams (16 runs per stream side by side) -> literal scratch
+//   zra_dec_parse_kernel      wave per frame    headers, Huffman tree descriptions, FSE tables -> per-frame table scratch; the literal
+//                                               streams of a block with a new tree (fused front end)          -> literal scratch
+//   zra_dec_huf_kernel        wave per frame    the other Huffman literal streams (16 runs per stream side by side) -> literal scratch
 //   zra_dec_chain_kernel      LANE per frame    the serial FSE sequence chains, every check of the reference's sequence loop
 //   zra_dec_chain_lds_kernel  (the same, tables in LDS, beside it)                                              -> sequence scratch
 //   zra_dec_exec_kernel       wave per frame    data movement: literal + match copies, frame end, random-access slices
@@ -108,7 +109,7 @@ struct ZraDecodeArgs {
   uint32_t* status;          // [nFrames] zstd error code per frame (0 = ok)
   uint32_t* produced;        // [nFrames] bytes regenerated
   uint32_t* frameMeta;       // [2*nFrames] {1 = has checksum / 2 = stopped early (no frame-end checks), stored checksum}
-  uint32_t debugSkip;        // unused
+  uint32_t decFront;         // the parse wave of the classic rounds decodes the Huffman-coded literals of a block with a new tree itself (ZRA_DEC_FRONT)
   // block-parallel pass (round 6, frames of several blocks): the Huffman and chain stages take BLOCKS as jobs — job = frame * bpf + the
   // compressed block's ordinal, its record in `frames`, its tables in `tables` (the host points both at the block arrays for those two
   // launches) —, zra_dec_parse_all_kernel writes them from the frame records, zra_dec_exec_all_kernel walks a frame's blocks in order
