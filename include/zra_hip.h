@@ -703,6 +703,58 @@ ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecordsExpr(ZraHipArchive* archive,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
     void* dData, size_t dataCapacity, uint64_t* dataSize);
 
+/* ---- grep with a record predicate: AND, OR and NOT of the patterns, per record, in one pass ----
+ * ZraHipGrepArchive selects a record when ANY pattern occurs in it. "Lines with ERROR and user=42 but not healthcheck" is
+ * `grep A | grep B | grep -v C`: one grep per term, each decoding the range again, and an intersection of the lists on the host.
+ * The scan already knows WHICH patterns hit at a position; this call keeps that set per record and tests a predicate on it. */
+#define ZRA_HIP_WHERE_MAX_CLAUSES 8
+
+typedef struct ZraHipRecordClause { uint64_t all, any, none; } ZraHipRecordClause;  /* bit i = pattern i */
+
+/** Rule 1 of ZraHipGrepArchiveWhere as far as the clauses go, on the host alone: no engine, no device. {ZStdError, 42} when hClauses
+ *  is NULL, nClauses is 0 or above ZRA_HIP_WHERE_MAX_CLAUSES, nPatterns is 0 or above ZRA_HIP_SEARCH_MAX_PATTERNS, a clause has a bit
+ *  at or above nPatterns, or a clause has all & none != 0 or any & none != 0 (it demands and forbids one pattern). Else Success. */
+ZRA_EXPORT ZraStatus ZraHipCheckRecordClauses(const ZraHipRecordClause* hClauses, size_t nClauses, size_t nPatterns);
+
+/** ZraHipGrepArchiveExpr with a predicate over the patterns in the place of "any pattern". Patterns with their `syntax` word (0:
+ *  literal bytes; ZRA_HIP_PATTERN_FOLD_CASE, ZRA_HIP_PATTERN_CLASSES), `delimiter`, the range, stagingBytes, passes, ownership, the
+ *  records and the matches are that call's, word for word.
+ *  Selection. The hit set of a record is H = { i : a match (p, i) of the multi search on [lo, hi) starts inside the record }.
+ *  A clause {all, any, none} holds for H when (H & all) == all, and any == 0 or (H & any) != 0, and (H & none) == 0. A record is
+ *  selected when one of the nClauses clauses holds; ZRA_HIP_GREP_INVERT in `mode` complements that answer.
+ *  - {0, all patterns, 0} is the plain grep; {0, 0, all patterns} is grep -v; {0, 0, 0} selects every record.
+ *  - "A and B and not C" is {A|B, 0, C}; "(A and B) or not C" is the two clauses {A|B, 0, 0}, {0, 0, C}.
+ *  Result, capacity 0 as `grep -c`, "nothing reaches the host before the last pass" and the stats: ZraHipGrepArchive's. The call
+ *  writes ZraHipGetGrepStats (matches = the (p, i) pairs, whatever the predicate) and ZraHipDebugGrepScanMs.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchiveExpr's rule 1, then ZraHipCheckRecordClauses' refusals -> {ZStdError, 42}. Nothing is decoded.
+ *   2. Header problems: ZraHipSearchArchive's rule 2.
+ *   3. The range: ZraHipSearchArchive's rule 3. The empty range is Success with 0 records. In a non-empty range shorter than the
+ *      shortest pattern every record has H = {}: when the predicate, INVERT applied, is false on the empty set, the call is Success
+ *      with 0 records, nothing decoded and stats {frames, 0, ...}; otherwise the range is scanned and every record of it is selected.
+ *   4. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the grep's, with 64 bytes per 8 KiB of window for the per-tile
+ *      tables in the place of 32: a tile's summary and its head carry a 64-bit pattern set each.
+ *   5. A decoded frame that fails: ZraHipSearchArchive's rule 5.
+ *  Cost: the grep's; a trip of 64 positions in which something hit pays one lane read per hitting lane and one ballot per distinct
+ *  pattern that hit in it, or, from 8 hitting lanes on, a six-step scan over the lanes: 1.01 to 1.04 times the grep's scan time on
+ *  log text, 1.35 times with a hit at nearly every position (profiles/grep_where.md). The plain entry points keep their own kernels.
+ *  Not covered: ZraHipExtractRecords with a predicate, per-pattern record counts, quantifiers, alternation inside a pattern, anchors,
+ *  context lines, shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipGrepArchiveWhere(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    const ZraHipRecordClause* hClauses, size_t nClauses,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+/** ZraHipGrepArchiveWhere through a ZraHipArchive handle: resident frames are staged from the cache as for ZraHipArchiveGrep, the
+ *  cache is not changed, and the handle's scan counters (ZraHipArchiveGetScanStats) move as for that call. */
+ZRA_EXPORT ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    const ZraHipRecordClause* hClauses, size_t nClauses,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte
  * ranges; the same content written at two levels raises the same question. A caller would have to ZraHipDecompressBuffer both contents

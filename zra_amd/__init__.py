@@ -205,6 +205,10 @@ def load():
         "ZraHipArchiveGrepExpr": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipArchiveExtractRecordsExpr": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz,
                                                 u64p]),
+        # the grep with a record predicate: clauses of ZraHipRecordClause {all, any, none} behind `mode`
+        "ZraHipCheckRecordClauses": (S, [vp, sz, sz]),
+        "ZraHipGrepArchiveWhere": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipArchiveGrepWhere": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -287,6 +291,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipExtractRecords", "ZraHipGetExtractStats", "ZraHipDebugExtractMs",
                    "ZraHipCheckPatternExpr", "ZraHipSearchArchiveMultiExpr", "ZraHipGrepArchiveExpr", "ZraHipExtractRecordsExpr",
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
+                   "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -554,20 +559,23 @@ class Engine:
         """bring-up: HIP-event time of the last search_multi()'s scan launches, summed over its passes."""
         return self.L.ZraHipDebugSearchMultiScanMs(self.h)
 
-    def grep(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0):
+    def grep(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0,
+             where=None):
         """ZraHipGrepArchive: the records of [offset, offset + length) (None: to the end) of the content of the archive at d_archive,
         cut at the byte `delimiter`, in which one of `patterns` (search_multi's, none holding the delimiter) occurs; invert: those in
         which none does. Returns (n_records, [(offset, size)]): every selected record is counted and the first max_records are listed
         in ascending order, without their delimiter. max_records=0 is `grep -c`. syntax: search_multi's (ZraHipGrepArchiveExpr).
-        ZraError is a call that could not grep."""
+        where: a non-empty list of clauses (all, any, none), each term an int mask or an iterable of pattern indices
+        (ZraHipGrepArchiveWhere): a record is selected when some clause holds for the set of patterns that occur in it; invert
+        complements that. ZraError is a call that could not grep."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n = ctypes.c_uint64(0)
         self._order()
-        fn, sx = _scan_call(self.L, "ZraHipGrepArchive", syntax)
+        fn, sx, wx = _grep_call(self.L, "ZraHipGrepArchive", syntax, where)
         _chk(fn(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter,
-                GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                GREP_INVERT if invert else 0, *wx, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
                 max_records, ctypes.byref(n)), fn.__name__)
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
@@ -862,6 +870,46 @@ def check_pattern_expr(patterns, syntax=PATTERN_CLASSES, delimiter=None):
          "ZraHipCheckPatternExpr")
     return [int(v) for v in lens[:len(patterns)]], int(ns.value)
 GREP_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "listed", "passes", "matches")
+WHERE_MAX_CLAUSES = 8                        # ZRA_HIP_WHERE_MAX_CLAUSES
+
+
+def _pattern_set(term):
+    """a clause's term as a 64-bit mask: an int mask as it is, else the indices of an iterable"""
+    if isinstance(term, int):
+        mask = term
+    else:
+        mask = 0
+        for i in term:
+            if not 0 <= int(i) < 64:
+                raise ValueError("pattern index %r outside 0 .. 63" % (i,))
+            mask |= 1 << int(i)
+    if not 0 <= mask < 1 << 64:
+        raise ValueError("pattern mask %r does not fit 64 bits" % (term,))
+    return mask
+
+
+def _clauses(where):
+    """[(all, any, none)] as a ZraHipRecordClause array (three 64-bit words per clause) and its length"""
+    where = [tuple(_pattern_set(t) for t in c) for c in where]
+    if any(len(c) != 3 for c in where):
+        raise ValueError("a clause is (all, any, none)")
+    flat = [w for c in where for w in c]
+    return (ctypes.c_uint64 * max(len(flat), 3))(*flat), len(where)
+
+
+def _grep_call(L, name, syntax, where):
+    """the entry point of a grep, what goes behind nPatterns and what goes behind mode: _scan_call's without `where`, else the
+    ...Where call, which takes the syntax word always and the clauses"""
+    if not where:
+        return _scan_call(L, name, syntax) + ((),)
+    return getattr(L, name + "Where"), (syntax,), _clauses(where)
+
+
+def check_record_clauses(where, n_patterns):
+    """ZraHipCheckRecordClauses: the clause checks of grep(where=...), on the host alone (no engine, no device). ZraError is a refused
+    clause list."""
+    arr, k = _clauses(where)
+    _chk(load().ZraHipCheckRecordClauses(arr if k else None, k, n_patterns), "ZraHipCheckRecordClauses")
 EXTRACT_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "packed_bytes", "passes", "matches")
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
@@ -969,15 +1017,16 @@ class Archive:
         listed = [(int(arr[i].offset), int(arr[i].pattern)) for i in range(min(n.value, max_matches))] if arr is not None else []
         return n.value, listed, [int(v) for v in per[:len(patterns)]]
 
-    def grep(self, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0):
-        """ZraHipArchiveGrep (syntax != 0: ...Expr): Engine.grep through the handle. Returns (n_records, [(offset, size)])."""
+    def grep(self, patterns, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0, where=None):
+        """ZraHipArchiveGrep (syntax != 0: ...Expr; a non-empty where: ZraHipArchiveGrepWhere): Engine.grep through the handle.
+        Returns (n_records, [(offset, size)])."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n = ctypes.c_uint64(0)
         self.engine._order()
-        fn, sx = _scan_call(self.L, "ZraHipArchiveGrep", syntax)
-        _chk(fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, offset,
+        fn, sx, wx = _grep_call(self.L, "ZraHipArchiveGrep", syntax, where)
+        _chk(fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, *wx, offset,
                 (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n)), fn.__name__)
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]

@@ -9,6 +9,7 @@
 #include "zra_format.h"
 #include "zra_env.h"
 #include "zra_pattern_expr.h"
+#include "zra_where.h"
 
 #include <atomic>
 #include <algorithm>
@@ -937,6 +938,27 @@ ZraStatus ZraHipArchiveExtractRecordsExpr(ZraHipArchive* archive, const void* hP
   if (!archive) return mk(ZStdError, 42);
   return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
                                 nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+}
+// ---- the grep with a record predicate: kernels of its own (zra_grep_where.hip), the grep's stats row and milliseconds
+ZraStatus ZraHipCheckRecordClauses(const ZraHipRecordClause* hClauses, size_t nClauses, size_t nPatterns) {
+  static_assert(sizeof(ZraHipRecordClause) == sizeof(zra_where::Clause) && ZRA_HIP_WHERE_MAX_CLAUSES == zra_where::kMaxClauses, "one clause layout");
+  return zra_where::clauses_ok((const zra_where::Clause*)hClauses, nClauses, nPatterns) ? mk(Success, 0) : mk(ZStdError, 42);
+}
+ZraStatus ZraHipGrepArchiveWhere(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                                 uint32_t syntax, uint8_t delimiter, uint32_t mode, const ZraHipRecordClause* hClauses, size_t nClauses, uint64_t offset, uint64_t size,
+                                 size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->grep_archive_where((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset,
+                                          size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+}
+ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                 uint32_t mode, const ZraHipRecordClause* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
+                                 ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->grep_where(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset, size, stagingBytes, (uint64_t*)hRecords,
+                                   recordCapacity, nRecords));
 }
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {

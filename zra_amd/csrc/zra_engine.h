@@ -244,6 +244,12 @@ class Engine {
   void grep_stats(uint64_t out[8]) const { call_stats(kScanGrep, out); }
   // bring-up: HIP-event time of the last grep's scan launches (count, scan, fill, carry), summed over its passes
   double grep_scan_ms() const { return callMs_[kScanGrep]; }
+  // grep_archive with a record predicate (zra_grep_where.hip, zra_where.h): a record is selected when one of the nClauses clauses
+  // {all, any, none} at hClauses (ZraHipRecordClause) holds for the set of patterns that hit in it; mode 1 complements that. Kernels of
+  // its own; it writes grep_archive's counters and milliseconds. Statuses and their order: zra_hip.h, ZraHipGrepArchiveWhere.
+  Status grep_archive_where(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+                            uint8_t delimiter, uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
+                            uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
 
   // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
   // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:

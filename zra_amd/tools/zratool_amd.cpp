@@ -21,6 +21,10 @@
 //         a pattern is an expression of fixed length, . [set] [^set] \escape (zra_hip.h: ZraHipCheckPatternExpr); -i: ASCII letters
 //         match either case, -F: the patterns are literal after all; behind "hex:" a pattern is literal bytes either way. A refused
 //         expression is exit status 2 with a message that names the pattern's index; otherwise output and exit status of gm, gl, gx
+//   glw : gle with a record predicate (ZraHipGrepArchiveWhere): one or more -w {clause}; a clause is comma-separated items +i (pattern i
+//         must occur in the record), ?i (one of the ?-patterns must), -i (pattern i must not), i = the pattern's position on the command
+//         line from 0; a record is selected when some clause holds, -v complements that. Output and exit status of gl; a refused
+//         clause is exit status 2
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
@@ -264,12 +268,33 @@ int search_archive_multi(const char* path, char** texts, int n, const ExprOpt* e
   return total ? 0 : 1;
 }
 
-// modes gl and (ex) gle: the patterns texts[0 .. n)
-int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts, int n, const ExprOpt* ex) {
+// mode glw: "+0,-1,?2,?3" -> {all, any, none}
+bool parse_clause(const char* text, ZraHipRecordClause* c) {
+  *c = ZraHipRecordClause{0, 0, 0};
+  for (const char* p = text; *p;) {
+    const char kind = *p++;
+    char* end = nullptr;
+    const unsigned long i = (*p >= '0' && *p <= '9') ? std::strtoul(p, &end, 10) : ZRA_HIP_SEARCH_MAX_PATTERNS;
+    if ((kind != '+' && kind != '?' && kind != '-') || i >= ZRA_HIP_SEARCH_MAX_PATTERNS || (*end && *end != ',') || (*end == ',' && !end[1])) {
+      std::fprintf(stderr, "a clause is +i, ?i or -i items with commas between them, i below %u: %s\n", ZRA_HIP_SEARCH_MAX_PATTERNS, text);
+      return false;
+    }
+    (kind == '+' ? c->all : kind == '?' ? c->any : c->none) |= 1ull << i;
+    p = *end ? end + 1 : end;
+  }
+  return true;
+}
+
+// modes gl, (ex) gle and (where) glw: the patterns texts[0 .. n)
+int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts, int n, const ExprOpt* ex, const std::vector<ZraHipRecordClause>* where = nullptr) {
   std::string all;
   std::vector<uint32_t> sizes;
   uint32_t syntax = 0;
   if (!gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
+  if (where && ZraHipCheckRecordClauses(where->data(), where->size(), sizes.size()).zra != Success) {
+    std::fprintf(stderr, "1 to %u clauses over the patterns 0 .. %d, none with a pattern both wanted and unwanted\n", ZRA_HIP_WHERE_MAX_CLAUSES, n - 1);
+    return 2;
+  }
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -279,7 +304,9 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   std::vector<ZraHipContentRange> at(1u << 20);
   uint64_t total = 0;
   const uint32_t mode = invert ? ZRA_HIP_GREP_INVERT : 0u;
-  st = ex ? ZraHipGrepArchiveExpr(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, at.data(), at.size(), &total)
+  st = where ? ZraHipGrepArchiveWhere(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, where->data(), where->size(), 0, UINT64_MAX,
+                                      0, at.data(), at.size(), &total)
+     : ex ? ZraHipGrepArchiveExpr(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, at.data(), at.size(), &total)
           : ZraHipGrepArchive(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, at.data(), at.size(), &total);
   if (dArc) (void)hipFree(dArc);
   ZraHipDestroyEngine(eng);
@@ -548,6 +575,7 @@ int main(int argc, char** argv) {
                 "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}... - Grep an archive on the device: offset and size of every record (line) that holds a match, -v: that holds none (exit status 0 some, 1 none, 2 trouble)\n"
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
+                "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -577,8 +605,9 @@ int main(int argc, char** argv) {
     if (i >= argc) { std::fprintf(stderr, "gme {file} {-i} {-F} {expression | hex:digits}...\n"); return 2; }
     return search_archive_multi(argv[2], argv + i, argc - i, &ex);
   }
-  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe") {
-    const bool text = mode[1] == 'x', expr = mode.size() == 3;
+  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw") {
+    const bool text = mode[1] == 'x', expr = mode.size() == 3, pred = mode == "glw";
+    std::vector<ZraHipRecordClause> where;
     ExprOpt ex = {false, false};
     bool invert = false;
     unsigned long delimiter = 0x0A;
@@ -589,7 +618,12 @@ int main(int argc, char** argv) {
       if (opt == "-v") invert = true;
       else if (expr && opt == "-i") ex.fold = true;
       else if (expr && opt == "-F") ex.fixed = true;
-      else if (text && opt == "-o") {
+      else if (pred && opt == "-w") {
+        ZraHipRecordClause c;
+        if (++i >= argc || !*argv[i]) { std::fprintf(stderr, "-w takes a clause\n"); return 2; }
+        if (!parse_clause(argv[i], &c)) return 2;
+        where.push_back(c);
+      } else if (text && opt == "-o") {
         if (++i >= argc || !*argv[i]) { std::fprintf(stderr, "-o takes a file name\n"); return 2; }
         outPath = argv[i];
       } else if (opt == "-d") {
@@ -598,11 +632,12 @@ int main(int argc, char** argv) {
         if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
       } else break;
     }
-    if (i >= argc) {
-      std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s%s{%s | hex:digits}...\n", mode.c_str(), expr ? "{-i} {-F} " : "", text ? "{-o file} " : "",
-                   expr ? "expression" : "pattern");
+    if (i >= argc || (pred && where.empty())) {
+      std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s%s%s{%s | hex:digits}...\n", mode.c_str(), expr ? "{-i} {-F} " : "", text ? "{-o file} " : "",
+                   pred ? "-w clause {-w clause}... " : "", expr ? "expression" : "pattern");
       return 2;
     }
+    if (pred) return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, &ex, &where);
     if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, expr ? &ex : nullptr);
     return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, expr ? &ex : nullptr);
   }
