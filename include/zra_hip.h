@@ -552,7 +552,7 @@ typedef struct ZraHipContentRange { uint64_t offset; uint64_t size; } ZraHipCont
  *  Cost: one decode of the range and the multi search's filter; on top of it one byte compare per position and a segmented reduction
  *  over the positions between delimiters (profiles/grep_scan.md).
  *  Not covered: the BYTES of the records (ZraHipExtractRecords below keeps them from the same pass; with this call alone, fetch them
- *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), quantifiers, alternation, anchors (case folding and byte classes: ZraHipGrepArchiveExpr, below), multi-byte delimiters, shards, the
+ *  with ZraHipDecompressRABatch or ZraHipArchiveRead from the listed ranges, under those calls' own bound rule), quantifiers, alternation, anchors (ZraHipGrepArchiveRegex, below; case folding and byte classes: ZraHipGrepArchiveExpr, below), multi-byte delimiters, shards, the
  *  host-pointer API. Through a ZraHipArchive handle, resident frames staged from its cache: ZraHipArchiveGrep, above. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
@@ -662,7 +662,7 @@ ZRA_EXPORT ZraStatus ZraHipCheckPatternExpr(const void* hPatterns, const uint32_
  *  Cost: a position is tested against the patterns whose first two elements admit its first two bytes, element by element from the
  *  third. A pattern that begins `..` makes every position a candidate (as 64 patterns of zeros in a content of zeros do for the
  *  literal call); the work per position is bounded by 64 patterns x 256 elements (profiles/pattern_expr.md).
- *  Not covered: quantifiers, alternation, anchors, POSIX classes, UTF-8 awareness, patterns in device memory, shards, the host-pointer
+ *  Not covered: quantifiers, alternation, anchors (for the grep: ZraHipGrepArchiveRegex, below), POSIX classes, UTF-8 awareness, patterns in device memory, shards, the host-pointer
  *  API, the single-pattern ZraHipSearchArchive (one expression goes through this call). */
 ZRA_EXPORT ZraStatus ZraHipSearchArchiveMultiExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
@@ -738,7 +738,7 @@ ZRA_EXPORT ZraStatus ZraHipCheckRecordClauses(const ZraHipRecordClause* hClauses
  *  Cost: the grep's; a trip of 64 positions in which something hit pays one lane read per hitting lane and one ballot per distinct
  *  pattern that hit in it, or, from 8 hitting lanes on, a six-step scan over the lanes: 1.01 to 1.04 times the grep's scan time on
  *  log text, 1.35 times with a hit at nearly every position (profiles/grep_where.md). The plain entry points keep their own kernels.
- *  Not covered: ZraHipExtractRecords with a predicate, per-pattern record counts, quantifiers, alternation inside a pattern, anchors,
+ *  Not covered: ZraHipExtractRecords with a predicate, per-pattern record counts, quantifiers, alternation inside a pattern, anchors (ZraHipGrepArchiveRegex, below),
  *  context lines, shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchiveWhere(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
@@ -752,6 +752,88 @@ ZRA_EXPORT ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
     uint8_t delimiter, uint32_t mode,
     const ZraHipRecordClause* hClauses, size_t nClauses,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+
+/* ---- grep with regular expressions: quantifiers, alternation and anchors ----
+ * The calls above take patterns of fixed length, tested per position. A regular expression is a state machine over the bytes of a
+ * record: this call compiles the expressions into one deterministic automaton on the host and carries its STATE through the scan
+ * where the grep carries one bit. The expressions use the characters that the pattern expressions reserved; no expression accepted
+ * by the ...Expr calls changes its meaning there, and those calls go on refusing every syntax bit but their two. */
+#define ZRA_HIP_REGEX_MAX_STATES     64u    /* states of the minimal automaton of a call */
+#define ZRA_HIP_REGEX_MAX_POSITIONS  4096u  /* atoms of all expressions after counted repetitions are expanded */
+
+typedef struct ZraHipRegexInfo { uint32_t states, classes, positions, why, pattern; } ZraHipRegexInfo;
+
+/** Rule 1 of ZraHipGrepArchiveRegex as far as the expressions go, on the host alone: no engine, no device. hPatterns /
+ *  hPatternSizes / nPatterns: 1 .. ZRA_HIP_SEARCH_MAX_PATTERNS expressions laid end to end, each of 1 byte or more,
+ *  ZRA_HIP_PATTERN_MAX_EXPR_BYTES in all (the sizes are summed in 64 bits before a byte is read); they are alternatives, as with
+ *  `grep -e A -e B`. syntax: 0 or ZRA_HIP_PATTERN_FOLD_CASE. delimiter: 0 .. 255. Success, or {ZStdError, 42}; `info` (may be NULL)
+ *  is filled on both outcomes: why = 0 accepted, 1 arguments or a size limit, 2 syntax, 3 an atom whose set is empty once the
+ *  delimiter is removed, 4 more than ZRA_HIP_REGEX_MAX_STATES states or the construction bound; pattern = the index of the refused
+ *  expression for reasons 2 and 3, else 0; states, classes and positions are valid on Success and 0 otherwise.
+ *
+ *  Grammar: POSIX ERE over bytes.
+ *   atoms        ZraHipCheckPatternExpr's elements, unchanged: a literal byte, . [items] [^items] \xHH \n \t \r \d \w \s, and \c for
+ *                c one of . [ ] \ * + ? { } ( ) | ^ $ -. FOLD_CASE closes an atom's set under the ASCII case swap before a ^
+ *                complements it. [: stays refused (POSIX classes are reserved).
+ *   delimiter    removed silently from EVERY atom (a record never holds it, so no answer changes; `\s+` and `[ \n]` can be written
+ *                with the newline as delimiter). Only an atom whose set is then empty is refused (reason 3): the literal delimiter,
+ *                `[\n]`. ZRA_HIP_PATTERN_MAX_SETS does not apply.
+ *   x* x+ x?     x{n} x{n,} x{n,m}, 0 <= n <= m <= 255, behind an atom or a group. {0} and {0,0} are legal; {,m} is refused.
+ *   ( )          groups; nothing is captured.      |   alternation.      ^ $   anchors, anywhere.
+ *  Refused (reason 2): a quantifier with nothing in front of it (at the start, behind ( or |), directly behind a quantifier (`*?`
+ *  `+?` `*+` stay reserved) or on an anchor; an empty group; an empty branch (`a|`, `|a`, `(a|)`); unbalanced ( or ); a { that does
+ *  not begin a valid bound; an unescaped ] or } outside a set or a bound; everything ZraHipCheckPatternExpr refuses in an atom.
+ *  Reason 1: more than 64 expressions, an expression of 0 bytes, more than ZRA_HIP_PATTERN_MAX_EXPR_BYTES bytes, more than
+ *  ZRA_HIP_REGEX_MAX_POSITIONS positions. A position is an atom or an anchor; x* x+ x? count as x, x{n,m} as m times x, x{n,} as
+ *  max(n, 1) times x. Syntax is checked for every expression before the positions are counted.
+ *  Meaning. BOL and EOL are two symbols that no atom admits; ^ reads BOL and $ reads EOL. With S = any byte but the delimiter, BOL
+ *  or EOL, a record r is matched iff BOL r EOL is in S* (e_1 | ... | e_K) S*. So ^ holds at the start of a record and $ at its end,
+ *  `^$` and `a*` match the empty record, and an expression that can match nothing (`a^b`, `^^a`) is legal and selects nothing.
+ *  states = the states of the minimal complete DFA over the non-delimiter bytes for the set of matched records, restricted to the
+ *  states reachable from its start (the dead state included if reachable): a defined number. classes = the classes of non-delimiter
+ *  bytes with identical columns in it. The subset construction stops at 4,096 distinct position sets (reason 4), which bounds the
+ *  host's time on `(a|b)*a(a|b){12}`; the limit of 64 states is the width of a wave: a state map is one lane per state and 64 bytes
+ *  in the per-tile tables. */
+ZRA_EXPORT ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+    uint32_t syntax, int delimiter, ZraHipRegexInfo* info);
+
+/** The records of a content range that a regular expression matches. The records and the range [lo, hi) with its inclusive bound and
+ *  size = UINT64_MAX, stagingBytes, the passes, whole frames with verified checksums, "only the frames of the range", `mode`
+ *  (ZRA_HIP_GREP_INVERT only), capacity 0 as `grep -c`, *nRecords above the capacity, "nothing reaches the host before the last
+ *  pass" and the zeroing of outputs and stats on every status but Success: ZraHipGrepArchive's, word for word.
+ *  Selection. A record is selected iff the expression matches somewhere inside the record's bytes (ZraHipCheckRegex, Meaning); with
+ *  INVERT iff it does not. lo and hi cut records the way delimiters do: ^ holds at the start of a record as reported and $ at its
+ *  end as reported, so a clipped record is anchored at the clip.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchive's rule 1 with its pointer and capacity checks; `syntax` with any bit other than ZRA_HIP_PATTERN_FOLD_CASE
+ *      and every refusal of ZraHipCheckRegex -> {ZStdError, 42}. Nothing is decoded.
+ *   2. Header problems: ZraHipGrepArchive's rule 2.
+ *   3. The range: ZraHipGrepArchive's rule 3. The empty range is Success with 0 records, nothing decoded and stats {frames, 0, ...}.
+ *      There is no "shorter than the shortest pattern" shortcut: every non-empty range is scanned.
+ *   4. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the grep's with 112 bytes per 8 KiB of window for the
+ *      per-tile tables: a summary, a head and a 64-byte state map.
+ *   5. A decoded frame that fails: ZraHipGrepArchive's rule 5.
+ *  The call writes ZraHipGetGrepStats and ZraHipDebugGrepScanMs as ZraHipGrepArchiveWhere does. Word 7, matches, is the number of
+ *  records of the range that the expression matches, before INVERT: with INVERT, selected = records - matches.
+ *  Cost: one dependent table step per byte. A record inside a tile is one lane's walk; the bytes in front of a tile's first
+ *  delimiter are stepped for all 64 states at once by one wave. Content without delimiters makes every tile one such head: 8,192
+ *  dependent steps per tile on one wave. The cost does not depend on the expression, only on the bytes and on how the delimiters
+ *  fall.
+ *  Not covered: match offsets, leftmost-longest spans, captures; ZraHipExtractRecords and ZraHipGrepArchiveWhere with regular
+ *  expressions; more than ZRA_HIP_REGEX_MAX_STATES states; backreferences, lazy or possessive quantifiers, look-around, word
+ *  boundaries, POSIX classes, UTF-8 awareness; multi-byte delimiters, context lines, shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipGrepArchiveRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+/** ZraHipGrepArchiveRegex through a ZraHipArchive handle: resident frames are staged from the cache as for ZraHipArchiveGrep, the
+ *  cache is not changed, and the handle's scan counters (ZraHipArchiveGetScanStats) move as for ZraHipArchiveGrepWhere. */
+ZRA_EXPORT ZraStatus ZraHipArchiveGrepRegex(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
     uint64_t offset, uint64_t size, size_t stagingBytes,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
 

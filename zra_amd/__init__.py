@@ -209,6 +209,10 @@ def load():
         "ZraHipCheckRecordClauses": (S, [vp, sz, sz]),
         "ZraHipGrepArchiveWhere": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipArchiveGrepWhere": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        # the grep with regular expressions: the syntax word behind nPatterns; ZraHipRegexInfo is five 32-bit words
+        "ZraHipCheckRegex": (S, [vp, ctypes.POINTER(u32), sz, u32, ctypes.c_int, ctypes.POINTER(u32)]),
+        "ZraHipGrepArchiveRegex": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        "ZraHipArchiveGrepRegex": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -292,6 +296,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCheckPatternExpr", "ZraHipSearchArchiveMultiExpr", "ZraHipGrepArchiveExpr", "ZraHipExtractRecordsExpr",
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
                    "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere",
+                   "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -577,6 +582,23 @@ class Engine:
         _chk(fn(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter,
                 GREP_INVERT if invert else 0, *wx, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
                 max_records, ctypes.byref(n)), fn.__name__)
+        k = min(n.value, max_records)
+        return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_regex(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0,
+                   max_records=1 << 20):
+        """ZraHipGrepArchiveRegex: grep()'s records of the range that one of `patterns` matches: POSIX extended regular expressions
+        over bytes (check_regex), alternatives as with grep -e A -e B; invert: the records none matches; fold_case: grep -i. Returns
+        (n_records, [(offset, size)]) as grep() does and writes grep_stats(), whose `matches` is the number of matched records.
+        ZraError is a call that could not grep."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n = ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipGrepArchiveRegex(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), PATTERN_FOLD_CASE if fold_case else 0,
+                                           delimiter, GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                                           max_records, ctypes.byref(n)), "ZraHipGrepArchiveRegex")
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
 
@@ -910,6 +932,24 @@ def check_record_clauses(where, n_patterns):
     clause list."""
     arr, k = _clauses(where)
     _chk(load().ZraHipCheckRecordClauses(arr if k else None, k, n_patterns), "ZraHipCheckRecordClauses")
+REGEX_MAX_STATES = 64                        # ZRA_HIP_REGEX_MAX_STATES
+REGEX_MAX_POSITIONS = 4096                   # ZRA_HIP_REGEX_MAX_POSITIONS
+REGEX_INFO = ("states", "classes", "positions", "why", "pattern")
+
+
+def check_regex(patterns, fold_case=False, delimiter=0x0A):
+    """ZraHipCheckRegex: the expression checks of grep_regex(), on the host alone (no engine, no device). Returns ZraHipRegexInfo as a
+    dict keyed by REGEX_INFO; ZraError is a refused expression list, with the same dict in ZraError.info."""
+    patterns = [bytes(p) for p in patterns]
+    sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+    info = (ctypes.c_uint32 * 5)()
+    st = load().ZraHipCheckRegex(_cbuf(b"".join(patterns)), sizes, len(patterns), PATTERN_FOLD_CASE if fold_case else 0, delimiter, info)
+    d = dict(zip(REGEX_INFO, (int(v) for v in info)))
+    if st.zra != 0:
+        e = ZraError(st.tup(), "ZraHipCheckRegex")
+        e.info = d
+        raise e
+    return d
 EXTRACT_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "packed_bytes", "passes", "matches")
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
@@ -1028,6 +1068,19 @@ class Archive:
         fn, sx, wx = _grep_call(self.L, "ZraHipArchiveGrep", syntax, where)
         _chk(fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, *wx, offset,
                 (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n)), fn.__name__)
+        k = min(n.value, max_records)
+        return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_regex(self, patterns, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20):
+        """ZraHipArchiveGrepRegex: Engine.grep_regex through the handle. Returns (n_records, [(offset, size)])."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n = ctypes.c_uint64(0)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveGrepRegex(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), PATTERN_FOLD_CASE if fold_case else 0, delimiter,
+                                           GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records,
+                                           ctypes.byref(n)), "ZraHipArchiveGrepRegex")
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
 

@@ -303,6 +303,16 @@ Status ArchiveCache::grep_where(const void* hPatterns, const uint32_t* hPatternS
   }), v);
 }
 
+Status ArchiveCache::grep_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode,
+                                uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
+  Engine& E = *e_;
+  ScanCacheView v = scan_view();
+  return scanned(ScanImpl::call(E, kScanGrep, nRecords, nullptr, [&] {
+    return ScanImpl::grep_regex(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords,
+                                recordCap, nRecords, &v);
+  }), v);
+}
+
 Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
                              uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                              uint64_t* dataSize) {

@@ -10,6 +10,7 @@
 #include "zra_env.h"
 #include "zra_pattern_expr.h"
 #include "zra_where.h"
+#include "zra_regex.h"
 
 #include <atomic>
 #include <algorithm>
@@ -959,6 +960,31 @@ ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive, const void* hPatterns, 
   if (!archive) return mk(ZStdError, 42);
   return mk(archive->c->grep_where(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset, size, stagingBytes, (uint64_t*)hRecords,
                                    recordCapacity, nRecords));
+}
+// ---- the grep with regular expressions: the compiler is zra_regex.h's, the kernels zra_grep_regex.hip's; the grep's stats row and milliseconds
+ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, int delimiter, ZraHipRegexInfo* info) {
+  static_assert(sizeof(ZraHipRegexInfo) == sizeof(zra_regex::Info) && ZRA_HIP_REGEX_MAX_STATES == zra_regex::kMaxStates &&
+                ZRA_HIP_REGEX_MAX_POSITIONS == zra_regex::kMaxPositions, "one info layout");
+  zra_regex::Compiled C;
+  const bool good = zra_regex::compile((const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, &C);
+  if (info) std::memcpy(info, &C.info, sizeof(*info));
+  return good ? mk(Success, 0) : mk(ZStdError, 42);
+}
+ZraStatus ZraHipGrepArchiveRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                                 uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
+                                 size_t recordCapacity, uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->grep_archive_regex((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                          (uint64_t*)hRecords, recordCapacity, nRecords));
+}
+ZraStatus ZraHipArchiveGrepRegex(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                 uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity,
+                                 uint64_t* nRecords) {
+  if (nRecords) *nRecords = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->grep_regex(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
+                                   nRecords));
 }
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {

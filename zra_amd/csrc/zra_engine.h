@@ -250,6 +250,12 @@ class Engine {
   Status grep_archive_where(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
                             uint8_t delimiter, uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
                             uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
+  // grep_archive with regular expressions (zra_grep_regex.hip, zra_regex.h): a record is selected when the automaton of the nPatterns
+  // expressions (alternatives; syntax: 0 or fold case) matches inside it; mode 1 complements that. Kernels of its own; it writes
+  // grep_archive's counters and milliseconds. Statuses and their order: zra_hip.h, ZraHipGrepArchiveRegex.
+  Status grep_archive_regex(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+                            uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap,
+                            uint64_t* nRecords);
 
   // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
   // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:

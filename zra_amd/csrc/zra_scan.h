@@ -56,6 +56,10 @@ struct ScanImpl {
   static Status grep_where(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
                            uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords,
                            size_t recordCap, uint64_t* nRecords, ScanCacheView* cv = nullptr);
+  // the grep with regular expressions (zra_grep_regex.hip): hPat = nPat expressions, alternatives (zra_regex.h)
+  static Status grep_regex(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
+                           uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
+                           ScanCacheView* cv = nullptr);
   static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
                         uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                         uint64_t* dataSize, ScanCacheView* cv = nullptr);

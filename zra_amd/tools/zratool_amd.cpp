@@ -25,6 +25,9 @@
 //         must occur in the record), ?i (one of the ?-patterns must), -i (pattern i must not), i = the pattern's position on the command
 //         line from 0; a record is selected when some clause holds, -v complements that. Output and exit status of gl; a refused
 //         clause is exit status 2
+//   glr : gl with regular expressions (ZraHipGrepArchiveRegex): POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on top of
+//         gle's atoms (zra_hip.h: ZraHipCheckRegex); several expressions are alternatives; -i: ASCII letters match either case, -v, -d as
+//         gl; -c: only the count. Output and exit status of gl; a refused expression is exit status 2 with the reason and its index
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
@@ -317,6 +320,39 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   return total ? 0 : 1;
 }
 
+// mode glr: the expressions texts[0 .. n), alternatives
+int grep_archive_regex(const char* path, bool invert, bool fold, bool countOnly, uint8_t delimiter, char** texts, int n) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  for (int i = 0; i < n; i++) { all += texts[i]; sizes.push_back((uint32_t)std::strlen(texts[i])); }
+  const uint32_t syntax = fold ? ZRA_HIP_PATTERN_FOLD_CASE : 0u;
+  ZraHipRegexInfo info;
+  if (ZraHipCheckRegex(all.data(), sizes.data(), sizes.size(), syntax, delimiter, &info).zra != Success) {
+    static const char* const why[] = {"", "1 to 64 expressions of 1 byte or more, 16384 bytes and 4096 positions in all", "not a regular expression",
+                                      "an atom matches only the delimiter", "more than 64 states"};
+    if (info.why == 2 || info.why == 3) std::fprintf(stderr, "expression %u: %s\n", info.pattern, why[info.why]);
+    else std::fprintf(stderr, "%s\n", why[info.why <= 4 ? info.why : 1]);
+    return 2;
+  }
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  std::vector<ZraHipContentRange> at(countOnly ? 0 : 1u << 20);
+  uint64_t total = 0;
+  st = ZraHipGrepArchiveRegex(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, invert ? ZRA_HIP_GREP_INVERT : 0u, 0, UINT64_MAX, 0,
+                              countOnly ? nullptr : at.data(), at.size(), &total);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot grep: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(total, at.size()); i++) std::printf("%llu\t%llu\n", (unsigned long long)at[i].offset, (unsigned long long)at[i].size);
+  if (!countOnly && total > at.size()) std::printf("... and %llu more\n", (unsigned long long)(total - at.size()));
+  std::printf("%llu records\n", (unsigned long long)total);
+  return total ? 0 : 1;
+}
+
 // modes gx and (ex) gxe: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to stdout when it is
 // null. Nothing is written when a call fails or when nothing is selected.
 int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex) {
@@ -555,6 +591,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gme {file} {-i} {-F} {expression | hex:digits}...
 //       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
 //       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
+//       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
@@ -576,6 +613,7 @@ int main(int argc, char** argv) {
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
                 "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
+                "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}... - gl with regular expressions: POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on gle's atoms, several expressions are alternatives; -c: only the count (a refused expression: exit status 2)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -640,6 +678,24 @@ int main(int argc, char** argv) {
     if (pred) return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, &ex, &where);
     if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, expr ? &ex : nullptr);
     return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, expr ? &ex : nullptr);
+  }
+  if (mode == "glr") {
+    bool invert = false, fold = false, countOnly = false;
+    unsigned long delimiter = 0x0A;
+    int i = 3;
+    for (; i < argc; i++) {
+      const std::string opt = argv[i];
+      if (opt == "-v") invert = true;
+      else if (opt == "-i") fold = true;
+      else if (opt == "-c") countOnly = true;
+      else if (opt == "-d") {
+        char* end = nullptr;
+        if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
+        if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
+      } else break;
+    }
+    if (i >= argc) { std::fprintf(stderr, "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...\n"); return 2; }
+    return grep_archive_regex(argv[2], invert, fold, countOnly, (uint8_t)delimiter, argv + i, argc - i);
   }
   if (mode == "cmp") {
     if (argc < 4) { std::fprintf(stderr, "cmp {file A} {file B}\n"); return 2; }
