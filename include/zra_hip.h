@@ -821,8 +821,8 @@ ZRA_EXPORT ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPa
  *  delimiter are stepped for all 64 states at once by one wave. Content without delimiters makes every tile one such head: 8,192
  *  dependent steps per tile on one wave. The cost does not depend on the expression, only on the bytes and on how the delimiters
  *  fall.
- *  Not covered: match offsets, leftmost-longest spans, captures; ZraHipExtractRecords and ZraHipGrepArchiveWhere with regular
- *  expressions; more than ZRA_HIP_REGEX_MAX_STATES states; backreferences, lazy or possessive quantifiers, look-around, word
+ *  Not covered: match offsets, leftmost-longest spans, captures; ZraHipGrepArchiveWhere with regular expressions (the selected
+ *  records' bytes: ZraHipExtractRecordsRegex, below); more than ZRA_HIP_REGEX_MAX_STATES states; backreferences, lazy or possessive quantifiers, look-around, word
  *  boundaries, POSIX classes, UTF-8 awareness; multi-byte delimiters, context lines, shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchiveRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
@@ -836,6 +836,53 @@ ZRA_EXPORT ZraStatus ZraHipArchiveGrepRegex(ZraHipArchive* archive,
     uint8_t delimiter, uint32_t mode,
     uint64_t offset, uint64_t size, size_t stagingBytes,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+
+/** The records ZraHipGrepArchiveRegex selects WITH their bytes, packed: the text `grep -E` (with INVERT: `grep -E -v`) prints, from
+ *  the one decode pass that selects the records. The meaning is the composition of two contracts, word for word.
+ *  Selection: ZraHipGrepArchiveRegex's. 1 .. 64 expressions are alternatives, `syntax` is 0 or ZRA_HIP_PATTERN_FOLD_CASE, lo and hi
+ *  cut records the way delimiters do (^ and $ hold at a clip), `mode` is ZRA_HIP_GREP_INVERT only, and every non-empty range is
+ *  scanned.
+ *  Result: ZraHipExtractRecords's. *nRecords = the selected records; *dataSize = the sum of (n_i + 1) over them; dData (device
+ *  memory) receives each selected record's bytes followed by one `delimiter` byte, in ascending order, the last record, which hi
+ *  ends, included. The list goes to hRecords once, after the last pass, and only when recordCapacity != 0. The bytes of dData in
+ *  [*dataSize, dataCapacity) are undefined after Success (a record open at the end of a pass is copied before its selection is
+ *  known); no byte outside [dData, dData + dataCapacity) is ever written, whatever the outcome.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchiveRegex's rule 1 (every refusal of ZraHipCheckRegex, every foreign `syntax` bit); dataSize NULL; hRecords
+ *      NULL with recordCapacity != 0; dData NULL with dataCapacity != 0 -> {ZStdError, 42}. Nothing is decoded.
+ *   2. dData overlaps the archive (through a handle: or the handle's arena) -> {ZStdError, 42}.
+ *   3. Header problems: ZraHipGrepArchive's rule 2.
+ *   4. The range: ZraHipGrepArchive's rule 3. The empty range is Success with 0 records and 0 bytes, nothing decoded and stats
+ *      {frames, 0, ...}.
+ *   5. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the regex grep's with 128 bytes per 8 KiB of window.
+ *   6. A decoded frame that fails: ZraHipGrepArchive's rule 5.
+ *   7. OutputBufferTooSmall: ZraHipExtractRecords's rule 7, word for word: *nRecords and *dataSize then hold what the call needs,
+ *      hRecords is not written. recordCapacity 0 and dataCapacity 0 make the sizing call, which launches no copy kernel.
+ *  Zeroing of the outputs and the stats on every other status: ZraHipExtractRecords's rules.
+ *  The call writes ZraHipGetExtractStats and ZraHipDebugExtractMs as ZraHipExtractRecordsExpr does; word 7, matches, is
+ *  ZraHipGrepArchiveRegex's: the records of the range that the expression matches, before INVERT. The grep's and the searches' stats
+ *  are left alone.
+ *  Cost: ZraHipGrepArchiveRegex's, plus a second walk of the tiles that hold a copied byte: measured on 1 GiB of log lines, the
+ *  call's launches take 1.10 to 1.63 times the regex grep's scan, and the call 0.68 to 0.78 of the wall time of the regex grep
+ *  followed by a ZraHipDecompressRABatch of the listed ranges (profiles/extract_regex.md).
+ *  Not covered: ZraHipGrepArchiveWhere with bytes or with regular expressions; match offsets, spans, captures; more than
+ *  ZRA_HIP_REGEX_MAX_STATES states; context lines, output without delimiter bytes; multi-byte delimiters, shards, the host-pointer
+ *  API. */
+ZRA_EXPORT ZraStatus ZraHipExtractRecordsRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** ZraHipExtractRecordsRegex through a ZraHipArchive handle: resident frames are staged from the cache as for
+ *  ZraHipArchiveExtractRecords, the cache is not changed, dData must overlap neither the archive nor the handle's arena (rule 2),
+ *  and the handle's scan counters (ZraHipArchiveGetScanStats) move as for ZraHipArchiveExtractRecords. */
+ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecordsRegex(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
 
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte

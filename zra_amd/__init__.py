@@ -213,6 +213,11 @@ def load():
         "ZraHipCheckRegex": (S, [vp, ctypes.POINTER(u32), sz, u32, ctypes.c_int, ctypes.POINTER(u32)]),
         "ZraHipGrepArchiveRegex": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipArchiveGrepRegex": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        # the extract with regular expressions: ZraHipExtractRecordsExpr's arguments
+        "ZraHipExtractRecordsRegex": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp,
+                                          sz, u64p]),
+        "ZraHipArchiveExtractRecordsRegex": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz,
+                                                 u64p]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -297,6 +302,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
                    "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere",
                    "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
+                   "ZraHipExtractRecordsRegex", "ZraHipArchiveExtractRecordsRegex",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -631,6 +637,26 @@ class Engine:
                 max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
         if st.zra != 0:
             e = ZraError(st.tup(), fn.__name__)
+            e.needed_records, e.needed_data = n.value, ds.value
+            raise e
+        k = n.value if max_records else 0
+        return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def extract_regex(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None,
+                      staging_bytes=0, max_records=0):
+        """ZraHipExtractRecordsRegex: grep_regex()'s selected records with their bytes, packed at d_data as extract() packs them: the
+        text `grep -E` prints, from one decode pass. Returns what extract() returns and writes extract_stats(), whose `matches` is the
+        number of matched records; OutputBufferTooSmall carries ZraError.needed_records and ZraError.needed_data."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._order()
+        st = self.L.ZraHipExtractRecordsRegex(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), PATTERN_FOLD_CASE if fold_case else 0,
+                                              delimiter, GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                                              max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipExtractRecordsRegex")
             e.needed_records, e.needed_data = n.value, ds.value
             raise e
         k = n.value if max_records else 0
@@ -1098,6 +1124,24 @@ class Archive:
                 d_data or None, data_cap, ctypes.byref(ds))
         if st.zra != 0:
             e = ZraError(st.tup(), fn.__name__)
+            e.needed_records, e.needed_data = n.value, ds.value
+            raise e
+        k = n.value if max_records else 0
+        return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def extract_regex(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0, max_records=0):
+        """ZraHipArchiveExtractRecordsRegex: Engine.extract_regex through the handle; d_data must overlap neither the archive nor the cache. Returns
+        (n_records, data_size, [(offset, size)]); OutputBufferTooSmall carries ZraError.needed_records and ZraError.needed_data."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._order()
+        st = self.L.ZraHipArchiveExtractRecordsRegex(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), PATTERN_FOLD_CASE if fold_case else 0, delimiter,
+                                                     GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                                                     max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
+        if st.zra != 0:
+            e = ZraError(st.tup(), "ZraHipArchiveExtractRecordsRegex")
             e.needed_records, e.needed_data = n.value, ds.value
             raise e
         k = n.value if max_records else 0

@@ -42,6 +42,8 @@ class ArchiveCache {
                     uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
   Status extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
                  size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+  Status extract_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
+                       uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
   // {scans accepted, frames staged from the cache (last accepted scan), frames decoded (last), passes (last), staged (cumulative),
   // decoded (cumulative), 0, 0}
   void scan_stats(uint64_t out[8]) const;

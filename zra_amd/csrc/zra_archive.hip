@@ -324,6 +324,17 @@ Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSize
   }), v);
 }
 
+Status ArchiveCache::extract_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
+                                   uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
+                                   uint64_t* dataSize) {
+  Engine& E = *e_;
+  ScanCacheView v = scan_view();
+  return scanned(ScanImpl::call(E, kScanExtract, nRecords, dataSize, [&] {
+    return ScanImpl::extract_regex(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords,
+                                   recordCap, nRecords, dData, dataCap, dataSize, &v);
+  }), v);
+}
+
 // ---- the record calls through the handle. Index and locate are not reads, like the scans above: their sweeps read the arena and slotOf
 // and write neither. The read's byte fetch is a read of the handle, through read() itself: reads / hits / misses / evictions / resident
 // move exactly as for ZraHipArchiveRead of the located ranges. The call is one of its kind on the handle's engine.

@@ -986,6 +986,26 @@ ZraStatus ZraHipArchiveGrepRegex(ZraHipArchive* archive, const void* hPatterns, 
   return mk(archive->c->grep_regex(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
                                    nRecords));
 }
+// ---- the extract with regular expressions: the regex grep's compiler, kernels of its own (zra_extract_regex.hip); the extract's stats row and
+// milliseconds
+ZraStatus ZraHipExtractRecordsRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes,
+                                    size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes,
+                                    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->extract_records_regex((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size,
+                                             stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+}
+ZraStatus ZraHipArchiveExtractRecordsRegex(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+                                           uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
+                                           size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->extract_regex(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
+                                      nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+}
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {
   static_assert(sizeof(ZraHipContentRange) == 16, "two 64-bit words per range");

@@ -268,6 +268,12 @@ class Engine {
   void extract_stats(uint64_t out[8]) const { call_stats(kScanExtract, out); }
   // bring-up: HIP-event time of the last extract's own launches (count, scan, copy, carry), summed over its passes
   double extract_ms() const { return callMs_[kScanExtract]; }
+  // extract_records with regular expressions (zra_extract_regex.hip, zra_regex.h): grep_archive_regex's selection, extract_records'
+  // outputs, in one pass. Kernels of its own; it writes extract_records' counters (word 7: the matched records before the mode) and
+  // milliseconds. Statuses and their order: zra_hip.h, ZraHipExtractRecordsRegex.
+  Status extract_records_regex(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+                               uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap,
+                               uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
 
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are

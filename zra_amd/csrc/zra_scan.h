@@ -63,6 +63,10 @@ struct ScanImpl {
   static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
                         uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
                         uint64_t* dataSize, ScanCacheView* cv = nullptr);
+  // the extract with regular expressions (zra_extract_regex.hip): grep_regex's selection, extract's outputs
+  static Status extract_regex(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
+                              uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData,
+                              size_t dataCap, uint64_t* dataSize, ScanCacheView* cv = nullptr);
 
   // What a call of the family leaves behind: entry_call's rule (zra_host.h). `which`: kScanSearch .. kScanExtract; out0 / out1: the
   // call's output words (either may be nullptr), kept on OutputTooSmall (the extract's rule 7, whose two words say what the call needs).

@@ -28,6 +28,8 @@
 //   glr : gl with regular expressions (ZraHipGrepArchiveRegex): POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on top of
 //         gle's atoms (zra_hip.h: ZraHipCheckRegex); several expressions are alternatives; -i: ASCII letters match either case, -v, -d as
 //         gl; -c: only the count. Output and exit status of gl; a refused expression is exit status 2 with the reason and its index
+//   gxr : gx with glr's regular expressions (ZraHipExtractRecordsRegex): the text `grep -E` prints; -i, -v, -d as glr, -o as gx. Output
+//         and exit status of gx; a refused expression as glr
 //   cmp : compare the contents of two archives like `cmp` (ZraHipCompareArchives, on the device); one line `offset size` per differing
 //         range (the first 2^20; the summary counts all) and a summary; exit status as cmp: 0 equal content and equal length, 1 different, 2 trouble
 //   diff: the patch that turns the content of archive A into that of archive B (ZraHipDiffArchives, on the device); one line `offset size`
@@ -182,6 +184,7 @@ bool parse_pattern(const char* text, std::string* out) {
 
 // The modes with pattern expressions (gme, gle, gxe): -i and -F. Null for gm, gl and gx.
 struct ExprOpt { bool fold, fixed; };
+struct RegexOpt { bool fold; };                                                // gxr: the patterns are regular expressions
 
 // The patterns texts[0 .. n) of a multi-pattern mode laid end to end, their sizes and the calls' syntax word. delimiter: gl's and gx's,
 // -1 for gm. Without ex the patterns are literal (syntax 0). With ex a pattern is an expression unless -F was given; a "hex:" pattern
@@ -320,20 +323,25 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   return total ? 0 : 1;
 }
 
-// mode glr: the expressions texts[0 .. n), alternatives
+// glr's and gxr's expressions texts[0 .. n), alternatives: laid end to end and checked on the host
+bool gather_regex(char** texts, int n, bool fold, uint8_t delimiter, std::string* all, std::vector<uint32_t>* sizes, uint32_t* syntax) {
+  for (int i = 0; i < n; i++) { *all += texts[i]; sizes->push_back((uint32_t)std::strlen(texts[i])); }
+  *syntax = fold ? ZRA_HIP_PATTERN_FOLD_CASE : 0u;
+  ZraHipRegexInfo info;
+  if (ZraHipCheckRegex(all->data(), sizes->data(), sizes->size(), *syntax, delimiter, &info).zra == Success) return true;
+  static const char* const why[] = {"", "1 to 64 expressions of 1 byte or more, 16384 bytes and 4096 positions in all", "not a regular expression",
+                                    "an atom matches only the delimiter", "more than 64 states"};
+  if (info.why == 2 || info.why == 3) std::fprintf(stderr, "expression %u: %s\n", info.pattern, why[info.why]);
+  else std::fprintf(stderr, "%s\n", why[info.why <= 4 ? info.why : 1]);
+  return false;
+}
+
+// mode glr
 int grep_archive_regex(const char* path, bool invert, bool fold, bool countOnly, uint8_t delimiter, char** texts, int n) {
   std::string all;
   std::vector<uint32_t> sizes;
-  for (int i = 0; i < n; i++) { all += texts[i]; sizes.push_back((uint32_t)std::strlen(texts[i])); }
-  const uint32_t syntax = fold ? ZRA_HIP_PATTERN_FOLD_CASE : 0u;
-  ZraHipRegexInfo info;
-  if (ZraHipCheckRegex(all.data(), sizes.data(), sizes.size(), syntax, delimiter, &info).zra != Success) {
-    static const char* const why[] = {"", "1 to 64 expressions of 1 byte or more, 16384 bytes and 4096 positions in all", "not a regular expression",
-                                      "an atom matches only the delimiter", "more than 64 states"};
-    if (info.why == 2 || info.why == 3) std::fprintf(stderr, "expression %u: %s\n", info.pattern, why[info.why]);
-    else std::fprintf(stderr, "%s\n", why[info.why <= 4 ? info.why : 1]);
-    return 2;
-  }
+  uint32_t syntax = 0;
+  if (!gather_regex(texts, n, fold, delimiter, &all, &sizes, &syntax)) return 2;
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -353,13 +361,13 @@ int grep_archive_regex(const char* path, bool invert, bool fold, bool countOnly,
   return total ? 0 : 1;
 }
 
-// modes gx and (ex) gxe: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to stdout when it is
-// null. Nothing is written when a call fails or when nothing is selected.
-int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex) {
+// modes gx, (ex) gxe and (rx) gxr: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to
+// stdout when it is null. Nothing is written when a call fails or when nothing is selected.
+int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex, const RegexOpt* rx = nullptr) {
   std::string all;
   std::vector<uint32_t> sizes;
   uint32_t syntax = 0;
-  if (!gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
+  if (rx ? !gather_regex(texts, n, rx->fold, delimiter, &all, &sizes, &syntax) : !gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -370,6 +378,9 @@ int extract_records(const char* path, bool invert, uint8_t delimiter, const char
   uint64_t total = 0, bytes = 0;
   std::string text;
   auto extract = [&](void* dOut, size_t cap) {
+    if (rx)
+      return ZraHipExtractRecordsRegex(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dOut,
+                                       cap, &bytes);
     return ex ? ZraHipExtractRecordsExpr(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dOut,
                                          cap, &bytes)
               : ZraHipExtractRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dOut, cap, &bytes);
@@ -592,6 +603,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
 //       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
 //       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
+//       gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
@@ -614,6 +626,7 @@ int main(int argc, char** argv) {
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
                 "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
                 "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}... - gl with regular expressions: POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on gle's atoms, several expressions are alternatives; -c: only the count (a refused expression: exit status 2)\n"
+                "gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}... - gx with glr's regular expressions: the text of the records glr lists, each with its delimiter, to stdout or to a file (exit status as glr)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -679,22 +692,29 @@ int main(int argc, char** argv) {
     if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, expr ? &ex : nullptr);
     return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, expr ? &ex : nullptr);
   }
-  if (mode == "glr") {
+  if (mode == "glr" || mode == "gxr") {
+    const bool text = mode == "gxr";
     bool invert = false, fold = false, countOnly = false;
     unsigned long delimiter = 0x0A;
+    const char* outPath = nullptr;
     int i = 3;
     for (; i < argc; i++) {
       const std::string opt = argv[i];
       if (opt == "-v") invert = true;
       else if (opt == "-i") fold = true;
-      else if (opt == "-c") countOnly = true;
-      else if (opt == "-d") {
+      else if (!text && opt == "-c") countOnly = true;
+      else if (text && opt == "-o") {
+        if (++i >= argc || !*argv[i]) { std::fprintf(stderr, "-o takes a file name\n"); return 2; }
+        outPath = argv[i];
+      } else if (opt == "-d") {
         char* end = nullptr;
         if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
         if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
       } else break;
     }
-    if (i >= argc) { std::fprintf(stderr, "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...\n"); return 2; }
+    if (i >= argc) { std::fprintf(stderr, "%s {file} {-i} {-v} %s{-d hex byte = 0a} {expression}...\n", mode.c_str(), text ? "{-o file} " : "{-c} "); return 2; }
+    const RegexOpt rx = {fold};
+    if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, nullptr, &rx);
     return grep_archive_regex(argv[2], invert, fold, countOnly, (uint8_t)delimiter, argv + i, argc - i);
   }
   if (mode == "cmp") {
