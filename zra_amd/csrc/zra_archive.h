@@ -34,16 +34,8 @@ class ArchiveCache {
   Status search(const void* hPattern, size_t patternSize, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hMatches, size_t matchCap, uint64_t* nMatches);
   Status search_multi(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset, uint64_t size, size_t stagingBytes, void* hMatches,
                       size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern);
-  Status grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
-              size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-  Status grep_where(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, const void* hClauses,
-                    size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-  Status grep_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
-                    uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-  Status extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
-                 size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
-  Status extract_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
-                       uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
+  // Engine::record_scan of c with the handle's archive in place of c.dArc / c.arcSize: the five record scans
+  Status record_scan(RecordCall c);
   // {scans accepted, frames staged from the cache (last accepted scan), frames decoded (last), passes (last), staged (cumulative),
   // decoded (cumulative), 0, 0}
   void scan_stats(uint64_t out[8]) const;

@@ -282,57 +282,10 @@ Status ArchiveCache::search_multi(const void* hPatterns, const uint32_t* hPatter
   }), v);
 }
 
-Status ArchiveCache::grep(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size,
-                          size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
-  Engine& E = *e_;
+Status ArchiveCache::record_scan(RecordCall c) {
   ScanCacheView v = scan_view();
-  return scanned(ScanImpl::call(E, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords, recordCap,
-                          nRecords, &v);
-  }), v);
-}
-
-Status ArchiveCache::grep_where(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode,
-                                const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap,
-                                uint64_t* nRecords) {
-  Engine& E = *e_;
-  ScanCacheView v = scan_view();
-  return scanned(ScanImpl::call(E, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep_where(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset, size,
-                                stagingBytes, hRecords, recordCap, nRecords, &v);
-  }), v);
-}
-
-Status ArchiveCache::grep_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode,
-                                uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
-  Engine& E = *e_;
-  ScanCacheView v = scan_view();
-  return scanned(ScanImpl::call(E, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep_regex(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords,
-                                recordCap, nRecords, &v);
-  }), v);
-}
-
-Status ArchiveCache::extract(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
-                             uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                             uint64_t* dataSize) {
-  Engine& E = *e_;
-  ScanCacheView v = scan_view();
-  return scanned(ScanImpl::call(E, kScanExtract, nRecords, dataSize, [&] {
-    return ScanImpl::extract(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords,
-                             recordCap, nRecords, dData, dataCap, dataSize, &v);
-  }), v);
-}
-
-Status ArchiveCache::extract_regex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset,
-                                   uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                                   uint64_t* dataSize) {
-  Engine& E = *e_;
-  ScanCacheView v = scan_view();
-  return scanned(ScanImpl::call(E, kScanExtract, nRecords, dataSize, [&] {
-    return ScanImpl::extract_regex(E, dArc_, arcSize_, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, hRecords,
-                                   recordCap, nRecords, dData, dataCap, dataSize, &v);
-  }), v);
+  c.dArc = dArc_; c.arcSize = arcSize_;
+  return scanned(e_->record_scan(c, &v), v);
 }
 
 // ---- the record calls through the handle. Index and locate are not reads, like the scans above: their sweeps read the arena and slotOf

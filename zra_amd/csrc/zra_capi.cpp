@@ -6,6 +6,7 @@
 #include "zra_hip.h"
 #include "zra_engine.h"
 #include "zra_archive.h"
+#include "zra_scan.h"
 #include "zra_format.h"
 #include "zra_env.h"
 #include "zra_pattern_expr.h"
@@ -21,6 +22,7 @@
 #include <vector>
 
 using zra_eng::Engine;
+using zra_eng::kRecGrep, zra_eng::kRecGrepWhere, zra_eng::kRecGrepRegex, zra_eng::kRecExtract, zra_eng::kRecExtractRegex;   // the record scans' entry points fill a RecordCall
 namespace fmt = zra_fmt;
 
 namespace {
@@ -763,7 +765,8 @@ ZraStatus ZraHipArchiveGrep(ZraHipArchive* archive, const void* hPatterns, const
                             uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->grep(hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(archive->c->record_scan({kRecGrep, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords}));
 }
 ZraStatus ZraHipArchiveExtractRecords(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint8_t delimiter,
                                       uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity,
@@ -771,8 +774,8 @@ ZraStatus ZraHipArchiveExtractRecords(ZraHipArchive* archive, const void* hPatte
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords,
-                                (uint8_t*)dData, dataCapacity, dataSize));
+  return mk(archive->c->record_scan({kRecExtract, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize}));
 }
 void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t* out8) {
   if (!out8) return;
@@ -859,8 +862,8 @@ ZraStatus ZraHipGrepArchive(ZraHipEngine* engine, const void* dArchive, size_t a
                             size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->grep_archive((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
-                                    (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(engine->e->record_scan({kRecGrep, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords}));
 }
 void ZraHipGetGrepStats(ZraHipEngine* engine, uint64_t* out8) {
   if (!out8) return;
@@ -873,8 +876,8 @@ ZraStatus ZraHipExtractRecords(ZraHipEngine* engine, const void* dArchive, size_
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->extract_records((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
-                                       (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+  return mk(engine->e->record_scan({kRecExtract, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, 0, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize}));
 }
 void ZraHipGetExtractStats(ZraHipEngine* engine, uint64_t* out8) {
   if (!out8) return;
@@ -905,8 +908,8 @@ ZraStatus ZraHipGrepArchiveExpr(ZraHipEngine* engine, const void* dArchive, size
                                 size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->grep_archive((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
-                                    (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(engine->e->record_scan({kRecGrep, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords}));
 }
 ZraStatus ZraHipExtractRecordsExpr(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes,
                                    size_t nPatterns, uint32_t syntax, uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes,
@@ -914,8 +917,8 @@ ZraStatus ZraHipExtractRecordsExpr(ZraHipEngine* engine, const void* dArchive, s
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->extract_records((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size,
-                                       stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+  return mk(engine->e->record_scan({kRecExtract, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize}));
 }
 ZraStatus ZraHipArchiveSearchMultiExpr(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint64_t offset,
                                        uint64_t size, size_t stagingBytes, ZraHipPatternMatch* hMatches, size_t matchCapacity, uint64_t* nMatches,
@@ -929,7 +932,8 @@ ZraStatus ZraHipArchiveGrepExpr(ZraHipArchive* archive, const void* hPatterns, c
                                 uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->grep(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(archive->c->record_scan({kRecGrep, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords}));
 }
 ZraStatus ZraHipArchiveExtractRecordsExpr(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
                                           uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
@@ -937,8 +941,8 @@ ZraStatus ZraHipArchiveExtractRecordsExpr(ZraHipArchive* archive, const void* hP
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->extract(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
-                                nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+  return mk(archive->c->record_scan({kRecExtract, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize}));
 }
 // ---- the grep with a record predicate: kernels of its own (zra_grep_where.hip), the grep's stats row and milliseconds
 ZraStatus ZraHipCheckRecordClauses(const ZraHipRecordClause* hClauses, size_t nClauses, size_t nPatterns) {
@@ -950,16 +954,16 @@ ZraStatus ZraHipGrepArchiveWhere(ZraHipEngine* engine, const void* dArchive, siz
                                  size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->grep_archive_where((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset,
-                                          size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(engine->e->record_scan({kRecGrepWhere, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, nullptr, 0, nullptr, hClauses, nClauses}));
 }
 ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
                                  uint32_t mode, const ZraHipRecordClause* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
                                  ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->grep_where(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset, size, stagingBytes, (uint64_t*)hRecords,
-                                   recordCapacity, nRecords));
+  return mk(archive->c->record_scan({kRecGrepWhere, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, nullptr, 0, nullptr, hClauses, nClauses}));
 }
 // ---- the grep with regular expressions: the compiler is zra_regex.h's, the kernels zra_grep_regex.hip's; the grep's stats row and milliseconds
 ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, int delimiter, ZraHipRegexInfo* info) {
@@ -975,16 +979,16 @@ ZraStatus ZraHipGrepArchiveRegex(ZraHipEngine* engine, const void* dArchive, siz
                                  size_t recordCapacity, uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->grep_archive_regex((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
-                                          (uint64_t*)hRecords, recordCapacity, nRecords));
+  return mk(engine->e->record_scan({kRecGrepRegex, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords}));
 }
 ZraStatus ZraHipArchiveGrepRegex(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
                                  uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity,
                                  uint64_t* nRecords) {
   if (nRecords) *nRecords = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->grep_regex(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
-                                   nRecords));
+  return mk(archive->c->record_scan({kRecGrepRegex, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords}));
 }
 // ---- the extract with regular expressions: the regex grep's compiler, kernels of its own (zra_extract_regex.hip); the extract's stats row and
 // milliseconds
@@ -994,8 +998,8 @@ ZraStatus ZraHipExtractRecordsRegex(ZraHipEngine* engine, const void* dArchive, 
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!engine) return mk(ZStdError, 42);
-  return mk(engine->e->extract_records_regex((const uint8_t*)dArchive, archiveSize, hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size,
-                                             stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+  return mk(engine->e->record_scan({kRecExtractRegex, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize}));
 }
 ZraStatus ZraHipArchiveExtractRecordsRegex(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
                                            uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
@@ -1003,8 +1007,8 @@ ZraStatus ZraHipArchiveExtractRecordsRegex(ZraHipArchive* archive, const void* h
   if (nRecords) *nRecords = 0;
   if (dataSize) *dataSize = 0;
   if (!archive) return mk(ZStdError, 42);
-  return mk(archive->c->extract_regex(hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity,
-                                      nRecords, (uint8_t*)dData, dataCapacity, dataSize));
+  return mk(archive->c->record_scan({kRecExtractRegex, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                    (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize}));
 }
 ZraStatus ZraHipCompareArchives(ZraHipEngine* engine, const void* dA, size_t sizeA, const void* dB, size_t sizeB, uint32_t mode, uint64_t offset, uint64_t size,
                                 size_t stagingBytes, ZraHipContentRange* hRanges, size_t rangeCapacity, uint64_t* nRanges, uint64_t* differingBytes) {

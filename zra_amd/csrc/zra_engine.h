@@ -86,6 +86,35 @@ struct ScanCacheView {
   uint64_t staged = 0, decoded = 0, decodedBytes = 0, passes = 0;
   double stageMs = 0;
 };
+// A record scan (Engine::record_scan, zra_record_scan.h): the arguments the entry points of zra_hip.h share, as the caller gave them.
+// The records of [offset, offset + size), cut at `delimiter`, that the kind selects, ascending, in ONE decode of the range's frames;
+// kind picks what selects a record and the kernels (a file each). Statuses and their order: zra_hip.h, the entry point named.
+enum RecordKind : uint32_t {
+  kRecGrep,          // ZraHipGrepArchive[Expr] (zra_grep.hip): a match of one of the patterns starts in the record. Writes grep_stats / grep_scan_ms
+  kRecGrepWhere,     // ZraHipGrepArchiveWhere (zra_grep_where.hip, zra_where.h): one of the clauses holds for the set of patterns that hit in the
+                     // record. Kernels of its own; writes the grep's counters and milliseconds
+  kRecGrepRegex,     // ZraHipGrepArchiveRegex (zra_grep_regex.hip, zra_regex.h): the automaton of the expressions (alternatives; syntax: 0 or fold
+                     // case) matches inside the record. Kernels of its own; writes the grep's counters (word 7: the matched records) and milliseconds
+  kRecExtract,       // ZraHipExtractRecords[Expr] (zra_extract.hip): kRecGrep's selection with the records' bytes. Writes extract_stats / extract_ms
+  kRecExtractRegex,  // ZraHipExtractRecordsRegex (zra_extract_regex.hip): kRecGrepRegex's selection, kRecExtract's outputs, in one pass. Kernels of
+                     // its own; writes the extract's counters (word 7: the matched records before the mode) and milliseconds
+};
+struct RecordCall {
+  RecordKind kind;
+  const uint8_t* dArc; size_t arcSize;                 // (through a handle: filled in by it)
+  // nPat host patterns laid end to end at hPat, pattern i of hSizes[i] bytes; syntax: the word of the ...Expr, ...Where and ...Regex
+  // entry points, 0 for the literal ones
+  const uint8_t* hPat; const uint32_t* hSizes; size_t nPat; uint32_t syntax;
+  uint8_t delimiter; uint32_t mode;                    // mode 1: the records NOT selected
+  uint64_t offset, size; size_t stagingBytes;          // the range (size ~0: to the end), the staging window
+  uint64_t* hRecords; size_t recordCap; uint64_t* nRecords;   // the list, {offset, size} pairs, ascending
+  // the extracts: each selected record's content and one delimiter byte, packed at dData (device memory); the list goes to hRecords
+  // iff recordCap != 0. *dataSize: the packed bytes
+  uint8_t* dData = nullptr; size_t dataCap = 0; uint64_t* dataSize = nullptr;
+  // kRecGrepWhere: a record is selected when one of the nClauses clauses {all, any, none} (ZraHipRecordClause) holds for the set of
+  // patterns that hit in it
+  const void* hClauses = nullptr; size_t nClauses = 0;
+};
 // The byte fetch of a record read through an archive handle (zra_records.hip): the located ranges as one read of the handle, a query
 // allowed to end AT the content's end. *jobs: the frames the fetch decoded.
 struct RecordFetch {
@@ -234,46 +263,21 @@ class Engine {
   // bring-up: HIP-event time of the last multi search's scan launches (count, scan, fill, carry), summed over its passes
   double search_multi_scan_ms() const { return callMs_[kScanMulti]; }
 
-  // ---- grep (zra_grep.hip): the records of [offset, offset + size) (size ~0: to the end), cut at `delimiter`, in which a match of one
-  // of the nPatterns host patterns starts (mode 1: in which none does), ascending, as {offset, size} pairs in hRecords, in ONE decode of
-  // the range's frames. Patterns, range and passes are search_archive_multi's. Statuses and their order: zra_hip.h, ZraHipGrepArchive.
-  Status grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
-                      uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-  // the last grep_archive: {frames, decoded, content bytes regenerated, records of the range, records selected, records listed, passes,
-  // matches}; all zero unless it succeeded. The searches and the grep leave each other's counters alone
+  // ---- the record scans (zra_record_scan.h): grep, grep with a record predicate, grep with regular expressions, extract, extract with
+  // regular expressions, by c.kind; one decode of the range's frames. Patterns, range and passes are search_archive_multi's. Statuses
+  // and their order: zra_hip.h, the entry point of the kind. cv: the call goes through an archive handle.
+  Status record_scan(const RecordCall& c, ScanCacheView* cv = nullptr);
+  // the last grep of any kind: {frames, decoded, content bytes regenerated, records of the range, records selected, records listed,
+  // passes, matches}; all zero unless it succeeded. The searches and the grep leave each other's counters alone
   void grep_stats(uint64_t out[8]) const { call_stats(kScanGrep, out); }
   // bring-up: HIP-event time of the last grep's scan launches (count, scan, fill, carry), summed over its passes
   double grep_scan_ms() const { return callMs_[kScanGrep]; }
-  // grep_archive with a record predicate (zra_grep_where.hip, zra_where.h): a record is selected when one of the nClauses clauses
-  // {all, any, none} at hClauses (ZraHipRecordClause) holds for the set of patterns that hit in it; mode 1 complements that. Kernels of
-  // its own; it writes grep_archive's counters and milliseconds. Statuses and their order: zra_hip.h, ZraHipGrepArchiveWhere.
-  Status grep_archive_where(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
-                            uint8_t delimiter, uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
-                            uint64_t* hRecords, size_t recordCap, uint64_t* nRecords);
-  // grep_archive with regular expressions (zra_grep_regex.hip, zra_regex.h): a record is selected when the automaton of the nPatterns
-  // expressions (alternatives; syntax: 0 or fold case) matches inside it; mode 1 complements that. Kernels of its own; it writes
-  // grep_archive's counters and milliseconds. Statuses and their order: zra_hip.h, ZraHipGrepArchiveRegex.
-  Status grep_archive_regex(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
-                            uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap,
-                            uint64_t* nRecords);
-
-  // ---- extract (zra_extract.hip): grep_archive's selected records with their bytes: for each one, in order, its content and then one
-  // delimiter byte, packed at dData (device memory) in the same decode pass; the list goes to hRecords iff recordCap != 0. *dataSize:
-  // the packed bytes. Statuses and their order: zra_hip.h, ZraHipExtractRecords.
-  Status extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
-                         uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
-                         uint8_t* dData, size_t dataCap, uint64_t* dataSize);
-  // the last extract_records: {frames, decoded, content bytes regenerated, records of the range, records selected, packed bytes,
-  // passes, matches}; all zero unless it succeeded. The searches, the grep and the extract leave each other's counters alone
+  // the last extract of either kind: {frames, decoded, content bytes regenerated, records of the range, records selected, packed bytes,
+  // passes, matches (with regular expressions: the matched records before the mode)}; all zero unless it succeeded. The searches, the
+  // grep and the extract leave each other's counters alone
   void extract_stats(uint64_t out[8]) const { call_stats(kScanExtract, out); }
   // bring-up: HIP-event time of the last extract's own launches (count, scan, copy, carry), summed over its passes
   double extract_ms() const { return callMs_[kScanExtract]; }
-  // extract_records with regular expressions (zra_extract_regex.hip, zra_regex.h): grep_archive_regex's selection, extract_records'
-  // outputs, in one pass. Kernels of its own; it writes extract_records' counters (word 7: the matched records before the mode) and
-  // milliseconds. Statuses and their order: zra_hip.h, ZraHipExtractRecordsRegex.
-  Status extract_records_regex(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
-                               uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap,
-                               uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize);
 
   // ---- compare (zra_compare.hip): the maximal runs of content positions of [offset, offset + size) (size ~0: to the end of the common
   // content) at which the archives at dA and dB differ, ascending, as {offset, size} pairs in hRanges. A frame whose compressed bytes are
@@ -470,14 +474,14 @@ class Engine {
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
-  friend struct ScanImpl;          // the range scans drive the decoder's job arrays as the verifier does (zra_scan.h and the four calls' files)
+  friend struct ScanImpl;          // the range scans drive the decoder's job arrays as the verifier does (zra_scan.h, zra_record_scan.h and the seven calls' files)
   friend struct FramePasses;       // the one pass driver of compare, diff, sign, signature diff and index: scratch, job arrays, call events (zra_framepass.h)
   friend struct RecordsImpl;       // the locate sweep drives the decoder's job arrays of the needed frames on its own (zra_records.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 
 // The range scans' per-pass steps that do not depend on the pattern, launched on stream s (zra_search.hip; the driver in zra_scan.h
-// makes the first and the third for all four calls, the multi-pattern search shares the second; the frame-pass driver, zra_framepass.h,
+// makes the first and the third for all seven calls, the multi-pattern search shares the second; the frame-pass driver, zra_framepass.h,
 // makes the first for its plain passes): the decode jobs of frames [first, first + n) into slots 0 .. n - 1; bases[t] = *cntIn + the counts in front of item
 // t, *cntOut = *cntIn + all of them; the last n bytes of the run win[.., L) moved to win[-n, 0), n <= 255.
 void search_launch_jobs(hipStream_t s, const uint8_t* table, uint64_t fs, uint64_t total, uint64_t first, uint32_t n, uint64_t* frameOff, uint64_t* outOff,

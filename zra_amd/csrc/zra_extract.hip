@@ -24,7 +24,8 @@
 //  (stores) every store to dData is clamped to [0, dataCapacity), so the sizing call and a short buffer run the same code.
 //  (launches) zra_extract_count_kernel, zra_extract_scan_kernel (ONE workgroup), zra_extract_copy_kernel: the grep's three, the third
 //      redoing the tiles that hold a copied byte or a listed record.
-#include "zra_patterns.h"
+#include "zra_record_scan.h"
+#include "zra_extract_tail.h"
 
 namespace {
 // (summary). flags: 1 a delimiter, 2 a hit in front of the first delimiter, 4 a hit behind the last, 8 (set by the scan) the record
@@ -152,8 +153,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_extract_count_class_kernel
 extern "C" __global__ void __launch_bounds__(1024) zra_extract_scan_kernel(XSum* sums, u32 nTiles, XHead* heads, const XState* in, XState* out, u32 inv, u32 lastPass,
                                                                            u64 hi, u64 p0, u64 nPos, Range* list, u64 cap, u8* dData, u64 dataCap, u32 delim) {
   __shared__ u64 sFirst[1024], sLast[1024], sSel[1024], sBytes[1024];
-  __shared__ u32 sF[1024], sLook[1024];
-  __shared__ u32 sTailSel;
+  __shared__ u32 sF[1024];
   const u32 tid = threadIdx.x;
   const u32 per = (nTiles + 1023) / 1024;
   const u32 b0 = min(nTiles, tid * per), b1 = min(nTiles, b0 + per);
@@ -184,43 +184,14 @@ extern "C" __global__ void __launch_bounds__(1024) zra_extract_scan_kernel(XSum*
     }
     advance(e, s.flags, s.first, s.last, s.sel, s.bytes, inv);
   }
+  u32 tailSel = 0;
   if (tid == 1023) {                                                         // (its run is the last one, or empty behind the last one)
-    u64 tail = 0;
-    u32 tailSel = 1;                                                         // (provisional tail)
-    if (lastPass) {
-      tailSel = 0;
-      if (e.start < hi) {
-        tail = 1;
-        if ((u32)e.hit != inv) {
-          tailSel = 1;
-          if (e.idx < cap) { Range q; q.offset = e.start; q.size = hi - e.start; list[e.idx] = q; }
-          const u64 at = e.at + (hi - e.start);
-          if (at < dataCap) dData[at] = (u8)delim;
-          e.idx++; e.at = at + 1;
-        }
-      }
-    }
+    u64 tail;
+    tailSel = extract_pass_end(lastPass, (u32)e.hit != inv, e.start, hi, e.idx, e.at, tail, list, cap, dData, dataCap, delim);
     XState o; o.start = e.start; o.hit = e.hit; o.sel = e.idx; o.tail = tail; o.bytes = e.at; o.pad[0] = o.pad[1] = o.pad[2] = 0;
     *out = o;
-    sTailSel = tailSel;
   }
-  sLook[tid] = look;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                                       // the nearest lane at or behind this one whose run has a delimiter
-    const u32 o = tid + d < 1024 ? sLook[tid + d] : 0;
-    __syncthreads();
-    if (!(look & 2)) look = o;
-    sLook[tid] = look;
-    __syncthreads();
-  }
-  u32 carry = tid < 1023 ? sLook[tid + 1] : 0;
-  carry = (carry & 2) ? carry & 1 : sTailSel;
-  for (u32 t = b1; t-- > b0;) {
-    const XSum s = sums[t];                                                  // (this lane's own stores above)
-    const u64 tileEnd = p0 + min((u64)(t + 1) * kTile, nPos);
-    heads[t].look = (s.flags & 1) && s.last == tileEnd ? 0 : carry;         // (no position behind the tile's last delimiter)
-    if (s.flags & 1) carry = (s.flags >> 3) & 1;
-  }
+  look_ahead(look, tailSel, b0, b1, p0, nPos, heads, [&](u32 t) { const XSum s = sums[t]; return LookTile{(s.flags & 1) != 0, (s.flags >> 3) & 1, s.last}; });
 }
 
 // The count's workgroups redo the tiles that hold a byte of a selected record or a listed record in front of the capacities (the
@@ -340,89 +311,33 @@ extern "C" __global__ void __launch_bounds__(256) zra_extract_copy_class_kernel(
 }
 
 // =================================================================================================
-namespace zra_eng {
-
-Status Engine::extract_records(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
-                               uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
-                               uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
-  return ScanImpl::call(*this, kScanExtract, nRecords, dataSize, [&] {
-    return ScanImpl::extract(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
-                             hRecords, recordCap, nRecords, dData, dataCap, dataSize);
-  });
-}
-
-Status ScanImpl::extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                         uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                         uint64_t* dataSize, ScanCacheView* cv) {
-  // ---- 1. arguments
-  if (!nRecords || !dataSize || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (!dData && dataCap) || (mode & ~1u)) return zerr(42);
-  PatternSet pset;
-  if (!patterns_ok(hPat, hSizes, nPat, syntax, delimiter, &pset)) return zerr(42);
-  const uint32_t M = pset.M, mMin = pset.mMin;
-  // ---- 2. overlap (with the archive, and with the arena of the handle the call goes through)
-  if (dataCap && arcSize && (uintptr_t)dData < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dData + dataCap) return zerr(42);
-  if (cv && cv->slots && dataCap && (uintptr_t)dData < (uintptr_t)cv->arena + (size_t)cv->slots * cv->h.frameSize && (uintptr_t)cv->arena < (uintptr_t)dData + dataCap)
-    return zerr(42);
-  const uint32_t inv = mode & 1u;
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 3. header: the statuses of ZraHipArchiveOpen, as the grep
-  ArchiveView arc;
-  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
-  // ---- 4. the range [lo, hi)
-  uint64_t lo, hi;
-  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.callStats_[kScanExtract];
-  if (hi == lo || (!inv && hi - lo < mMin)) { stats[0] = arc.frames; return ok(); }   // no record, or none that could hold a match
-  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
-  // ---- 5. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | XTotals | sums[tiles] | heads[tiles]
-  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
-  const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  const size_t kTotals = pset.table_bytes() + 64, kHead = kTotals + sizeof(XTotals);
-  static_assert((sizeof(Table) + 64 + sizeof(XTotals)) % 16 == 0 && (sizeof(ClassTable) + 64 + sizeof(XTotals)) % 16 == 0 && sizeof(XSum) == 32 && sizeof(XHead) == 32 && sizeof(Range) == 16 && sizeof(XState) == 64, "16-byte entries behind a 16-byte head");
-  std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo")
-  build_pattern_table(head.data(), pset, hPat, hSizes, nPat);
-  ((XTotals*)(head.data() + kTotals))->st[0].start = lo;
-  uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
-  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanExtract], head.data(), kHead, kTotals, sizeof(XTotals), kHead + P.tilesMax * (sizeof(XSum) + sizeof(XHead)) + 64,
-                               listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
-    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
-    const Table* const tbl = (const Table*)tb;
-    const ClassTable* const ctbl = (const ClassTable*)tb;                    // (one of the two, by the syntax word)
-    XTotals* const tot = (XTotals*)(tb + kTotals);
-    XSum* const sums = (XSum*)(tb + kHead);
-    XHead* const heads = (XHead*)(sums + P.tilesMax);
-    Range* const list = E.scan_.list.as<Range>();
-    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    if (pset.classes)
-      hipLaunchKernelGGL(zra_extract_count_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
+// The kernel set of the extract for zra_record_scan.h's call path. tables: Table | XTotals | sums[tiles] | heads[tiles]
+namespace {
+struct ExtractKernels {
+  using Sum = XSum; using Head = XHead; using Totals = XTotals;
+  static constexpr size_t kMapBytes = 0;
+  static constexpr bool kData = true;
+  static void launch(hipStream_t s, const LiteralSelect& sel, const RecordCall& c, const zra_eng::ScanPass& ps, const RecordPass<ExtractKernels>& p, u32 parity) {
+    const Table* const tbl = (const Table*)p.table;
+    const ClassTable* const ctbl = (const ClassTable*)p.table;                // (one of the two, by the syntax word)
+    const u32 delim = c.delimiter, inv = sel.inv, M = sel.M;
+    if (sel.pset.classes)
+      hipLaunchKernelGGL(zra_extract_count_class_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, delim, inv, (u64)ps.p0, p.sums, p.tot);
     else
-      hipLaunchKernelGGL(zra_extract_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
-    hipLaunchKernelGGL(zra_extract_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
-                       (u32)ps.lastPass, (u64)hi, (u64)ps.p0, (u64)ps.nPos, list, (u64)listCap, dData, (u64)dataCap, (u32)delimiter);
-    if ((listCap || dataCap) && pset.classes)
-      hipLaunchKernelGGL(zra_extract_copy_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums,
-                         heads, list, (u64)listCap, dData, (u64)dataCap);
-    else if (listCap || dataCap)
-      hipLaunchKernelGGL(zra_extract_copy_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums,
-                         heads, list, (u64)listCap, dData, (u64)dataCap);
-  }, &launches, cv);
-  if (st.zra) return st;
-  // ---- 6. the totals (they came back with the last synchronisation), then the list, once
-  const XTotals& h = *(const XTotals*)(head.data() + kTotals);
-  const XState& fin = h.st[launches & 1];
-  const uint64_t total = fin.sel, packed = fin.bytes;
-  *nRecords = total;
-  *dataSize = packed;
-  if ((recordCap && total > recordCap) || packed > dataCap) return {kOutputTooSmall, 0};   // 7: the two words say what the call needs
-  if (recordCap && total) {
-    HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, (size_t)total * sizeof(Range), hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
+      hipLaunchKernelGGL(zra_extract_count_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, delim, inv, (u64)ps.p0, p.sums, p.tot);
+    hipLaunchKernelGGL(zra_extract_scan_kernel, dim3(1), dim3(1024), 0, s, p.sums, p.tiles, p.heads, p.tot->st + parity, p.tot->st + (parity ^ 1), inv, (u32)ps.lastPass,
+                       (u64)p.hi, (u64)ps.p0, (u64)ps.nPos, p.list, (u64)p.listCap, c.dData, (u64)c.dataCap, delim);
+    if ((p.listCap || c.dataCap) && sel.pset.classes)
+      hipLaunchKernelGGL(zra_extract_copy_class_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, delim, inv, (u64)ps.p0, p.sums,
+                         p.heads, p.list, (u64)p.listCap, c.dData, (u64)c.dataCap);
+    else if (p.listCap || c.dataCap)
+      hipLaunchKernelGGL(zra_extract_copy_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, delim, inv, (u64)ps.p0, p.sums, p.heads,
+                         p.list, (u64)p.listCap, c.dData, (u64)c.dataCap);
   }
-  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, packed, P.passes, h.matches};
-  std::copy(st8, st8 + 8, stats);
-  return ok();
-}
+};
+static_assert(sizeof(XState) == 64 && sizeof(XSum) == 32 && sizeof(XHead) == 32, "the entries as the kernels index them");
+}  // namespace
 
+namespace zra_eng {
+Status ScanImpl::extract(Engine& E, const RecordCall& c, ScanCacheView* cv) { return record_scan<LiteralSelect, ExtractKernels>(E, c, cv); }
 }  // namespace zra_eng

@@ -3,8 +3,10 @@
 // `grep -E` (and `-v`) prints, from the one decode pass that selects the records.
 //
 // Selection, (state), (count) and the driver with M = 1 are the regex grep's, word for word; (compaction), (look-ahead), (provisional
-// tail) and (stores) are the extract's. Neither file is touched: the regex grep's helpers live in its anonymous namespace and are
-// repeated here. What this call joins:
+// tail) and (stores) are the extract's. What it runs as the regex grep does lies in zra_regex_tile.h (the automaton in LDS, the walks,
+// the forward half of the scan with this call's two fields switched on, phase 1 of the copy), what it runs as the
+// extract does behind the forward scan in zra_extract_tail.h; the host path is zra_record_scan.h's (the regex selector, the kernel
+// set at the end of this file). This file keeps its count, the end of the scan and phases 2 and 3 of the copy. What this call joins:
 //  (summary) the regex grep's {has, F[64], tail, last, sel} plus {first, bytes}: the position of the run's first delimiter, and the
 //      packed bytes (n + 1 each) of the selected records that end inside the run APART from the one its first delimiter ends. For A
 //      followed by B, both with a delimiter, s = accept(B.F[A.tail]) ^ invert: bytes = A.bytes + B.bytes + s * (B.first - A.last + 1),
@@ -21,15 +23,11 @@
 //      (ballots, a running count) and stores q's byte at its record's base + (q - the record's start).
 // Every store to dData is clamped to [0, dataCapacity); no atomic decides an address; no workgroup waits for another one; every loop
 // is bounded by the tile's size; a tile stages n bytes, n the positions it owns inside [lo, hi).
-#include "zra_scan.h"
-#include "zra_scan_tile.h"
-#include "zra_regex.h"
+#include "zra_record_scan.h"
+#include "zra_regex_tile.h"
+#include "zra_extract_tail.h"
 
 namespace {
-using zra_regex::Table;
-constexpr u32 kGroup = 8;                                   // consecutive tiles of one workgroup, as the family's
-struct __attribute__((aligned(16))) Range { u64 offset, size; };   // ZraHipContentRange
-
 // (summary) without the map. sel: after the scan ALL the selected records that end in the tile; fsel (set by the scan): the record
 // the first delimiter ends is selected
 struct __attribute__((aligned(16))) SumR { u64 first, last; u32 bytes, sel; u8 has, tail, fsel, pad[5]; };
@@ -39,52 +37,12 @@ struct __attribute__((aligned(16))) HeadR { u64 base, open, at; u32 state, look;
 // the state carried from pass to pass; tail: the last pass ended an open record at hi; bytes: packed so far, (provisional tail)'s D
 struct StateR { u64 start, state, sel, tail, bytes, pad[3]; };
 struct TotalsR { StateR st[2]; u64 matches, delims, pad[6]; };
-
-// the automaton in LDS: the class of every byte and the rows of the classes in use
-struct Dfa { u8 classOf[256]; u8 next[256 * 64]; };
-
-__device__ __forceinline__ void stage_dfa(const Table* tbl, Dfa* s, u32 classes) {
-  const uint4* const g = (const uint4*)tbl;
-  for (u32 c = threadIdx.x; c < 16 + classes * 4; c += 256) lds_st128((u8*)s + 16 * (size_t)c, g[c]);
-}
-__device__ __forceinline__ u32 tile_byte(const u32* sTile, u32 i) { return ((const u8*)sTile)[i]; }
-
-// one lane's walk over the tile bytes [from, to) from state st
-__device__ __forceinline__ u32 walk(const Dfa* D, const u32* sTile, u32 d, u32 from, u32 to, u32 st) {
-#pragma unroll 2
-  for (u32 j = from; j < to; j++) st = D->next[(u32)D->classOf[tile_byte(sTile, d + j)] * 64 + st];
-  return st;
-}
-
-// The delimiter positions of a tile of n positions, in order, into sPos; returns their number (the same in every lane). sCnt[w]
-// keeps wave w's number. A wave takes its 2,048 consecutive positions twice: to count, and behind the prefix over the waves to write.
-__device__ __forceinline__ u32 compact_delims(const u32* sTile, u32 d, u32 n, u32 delim, u16* sPos, u32* sCnt) {
-  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, w0 = wave * kWavePos;
-  u32 mine = 0;
-#pragma unroll 1
-  for (u32 t = 0; t < kWaveIters && w0 + t * 64 < n; t++) {
-    const u32 j = w0 + t * 64 + lane;
-    mine += (u32)__popcll(__ballot(j < n && tile_byte(sTile, d + j) == delim));
-  }
-  if (lane == 0) sCnt[wave] = mine;
-  __syncthreads();
-  u32 at = 0, all = 0;
-  for (u32 v = 0; v < 4; v++) { if (v < wave) at += sCnt[v]; all += sCnt[v]; }
-#pragma unroll 1
-  for (u32 t = 0; t < kWaveIters && w0 + t * 64 < n; t++) {
-    const u32 j = w0 + t * 64 + lane;
-    const bool isD = j < n && tile_byte(sTile, d + j) == delim;
-    const u64 dm = __ballot(isD);
-    if (isD) sPos[at + (u32)__popcll(dm & ((1ull << lane) - 1))] = (u16)j;
-    at += (u32)__popcll(dm);
-  }
-  __syncthreads();
-  return all;
-}
 }  // namespace
 
-// The run of a pass, its tiles and workgroups: zra_grepx_count_kernel. Per tile its summary -> sums[tile] and its map -> maps[tile].
-extern "C" __global__ void __launch_bounds__(256) zra_extractx_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, const Table* tbl, u32 delim, u32 inv,
+// The run of a pass, its tiles and workgroups: zra_grepx_count_kernel with (summary)'s two fields. Per tile its summary -> sums[tile]
+// and its map -> maps[tile]. (Kept beside the regex grep's count, not joined with it: one body for both, with the two fields switched
+// on, cost this kernel 0.06 ms per GiB, profiles/record_scan_refactor.md.)
+extern "C" __global__ void __launch_bounds__(256) zra_extractx_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, const RxTable* tbl, u32 delim, u32 inv,
                                                                             u64 p0, SumR* sums, u8* maps, TotalsR* tot) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
   __shared__ __attribute__((aligned(16))) Dfa sD;
@@ -143,157 +101,32 @@ extern "C" __global__ void __launch_bounds__(256) zra_extractx_count_kernel(cons
   if (tid == 0 && delims) atomicAdd((unsigned long long*)&tot->delims, (unsigned long long)delims);
 }
 
-// One workgroup. Forward, zra_grepx_scan_kernel with (summary)'s two fields: every lane reduces a run of consecutive tiles, the 1,024
-// summaries are scanned in LDS, then the lane walks its run again from the front state: heads[t], sums[t].sel becomes ALL the
-// selected records that end in tile t and sums[t].fsel says whether the first of them is one. The last lane ends the pass: in the
-// last pass the record open at hi ends there (its list entry and its delimiter byte). Backward, zra_extract_scan_kernel's
-// (look-ahead): the bit of the nearest following tile with a delimiter, or of the pass's end, reaches every tile's head.
+// One workgroup, (scan). Forward, zra_regex_tile.h's with (summary)'s two fields. The last lane ends the pass: in the last pass the
+// record open at hi ends there (its list entry and its delimiter byte). Backward, the extracts' (look-ahead): the bit of the nearest
+// following tile with a delimiter, or of the pass's end, reaches every tile's head.
 extern "C" __global__ void __launch_bounds__(1024) zra_extractx_scan_kernel(SumR* sums, const u8* maps, u32 nTiles, HeadR* heads, const StateR* in, StateR* out,
-                                                                            const Table* tbl, u32 inv, u32 lastPass, u64 hi, u64 p0, u64 nPos, Range* list, u64 cap,
+                                                                            const RxTable* tbl, u32 inv, u32 lastPass, u64 hi, u64 p0, u64 nPos, Range* list, u64 cap,
                                                                             u8* dData, u64 dataCap, u32 delim, TotalsR* tot) {
-  __shared__ __attribute__((aligned(16))) u32 sMap[1024 * 16];
-  __shared__ u64 sFirst[1024], sLast[1024], sSel[1024], sBytes[1024];
-  __shared__ u32 sLook[1024];
-  __shared__ u8 sHas[1024], sTl[1024];
-  __shared__ u32 sTailSel;
-  const u32 tid = threadIdx.x;
-  const u32 per = (nTiles + 1023) / 1024;
-  const u32 b0 = min(nTiles, tid * per), b1 = min(nTiles, b0 + per);
   const u64 accept = tbl->accept;
-  const u8* const myMap = (const u8*)(sMap + tid * 16);
-  // ---- the lane's run. F starts as the identity
-  u32 F[16];
-#pragma unroll
-  for (u32 w = 0; w < 16; w++) F[w] = 0x03020100u + 0x04040404u * w;
-  u64 first = 0, last = 0, sel = 0, bytes = 0;
-  u32 has = 0, tail = 0;
-  for (u32 t = b0; t < b1; t++) {
-    const SumR s = sums[t];
-    const u8* const m = maps + (size_t)t * 64;
-    if (has) {
-      if (!s.has) { tail = m[tail]; continue; }
-      const u32 j = ((u32)(accept >> m[tail]) & 1) ^ inv;
-      sel += s.sel + j; bytes += s.bytes + (j ? s.first - last + 1 : 0);
-      tail = s.tail; last = s.last;
-      continue;
-    }
-#pragma unroll
-    for (u32 w = 0; w < 16; w++) {
-      const u32 a = F[w];
-      F[w] = (u32)m[a & 0xFF] | (u32)m[(a >> 8) & 0xFF] << 8 | (u32)m[(a >> 16) & 0xFF] << 16 | (u32)m[a >> 24] << 24;
-    }
-    if (s.has) { has = 1; sel = s.sel; bytes = s.bytes; tail = s.tail; first = s.first; last = s.last; }
-  }
-#pragma unroll
-  for (u32 w = 0; w < 16; w++) sMap[tid * 16 + w] = F[w];
-  sFirst[tid] = first; sLast[tid] = last; sSel[tid] = sel; sBytes[tid] = bytes; sHas[tid] = (u8)has; sTl[tid] = (u8)tail;
-  __syncthreads();
-  // ---- the scan: A = the lanes in front (at tid - d), B = this lane
-  for (u32 d = 1; d < 1024; d <<= 1) {
-    const bool on = tid >= d;
-    if (on) {
-      const u32 a = tid - d;
-      if (sHas[a]) {
-        // A's map stands; B's acts on A's tail
-        const u32 through = myMap[sTl[a]];
-        if (has) {
-          const u32 j = ((u32)(accept >> through) & 1) ^ inv;
-          sel += sSel[a] + j; bytes += sBytes[a] + (j ? first - sLast[a] + 1 : 0);
-        } else { has = 1; sel = sSel[a]; bytes = sBytes[a]; last = sLast[a]; tail = through; }
-        first = sFirst[a];
-#pragma unroll
-        for (u32 w = 0; w < 16; w++) F[w] = sMap[a * 16 + w];
-      } else {
-#pragma unroll
-        for (u32 w = 0; w < 16; w++) {
-          const u32 x = sMap[a * 16 + w];
-          F[w] = (u32)myMap[x & 0xFF] | (u32)myMap[(x >> 8) & 0xFF] << 8 | (u32)myMap[(x >> 16) & 0xFF] << 16 | (u32)myMap[x >> 24] << 24;
-        }
-      }
-    }
-    __syncthreads();
-    if (on) {
-#pragma unroll
-      for (u32 w = 0; w < 16; w++) sMap[tid * 16 + w] = F[w];
-      sFirst[tid] = first; sLast[tid] = last; sSel[tid] = sel; sBytes[tid] = bytes; sHas[tid] = (u8)has; sTl[tid] = (u8)tail;
-    }
-    __syncthreads();
-  }
-  // ---- the front of this lane's run: the carried one, moved over the lanes in front
-  u64 start = in->start, count = in->sel, at = in->bytes;
-  u32 state = (u32)in->state, matched = 0;
-  if (tid) {
-    const u32 a = tid - 1;
-    const u32 through = ((const u8*)(sMap + a * 16))[state];
-    if (sHas[a]) {
-      const u32 j = ((u32)(accept >> through) & 1) ^ inv;
-      count += sSel[a] + j; at += sBytes[a] + (j ? sFirst[a] - start + 1 : 0);
-      state = sTl[a]; start = sLast[a];
-    } else state = through;
-  }
-  u32 look = 0;                                                              // 2: the run has a delimiter, 1: the record its first one ends is selected
-  for (u32 t = b0; t < b1; t++) {
-    const SumR s = sums[t];
-    HeadR h; h.base = count; h.open = start; h.at = at; h.state = state; h.look = 0;
-    heads[t] = h;
-    const u32 through = maps[(size_t)t * 64 + state];
-    if (s.has) {
-      const u32 m = (u32)(accept >> through) & 1, j = m ^ inv;
-      sums[t].sel = s.sel + j;
-      sums[t].fsel = (u8)j;
-      if (!look) look = 2 | j;
-      matched += m; count += s.sel + j; at += s.bytes + (j ? s.first - start + 1 : 0);
-      state = s.tail; start = s.last;
-    } else state = through;
-  }
-  if (tid == 1023) {                                                         // (its run is the last one, or empty behind the last one)
-    u64 tl = 0;
-    u32 tailSel = 1;                                                         // (provisional tail)
-    if (lastPass) {
-      tailSel = 0;
-      if (start < hi) {
-        tl = 1;
-        const u32 m = (u32)(accept >> state) & 1;
-        matched += m;
-        if (m ^ inv) {
-          tailSel = 1;
-          if (count < cap) { Range r; r.offset = start; r.size = hi - start; list[count] = r; }
-          const u64 end = at + (hi - start);
-          if (end < dataCap) dData[end] = (u8)delim;
-          count++; at = end + 1;
-        }
-      }
-    }
-    StateR o; o.start = start; o.state = state; o.sel = count; o.tail = tl; o.bytes = at; o.pad[0] = o.pad[1] = o.pad[2] = 0;
+  RegexFront e = regex_scan_forward<true>(sums, maps, nTiles, heads, in, accept, inv);
+  u32 tailSel = 0;
+  if (threadIdx.x == 1023) {                                                 // (its run is the last one, or empty behind the last one)
+    const u32 m = (u32)(accept >> e.state) & 1;
+    if (lastPass && e.start < hi) e.matched += m;
+    u64 tl;
+    tailSel = extract_pass_end(lastPass, (m ^ inv) != 0, e.start, hi, e.count, e.at, tl, list, cap, dData, dataCap, delim);
+    StateR o; o.start = e.start; o.state = e.state; o.sel = e.count; o.tail = tl; o.bytes = e.at; o.pad[0] = o.pad[1] = o.pad[2] = 0;
     *out = o;
-    sTailSel = tailSel;
   }
-  if (matched) atomicAdd((unsigned long long*)&tot->matches, (unsigned long long)matched);
-  // ---- (look-ahead)
-  sLook[tid] = look;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {                                       // the nearest lane at or behind this one whose run has a delimiter
-    const u32 o = tid + d < 1024 ? sLook[tid + d] : 0;
-    __syncthreads();
-    if (!(look & 2)) look = o;
-    sLook[tid] = look;
-    __syncthreads();
-  }
-  u32 carry = tid < 1023 ? sLook[tid + 1] : 0;
-  carry = (carry & 2) ? carry & 1 : sTailSel;
-  for (u32 t = b1; t-- > b0;) {
-    const SumR s = sums[t];                                                  // (this lane's own stores above)
-    const u64 tileEnd = p0 + min((u64)(t + 1) * kTile, nPos);
-    heads[t].look = s.has && s.last == tileEnd ? 0 : carry;                  // (no position behind the tile's last delimiter)
-    if (s.has) carry = s.fsel;
-  }
+  if (e.matched) atomicAdd((unsigned long long*)&tot->matches, (unsigned long long)e.matched);
+  look_ahead(e.look, tailSel, e.b0, e.b1, p0, nPos, heads, [&](u32 t) { const SumR s = sums[t]; return LookTile{s.has != 0, s.fsel, s.last}; });
 }
 
 // The count's workgroups redo the tiles that hold a byte of a selected record or a listed record in front of the capacities (the
 // others are skipped; a workgroup without such a tile leaves at once).
-extern "C" __global__ void __launch_bounds__(256) zra_extractx_copy_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, const Table* tbl, u32 delim, u32 inv,
+extern "C" __global__ void __launch_bounds__(256) zra_extractx_copy_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, const RxTable* tbl, u32 delim, u32 inv,
                                                                            u64 p0, const SumR* sums, const HeadR* heads, Range* list, u64 cap, u8* dData, u64 dataCap) {
-  constexpr u32 kSelBit = 0x8000u;                                           // in sPos: the record this delimiter ends is selected (a position is below 2^13)
+  constexpr u32 kSelBit = 0x8000u;                                           // in sPos: the record this delimiter ends is selected (above kPosMask)
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
   __shared__ __attribute__((aligned(16))) Dfa sD;
   __shared__ u16 sPos[kTile];
@@ -324,23 +157,14 @@ extern "C" __global__ void __launch_bounds__(256) zra_extractx_copy_kernel(const
     __syncthreads();
     const u32 d = stage_tile(win + x0, n, sTile);
     __syncthreads();
-    // ---- phase 1: the delimiters, and the selection bit of the record that delimiter k ends: record 0 goes on from the head's state
-    const u32 nD = compact_delims(sTile, d, n, delim, sPos, sCnt);
-    for (u32 k = tid; k < nD; k += 256) {
-      const u32 from = k ? ((u32)sPos[k - 1] & 0x1FFFu) + 1 : 0, to = (u32)sPos[k];
-      const u32 st = walk(&sD, sTile, d, from, to, k ? start : head.state);
-      // Lane k + 1 may read sPos[k] for its `from` while this store is under way, with no barrier between: it masks the word with
-      // 0x1FFF, the store is one 16-bit LDS write (ds_write_b16, never torn) and leaves those 13 bits as they are, so either value
-      // it sees gives the same `from`. The bit itself is read behind the barrier below.
-      if (((u32)(accept >> st) & 1) ^ inv) sPos[k] = (u16)(to | kSelBit);
-    }
-    __syncthreads();
+    // ---- phase 1: the delimiters, and in sPos[k] the selection bit of the record that delimiter k ends
+    const u32 nD = regex_select(&sD, sTile, d, n, delim, sPos, sCnt, start, head.state, accept, inv, [&](u32 k, u32 to, u32 bit) { if (bit) sPos[k] = (u16)(to | kSelBit); });
     // ---- phase 2: the exclusive prefix. A lane takes `chunk` consecutive delimiters; the 256 lane sums are scanned by wave
     const u32 chunk = (nD + 255) / 256, k0 = min(nD, tid * chunk), k1 = min(nD, k0 + chunk);
     u32 mine = 0;
     for (u32 k = k0; k < k1; k++) {
       const u32 e = sPos[k];
-      if (e & kSelBit) mine += 0x10000u + (k ? (e & 0x1FFFu) - ((u32)sPos[k - 1] & 0x1FFFu) : 0);
+      if (e & kSelBit) mine += 0x10000u + (k ? (e & kPosMask) - ((u32)sPos[k - 1] & kPosMask) : 0);
     }
     const u32 incl = wave_incl_scan(mine);
     if (lane == 63) sW[wave] = incl;
@@ -350,14 +174,14 @@ extern "C" __global__ void __launch_bounds__(256) zra_extractx_copy_kernel(const
     for (u32 k = k0; k < k1; k++) {
       sPre[k] = run;
       const u32 e = sPos[k];
-      if (e & kSelBit) run += 0x10000u + (k ? (e & 0x1FFFu) - ((u32)sPos[k - 1] & 0x1FFFu) : 0);
+      if (e & kSelBit) run += 0x10000u + (k ? (e & kPosMask) - ((u32)sPos[k - 1] & kPosMask) : 0);
     }
     if (tid == 255) sPre[nD] = sW[0] + sW[1] + sW[2] + sW[3];                // (lane 255's chunk is the last one, or empty)
     __syncthreads();
     // ---- phase 3: a lane per position. k = the delimiters in front of q = the record q lies in; q's record ends at delimiter k
     if (w0 >= n) continue;                                                   // (uniform in the wave; the barriers are at the loop's head)
     // the packed bytes of record 0, which began at head.open, when it is selected
-    const u64 firstAdd = nD && (sPos[0] & kSelBit) ? pos0 + ((u32)sPos[0] & 0x1FFFu) - head.open + 1 : 0;
+    const u64 firstAdd = nD && (sPos[0] & kSelBit) ? pos0 + ((u32)sPos[0] & kPosMask) - head.open + 1 : 0;
     u32 kw = 0;
     for (u32 v = 0; v < wave; v++) kw += sCnt[v];
 #pragma unroll 1
@@ -374,13 +198,13 @@ extern "C" __global__ void __launch_bounds__(256) zra_extractx_copy_kernel(const
       if (inside) {
         sel = k < nD ? (sPos[k] & kSelBit) != 0 : head.look != 0;
         if (k == 0) to = head.at + (pos0 + q - head.open);                   // the record open at the tile's head
-        else to = head.at + firstAdd + (sPre[k] & 0xFFFFu) + (q - (((u32)sPos[k - 1] & 0x1FFFu) + 1));
+        else to = head.at + firstAdd + (sPre[k] & 0xFFFFu) + (q - (((u32)sPos[k - 1] & kPosMask) + 1));
       }
       if (sel && to < dataCap) dData[to] = (u8)byte;
       if (sel && isD) {
         const u64 idx = head.base + (sPre[k] >> 16);
         if (idx < cap) {
-          const u64 from = k ? pos0 + ((u32)sPos[k - 1] & 0x1FFFu) + 1 : head.open;
+          const u64 from = k ? pos0 + ((u32)sPos[k - 1] & kPosMask) + 1 : head.open;
           Range r; r.offset = from; r.size = pos0 + q - from;
           list[idx] = r;
         }
@@ -390,88 +214,26 @@ extern "C" __global__ void __launch_bounds__(256) zra_extractx_copy_kernel(const
 }
 
 // =================================================================================================
+// The kernel set of the regex extract for zra_record_scan.h's call path. tables: Table | Totals | sums[tiles] | heads[tiles] | maps[tiles]
+namespace {
+struct ExtractRegexKernels {
+  using Sum = SumR; using Head = HeadR; using Totals = TotalsR;
+  static constexpr size_t kMapBytes = 64;
+  static constexpr bool kData = true;
+  static void launch(hipStream_t s, const RegexSelect& sel, const RecordCall& c, const zra_eng::ScanPass& ps, const RecordPass<ExtractRegexKernels>& p, u32 parity) {
+    const RxTable* const tbl = (const RxTable*)p.table;
+    const u32 delim = c.delimiter, inv = sel.inv;
+    hipLaunchKernelGGL(zra_extractx_count_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, tbl, delim, inv, (u64)ps.p0, p.sums, p.maps, p.tot);
+    hipLaunchKernelGGL(zra_extractx_scan_kernel, dim3(1), dim3(1024), 0, s, p.sums, p.maps, p.tiles, p.heads, p.tot->st + parity, p.tot->st + (parity ^ 1), tbl, inv,
+                       (u32)ps.lastPass, (u64)p.hi, (u64)ps.p0, (u64)ps.nPos, p.list, (u64)p.listCap, c.dData, (u64)c.dataCap, delim, p.tot);
+    if (p.listCap || c.dataCap)
+      hipLaunchKernelGGL(zra_extractx_copy_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, tbl, delim, inv, (u64)ps.p0, p.sums, p.heads, p.list,
+                         (u64)p.listCap, c.dData, (u64)c.dataCap);
+  }
+};
+static_assert(sizeof(TotalsR) == 192 && sizeof(SumR) == 32 && sizeof(HeadR) == 32, "the entries as the kernels index them");
+}  // namespace
+
 namespace zra_eng {
-
-Status Engine::extract_records_regex(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
-                                     uint8_t delimiter, uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap,
-                                     uint64_t* nRecords, uint8_t* dData, size_t dataCap, uint64_t* dataSize) {
-  return ScanImpl::call(*this, kScanExtract, nRecords, dataSize, [&] {
-    return ScanImpl::extract_regex(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
-                                   hRecords, recordCap, nRecords, dData, dataCap, dataSize);
-  });
-}
-
-// ScanImpl::grep_regex's steps with ScanImpl::extract's outputs: the statuses and their order are zra_hip.h's, ZraHipExtractRecordsRegex.
-Status ScanImpl::extract_regex(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                               uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData,
-                               size_t dataCap, uint64_t* dataSize, ScanCacheView* cv) {
-  // ---- 1. arguments
-  if (!nRecords || !dataSize || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (!dData && dataCap) || (mode & ~1u)) return zerr(42);
-  const size_t kTotals = sizeof(Table), kHead = kTotals + sizeof(TotalsR);
-  static_assert(sizeof(Table) % 16 == 0 && sizeof(TotalsR) == 192 && sizeof(SumR) == 32 && sizeof(HeadR) == 32 && sizeof(Range) == 16 && offsetof(Table, next) == 256,
-                "16-byte entries behind a 16-byte head; stage_dfa's chunks");
-  std::vector<uint8_t> head;
-  {
-    zra_regex::Compiled C;
-    if (!zra_regex::compile(hPat, hSizes, nPat, syntax, delimiter, &C)) return zerr(42);
-    head.assign(kHead, 0);                                                   // (the totals go up as zeros, the state as "a record opens at lo" in the start state)
-    std::memcpy(head.data(), &C.table, sizeof(Table));
-    ((TotalsR*)(head.data() + kTotals))->st[0].state = C.table.start;
-  }
-  // ---- 2. overlap (with the archive, and with the arena of the handle the call goes through)
-  if (dataCap && arcSize && (uintptr_t)dData < (uintptr_t)dArc + arcSize && (uintptr_t)dArc < (uintptr_t)dData + dataCap) return zerr(42);
-  if (cv && cv->slots && dataCap && (uintptr_t)dData < (uintptr_t)cv->arena + (size_t)cv->slots * cv->h.frameSize && (uintptr_t)cv->arena < (uintptr_t)dData + dataCap)
-    return zerr(42);
-  const u32 inv = mode & 1u;
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 3. header: the statuses of ZraHipArchiveOpen, as the grep
-  ArchiveView arc;
-  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
-  // ---- 4. the range [lo, hi): every non-empty one is scanned
-  uint64_t lo, hi;
-  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.callStats_[kScanExtract];
-  if (hi == lo) { stats[0] = arc.frames; return ok(); }
-  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
-  // ---- 5. the passes. tables: Table | Totals | sums[tiles] | heads[tiles] | maps[tiles]
-  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, 1, 0, stagingBytes);
-  const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  ((TotalsR*)(head.data() + kTotals))->st[0].start = lo;
-  uint32_t launches = 0;
-  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanExtract], head.data(), kHead, kTotals, sizeof(TotalsR),
-                               kHead + P.tilesMax * (sizeof(SumR) + sizeof(HeadR) + 64) + 64, listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
-    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
-    const Table* const tbl = (const Table*)tb;
-    TotalsR* const tot = (TotalsR*)(tb + kTotals);
-    SumR* const sums = (SumR*)(tb + kHead);
-    HeadR* const heads = (HeadR*)(sums + P.tilesMax);
-    u8* const maps = (u8*)(heads + P.tilesMax);
-    Range* const list = E.scan_.list.as<Range>();
-    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    hipLaunchKernelGGL(zra_extractx_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, maps, tot);
-    hipLaunchKernelGGL(zra_extractx_scan_kernel, dim3(1), dim3(1024), 0, s, sums, maps, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), tbl, inv,
-                       (u32)ps.lastPass, (u64)hi, (u64)ps.p0, (u64)ps.nPos, list, (u64)listCap, dData, (u64)dataCap, (u32)delimiter, tot);
-    if (listCap || dataCap)
-      hipLaunchKernelGGL(zra_extractx_copy_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, heads, list,
-                         (u64)listCap, dData, (u64)dataCap);
-  }, &launches, cv);
-  if (st.zra) return st;
-  // ---- 6. the totals (they came back with the last synchronisation), then the list, once
-  const TotalsR& h = *(const TotalsR*)(head.data() + kTotals);
-  const StateR& fin = h.st[launches & 1];
-  const uint64_t total = fin.sel, packed = fin.bytes;
-  *nRecords = total;
-  *dataSize = packed;
-  if ((recordCap && total > recordCap) || packed > dataCap) return {kOutputTooSmall, 0};   // 7: the two words say what the call needs
-  if (recordCap && total) {
-    HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, (size_t)total * sizeof(Range), hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-  }
-  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, packed, P.passes, h.matches};
-  std::copy(st8, st8 + 8, stats);
-  return ok();
-}
-
+Status ScanImpl::extract_regex(Engine& E, const RecordCall& c, ScanCacheView* cv) { return record_scan<RegexSelect, ExtractRegexKernels>(E, c, cv); }
 }  // namespace zra_eng

@@ -26,7 +26,7 @@
 //      earlier trips, plus the selected lanes below), never the result of an atomic. No workgroup waits for another one: no spin-wait,
 //      no look-back; the dependency runs through the launches.
 //  (d) nothing goes to the caller's array before the last pass is done: a call that fails midway writes nothing.
-#include "zra_patterns.h"
+#include "zra_record_scan.h"
 
 namespace {
 // (summary). flags: 1 a delimiter, 2 a hit in front of the first delimiter, 4 a hit behind the last; last: the content offset behind
@@ -252,82 +252,34 @@ extern "C" __global__ void __launch_bounds__(256) zra_grep_fill_class_kernel(con
 }
 
 // =================================================================================================
+// The kernel set of the plain grep for zra_record_scan.h's call path. tables: Table | Totals | sums[tiles] | heads[tiles]
+namespace {
+struct GrepKernels {
+  using Sum = ::Sum; using Head = ::Head; using Totals = ::Totals;
+  static constexpr size_t kMapBytes = 0;
+  static constexpr bool kData = false;
+  static void launch(hipStream_t s, const LiteralSelect& sel, const RecordCall& c, const zra_eng::ScanPass& ps, const RecordPass<GrepKernels>& p, u32 parity) {
+    const Table* const tbl = (const Table*)p.table;
+    const ClassTable* const ctbl = (const ClassTable*)p.table;                // (one of the two, by the syntax word)
+    const u32 delim = c.delimiter, inv = sel.inv, M = sel.M;
+    if (sel.pset.classes)
+      hipLaunchKernelGGL(zra_grep_count_class_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, delim, inv, (u64)ps.p0, p.sums, p.tot);
+    else
+      hipLaunchKernelGGL(zra_grep_count_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, delim, inv, (u64)ps.p0, p.sums, p.tot);
+    hipLaunchKernelGGL(zra_grep_scan_kernel, dim3(1), dim3(1024), 0, s, p.sums, p.tiles, p.heads, p.tot->st + parity, p.tot->st + (parity ^ 1), inv, (u32)ps.lastPass,
+                       (u64)p.hi, p.list, (u64)p.listCap);
+    if (p.listCap && sel.pset.classes)
+      hipLaunchKernelGGL(zra_grep_fill_class_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, delim, inv, (u64)ps.p0, p.sums, p.heads,
+                         p.list, (u64)p.listCap);
+    else if (p.listCap)
+      hipLaunchKernelGGL(zra_grep_fill_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, delim, inv, (u64)ps.p0, p.sums, p.heads, p.list,
+                         (u64)p.listCap);
+  }
+};
+}  // namespace
+
 namespace zra_eng {
 
-Status Engine::grep_archive(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
-                            uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
-  return ScanImpl::call(*this, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
-                          hRecords, recordCap, nRecords);
-  });
-}
-
-Status ScanImpl::grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                      uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv) {
-  // ---- 1. arguments
-  if (!nRecords || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (mode & ~1u)) return zerr(42);
-  PatternSet pset;
-  if (!patterns_ok(hPat, hSizes, nPat, syntax, delimiter, &pset)) return zerr(42);
-  const uint32_t M = pset.M, mMin = pset.mMin;
-  const uint32_t inv = mode & 1u;
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 2. header: the statuses of ZraHipArchiveOpen, as the search
-  ArchiveView arc;
-  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
-  // ---- 3. the range [lo, hi)
-  uint64_t lo, hi;
-  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.callStats_[kScanGrep];
-  if (hi == lo || (!inv && hi - lo < mMin)) { stats[0] = arc.frames; return ok(); }   // no record, or none that could hold a match
-  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
-  // ---- 4. the passes (the last one always owns a position: it holds byte hi - 1). tables: Table | Totals | sums[tiles] | heads[tiles]
-  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
-  const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);     // (no list is longer: a record per delimiter, or the one open at hi)
-  const size_t kTotals = pset.table_bytes() + 64, kHead = kTotals + sizeof(Totals);
-  static_assert((sizeof(Table) + 64 + sizeof(Totals)) % 16 == 0 && (sizeof(ClassTable) + 64 + sizeof(Totals)) % 16 == 0 && sizeof(Sum) == 16 && sizeof(Head) == 16 && sizeof(Range) == 16, "16-byte entries behind a 16-byte head");
-  std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo")
-  build_pattern_table(head.data(), pset, hPat, hSizes, nPat);
-  ((Totals*)(head.data() + kTotals))->st[0].start = lo;
-  uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
-  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanGrep], head.data(), kHead, kTotals, sizeof(Totals), kHead + P.tilesMax * (sizeof(Sum) + sizeof(Head)) + 64,
-                               listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
-    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
-    const Table* const tbl = (const Table*)tb;
-    const ClassTable* const ctbl = (const ClassTable*)tb;                    // (one of the two, by the syntax word)
-    Totals* const tot = (Totals*)(tb + kTotals);
-    Sum* const sums = (Sum*)(tb + kHead);
-    Head* const heads = (Head*)(sums + P.tilesMax);
-    Range* const list = E.scan_.list.as<Range>();
-    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    if (pset.classes)
-      hipLaunchKernelGGL(zra_grep_count_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
-    else
-      hipLaunchKernelGGL(zra_grep_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, tot);
-    hipLaunchKernelGGL(zra_grep_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), inv,
-                       (u32)ps.lastPass, (u64)hi, list, (u64)listCap);
-    if (listCap && pset.classes)
-      hipLaunchKernelGGL(zra_grep_fill_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, inv, (u64)ps.p0, sums,
-                         heads, list, (u64)listCap);
-    else if (listCap)
-      hipLaunchKernelGGL(zra_grep_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, inv, (u64)ps.p0, sums, heads,
-                         list, (u64)listCap);
-  }, &launches, cv);
-  if (st.zra) return st;
-  // ---- 5. the totals (they came back with the last synchronisation), then the list, once
-  const Totals& h = *(const Totals*)(head.data() + kTotals);
-  const State& fin = h.st[launches & 1];
-  const uint64_t total = fin.sel;
-  const size_t nOut = (size_t)std::min<uint64_t>(total, listCap);
-  if (nOut) {
-    HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, nOut * sizeof(Range), hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
-  }
-  *nRecords = total;
-  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, nOut, P.passes, h.matches};
-  std::copy(st8, st8 + 8, stats);
-  return ok();
-}
+Status ScanImpl::grep(Engine& E, const RecordCall& c, ScanCacheView* cv) { return record_scan<LiteralSelect, GrepKernels>(E, c, cv); }
 
 }  // namespace zra_eng

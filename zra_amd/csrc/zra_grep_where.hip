@@ -3,8 +3,9 @@
 // What `grep A | grep B | grep -v C` is to one grep per term.
 //
 // Records, matches, range, passes, ownership, (stream), (forward), (launches), (order) and (d) are the plain grep's (zra_grep.hip), word
-// for word; the pattern table, the staging and the test of one position are zra_patterns.h's, the driver is zra_scan.h's. The plain
-// grep's kernels are not touched: these are their twins, in a translation unit of their own. What differs:
+// for word; the pattern table, the staging and the test of one position are zra_patterns.h's, the driver is zra_scan.h's, the host
+// path in front of it zra_record_scan.h's (the literal selector's patterns under clauses, the kernel set at the end of this file). The
+// kernels are the plain grep's twins, in a translation unit of their own. What differs:
 //  (set) where the plain grep carries one bit (has the open record matched yet), this call carries a 64-bit word: the patterns that
 //      have hit in the open record so far. Sets are ORed where the grep ORs bits, and a record is selected by where_selected(set)
 //      (zra_where.h) where the grep tests bit ^ invert.
@@ -23,8 +24,7 @@
 //  (second walk) only the FIRST delimiter of a trip depends on what lies in front of the trip. The fill keeps four words per trip in
 //      LDS: the delimiter ballot, the selection ballot of the other delimiters, front and behind. Its second walk selects the first
 //      delimiter by one uniform test and never looks at a lane's set again.
-#include "zra_patterns.h"
-#include "zra_where.h"
+#include "zra_record_scan.h"
 
 namespace {
 using zra_where::Block;
@@ -337,88 +337,33 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepw_fill_class_kernel(co
 }
 
 // =================================================================================================
-namespace zra_eng {
-
-Status Engine::grep_archive_where(const uint8_t* dArc, size_t arcSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
-                                  uint8_t delimiter, uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
-                                  uint64_t* hRecords, size_t recordCap, uint64_t* nRecords) {
-  return ScanImpl::call(*this, kScanGrep, nRecords, nullptr, [&] {
-    return ScanImpl::grep_where(*this, dArc, arcSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, hClauses, nClauses, offset, size,
-                                stagingBytes, hRecords, recordCap, nRecords);
-  });
-}
-
-// ScanImpl::grep step by step; the differences are the clause checks in step 1, the shortcut of step 3 and the 32-byte entries.
-Status ScanImpl::grep_where(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                            uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords,
-                            size_t recordCap, uint64_t* nRecords, ScanCacheView* cv) {
-  // ---- 1. arguments
-  if (!nRecords || !hPat || !hSizes || (!dArc && arcSize) || (!hRecords && recordCap) || (mode & ~1u)) return zerr(42);
-  PatternSet pset;
-  if (!patterns_ok(hPat, hSizes, nPat, syntax, delimiter, &pset)) return zerr(42);
-  if (!zra_where::clauses_ok((const zra_where::Clause*)hClauses, nClauses, nPat)) return zerr(42);
-  const Block w = zra_where::make_block((const zra_where::Clause*)hClauses, nClauses, (mode & 1u) != 0);
-  const uint32_t M = pset.M, mMin = pset.mMin;
-  HIPCHK_CLR(hipSetDevice(E.device_));
-  hipStream_t s = E.stream_;
-  E.reset_decode_stats();
-  // ---- 2. header: the statuses of ZraHipArchiveOpen, as the search
-  ArchiveView arc;
-  { Status st = view(E, dArc, arcSize, cv, &arc); if (st.zra) return st; }
-  // ---- 3. the range [lo, hi)
-  uint64_t lo, hi;
-  if (!scan_range(arc.U, offset, size, &lo, &hi)) return {kOutOfBounds, 0};
-  uint64_t* const stats = E.callStats_[kScanGrep];
-  // no record, or every record's set is empty and the empty set is not selected
-  if (hi == lo || (hi - lo < mMin && !where_selected(w, 0))) { stats[0] = arc.frames; return ok(); }
-  if (arc.fs == 0 || arc.frames == 0) return {kHeaderInvalid, 0};
-  // ---- 4. the passes. tables: Table | Totals | sums[tiles] | heads[tiles]
-  const ScanPlan P = scan_plan(arc.U, arc.fs, lo, hi, M, 0, stagingBytes);
-  const size_t listCap = (size_t)std::min<uint64_t>(recordCap, hi - lo);
-  const size_t kTotals = pset.table_bytes() + 64, kHead = kTotals + sizeof(TotalsW);
-  static_assert((sizeof(Table) + 64 + sizeof(TotalsW)) % 16 == 0 && (sizeof(ClassTable) + 64 + sizeof(TotalsW)) % 16 == 0 && sizeof(SumW) == 32 && sizeof(HeadW) == 32 &&
-                sizeof(Range) == 16, "16-byte entries behind a 16-byte head");
-  std::vector<uint8_t> head(kHead, 0);                                       // (the totals go up as zeros, the state as "a record opens at lo", its set empty)
-  build_pattern_table(head.data(), pset, hPat, hSizes, nPat);
-  ((TotalsW*)(head.data() + kTotals))->st[0].start = lo;
-  uint32_t launches = 0;
-  Status st = ScanImpl::passes(E, arc, P, &E.callMs_[kScanGrep], head.data(), kHead, kTotals, sizeof(TotalsW), kHead + P.tilesMax * (sizeof(SumW) + sizeof(HeadW)) + 64,
-                               listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
-    uint8_t* const win = window(E), * const tb = E.scan_.tables.as<uint8_t>();
-    const Table* const tbl = (const Table*)tb;
-    const ClassTable* const ctbl = (const ClassTable*)tb;                    // (one of the two, by the syntax word)
-    TotalsW* const tot = (TotalsW*)(tb + kTotals);
-    SumW* const sums = (SumW*)(tb + kHead);
-    HeadW* const heads = (HeadW*)(sums + P.tilesMax);
-    Range* const list = E.scan_.list.as<Range>();
-    const uint32_t tiles = (uint32_t)((ps.nPos + kTile - 1) / kTile), groups = (tiles + kGroup - 1) / kGroup;
-    if (pset.classes)
-      hipLaunchKernelGGL(zra_grepw_count_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, w, (u64)ps.p0, sums, tot);
+// The kernel set of the grep with a record predicate for zra_record_scan.h's call path. tables: Table | Totals | sums[tiles] | heads[tiles]
+namespace {
+struct WhereKernels {
+  using Sum = SumW; using Head = HeadW; using Totals = TotalsW;
+  static constexpr size_t kMapBytes = 0;
+  static constexpr bool kData = false;
+  static void launch(hipStream_t s, const WhereSelect& sel, const RecordCall& c, const zra_eng::ScanPass& ps, const RecordPass<WhereKernels>& p, u32 parity) {
+    const Table* const tbl = (const Table*)p.table;
+    const ClassTable* const ctbl = (const ClassTable*)p.table;                // (one of the two, by the syntax word)
+    const u32 delim = c.delimiter, M = sel.M;
+    const Block& w = sel.w;
+    if (sel.pset.classes)
+      hipLaunchKernelGGL(zra_grepw_count_class_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, delim, w, (u64)ps.p0, p.sums, p.tot);
     else
-      hipLaunchKernelGGL(zra_grepw_count_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, w, (u64)ps.p0, sums, tot);
-    hipLaunchKernelGGL(zra_grepw_scan_kernel, dim3(1), dim3(1024), 0, s, sums, tiles, heads, tot->st + (launches & 1), tot->st + ((launches + 1) & 1), w,
-                       (u32)ps.lastPass, (u64)hi, list, (u64)listCap);
-    if (listCap && pset.classes)
-      hipLaunchKernelGGL(zra_grepw_fill_class_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, (u32)delimiter, w, (u64)ps.p0, sums,
-                         heads, list, (u64)listCap);
-    else if (listCap)
-      hipLaunchKernelGGL(zra_grepw_fill_kernel, dim3(groups), dim3(256), 0, s, win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, (u32)delimiter, w, (u64)ps.p0, sums, heads,
-                         list, (u64)listCap);
-  }, &launches, cv);
-  if (st.zra) return st;
-  // ---- 5. the totals (they came back with the last synchronisation), then the list, once
-  const TotalsW& h = *(const TotalsW*)(head.data() + kTotals);
-  const StateW& fin = h.st[launches & 1];
-  const uint64_t total = fin.sel;
-  const size_t nOut = (size_t)std::min<uint64_t>(total, listCap);
-  if (nOut) {
-    HIPCHK_CLR(hipMemcpyAsync(hRecords, E.scan_.list.p, nOut * sizeof(Range), hipMemcpyDeviceToHost, s));
-    HIPCHK_CLR(hipStreamSynchronize(s));
+      hipLaunchKernelGGL(zra_grepw_count_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, delim, w, (u64)ps.p0, p.sums, p.tot);
+    hipLaunchKernelGGL(zra_grepw_scan_kernel, dim3(1), dim3(1024), 0, s, p.sums, p.tiles, p.heads, p.tot->st + parity, p.tot->st + (parity ^ 1), w, (u32)ps.lastPass,
+                       (u64)p.hi, p.list, (u64)p.listCap);
+    if (p.listCap && sel.pset.classes)
+      hipLaunchKernelGGL(zra_grepw_fill_class_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, ctbl, delim, w, (u64)ps.p0, p.sums, p.heads,
+                         p.list, (u64)p.listCap);
+    else if (p.listCap)
+      hipLaunchKernelGGL(zra_grepw_fill_kernel, dim3(p.groups), dim3(256), 0, s, p.win, ps.xLo, ps.xHi, (u64)ps.nPos, M, tbl, delim, w, (u64)ps.p0, p.sums, p.heads, p.list,
+                         (u64)p.listCap);
   }
-  *nRecords = total;
-  const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, nOut, P.passes, h.matches};
-  std::copy(st8, st8 + 8, stats);
-  return ok();
-}
+};
+}  // namespace
 
+namespace zra_eng {
+Status ScanImpl::grep_where(Engine& E, const RecordCall& c, ScanCacheView* cv) { return record_scan<WhereSelect, WhereKernels>(E, c, cv); }
 }  // namespace zra_eng

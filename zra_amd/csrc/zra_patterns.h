@@ -1,8 +1,9 @@
 // zra_amd — the pattern table of the calls that look for several byte patterns in one pass over a staging window's plaintext
 // (zra_msearch.hip: ZraHipSearchArchiveMulti; zra_grep.hip: ZraHipGrepArchive; zra_extract.hip: ZraHipExtractRecords): its layout in
 // device memory and in LDS, the host code that builds it, and the device code that stages it and a tile of the window and tests one
-// position; for the two calls that cut the range into records, the two flags of a position and the list entry. Included by those three
-// files only (device code: a .hip translation unit). The tile and its staging: zra_scan_tile.h, shared with zra_search.hip.
+// position; for the calls that cut the range into records, the two flags of a position. Included by those files, zra_grep_where.hip
+// and, for the selectors of zra_record_scan.h, the two regex files (device code: a .hip translation unit). The tile, its staging and
+// the list entry: zra_scan_tile.h, shared with zra_search.hip.
 //  (filter) a 65,536-bit table in LDS: bit (b0 | b1 << 8) is set iff some pattern begins with b0 and is one byte long or goes on with
 //      b1. A position whose byte pair has no bit costs that one bit test; only a survivor is compared, against the patterns that begin
 //      with its first byte (bucketed on the host). The position hi - 1 has no second byte: it is a survivor iff a 1-byte pattern
@@ -20,7 +21,6 @@
 namespace {
 constexpr u32 kMaxPatterns = 64;          // ZRA_HIP_SEARCH_MAX_PATTERNS
 constexpr u32 kMaxPatternBytes = 4096;    // ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
-constexpr u32 kGroup = 8;                 // consecutive tiles of one workgroup
 
 // What the host makes of the patterns, as it lies in device memory and in LDS (13,376 bytes).
 struct __attribute__((aligned(16))) Table {
@@ -185,8 +185,7 @@ __device__ __forceinline__ u64 position_mask(const ClassTable* sT, const u32* sT
   return mask;
 }
 
-// ---- the grep and the extract: a position's two flags, a list entry
-struct __attribute__((aligned(16))) Range { u64 offset, size; };   // ZraHipContentRange
+// ---- the grep and the extract: a position's two flags (the list entry, Range, is zra_scan_tile.h's)
 constexpr u64 kHitBit = 1ull << 63;                                // the hit bit of the record open at a tile's head, beside its start
 
 // The two ballots of trip t of a wave (tile position j = w0 + 64 t + lane; d = the index of the tile's first byte in sTile; toHi = the

@@ -2,7 +2,7 @@
 // DESIGN.md §28): caller-supplied expressions, the syntax word and the delimiter become the minimal complete DFA of the set of matched
 // records, or a refusal with its reason. POSIX ERE over bytes on top of zra_pattern_expr.h's atoms: * + ? {n} {n,} {n,m} ( ) | ^ $.
 // Plain C++17, host only, no HIP types and nothing of the engine: tools/model/regex_check.cpp walks it on the CPU under the address
-// and undefined-behaviour sanitizers (tests/test_regex_abi.py). zra_grep_regex.hip uploads the table it makes.
+// and undefined-behaviour sanitizers (tests/test_regex_abi.py). The regex selector of zra_record_scan.h uploads the table it makes.
 //
 //  (parser) one loop over the bytes with an explicit stack of open groups: no recursion on what a caller wrote. Every read is behind a
 //      test against the expression's end, and the sizes are summed (in 64 bits) and bounded before the first byte is looked at. Nodes
@@ -39,7 +39,7 @@ enum : uint32_t { kAccepted = 0, kWhyArguments = 1, kWhySyntax = 2, kWhyEmptyAto
 
 struct Info { uint32_t states, classes, positions, why, pattern; };   // ZraHipRegexInfo
 
-// What the device steps through (zra_grep_regex.hip): uploaded as the head of the call's tables. Rows behind `classes` and columns
+// What the device steps through (zra_regex_tile.h): uploaded as the head of the call's tables. Rows behind `classes` and columns
 // behind `states` are zero: state 0 exists, so every entry is a state.
 struct alignas(16) Table {
   uint8_t classOf[256];          // the delimiter's entry is 0 and never read: the delimiter belongs to no class
@@ -422,7 +422,7 @@ inline bool compile(const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, ui
   return true;
 }
 
-// Is the record [r, r + n) matched: the table walked on the host (the checker and the tools; the device walks it in zra_grep_regex.hip)
+// Is the record [r, r + n) matched: the table walked on the host (the checker and the tools; the device walks it in zra_regex_tile.h)
 inline bool matches(const Table& t, const uint8_t* r, size_t n) {
   uint32_t s = t.start;
   for (size_t i = 0; i < n; i++) s = t.next[t.classOf[r[i]]][s];

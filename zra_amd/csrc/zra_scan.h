@@ -1,6 +1,8 @@
-// zra_amd — the host driver of the range scans: ZraHipSearchArchive (zra_search.hip), ZraHipSearchArchiveMulti (zra_msearch.hip),
-// ZraHipGrepArchive (zra_grep.hip) and ZraHipExtractRecords (zra_extract.hip). The four calls decode the frames of a content range a
-// staging window at a time and scan the window's plaintext with kernels of their own; what they share is written once, here:
+// zra_amd — the host driver of the range scans: ZraHipSearchArchive (zra_search.hip), ZraHipSearchArchiveMulti (zra_msearch.hip), and
+// the five record scans, which reach it through one call path (zra_record_scan.h): ZraHipGrepArchive (zra_grep.hip), its forms with a
+// record predicate (zra_grep_where.hip) and with regular expressions (zra_grep_regex.hip), ZraHipExtractRecords (zra_extract.hip) and
+// its form with regular expressions (zra_extract_regex.hip). The seven calls decode the frames of a content range a staging window at
+// a time and scan the window's plaintext with kernels of their own; what they share is written once, here:
 //
 //   1. the fixed header comes to the host (Engine::archive_view); the range becomes frames [f0, f1]       scan_range, scan_plan
 //   2. per pass of at most passSlots consecutive frames: the frames become decode jobs                   zra_search_jobs_kernel
@@ -44,29 +46,21 @@
 namespace zra_eng {
 
 struct ScanImpl {
-  // the four calls behind Engine's entry points, each in its own file. syntax: the pattern syntax word of the ...Expr entry points
+  // the two searches behind Engine's entry points, each in its own file. syntax: the pattern syntax word of the ...Expr entry points
   // (zra_pattern_expr.h), 0 for the literal ones
   static Status search(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, size_t m, uint64_t offset, uint64_t size, size_t stagingBytes,
                        uint64_t* hMatches, size_t matchCap, uint64_t* nMatches, ScanCacheView* cv = nullptr);
   static Status msearch(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint64_t offset,
                         uint64_t size, size_t stagingBytes, void* hMatches, size_t matchCap, uint64_t* nMatches, uint64_t* hPerPattern, ScanCacheView* cv = nullptr);
-  static Status grep(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                     uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, ScanCacheView* cv = nullptr);
-  // the grep with a record predicate (zra_grep_where.hip): hClauses = nClauses ZraHipRecordClause
-  static Status grep_where(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                           uint32_t mode, const void* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords,
-                           size_t recordCap, uint64_t* nRecords, ScanCacheView* cv = nullptr);
-  // the grep with regular expressions (zra_grep_regex.hip): hPat = nPat expressions, alternatives (zra_regex.h)
-  static Status grep_regex(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                           uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords,
-                           ScanCacheView* cv = nullptr);
-  static Status extract(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                        uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData, size_t dataCap,
-                        uint64_t* dataSize, ScanCacheView* cv = nullptr);
-  // the extract with regular expressions (zra_extract_regex.hip): grep_regex's selection, extract's outputs
-  static Status extract_regex(Engine& E, const uint8_t* dArc, size_t arcSize, const uint8_t* hPat, const uint32_t* hSizes, size_t nPat, uint32_t syntax, uint8_t delimiter,
-                              uint32_t mode, uint64_t offset, uint64_t size, size_t stagingBytes, uint64_t* hRecords, size_t recordCap, uint64_t* nRecords, uint8_t* dData,
-                              size_t dataCap, uint64_t* dataSize, ScanCacheView* cv = nullptr);
+  // the five record scans: zra_record_scan.h's one call path, instantiated with the selector and the kernel set of the file named;
+  // Engine::record_scan (below) picks one by RecordCall::kind. record_scan() itself goes through call(), for the row its kernel set names
+  template <class Selector, class Kernels>
+  static Status record_scan(Engine& E, const RecordCall& c, ScanCacheView* cv);
+  static Status grep(Engine& E, const RecordCall& c, ScanCacheView* cv);            // zra_grep.hip
+  static Status grep_where(Engine& E, const RecordCall& c, ScanCacheView* cv);      // zra_grep_where.hip
+  static Status grep_regex(Engine& E, const RecordCall& c, ScanCacheView* cv);      // zra_grep_regex.hip
+  static Status extract(Engine& E, const RecordCall& c, ScanCacheView* cv);         // zra_extract.hip
+  static Status extract_regex(Engine& E, const RecordCall& c, ScanCacheView* cv);   // zra_extract_regex.hip
 
   // What a call of the family leaves behind: entry_call's rule (zra_host.h). `which`: kScanSearch .. kScanExtract; out0 / out1: the
   // call's output words (either may be nullptr), kept on OutputTooSmall (the extract's rule 7, whose two words say what the call needs).
@@ -171,5 +165,17 @@ struct ScanImpl {
     return E.archive_view(dArc, arcSize, arc);
   }
 };
+
+// the one entry of the five record scans
+inline Status Engine::record_scan(const RecordCall& c, ScanCacheView* cv) {
+  switch (c.kind) {
+    case kRecGrep: return ScanImpl::grep(*this, c, cv);
+    case kRecGrepWhere: return ScanImpl::grep_where(*this, c, cv);
+    case kRecGrepRegex: return ScanImpl::grep_regex(*this, c, cv);
+    case kRecExtract: return ScanImpl::extract(*this, c, cv);
+    case kRecExtractRegex: return ScanImpl::extract_regex(*this, c, cv);
+  }
+  return zerr(42);
+}
 
 }  // namespace zra_eng

@@ -1,5 +1,6 @@
-// zra_amd — the tile of the range scans (zra_search.hip, and through zra_patterns.h zra_msearch.hip, zra_grep.hip, zra_extract.hip): how
-// many start positions a workgroup takes, how a tile of the staging window's plaintext gets into LDS and how a lane reads it there.
+// zra_amd — the tile of the range scans (zra_search.hip, through zra_patterns.h zra_msearch.hip, zra_grep.hip, zra_grep_where.hip and
+// zra_extract.hip, through zra_regex_tile.h the two regex files): how many start positions a workgroup takes, how a tile of the
+// staging window's plaintext gets into LDS and how a lane reads it there; the record scans' list entry.
 // Device code: included by .hip translation units only.
 #pragma once
 #include "zra_host.h"
@@ -18,6 +19,8 @@ constexpr u32 kWaveIters = kWavePos / 64;
 // staged bytes: up to 15 in front (the 16-byte alignment of the first global load), the tile, M - 1 halo bytes, rounded up to 16; the
 // compare reads whole words and may look up to 7 bytes beyond a pattern's end (masked off)
 constexpr u32 kLdsWords = (kTile + kMaxPattern + 64) / 4;
+constexpr u32 kGroup = 8;                 // consecutive tiles of one workgroup, in every call but the single search
+struct __attribute__((aligned(16))) Range { u64 offset, size; };   // a list entry of the record scans: ZraHipContentRange
 
 // the four bytes at byte index i of an LDS word array
 __device__ __forceinline__ u32 lds_word(const u32* s, u32 i) {
