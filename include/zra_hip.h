@@ -755,6 +755,53 @@ ZRA_EXPORT ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive,
     uint64_t offset, uint64_t size, size_t stagingBytes,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
 
+/* ---- grep with context records: the records in front of and behind each selected one ----
+ * `grep -A`, `-B`, `-C`. A log search wants the lines around a hit; with the calls above a caller decodes the neighbourhood of every
+ * hit a second time and cuts it at delimiters on the host. The grep pass sees every delimiter and every selection in order: this call
+ * keeps a summary that counts in records as well as in hits. */
+#define ZRA_HIP_GREP_MAX_CONTEXT   64u             /* records before, and records after: the width of a wave */
+#define ZRA_HIP_CONTEXT_SELECTED   (1ull << 63)    /* in ZraHipContentRange.size: the record itself is selected */
+
+/** ZraHipGrepArchiveExpr with `before` records in front of and `after` records behind every selected record. The patterns with their
+ *  `syntax` word (0, ZRA_HIP_PATTERN_FOLD_CASE, ZRA_HIP_PATTERN_CLASSES) and `delimiter`, `mode` (ZRA_HIP_GREP_INVERT only), the
+ *  range with its inclusive bound and size = UINT64_MAX, stagingBytes, the passes and ownership, "only the frames of the range" (whole
+ *  frames with verified checksums), host synchrony and the definition of the records of [lo, hi) are that call's, word for word.
+ *  Meaning. R_0 .. R_(n-1) are the records of [lo, hi), S the set of indices ZraHipGrepArchiveExpr selects (INVERT applied). The
+ *  output set is O = { k : some j in S has j - before <= k <= j + after }. Context never reaches outside the range: lo and hi end
+ *  the world as the file's ends do for grep. A group is a maximal run of consecutive indices in O: what grep separates by `--`.
+ *  Result. *nRecords = |O| (it may exceed the capacity); *nSelected = |S| and *nGroups = the number of groups (either pointer may be
+ *  NULL). The first min(|O|, recordCapacity) records of O go to hRecords, ascending, each once, as {offset, size} with
+ *  ZRA_HIP_CONTEXT_SELECTED set in size iff the record is in S (content sizes are 40-bit). Nothing is written behind them, and
+ *  nothing reaches the host before the last pass. recordCapacity 0 with hRecords NULL is the counting call. On any status but
+ *  Success hRecords is untouched, the three counts are 0 and the stats are zero. before == after == 0 is ZraHipGrepArchiveExpr's
+ *  list with the bit set in every entry. Every group is one contiguous content range (its first record's offset to its last
+ *  record's end), so ZraHipDecompressRABatch over the groups fetches the bytes.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchiveExpr's rule 1, then before or after above ZRA_HIP_GREP_MAX_CONTEXT -> {ZStdError, 42}.
+ *   2. to 5. Rules 2 to 5 of that call, both shortcuts included (the empty range, and without INVERT a range shorter than the
+ *      shortest pattern: Success, 0 records, nothing decoded, stats {frames, 0, ...}). Scratch is the grep's with 48 bytes per
+ *      8 KiB of window for the per-tile tables in the place of 32, and 16 * before bytes behind the list for the ranges that
+ *      wait for a later pass to select a record.
+ *  Stats: the call writes ZraHipGetGrepStats {frames, decoded, content bytes, records of the range, |O|, listed, passes, matches as
+ *  the grep counts them} and ZraHipDebugGrepScanMs.
+ *  Cost: profiles/grep_context.md.
+ *  Not covered: context with ZraHipGrepArchiveWhere, with regular expressions and with the two extracts; the packed bytes (see
+ *  above); more than ZRA_HIP_GREP_MAX_CONTEXT records of context; shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipGrepArchiveContext(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint32_t before, uint32_t after,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    uint64_t* nSelected, uint64_t* nGroups);
+/** ZraHipGrepArchiveContext through a ZraHipArchive handle: resident frames are staged from the cache as for ZraHipArchiveGrepExpr,
+ *  the cache is not changed, and the handle's scan counters (ZraHipArchiveGetScanStats) move as for that call. */
+ZRA_EXPORT ZraStatus ZraHipArchiveGrepContext(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint32_t before, uint32_t after,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    uint64_t* nSelected, uint64_t* nGroups);
+
 /* ---- grep with regular expressions: quantifiers, alternation and anchors ----
  * The calls above take patterns of fixed length, tested per position. A regular expression is a state machine over the bytes of a
  * record: this call compiles the expressions into one deterministic automaton on the host and carries its STATE through the scan

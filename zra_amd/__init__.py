@@ -209,6 +209,11 @@ def load():
         "ZraHipCheckRecordClauses": (S, [vp, sz, sz]),
         "ZraHipGrepArchiveWhere": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipArchiveGrepWhere": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        # the grep with context records: before and after behind `mode`, |S| and the groups behind nRecords
+        "ZraHipGrepArchiveContext": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
+                                         u64p, u64p]),
+        "ZraHipArchiveGrepContext": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p,
+                                         u64p]),
         # the grep with regular expressions: the syntax word behind nPatterns; ZraHipRegexInfo is five 32-bit words
         "ZraHipCheckRegex": (S, [vp, ctypes.POINTER(u32), sz, u32, ctypes.c_int, ctypes.POINTER(u32)]),
         "ZraHipGrepArchiveRegex": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
@@ -301,6 +306,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCheckPatternExpr", "ZraHipSearchArchiveMultiExpr", "ZraHipGrepArchiveExpr", "ZraHipExtractRecordsExpr",
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
                    "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere",
+                   "ZraHipGrepArchiveContext", "ZraHipArchiveGrepContext",
                    "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
                    "ZraHipExtractRecordsRegex", "ZraHipArchiveExtractRecordsRegex",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
@@ -590,6 +596,23 @@ class Engine:
                 max_records, ctypes.byref(n)), fn.__name__)
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_context(self, d_archive, size, patterns, *, before=0, after=0, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0,
+                     max_records=1 << 20, syntax=0):
+        """ZraHipGrepArchiveContext: grep()'s selected records (patterns, syntax, delimiter, invert and the range as there) with the
+        `before` records in front of and the `after` records behind each of them (`grep -B -A`; each at most GREP_MAX_CONTEXT), inside the
+        range. Returns (n_records, n_selected, n_groups, [(offset, size, selected)]): every output record is counted, the first
+        max_records are listed in ascending order, each once; a group is a run of consecutive output records (what grep separates by
+        `--`). Writes grep_stats(), whose `selected` is n_records. ZraError is a call that could not grep."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ns, ng = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipGrepArchiveContext(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), syntax, delimiter,
+                                             GREP_INVERT if invert else 0, before, after, offset, (1 << 64) - 1 if length is None else length, staging_bytes,
+                                             arr, max_records, ctypes.byref(n), ctypes.byref(ns), ctypes.byref(ng)), "ZraHipGrepArchiveContext")
+        return n.value, ns.value, ng.value, _context_list(arr, min(n.value, max_records))
 
     def grep_regex(self, d_archive, size, patterns, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0,
                    max_records=1 << 20):
@@ -895,6 +918,8 @@ SEARCH_MAX_PATTERNS = 64                     # ZRA_HIP_SEARCH_MAX_PATTERNS
 SEARCH_MAX_PATTERN_BYTES = 4096              # ZRA_HIP_SEARCH_MAX_PATTERN_BYTES
 SEARCH_MULTI_STATS = ("frames", "decoded", "content_bytes", "matches", "listed", "passes", "patterns", "survivors")
 GREP_INVERT = 1                              # ZRA_HIP_GREP_INVERT
+GREP_MAX_CONTEXT = 64                        # ZRA_HIP_GREP_MAX_CONTEXT: records before, and records after
+CONTEXT_SELECTED = 1 << 63                   # ZRA_HIP_CONTEXT_SELECTED, in a listed record's size
 PATTERN_FOLD_CASE = 1                        # ZRA_HIP_PATTERN_FOLD_CASE: ASCII letters match either case
 PATTERN_CLASSES = 2                          # ZRA_HIP_PATTERN_CLASSES: patterns are expressions: . [set] [^set] \escape
 PATTERN_MAX_SETS = 32                        # ZRA_HIP_PATTERN_MAX_SETS
@@ -919,6 +944,11 @@ def check_pattern_expr(patterns, syntax=PATTERN_CLASSES, delimiter=None):
     return [int(v) for v in lens[:len(patterns)]], int(ns.value)
 GREP_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "listed", "passes", "matches")
 WHERE_MAX_CLAUSES = 8                        # ZRA_HIP_WHERE_MAX_CLAUSES
+
+
+def _context_list(arr, k):
+    """the first k entries of a context grep's record array as (offset, size, selected)"""
+    return [(int(arr[2 * i]), int(arr[2 * i + 1]) & ~CONTEXT_SELECTED, bool(int(arr[2 * i + 1]) & CONTEXT_SELECTED)) for i in range(k)]
 
 
 def _pattern_set(term):
@@ -1096,6 +1126,18 @@ class Archive:
                 (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n)), fn.__name__)
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_context(self, patterns, *, before=0, after=0, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20, syntax=0):
+        """ZraHipArchiveGrepContext: Engine.grep_context through the handle. Returns (n_records, n_selected, n_groups, [(offset, size, selected)])."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ns, ng = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveGrepContext(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), syntax, delimiter, GREP_INVERT if invert else 0, before, after,
+                                             offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n), ctypes.byref(ns),
+                                             ctypes.byref(ng)), "ZraHipArchiveGrepContext")
+        return n.value, ns.value, ng.value, _context_list(arr, min(n.value, max_records))
 
     def grep_regex(self, patterns, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0, max_records=1 << 20):
         """ZraHipArchiveGrepRegex: Engine.grep_regex through the handle. Returns (n_records, [(offset, size)])."""

@@ -98,6 +98,8 @@ enum RecordKind : uint32_t {
   kRecExtract,       // ZraHipExtractRecords[Expr] (zra_extract.hip): kRecGrep's selection with the records' bytes. Writes extract_stats / extract_ms
   kRecExtractRegex,  // ZraHipExtractRecordsRegex (zra_extract_regex.hip): kRecGrepRegex's selection, kRecExtract's outputs, in one pass. Kernels of
                      // its own; writes the extract's counters (word 7: the matched records before the mode) and milliseconds
+  kRecGrepContext,   // ZraHipGrepArchiveContext (zra_grep_context.hip, zra_context.h): kRecGrep's selection with `before` records in front
+                     // of and `after` behind each selected one. Kernels of its own; writes the grep's counters (word 4: |O|) and milliseconds
 };
 struct RecordCall {
   RecordKind kind;
@@ -114,6 +116,9 @@ struct RecordCall {
   // kRecGrepWhere: a record is selected when one of the nClauses clauses {all, any, none} (ZraHipRecordClause) holds for the set of
   // patterns that hit in it
   const void* hClauses = nullptr; size_t nClauses = 0;
+  // kRecGrepContext: the context in records (each at most 64), and beside *nRecords = |O| the selected records and the groups (or null)
+  uint32_t before = 0, after = 0;
+  uint64_t* nSelected = nullptr, * nGroups = nullptr;
 };
 // The byte fetch of a record read through an archive handle (zra_records.hip): the located ranges as one read of the handle, a query
 // allowed to end AT the content's end. *jobs: the frames the fetch decoded.

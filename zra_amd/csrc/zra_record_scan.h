@@ -1,13 +1,14 @@
 // zra_amd — the one call path of the record scans: ZraHipGrepArchive (zra_grep.hip), ZraHipGrepArchiveWhere (zra_grep_where.hip),
 // ZraHipGrepArchiveRegex (zra_grep_regex.hip), ZraHipExtractRecords (zra_extract.hip), ZraHipExtractRecordsRegex
-// (zra_extract_regex.hip), their ...Expr forms and the same calls through an archive handle. The five cut a content range into
-// records at a delimiter, select records and return them as a list, the extracts with the records' bytes; they take the arguments of
+// (zra_extract_regex.hip), ZraHipGrepArchiveContext (zra_grep_context.hip), their ...Expr forms and the same calls through an archive
+// handle. They cut a content range into records at a delimiter, select records and return them as a list, the extracts with the
+// records' bytes, the grep with context with the records around the selected ones; they take the arguments of
 // one RecordCall (zra_engine.h) and differ in two things only, which record_scan() takes as types:
 //  a SELECTOR (three, below; host only): what the patterns of the call become. compile(): rule 1 beyond the nulls; M: the longest
 //      pattern, which the driver's (carry) and (ownership) run on; nothing(len): a range of len bytes in which no record can be
 //      selected; table_bytes() / build(): the table that heads the call's device tables; open(): the carried state of the record that
 //      opens at lo, beyond its start.
-//  a KERNEL SET (five, each next to its kernels): Sum / Head, the two per-tile entries, kMapBytes more per tile behind them; Totals =
+//  a KERNEL SET (six, each next to its kernels): Sum / Head, the two per-tile entries, kMapBytes more per tile behind them; Totals =
 //      {State st[2] (the ping-pong pair of zra_scan.h's (c)), matches, delims}; kData: the call packs bytes; launch(): the three
 //      launches of a pass, the third one only when a capacity asks for it.
 // record_scan() wraps its steps in ScanImpl::call for the row kData names, so the kernel set alone decides whose counters a call writes.
@@ -76,6 +77,13 @@ struct RecordPass {
   uint64_t listCap, hi;
   uint32_t tiles, groups;
 };
+
+// the two extra outputs of a kernel set whose carried state holds a context summary `c` (zra_context.h); nothing for the others
+template <class State> auto context_outputs(const State& fin, const RecordCall& c, int) -> decltype((void)fin.c) {
+  if (c.nSelected) *c.nSelected = fin.c.sel;
+  if (c.nGroups) *c.nGroups = fin.c.groups;
+}
+template <class State> void context_outputs(const State&, const RecordCall&, long) {}
 }  // namespace
 
 namespace zra_eng {
@@ -90,6 +98,7 @@ Status ScanImpl::record_scan(Engine& E, const RecordCall& c, ScanCacheView* cv) 
   return call(E, which, c.nRecords, K::kData ? c.dataSize : nullptr, [&]() -> Status {
   // ---- 1. arguments, the patterns, and (the calls with data) overlap with the archive and with the arena of the handle the call goes through
   if (!c.nRecords || !c.hPat || !c.hSizes || (!c.dArc && c.arcSize) || (!c.hRecords && c.recordCap) || (c.mode & ~1u)) return zerr(42);
+  if (c.before > 64 || c.after > 64) return zerr(42);                        // (ZRA_HIP_GREP_MAX_CONTEXT; 0 for every call but the one with context)
   if (K::kData && (!c.dataSize || (!c.dData && c.dataCap))) return zerr(42);
   Selector sel;
   if (!sel.compile(c)) return zerr(42);
@@ -121,7 +130,7 @@ Status ScanImpl::record_scan(Engine& E, const RecordCall& c, ScanCacheView* cv) 
   sel.open(h.st[0]);
   uint32_t launches = 0;                                                     // (the driver counts the callbacks in place: inside one, those in front of it)
   STCHK(passes(E, arc, P, &E.callMs_[which], head.data(), kHead, kTotals, sizeof(Totals),
-               kHead + P.tilesMax * (sizeof(typename K::Sum) + sizeof(typename K::Head) + K::kMapBytes) + 64, listCap * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
+               kHead + P.tilesMax * (sizeof(typename K::Sum) + sizeof(typename K::Head) + K::kMapBytes) + 64, (listCap + c.before) * sizeof(Range) + 64, true, [&](const ScanPass& ps) {
     uint8_t* const tb = E.scan_.tables.as<uint8_t>();
     RecordPass<K> p;
     p.win = window(E); p.table = tb;
@@ -146,6 +155,7 @@ Status ScanImpl::record_scan(Engine& E, const RecordCall& c, ScanCacheView* cv) 
     HIPCHK_CLR(hipMemcpyAsync(c.hRecords, E.scan_.list.p, (size_t)listed * sizeof(Range), hipMemcpyDeviceToHost, s));
     HIPCHK_CLR(hipStreamSynchronize(s));
   }
+  context_outputs(fin, c, 0);
   const uint64_t st8[8] = {arc.frames, decoded_frames(P, cv), decoded_bytes(P, cv), h.delims + fin.tail, total, word5, P.passes, h.matches};
   std::copy(st8, st8 + 8, stats);
   return ok();

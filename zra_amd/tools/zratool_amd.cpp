@@ -323,6 +323,37 @@ int grep_archive(const char* path, bool invert, uint8_t delimiter, char** texts,
   return total ? 0 : 1;
 }
 
+// mode glc: gle's patterns with `before` records in front of and `after` records behind every selected one; a selected record's line
+// ends in a tab and `*`, and `--` stands between two groups, as grep prints it
+int grep_archive_context(const char* path, bool invert, uint8_t delimiter, uint32_t before, uint32_t after, char** texts, int n, const ExprOpt* ex) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  uint32_t syntax = 0;
+  if (!gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  std::vector<ZraHipContentRange> at(1u << 20);
+  uint64_t total = 0, selected = 0, groups = 0;
+  st = ZraHipGrepArchiveContext(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, invert ? ZRA_HIP_GREP_INVERT : 0u, before, after, 0,
+                                UINT64_MAX, 0, at.data(), at.size(), &total, &selected, &groups);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot grep: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(total, at.size()); i++) {
+    const uint64_t size = at[i].size & ~ZRA_HIP_CONTEXT_SELECTED;
+    // neighbours in the range lie one delimiter apart: a record that does not begin there opens a group
+    if (i && at[i].offset != at[i - 1].offset + (at[i - 1].size & ~ZRA_HIP_CONTEXT_SELECTED) + 1) std::printf("--\n");
+    std::printf("%llu\t%llu%s\n", (unsigned long long)at[i].offset, (unsigned long long)size, (at[i].size & ZRA_HIP_CONTEXT_SELECTED) ? "\t*" : "");
+  }
+  if (total > at.size()) std::printf("... and %llu more\n", (unsigned long long)(total - at.size()));
+  std::printf("%llu records, %llu selected, %llu groups\n", (unsigned long long)total, (unsigned long long)selected, (unsigned long long)groups);
+  return total ? 0 : 1;
+}
+
 // glr's and gxr's expressions texts[0 .. n), alternatives: laid end to end and checked on the host
 bool gather_regex(char** texts, int n, bool fold, uint8_t delimiter, std::string* all, std::vector<uint32_t>* sizes, uint32_t* syntax) {
   for (int i = 0; i < n; i++) { *all += texts[i]; sizes->push_back((uint32_t)std::strlen(texts[i])); }
@@ -602,6 +633,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gme {file} {-i} {-F} {expression | hex:digits}...
 //       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
 //       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
+//       glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...
 //       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
 //       gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}...
 //       cmp {file A} {file B}
@@ -625,6 +657,7 @@ int main(int argc, char** argv) {
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
                 "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
+                "glc {file} {options of gle} {-A records} {-B records} {-C records} {expression | hex:digits}... - gle with context: up to 64 records behind (-A), in front of (-B) or around (-C) every selected record; a selected record is marked *, `--` separates groups (exit status as gl)\n"
                 "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}... - gl with regular expressions: POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on gle's atoms, several expressions are alternatives; -c: only the count (a refused expression: exit status 2)\n"
                 "gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}... - gx with glr's regular expressions: the text of the records glr lists, each with its delimiter, to stdout or to a file (exit status as glr)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
@@ -691,6 +724,31 @@ int main(int argc, char** argv) {
     if (pred) return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, &ex, &where);
     if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, expr ? &ex : nullptr);
     return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, expr ? &ex : nullptr);
+  }
+  if (mode == "glc") {
+    ExprOpt ex = {false, false};
+    bool invert = false;
+    unsigned long delimiter = 0x0A, before = 0, after = 0;
+    int i = 3;
+    for (; i < argc; i++) {
+      const std::string opt = argv[i];
+      char* end = nullptr;
+      if (opt == "-v") invert = true;
+      else if (opt == "-i") ex.fold = true;
+      else if (opt == "-F") ex.fixed = true;
+      else if (opt == "-A" || opt == "-B" || opt == "-C") {
+        unsigned long v = 0;
+        if (++i < argc) v = std::strtoul(argv[i], &end, 10);
+        if (i >= argc || !*argv[i] || *end || v > ZRA_HIP_GREP_MAX_CONTEXT) { std::fprintf(stderr, "%s takes 0 to %u records\n", opt.c_str(), ZRA_HIP_GREP_MAX_CONTEXT); return 2; }
+        if (opt != "-B") after = v;
+        if (opt != "-A") before = v;
+      } else if (opt == "-d") {
+        if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
+        if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
+      } else break;
+    }
+    if (i >= argc) { std::fprintf(stderr, "glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...\n"); return 2; }
+    return grep_archive_context(argv[2], invert, (uint8_t)delimiter, (uint32_t)before, (uint32_t)after, argv + i, argc - i, &ex);
   }
   if (mode == "glr" || mode == "gxr") {
     const bool text = mode == "gxr";
