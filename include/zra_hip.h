@@ -785,7 +785,8 @@ ZRA_EXPORT ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive,
  *  Stats: the call writes ZraHipGetGrepStats {frames, decoded, content bytes, records of the range, |O|, listed, passes, matches as
  *  the grep counts them} and ZraHipDebugGrepScanMs.
  *  Cost: profiles/grep_context.md.
- *  Not covered: context with ZraHipGrepArchiveWhere, with regular expressions and with the two extracts; the packed bytes (see
+ *  Not covered: context with ZraHipGrepArchiveWhere and with the two extracts (with regular expressions:
+ *  ZraHipGrepArchiveRegexContext, below); the packed bytes (see
  *  above); more than ZRA_HIP_GREP_MAX_CONTEXT records of context; shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchiveContext(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
@@ -870,7 +871,8 @@ ZRA_EXPORT ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPa
  *  fall.
  *  Not covered: match offsets, leftmost-longest spans, captures; ZraHipGrepArchiveWhere with regular expressions (the selected
  *  records' bytes: ZraHipExtractRecordsRegex, below); more than ZRA_HIP_REGEX_MAX_STATES states; backreferences, lazy or possessive quantifiers, look-around, word
- *  boundaries, POSIX classes, UTF-8 awareness; multi-byte delimiters, context lines, shards, the host-pointer API. */
+ *  boundaries, POSIX classes, UTF-8 awareness; multi-byte delimiters, shards, the host-pointer API. (Context lines:
+ *  ZraHipGrepArchiveRegexContext, below.) */
 ZRA_EXPORT ZraStatus ZraHipGrepArchiveRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
     uint8_t delimiter, uint32_t mode,
@@ -930,6 +932,46 @@ ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecordsRegex(ZraHipArchive* archive,
     uint64_t offset, uint64_t size, size_t stagingBytes,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
     void* dData, size_t dataCapacity, uint64_t* dataSize);
+
+/** The records ZraHipGrepArchiveRegex selects with `before` records in front of and `after` records behind each of them: what
+ *  `grep -E -A after -B before` prints, `--` lines counted, from one decode pass. The meaning is the composition of two contracts.
+ *  Selection: ZraHipGrepArchiveRegex's. 1 .. 64 expressions are alternatives, `syntax` is 0 or ZRA_HIP_PATTERN_FOLD_CASE, every
+ *  refusal of ZraHipCheckRegex applies, `mode` is ZRA_HIP_GREP_INVERT only, lo and hi cut records the way delimiters do (^ and $
+ *  hold at a clip), and every non-empty range is scanned: there is no "shorter than the shortest pattern" shortcut.
+ *  Result: ZraHipGrepArchiveContext's, with S the set of indices ZraHipGrepArchiveRegex selects (INVERT applied). O, the groups,
+ *  *nRecords = |O| (it may exceed the capacity), *nSelected = |S| and *nGroups (either pointer may be NULL); the first
+ *  min(|O|, recordCapacity) records of O in hRecords, ascending, ZRA_HIP_CONTEXT_SELECTED set in the size of the records of S.
+ *  Context never leaves [lo, hi). recordCapacity 0 with hRecords NULL is the counting call. Nothing is written behind the list,
+ *  nothing reaches the host before the last pass, and on every status but Success hRecords is untouched, the three counts are 0 and
+ *  the stats are zero. before == after == 0 gives ZraHipGrepArchiveRegex's list with the bit set in every entry.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchiveRegex's rule 1, then before or after above ZRA_HIP_GREP_MAX_CONTEXT -> {ZStdError, 42}.
+ *   2. to 5. Rules 2 to 5 of ZraHipGrepArchiveRegex. Scratch is the grep's with 128 bytes per 8 KiB of window for the per-tile
+ *      tables (a 16-byte summary, a 48-byte head and a 64-byte state map), and 16 * before bytes behind the list for the ranges that
+ *      wait for a later pass to select a record.
+ *  Stats: the call writes ZraHipGetGrepStats {frames, decoded, content bytes, records of the range, |O|, listed, passes, matches} and
+ *  ZraHipDebugGrepScanMs; matches is ZraHipGrepArchiveRegex's: the records of the range that the expression matches, before INVERT.
+ *  Cost: ZraHipGrepArchiveRegex's dependent walk per byte, unchanged; the context adds a reduction of the selection bits per tile, a
+ *  walk backwards in the one-workgroup scan and a second walk of the tiles that hold a listed record. Measured on 1 GiB of log lines
+ *  with a capacity of 2^20, the call's launches take 0.86 to 1.20 times the regex grep's scan: 1.08 to 1.20 at 0.1 % selected with 0
+ *  to 64 records each way, 1.09 down to 0.86 at 17.7 % (wider context reaches the capacity in fewer tiles), 1.09 with every record
+ *  selected (profiles/grep_regex_context.md).
+ *  Not covered: context with ZraHipGrepArchiveWhere and with the two extracts; match spans; more than ZRA_HIP_GREP_MAX_CONTEXT
+ *  records of context; shards, the host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipGrepArchiveRegexContext(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint32_t before, uint32_t after,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    uint64_t* nSelected, uint64_t* nGroups);
+/** ZraHipGrepArchiveRegexContext through a ZraHipArchive handle: resident frames are staged from the cache as for
+ *  ZraHipArchiveGrepRegex, the cache is not changed, and the handle's scan counters (ZraHipArchiveGetScanStats) move as for that call. */
+ZRA_EXPORT ZraStatus ZraHipArchiveGrepRegexContext(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint32_t before, uint32_t after,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    uint64_t* nSelected, uint64_t* nGroups);
 
 /* ---- compare: where the contents of two device-resident archives differ, without an output buffer for either ----
  * The `cmp` of the family. After an update there are two archives side by side, and a replica, or a checker, wants the changed byte

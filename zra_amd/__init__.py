@@ -223,6 +223,11 @@ def load():
                                           sz, u64p]),
         "ZraHipArchiveExtractRecordsRegex": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz,
                                                  u64p]),
+        # the regex grep with context records: ZraHipGrepArchiveContext's arguments
+        "ZraHipGrepArchiveRegexContext": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz,
+                                              u64p, u64p, u64p]),
+        "ZraHipArchiveGrepRegexContext": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
+                                              u64p, u64p]),
         # compare
         "ZraHipCompareArchives": (S, [vp, vp, sz, vp, sz, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, u64p]),
         "ZraHipGetCompareStats": (None, [vp, u64p]),
@@ -309,6 +314,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipGrepArchiveContext", "ZraHipArchiveGrepContext",
                    "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
                    "ZraHipExtractRecordsRegex", "ZraHipArchiveExtractRecordsRegex",
+                   "ZraHipGrepArchiveRegexContext", "ZraHipArchiveGrepRegexContext",
                    "ZraHipCompareArchives", "ZraHipGetCompareStats", "ZraHipGetCompareSizes", "ZraHipDebugCompareMs",
                    "ZraHipDiffArchives", "ZraHipGetDiffStats", "ZraHipDebugDiffMs",
                    "ZraHipSignArchive", "ZraHipGetSignStats", "ZraHipDebugSignMs",
@@ -630,6 +636,24 @@ class Engine:
                                            max_records, ctypes.byref(n)), "ZraHipGrepArchiveRegex")
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_regex_context(self, d_archive, size, patterns, *, before=0, after=0, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None,
+                           staging_bytes=0, max_records=1 << 20):
+        """ZraHipGrepArchiveRegexContext: grep_regex()'s selected records (expressions, delimiter, invert, fold_case and the range as
+        there) with the `before` records in front of and the `after` records behind each of them (`grep -E -B -A`; each at most
+        GREP_MAX_CONTEXT), inside the range. Returns what grep_context() returns, (n_records, n_selected, n_groups,
+        [(offset, size, selected)]), and writes grep_stats(), whose `selected` is n_records and whose `matches` is the number of
+        matched records. ZraError is a call that could not grep."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ns, ng = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._order()
+        _chk(self.L.ZraHipGrepArchiveRegexContext(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns),
+                                                  PATTERN_FOLD_CASE if fold_case else 0, delimiter, GREP_INVERT if invert else 0, before, after, offset,
+                                                  (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n), ctypes.byref(ns),
+                                                  ctypes.byref(ng)), "ZraHipGrepArchiveRegexContext")
+        return n.value, ns.value, ng.value, _context_list(arr, min(n.value, max_records))
 
     def grep_stats(self):
         """Counters of the last grep() on this engine (all zero unless it succeeded), keyed by GREP_STATS."""
@@ -1151,6 +1175,19 @@ class Archive:
                                            ctypes.byref(n)), "ZraHipArchiveGrepRegex")
         k = min(n.value, max_records)
         return n.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def grep_regex_context(self, patterns, *, before=0, after=0, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0,
+                           max_records=1 << 20):
+        """ZraHipArchiveGrepRegexContext: Engine.grep_regex_context through the handle. Returns (n_records, n_selected, n_groups, [(offset, size, selected)])."""
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+        n, ns, ng = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.engine._order()
+        _chk(self.L.ZraHipArchiveGrepRegexContext(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), PATTERN_FOLD_CASE if fold_case else 0, delimiter,
+                                                  GREP_INVERT if invert else 0, before, after, offset, (1 << 64) - 1 if length is None else length, staging_bytes,
+                                                  arr, max_records, ctypes.byref(n), ctypes.byref(ns), ctypes.byref(ng)), "ZraHipArchiveGrepRegexContext")
+        return n.value, ns.value, ng.value, _context_list(arr, min(n.value, max_records))
 
     def extract(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0, syntax=0):
         """ZraHipArchiveExtractRecords (syntax != 0: ...Expr): Engine.extract through the handle; d_data must overlap neither the archive nor the cache. Returns

@@ -967,6 +967,29 @@ ZraStatus ZraHipArchiveGrepContext(ZraHipArchive* archive, const void* hPatterns
   return mk(archive->c->record_scan({zra_eng::kRecGrepContext, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size,
                                      stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, nullptr, 0, nullptr, nullptr, 0, before, after, nSelected, nGroups}));
 }
+// ---- the regex grep with context records: kernels of its own (zra_grep_regex_context.hip), the grep's stats row and milliseconds
+ZraStatus ZraHipGrepArchiveRegexContext(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                                        uint32_t syntax, uint8_t delimiter, uint32_t mode, uint32_t before, uint32_t after, uint64_t offset, uint64_t size,
+                                        size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, uint64_t* nSelected,
+                                        uint64_t* nGroups) {
+  if (nRecords) *nRecords = 0;
+  if (nSelected) *nSelected = 0;
+  if (nGroups) *nGroups = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->record_scan({zra_eng::kRecGrepRegexContext, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter,
+                                    mode, offset, size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, nullptr, 0, nullptr, nullptr, 0, before, after, nSelected,
+                                    nGroups}));
+}
+ZraStatus ZraHipArchiveGrepRegexContext(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                        uint32_t mode, uint32_t before, uint32_t after, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
+                                        size_t recordCapacity, uint64_t* nRecords, uint64_t* nSelected, uint64_t* nGroups) {
+  if (nRecords) *nRecords = 0;
+  if (nSelected) *nSelected = 0;
+  if (nGroups) *nGroups = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->record_scan({zra_eng::kRecGrepRegexContext, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size,
+                                     stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, nullptr, 0, nullptr, nullptr, 0, before, after, nSelected, nGroups}));
+}
 // ---- the grep with a record predicate: kernels of its own (zra_grep_where.hip), the grep's stats row and milliseconds
 ZraStatus ZraHipCheckRecordClauses(const ZraHipRecordClause* hClauses, size_t nClauses, size_t nPatterns) {
   static_assert(sizeof(ZraHipRecordClause) == sizeof(zra_where::Clause) && ZRA_HIP_WHERE_MAX_CLAUSES == zra_where::kMaxClauses, "one clause layout");

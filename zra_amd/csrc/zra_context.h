@@ -1,6 +1,6 @@
 // zra_amd — context records (grep -A / -B / -C) over a stream of records whose selection bits are known: the algebra that does not
 // depend on HOW a record got selected. A kernel set hands it, per trip of 64 positions, the delimiter ballot and the ballot of "the
-// record this delimiter ends is selected"; zra_grep_context.hip is its first user, the where and regex sets can be the next.
+// record this delimiter ends is selected"; zra_grep_context.hip is its first user, zra_grep_regex_context.hip (trips of compacted delimiters) its second; the where set can be the next.
 //  (records) R_0 .. R_(n-1) with a selected set S; the output set is O = { k : some j in S has j - before <= k <= j + after }, a
 //      group is a maximal run of consecutive indices of O. before, after <= kMaxContext.
 //  (summary) Ctx describes a run of consecutive records AS IF no record outside the run were selected:

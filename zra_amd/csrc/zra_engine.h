@@ -100,6 +100,8 @@ enum RecordKind : uint32_t {
                      // its own; writes the extract's counters (word 7: the matched records before the mode) and milliseconds
   kRecGrepContext,   // ZraHipGrepArchiveContext (zra_grep_context.hip, zra_context.h): kRecGrep's selection with `before` records in front
                      // of and `after` behind each selected one. Kernels of its own; writes the grep's counters (word 4: |O|) and milliseconds
+  kRecGrepRegexContext,   // ZraHipGrepArchiveRegexContext (zra_grep_regex_context.hip, zra_regex_context.h): kRecGrepRegex's selection,
+                     // kRecGrepContext's outputs. Kernels of its own; writes the grep's counters (word 4: |O|, word 7: the matched records)
 };
 struct RecordCall {
   RecordKind kind;
@@ -116,7 +118,7 @@ struct RecordCall {
   // kRecGrepWhere: a record is selected when one of the nClauses clauses {all, any, none} (ZraHipRecordClause) holds for the set of
   // patterns that hit in it
   const void* hClauses = nullptr; size_t nClauses = 0;
-  // kRecGrepContext: the context in records (each at most 64), and beside *nRecords = |O| the selected records and the groups (or null)
+  // kRecGrepContext, kRecGrepRegexContext: the context in records (each at most 64), and beside *nRecords = |O| the selected records and the groups (or null)
   uint32_t before = 0, after = 0;
   uint64_t* nSelected = nullptr, * nGroups = nullptr;
 };

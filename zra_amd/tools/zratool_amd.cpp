@@ -367,6 +367,35 @@ bool gather_regex(char** texts, int n, bool fold, uint8_t delimiter, std::string
   return false;
 }
 
+// mode glrc: glr's expressions, glc's context, output and exit status
+int grep_archive_regex_context(const char* path, bool invert, bool fold, uint8_t delimiter, uint32_t before, uint32_t after, char** texts, int n) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  uint32_t syntax = 0;
+  if (!gather_regex(texts, n, fold, delimiter, &all, &sizes, &syntax)) return 2;
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  std::vector<ZraHipContentRange> at(1u << 20);
+  uint64_t total = 0, selected = 0, groups = 0;
+  st = ZraHipGrepArchiveRegexContext(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, invert ? ZRA_HIP_GREP_INVERT : 0u, before, after, 0,
+                                     UINT64_MAX, 0, at.data(), at.size(), &total, &selected, &groups);
+  if (dArc) (void)hipFree(dArc);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot grep: %s\n", path, ZraGetErrorString(st)); return 2; }
+  for (size_t i = 0; i < std::min<uint64_t>(total, at.size()); i++) {
+    const uint64_t size = at[i].size & ~ZRA_HIP_CONTEXT_SELECTED;
+    if (i && at[i].offset != at[i - 1].offset + (at[i - 1].size & ~ZRA_HIP_CONTEXT_SELECTED) + 1) std::printf("--\n");   // (as glc: a group opens)
+    std::printf("%llu\t%llu%s\n", (unsigned long long)at[i].offset, (unsigned long long)size, (at[i].size & ZRA_HIP_CONTEXT_SELECTED) ? "\t*" : "");
+  }
+  if (total > at.size()) std::printf("... and %llu more\n", (unsigned long long)(total - at.size()));
+  std::printf("%llu records, %llu selected, %llu groups\n", (unsigned long long)total, (unsigned long long)selected, (unsigned long long)groups);
+  return total ? 0 : 1;
+}
+
 // mode glr
 int grep_archive_regex(const char* path, bool invert, bool fold, bool countOnly, uint8_t delimiter, char** texts, int n) {
   std::string all;
@@ -636,6 +665,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...
 //       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
 //       gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}...
+//       glrc {file} {-i} {-v} {-d hex byte = 0a} {-A records} {-B records} {-C records} {expression}...
 //       cmp {file A} {file B}
 //       diff {file A} {file B} {-g grain}
 //       sign {file} {signature file} {-g grain} {-s seed}
@@ -660,6 +690,7 @@ int main(int argc, char** argv) {
                 "glc {file} {options of gle} {-A records} {-B records} {-C records} {expression | hex:digits}... - gle with context: up to 64 records behind (-A), in front of (-B) or around (-C) every selected record; a selected record is marked *, `--` separates groups (exit status as gl)\n"
                 "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}... - gl with regular expressions: POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on gle's atoms, several expressions are alternatives; -c: only the count (a refused expression: exit status 2)\n"
                 "gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}... - gx with glr's regular expressions: the text of the records glr lists, each with its delimiter, to stdout or to a file (exit status as glr)\n"
+                "glrc {file} {-i} {-v} {-d hex byte = 0a} {-A records} {-B records} {-C records} {expression}... - glr with glc's context: up to 64 records behind (-A), in front of (-B) or around (-C) every record glr selects; output and exit status as glc (a refused expression: exit status 2)\n"
                 "cmp {file A} {file B} - Compare the contents of two archives on the device: every differing range (exit status 0 equal, 1 different, 2 trouble)\n"
                 "diff {file A} {file B} {-g grain = 1} - The patch that gives archive A the content of archive B, on the device: every write, the tail (exit status 0 empty, 1 not empty, 2 trouble)\n"
                 "sign {file} {signature file} {-g grain = 4096} {-s seed = 0} - The content signature of an archive, on the device: per frame one hash of its compressed bytes and one per grain\n"
@@ -749,6 +780,29 @@ int main(int argc, char** argv) {
     }
     if (i >= argc) { std::fprintf(stderr, "glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...\n"); return 2; }
     return grep_archive_context(argv[2], invert, (uint8_t)delimiter, (uint32_t)before, (uint32_t)after, argv + i, argc - i, &ex);
+  }
+  if (mode == "glrc") {
+    bool invert = false, fold = false;
+    unsigned long delimiter = 0x0A, before = 0, after = 0;
+    int i = 3;
+    for (; i < argc; i++) {
+      const std::string opt = argv[i];
+      char* end = nullptr;
+      if (opt == "-v") invert = true;
+      else if (opt == "-i") fold = true;
+      else if (opt == "-A" || opt == "-B" || opt == "-C") {
+        unsigned long v = 0;
+        if (++i < argc) v = std::strtoul(argv[i], &end, 10);
+        if (i >= argc || !*argv[i] || *end || v > ZRA_HIP_GREP_MAX_CONTEXT) { std::fprintf(stderr, "%s takes 0 to %u records\n", opt.c_str(), ZRA_HIP_GREP_MAX_CONTEXT); return 2; }
+        if (opt != "-B") after = v;
+        if (opt != "-A") before = v;
+      } else if (opt == "-d") {
+        if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
+        if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
+      } else break;
+    }
+    if (i >= argc) { std::fprintf(stderr, "glrc {file} {-i} {-v} {-d hex byte = 0a} {-A records} {-B records} {-C records} {expression}...\n"); return 2; }
+    return grep_archive_regex_context(argv[2], invert, fold, (uint8_t)delimiter, (uint32_t)before, (uint32_t)after, argv + i, argc - i);
   }
   if (mode == "glr" || mode == "gxr") {
     const bool text = mode == "gxr";
