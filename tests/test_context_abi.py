@@ -1,6 +1,7 @@
 """CPU tests of the context grep's boundary (include/zra_hip.h: ZraHipGrepArchiveContext, ZraHipArchiveGrepContext): declared, exported
 and bound, every rule-1 refusal before anything touches a device with the outputs zeroed, no CPU result without a GPU, the zra_grepc_*
-kernels compiled without scratch, and the model the GPU tests use as their yardstick (tests/context_model.py) agrees with the system's
+kernels compiled without scratch, the end of a pass and its pending records under the host sanitizers
+(tools/model/context_pass_check.cpp), and the model the GPU tests use as their yardstick (tests/context_model.py) agrees with the system's
 `grep -F -b -A -B` (and `-v`) on generated lines and with answers pinned by hand."""
 import ctypes
 import json
@@ -86,6 +87,23 @@ def test_context_kernels_use_no_scratch():
         assert res[k]["scratch_bytes"] == 0 and res[k]["vgpr_spill"] == 0 and res[k]["sgpr_spill"] == 0, (k, res[k])
         assert res[k]["lds_bytes"] <= 65536, (k, res[k])
     assert all(res[k]["lds_bytes"] <= 32768 for k in kernels if "scan" not in k)
+
+
+def test_pending_check_program_under_the_host_sanitizers(tmp_path):
+    """(pending), zra_context.h's pass_end() and the slots the fill writes, pass by pass on streams of selection bits"""
+    checker = os.path.join(ROOT, "tools", "model", "context_pass_check.cpp")
+    csrc = os.path.join(ROOT, "zra_amd", "csrc")
+    exe = str(tmp_path / "context_pass_check")
+    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", csrc, checker, "-o", exe], check=True,
+                   capture_output=True, timeout=600)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
+    m = re.fullmatch(r"context_pass_check: (\d+) cases ok", r.stdout.strip().split("\n")[-1])
+    assert m and int(m.group(1)) >= 200000, r.stdout[-500:]
+    # stand-alone; the kernels of both sets include the header whose pass end it runs
+    assert re.findall(r'#include\s+"([^"]+)"', open(checker).read()) == ["zra_context.h"]
+    for name in ("zra_grep_context.hip", "zra_grep_regex_context.hip"):
+        assert '#include "zra_context_tile.h"' in open(os.path.join(csrc, name)).read(), name
 
 
 def _system_grep(tmp_path, data, pats, invert, after, before):

@@ -309,3 +309,43 @@ def test_cli_mode_glrc(zra, gpu_engine, tmp_path):
     for args in (("-A", 65, "a"), ("-B", "x", "a"), ("-C",), ("-A", 1), (), ("a**",), ("-C", 1, "(a"), ("a\\nb",)):
         r = run(*args)
         assert r.returncode == 2 and r.stdout == "", (args, r.stdout, r.stderr)
+
+
+# ---- 15
+def _both(eng, zra, d, size, pats, **kw):
+    """the literal call and the regex call on the same archive: they share zra_context_tile.h behind their selection bits"""
+    lit = ((0, 0),) + eng.grep_context(d.data_ptr(), size, pats, **kw)
+    rx = ((0, 0),) + eng.grep_regex_context(d.data_ptr(), size, pats, **kw)
+    assert rx == lit, (kw, rx[:4], lit[:4], sorted(set(rx[4]) ^ set(lit[4]))[:10])
+    return lit
+
+
+@pytest.mark.parametrize("before,after", [(3, 2), (64, 64), (0, 0)])
+def test_literal_and_regex_context_agree_at_frame_size_4(zra, gpu_engine, before, after):
+    """39 records of 0 to 6 bytes over `abc` in frames of 4 bytes, one frame to a pass: most passes end at most one record, so the
+    pending ranges are moved, kept and dropped pass by pass. `ab` as a literal pattern and as an expression selects the same
+    records; the lists, |S|, |O| and the groups of the two kernel sets must be identical, and the model's."""
+    data = SH.lines(np.random.RandomState(6), 150, b"abc", 6)
+    c = SH.case("seam_frame_size_4", data, 4, [b"ab"])
+    arc, d = _archive(gpu_engine, zra, c)
+    for inv in (False, True):
+        want, nsel, groups, recs, _ = SH.model(c, after, before, inv)
+        assert len(recs) == 39 and 0 < nsel < 39 and len(want) > 3
+        got = _both(gpu_engine, zra, d, len(arc), c["pats"], before=before, after=after, invert=inv, staging_bytes=1)
+        assert got == ((0, 0), len(want), nsel, groups, want), (inv, got[:4])
+        assert gpu_engine.grep_stats()["passes"] == -(-len(data) // 4)
+        cap = len(want) - 3                                                     # a capacity below |O|: the counts stay, the list is cut
+        got = _both(gpu_engine, zra, d, len(arc), c["pats"], before=before, after=after, invert=inv, staging_bytes=1, max_records=cap)
+        assert got == ((0, 0), len(want), nsel, groups, want[:cap]), (inv, cap, got[:4])
+
+
+def test_literal_and_regex_context_agree_with_more_tiles_than_scan_lanes(zra, gpu_engine):
+    """1,030 tiles: a lane of either scan kernel walks two tiles forwards and context_scan_tail walks them back; in nine passes of 128
+    tiles the carried state and the pending ranges cross the passes."""
+    c = SH.more_tiles_than_scan_lanes()
+    arc, d = _archive(gpu_engine, zra, c, level=1)
+    pats = [b"status=503", b"timeout after"]
+    for before, after, staging in ((64, 64, 16 * c["fs"]), (3, 2, 0)):
+        got = _both(gpu_engine, zra, d, len(arc), pats, before=before, after=after, staging_bytes=staging)
+        want, nsel, groups, _, _ = SH.model(c, after, before, False)         # (the literal patterns select what the case's expression does)
+        assert nsel == 16 and got == ((0, 0), len(want), nsel, groups, want), got[:4]

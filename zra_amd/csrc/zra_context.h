@@ -1,6 +1,7 @@
 // zra_amd — context records (grep -A / -B / -C) over a stream of records whose selection bits are known: the algebra that does not
 // depend on HOW a record got selected. A kernel set hands it, per trip of 64 positions, the delimiter ballot and the ballot of "the
-// record this delimiter ends is selected"; zra_grep_context.hip is its first user, zra_grep_regex_context.hip (trips of compacted delimiters) its second; the where set can be the next.
+// record this delimiter ends is selected"; zra_grep_context.hip is its first user, zra_grep_regex_context.hip (trips of compacted
+// delimiters) its second; the where set can be the next. What the kernels of such a set run alike is zra_context_tile.h's.
 //  (records) R_0 .. R_(n-1) with a selected set S; the output set is O = { k : some j in S has j - before <= k <= j + after }, a
 //      group is a maximal run of consecutive indices of O. before, after <= kMaxContext.
 //  (summary) Ctx describes a run of consecutive records AS IF no record outside the run were selected:
@@ -18,6 +19,14 @@
 //      when it is one of the stream's last `before` records outside every after-context: a later pass may still select a record.
 //  (true count) the records of O in front of a point = out of the run in front + confirmed(run in front, look at the point): the
 //      last min(uncovered tail, before - d) records of the run in front that only the next selected record brings in.
+//  (pending) -B breaks "nothing is ever patched later": whether the stream's last records are output is known only when a later pass
+//      selects a record, or never does. The carried state counts np <= before PENDING ranges, the stream's trailing records outside
+//      every after-context, kept ascending in a scratch of `before` entries. pass_end(): a pass whose first selected record has d
+//      unselected records of the pass in front keeps the last max(0, before - d) of them, moves those to the list behind the carried
+//      out count and drops the rest; a pass without a selected record keeps the last max(0, before - its own uncovered records) and
+//      moves them to the scratch's head; a pass that ends no record leaves them alone; the last pass drops what is pending. The pass's
+//      own pending records go behind the kept ones, the one with dist records behind it to slot pendBase + npThis - 1 - dist:
+//      np == min(uncovered tail of the stream, before) after every pass. tools/model/context_pass_check.cpp runs this on the host.
 #pragma once
 #include <stdint.h>
 
@@ -83,6 +92,42 @@ ZRA_CTX_FN uint32_t look_cat(uint32_t a, uint32_t b) { return look_has(a) ? a : 
 // (true count) how many of the uncovered tail records in front the next selected record brings in
 ZRA_CTX_FN uint32_t confirmed(uint32_t unc, uint32_t lk, uint32_t before) {
   return look_has(lk) && look_d(lk) < before ? umin(unc, before - look_d(lk)) : 0u;
+}
+
+// the (look) of a run of resolved records
+ZRA_CTX_FN uint32_t ctx_look(const Ctx& c) { return look(c.sel != 0, c.head); }
+// the (look) of a run with a delimiter whose first record is resolved: that record, then the run's others
+ZRA_CTX_FN uint32_t resolved_look(uint32_t sel1, const Ctx& rest) { return sel1 ? look(true, 0) : look(rest.sel != 0, 1 + rest.head); }
+
+// A Ctx in a per-tile summary word above the `low` bits the kernel set keeps for itself, `own`: a tile ends at most 8,192 records, so
+// own | head << low (8 bits) | tail << low + 8 (8) | sel << low + 16 (14) | out << low + 30 (14) | groups << low + 44 (13)
+ZRA_CTX_FN uint64_t ctx_pack(uint64_t own, const Ctx& c, uint32_t low) {
+  return own | (uint64_t)c.head << low | (uint64_t)c.tail << (low + 8) | c.sel << (low + 16) | c.out << (low + 30) | c.groups << (low + 44);
+}
+ZRA_CTX_FN Ctx ctx_unpack(uint64_t w, uint32_t low) {
+  Ctx c;
+  c.head = (uint32_t)(w >> low) & 0xFF; c.tail = (uint32_t)(w >> (low + 8)) & 0xFF;
+  c.sel = (w >> (low + 16)) & 0x3FFF; c.out = (w >> (low + 30)) & 0x3FFF; c.groups = w >> (low + 44);
+  return c;
+}
+
+// (pending) the end of a pass. passLook: the look of the pass's records, the record open at hi included; outIn, npIn: the stream's
+// out count and pending count carried into the pass; end: the Ctx at the pass's end. The old pending ranges [src, src + cnt) move to
+// the list at `to` (toList) or to the scratch's head; the pass's own go behind pendBase, npThis of them; np is carried on.
+struct PassEnd { uint32_t src, cnt, toList, pendBase, np, npThis; uint64_t to; };
+ZRA_CTX_FN PassEnd pass_end(uint32_t passLook, uint64_t outIn, uint32_t npIn, const Ctx& end, bool lastPass, uint32_t before, uint32_t after) {
+  const uint32_t d = look_d(passLook);
+  const bool has = look_has(passLook);
+  PassEnd e = {0, 0, has, npIn, 0, 0, outIn};
+  // d unselected records of the pass lie in front of its first selected one (has), or are all it ended: in both cases they push
+  // the older pending ranges out. (Without a selected record a carried after-context may cover some of the d, but then nothing is
+  // pending: npIn != 0 says that the stream's tail has left every after-context.)
+  if (has || d) { e.cnt = d < before ? umin(npIn, before - d) : 0; e.pendBase = has ? 0 : e.cnt; }
+  e.src = npIn - e.cnt;
+  e.np = lastPass ? 0 : umin(uncovered(end, after), before);
+  if (!has && !d) e.np = npIn;                                  // (the pass ended no record)
+  e.npThis = e.np > e.pendBase ? e.np - e.pendBase : 0;
+  return e;
 }
 
 #if defined(__HIPCC__)

@@ -3,58 +3,27 @@
 // {offset, size} pairs with ZRA_HIP_CONTEXT_SELECTED in the size of the selected ones; |S| and the number of groups beside |O|.
 // What `grep -F -f patterns -b -A after -B before` prints, `--` lines counted.
 //
-// The passes, the window, (stream), (launches) and (order) are zra_grep.hip's; the selector is the plain grep's (LiteralSelect), and the
-// algebra over records whose selection is known is zra_context.h's. This file's own:
+// The passes, the window, (stream), (launches) and (order) are zra_grep.hip's; the selector is the plain grep's (LiteralSelect); the
+// algebra over records whose selection is known, (pending) included, is zra_context.h's; the carried state, the head, the end of the
+// scan kernel and the fill's writing trip, which the regex set runs alike, are zra_context_tile.h's. This file's own:
 //  (summary) a run of positions reduces to Run = {flags, last: as the grep's Sum; c: zra_context.h's Ctx of the records that end inside
 //      the run APART from the first}, and combine() resolves the record that the second run's first delimiter ends, as the grep's does,
 //      and appends it: A.c + single(selected) + B.c.
 //  (launches) zra_grepc_count_kernel: per tile its Run; the totals as atomics. zra_grepc_scan_kernel, ONE workgroup: forwards, the
-//      tiles' Runs become per tile the Ctx of everything in front (the carried one included); backwards, per tile the (look) at its
-//      end, so a tile's Head has what its first and its last record need; the carried state moves on, (c). zra_grepc_fill_kernel: the
-//      workgroups redo the tiles that hold a listed or a pending record. A wave takes (forward) from the head and the waves in front
-//      and (look) from the head and the waves behind, walks its trips forwards (the selection), backwards (the look at every trip's
-//      end) and forwards again, writing: a record's list position is the (true count) in front of its wave plus the members of O in
-//      the earlier trips and lanes, never an atomic.
-//  (pending) -B breaks "nothing is ever patched later": whether the stream's last records are output is known only when a later pass
-//      selects a record, or never does. The carried state counts np <= before PENDING ranges, the stream's trailing records outside
-//      every after-context; they lie at pend = list + capacity, np entries, ascending. The scan of a pass whose first selected record
-//      has d unselected records of the pass in front keeps the last max(0, before - d) of them, moves those to the list behind the
-//      carried out count (a wave: read, barrier, write) and drops the rest; a pass without a selected record keeps the last
-//      max(0, before - its own uncovered records) and moves them to pend's head; a pass that ends no record leaves them alone; the
-//      last pass drops what is pending. The fill writes the pass's own pending records behind the kept ones: np == min(uncovered tail
-//      of the stream, before) after every pass. Nothing of this leaves the device before the last pass, (d).
+//      tiles' Runs become per tile the Ctx of everything in front (the carried one included) and the tile's own look; the walk
+//      backwards, the end of the pass and the carried state are context_scan_tail's. zra_grepc_fill_kernel: the workgroups redo the
+//      tiles that hold a listed or a pending record. A wave takes (forward) from the head and the waves in front and (look) from the
+//      head and the waves behind, walks its trips forwards (the selection, from the position masks kept in LDS), backwards (the look
+//      at every trip's end) and forwards again, writing.
 #include "zra_record_scan.h"
-#include "zra_context.h"
+#include "zra_context_tile.h"
 
 namespace {
-using zra_ctx::Ctx;
-constexpr u64 kSelectedBit = 1ull << 63;   // ZRA_HIP_CONTEXT_SELECTED
-
 struct __attribute__((aligned(16))) CRun { u64 last; u32 flags, pad; Ctx c; };
-// a tile's Run in device memory, 16 bytes as the grep's Sum: a tile ends at most 8,192 records, so w = flags (3 bits) | head << 3
-// (8) | tail << 11 (8) | sel << 19 (14) | out << 33 (14) | groups << 47 (13)
+// a tile's Run in device memory, 16 bytes as the grep's Sum: w = flags (3 bits) | zra_context.h's ctx_pack above them
 struct __attribute__((aligned(16))) CSum { u64 last, w; };
-__device__ __forceinline__ CSum pack(const CRun& r) {
-  CSum s;
-  s.last = r.last;
-  s.w = (u64)r.flags | (u64)r.c.head << 3 | (u64)r.c.tail << 11 | r.c.sel << 19 | r.c.out << 33 | r.c.groups << 47;
-  return s;
-}
-__device__ __forceinline__ CRun unpack(const CSum& s) {
-  CRun r;
-  r.last = s.last; r.flags = (u32)s.w & 7; r.pad = 0;
-  r.c.head = (u32)(s.w >> 3) & 0xFF; r.c.tail = (u32)(s.w >> 11) & 0xFF;
-  r.c.sel = (s.w >> 19) & 0x3FFF; r.c.out = (s.w >> 33) & 0x3FFF; r.c.groups = s.w >> 47;
-  return r;
-}
-// per tile for the fill: base = the (true count) in front of the tile, pend of which are confirmed records of the uncovered tail in
-// front; open = the grep's; fwd = {bit 31: a selected record in front, tail}; la = the (look) at the tile's end; cnt = the tile's
-// records in O
-struct __attribute__((aligned(16))) CHead { u64 base, open; u32 fwd, la, cnt, pend; };
-// the carried state: the grep's four words (sel = |O| so far), the Ctx of the stream so far, the pending count, and for the fill of
-// the pass that wrote it where its own pending records go
-struct CState { u64 start, hit, sel, tail; Ctx c; u32 np, pendBase, npThis, pad; };
-struct CTotals { CState st[2]; u64 matches, delims; };
+__device__ __forceinline__ CSum pack(const CRun& r) { return CSum{r.last, zra_ctx::ctx_pack((u64)r.flags, r.c, 3)}; }
+__device__ __forceinline__ CRun unpack(const CSum& s) { return CRun{s.last, (u32)s.w & 7, 0, zra_ctx::ctx_unpack(s.w, 3)}; }
 
 __device__ __forceinline__ void combine(CRun& A, const CRun& B, u32 inv, u32 before, u32 after) {
   if (!(B.flags & 1)) { if (B.flags & 2) A.flags |= (A.flags & 1) ? 4u : 6u; return; }
@@ -113,7 +82,7 @@ __device__ __forceinline__ CRun wave_run(const TB* sT, const u32* sTile, u32 d, 
 
 template <class TB>
 __device__ __forceinline__ void grepc_count(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 delim, u32 inv, u32 before, u32 after,
-                                            u64 p0, CSum* sums, CTotals* tot) {
+                                            u64 p0, CSum* sums, CtxTotals* tot) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
   __shared__ TB sT;
   __shared__ CRun sW[4];
@@ -142,31 +111,19 @@ __device__ __forceinline__ void grepc_count(const u8* win, long long xLo, long l
   if (lane == 0 && delims) atomicAdd((unsigned long long*)&tot->delims, (unsigned long long)delims);   // (a ballot's count: the same in every lane)
 }
 extern "C" __global__ void __launch_bounds__(256) zra_grepc_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
-                                                                         u32 inv, u32 before, u32 after, u64 p0, CSum* sums, CTotals* tot) {
+                                                                         u32 inv, u32 before, u32 after, u64 p0, CSum* sums, CtxTotals* tot) {
   grepc_count<Table>(win, xLo, xHi, nPos, M, tbl, delim, inv, before, after, p0, sums, tot);
 }
 extern "C" __global__ void __launch_bounds__(256) zra_grepc_count_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl,
-                                                                               u32 delim, u32 inv, u32 before, u32 after, u64 p0, CSum* sums, CTotals* tot) {
+                                                                               u32 delim, u32 inv, u32 before, u32 after, u64 p0, CSum* sums, CtxTotals* tot) {
   grepc_count<ClassTable>(win, xLo, xHi, nPos, M, tbl, delim, inv, before, after, p0, sums, tot);
 }
 
-namespace {
-// the record that a run's first delimiter ends, resolved, in front of the run's others: their look
-__device__ __forceinline__ u32 resolved_look(u32 sel1, const Ctx& rest) {
-  return sel1 ? zra_ctx::look(true, 0) : zra_ctx::look(rest.sel != 0, 1 + rest.head);
-}
-}  // namespace
-
 // One workgroup: (launches). Every lane reduces a run of consecutive tiles, the 1,024 Runs are scanned in LDS (Hillis-Steele over
-// combine()), the lane walks its run forwards from the state in front of it, the lanes' looks are scanned backwards, and the lane
-// walks its run backwards: heads[t]. Lane 1023 ends the open record at hi (lastPass), moves the pending ranges, (pending), and
-// writes the carried state. pend = list + cap.
-extern "C" __global__ void __launch_bounds__(1024) zra_grepc_scan_kernel(const CSum* sums, u32 nTiles, CHead* heads, const CState* in, CState* out, u32 inv, u32 before,
+// combine()), the lane walks its run forwards from the state in front of it, and context_scan_tail does the rest.
+extern "C" __global__ void __launch_bounds__(1024) zra_grepc_scan_kernel(const CSum* sums, u32 nTiles, CHead* heads, const CtxState* in, CtxState* out, u32 inv, u32 before,
                                                                          u32 after, u32 lastPass, u64 hi, Range* list, u64 cap) {
   __shared__ CRun sR[1024];
-  __shared__ u32 sLook[1024];
-  __shared__ u32 sMove[4];                                                   // {source in pend, count, to the list?, 0}
-  __shared__ u64 sMoveTo;
   const u32 tid = threadIdx.x;
   const u32 per = (nTiles + 1023) / 1024;
   const u32 b0 = min(nTiles, tid * per), b1 = min(nTiles, b0 + per);
@@ -183,7 +140,7 @@ extern "C" __global__ void __launch_bounds__(1024) zra_grepc_scan_kernel(const C
   }
   // forwards: the state in front of this lane's run is the carried one, then the lanes in front
   u64 start = in->start;
-  bool hit = in->hit != 0;
+  bool hit = in->state != 0;
   Ctx C = in->c;
   if (tid) {
     const CRun e = sR[tid - 1];
@@ -203,7 +160,7 @@ extern "C" __global__ void __launch_bounds__(1024) zra_grepc_scan_kernel(const C
     h.pend = zra_ctx::uncovered(C, after);                                    // (until the walk backwards knows how many of them count)
     if (s.flags & 1) {
       const u32 sel1 = (u32)(hit || (s.flags & 2)) ^ inv;
-      h.la = resolved_look(sel1, s.c);
+      h.la = zra_ctx::resolved_look(sel1, s.c);
       zra_ctx::push(C, sel1, before, after);
       zra_ctx::append(C, s.c, before, after);
       hit = (s.flags & 4) != 0; start = s.last;
@@ -211,81 +168,14 @@ extern "C" __global__ void __launch_bounds__(1024) zra_grepc_scan_kernel(const C
     runLook = zra_ctx::look_cat(runLook, h.la);
     heads[t] = h;
   }
-  // the record open at hi, and the look behind the last tile
-  u32 tailLook = zra_ctx::look(false, 0);
-  const bool tailRec = lastPass && start < hi, tailSel = (u32)hit != inv;
-  if (tid == 1023) {
-    if (tailRec) tailLook = tailSel ? zra_ctx::look(true, 0) : zra_ctx::look(false, 1);
-    runLook = zra_ctx::look_cat(runLook, tailLook);
-  }
-  sLook[tid] = runLook;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {
-    u32 b = 0;
-    const bool on = tid + d < 1024;
-    if (on) b = sLook[tid + d];
-    __syncthreads();
-    if (on) { runLook = zra_ctx::look_cat(runLook, b); sLook[tid] = runLook; }
-    __syncthreads();
-  }
-  // backwards: the look behind this lane's run, then tile by tile
-  u32 la = tid < 1023 ? sLook[tid + 1] : tailLook;
-  u64 nextBase = C.out + zra_ctx::confirmed(zra_ctx::uncovered(C, after), la, before);
-  for (u32 t = b1; t-- > b0;) {
-    CHead h = heads[t];
-    const u32 own = h.la;
-    h.la = la;
-    la = zra_ctx::look_cat(own, la);
-    h.pend = zra_ctx::confirmed(h.pend, la, before);
-    h.base += h.pend;
-    h.cnt = (u32)(nextBase - h.base);
-    nextBase = h.base;
-    heads[t] = h;
-  }
-  if (tid == 1023) {
-    const u32 passLook = sLook[0];                                           // the whole pass, the record open at hi included
-    const u32 npOld = in->np, d = zra_ctx::look_d(passLook);
-    u32 src = 0, cnt = 0, toList = 0, pendBase = npOld;
-    if (zra_ctx::look_has(passLook)) {
-      cnt = d < before ? min(npOld, before - d) : 0; src = npOld - cnt; toList = 1; pendBase = 0;
-    } else if (d) {
-      const u32 aOld = in->c.tail;
-      const u32 cov = in->c.sel && aOld < after ? min(after - aOld, d) : 0, u = d - cov;
-      cnt = u < before ? min(npOld, before - u) : 0; src = npOld - cnt; pendBase = cnt;
-    }
-    sMove[0] = src; sMove[1] = cnt; sMove[2] = toList; sMove[3] = 0;
-    sMoveTo = in->c.out;
-    u64 tail = 0;
-    if (tailRec) {
-      tail = 1;
-      const u64 at = C.out + (tailSel ? min(zra_ctx::uncovered(C, after), before) : 0u);
-      if ((tailSel || (C.sel && C.tail < after)) && at < cap) { Range q; q.offset = start; q.size = (hi - start) | (tailSel ? kSelectedBit : 0); list[at] = q; }
-      zra_ctx::push(C, tailSel, before, after);
-    }
-    CState o;
-    o.start = start; o.hit = hit; o.sel = C.out; o.tail = tail; o.c = C;
-    o.np = lastPass ? 0 : min(zra_ctx::uncovered(C, after), before);
-    if (!zra_ctx::look_has(passLook) && !d) o.np = npOld;
-    o.pendBase = pendBase; o.npThis = o.np > pendBase ? o.np - pendBase : 0; o.pad = 0;
-    *out = o;
-  }
-  __syncthreads();
-  // (pending) at most 64 entries, one wave's job; source and destination may overlap inside pend
-  const u32 cnt = sMove[1];
-  Range q; q.offset = 0; q.size = 0;
-  Range* const pend = list + cap;
-  if (tid < cnt && sMove[0] + tid < before) q = pend[sMove[0] + tid];
-  __syncthreads();
-  if (tid < cnt && sMove[0] + tid < before) {
-    if (sMove[2]) { if (sMoveTo + tid < cap) list[sMoveTo + tid] = q; }
-    else pend[tid] = q;
-  }
+  const bool tailRec = lastPass && start < hi, tailSel = (u32)hit != inv;      // the record open at hi
+  context_scan_tail(C, start, hit, runLook, tailRec, tailSel, b0, b1, heads, in, out, list, cap, hi, lastPass, before, after);
 }
 
 // The count's workgroups redo the tiles that hold a record of O in front of the capacity, or a pending one.
 template <class TB>
 __device__ __forceinline__ void grepc_fill(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const TB* tbl, u32 delim, u32 inv, u32 before, u32 after,
-                                           u64 p0, const CSum* sums, const CHead* heads, const CState* st, Range* list, u64 cap) {
+                                           u64 p0, const CSum* sums, const CHead* heads, const CtxState* st, Range* list, u64 cap) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
   __shared__ TB sT;
   __shared__ CRun sW[4];
@@ -294,17 +184,12 @@ __device__ __forceinline__ void grepc_fill(const u8* win, long long xLo, long lo
   const u32 tiles = (u32)((nPos + kTile - 1) / kTile);
   const u32 bBegin = blockIdx.x * kGroup, bEnd = min(tiles, bBegin + kGroup);
   const u32 pendBase = st->pendBase, npThis = st->npThis;
-  Range* const pend = list + cap;
-  auto wanted = [&](u32 b) {                                                 // (uniform in the workgroup)
-    const CHead h = heads[b];
-    return (h.cnt != 0 && h.base < cap) || (npThis != 0 && (sums[b].w & 1) && !zra_ctx::look_has(h.la) && zra_ctx::look_d(h.la) < npThis);
-  };
   bool any = false;
-  for (u32 b = bBegin; b < bEnd; b++) any |= wanted(b);
+  for (u32 b = bBegin; b < bEnd; b++) any |= context_wanted(heads, sums, b, npThis, cap);
   if (!any) return;
   stage_table(tbl, &sT);
   for (u32 b = bBegin; b < bEnd; b++) {
-    if (!wanted(b)) continue;
+    if (!context_wanted(heads, sums, b, npThis, cap)) continue;
     const CHead head = heads[b];
     const u64 t0 = (u64)b * kTile;
     const u32 n = (u32)min((u64)kTile, nPos - t0);
@@ -318,7 +203,7 @@ __device__ __forceinline__ void grepc_fill(const u8* win, long long xLo, long lo
     __syncthreads();
     if (!(mine.flags & 1)) continue;                                         // (uniform in the wave; the barriers are at the loop's head)
     // (forward) in front of this wave and the (look) behind it, from the head and the four Runs
-    Ctx C = Ctx{(head.fwd & zra_ctx::kLookHas) ? 1u : 0u, head.base - head.pend, 0, 0, head.fwd & ~zra_ctx::kLookHas};
+    Ctx C = context_front(head);
     bool hit = (head.open & kHitBit) != 0;
     u64 start = head.open & ~kHitBit;
 #pragma unroll 1
@@ -338,7 +223,7 @@ __device__ __forceinline__ void grepc_fill(const u8* win, long long xLo, long lo
     for (u32 w = wave + 1; w < 4; w++) {
       const u32 f = sW[w].flags;
       if (!(f & 1)) { hit |= (f & 2) != 0; continue; }
-      behind = zra_ctx::look_cat(behind, resolved_look((u32)(hit || (f & 2)) ^ inv, sW[w].c));
+      behind = zra_ctx::look_cat(behind, zra_ctx::resolved_look((u32)(hit || (f & 2)) ^ inv, sW[w].c));
       hit = (f & 4) != 0;
     }
     u32 la = zra_ctx::look_cat(behind, head.la);
@@ -355,12 +240,7 @@ __device__ __forceinline__ void grepc_fill(const u8* win, long long xLo, long lo
       const u32 tl = zra_ctx::ctx_trip_look(dm, sm);
       if (lane == t) keep = tl;
     }
-#pragma unroll 1
-    for (u32 t = trips; t-- > 0;) {
-      const u32 tl = (u32)__shfl((int)keep, (int)t, 64);
-      if (lane == t) keep = la;
-      la = zra_ctx::look_cat(tl, la);
-    }
+    la = context_looks_back(keep, la, trips, lane);
     // la is now the look at the wave's head: the (true count) in front of it
     u64 at = myC.out + zra_ctx::confirmed(zra_ctx::uncovered(myC, after), la, before);
     bool fAny = myC.sel != 0;
@@ -374,46 +254,31 @@ __device__ __forceinline__ void grepc_fill(const u8* win, long long xLo, long lo
       const u64 recStart = e.start;
       u64 dmr;
       const u64 sm = select_trip(e, dm, hm, lane, inv, pos, &dmr);
-      const u32 lk = (u32)__shfl((int)keep, (int)t, 64);
-      bool inO = false, has = false;
-      u32 dist = 0;
-      const bool isD = (dm >> lane) & 1;
-      if (isD) zra_ctx::ctx_member(dm, sm, lane, fAny, fTail, lk, before, after, &inO, &has, &dist);
-      const u64 om = __ballot(inO);
       const u64 below = (1ull << lane) - 1, dBelow = dm & below;
       Range q;
       q.offset = dBelow ? pos + (63 - (u32)__builtin_clzll(dBelow)) + 1 : recStart;
-      q.size = (pos + lane - q.offset) | (((sm >> lane) & 1) ? kSelectedBit : 0);
-      if (inO) {
-        const u64 idx = at + (u32)__popcll(om & below);
-        if (idx < cap) list[idx] = q;
-      } else if (isD && !has && dist < npThis) {
-        const u32 slot = pendBase + npThis - 1 - dist;
-        if (slot < before) pend[slot] = q;
-      }
-      at += (u32)__popcll(om);
-      if (sm) { fAny = true; const u32 ls = 63 - (u32)__builtin_clzll(sm); fTail = ls < 63 ? (u32)__popcll(dm >> (ls + 1)) : 0; }
-      else fTail = zra_ctx::sat(fTail + (u32)__popcll(dm));
+      q.size = pos + lane - q.offset;
+      context_write_trip(dm, sm, lane, q, (u32)__shfl((int)keep, (int)t, 64), at, fAny, fTail, list, cap, pendBase, npThis, before, after);
     }
   }
 }
 extern "C" __global__ void __launch_bounds__(256) zra_grepc_fill_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const Table* tbl, u32 delim,
-                                                                        u32 inv, u32 before, u32 after, u64 p0, const CSum* sums, const CHead* heads, const CState* st,
+                                                                        u32 inv, u32 before, u32 after, u64 p0, const CSum* sums, const CHead* heads, const CtxState* st,
                                                                         Range* list, u64 cap) {
   grepc_fill<Table>(win, xLo, xHi, nPos, M, tbl, delim, inv, before, after, p0, sums, heads, st, list, cap);
 }
 extern "C" __global__ void __launch_bounds__(256) zra_grepc_fill_class_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, u32 M, const ClassTable* tbl,
                                                                               u32 delim, u32 inv, u32 before, u32 after, u64 p0, const CSum* sums, const CHead* heads,
-                                                                              const CState* st, Range* list, u64 cap) {
+                                                                              const CtxState* st, Range* list, u64 cap) {
   grepc_fill<ClassTable>(win, xLo, xHi, nPos, M, tbl, delim, inv, before, after, p0, sums, heads, st, list, cap);
 }
 
 // =================================================================================================
-// The kernel set of the grep with context for zra_record_scan.h's call path. tables: Table | CTotals | sums[tiles] | heads[tiles];
+// The kernel set of the grep with context for zra_record_scan.h's call path. tables: Table | CtxTotals | sums[tiles] | heads[tiles];
 // the list scratch holds `before` pending entries behind the capacity.
 namespace {
 struct ContextKernels {
-  using Sum = ::CSum; using Head = ::CHead; using Totals = ::CTotals;
+  using Sum = ::CSum; using Head = ::CHead; using Totals = ::CtxTotals;
   static constexpr size_t kMapBytes = 0;
   static constexpr bool kData = false;
   static void launch(hipStream_t s, const LiteralSelect& sel, const RecordCall& c, const zra_eng::ScanPass& ps, const RecordPass<ContextKernels>& p, u32 parity) {

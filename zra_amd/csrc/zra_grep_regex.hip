@@ -147,8 +147,9 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepx_fill_kernel(const u8
     __syncthreads();
     // the selection bit of the record that delimiter k ends (nD is not zero: a record ends here)
     const u32 nD = regex_select(&sD, sTile, d, n, delim, sPos, sCnt, start, head.state, accept, inv, [&](u32 k, u32, u32 bit) { sBit[k] = (u8)bit; });
-    // a wave takes a quarter of the delimiters (whole trips): its selected records, then the ballot walk
-    const u32 quarter = ((nD + 255) / 256) * 64, k0 = wave * quarter, k1 = min(nD, k0 + quarter);
+    // a wave takes its share of the delimiters: its selected records, then the ballot walk
+    u32 k0, k1;
+    wave_share(nD, wave, &k0, &k1);
     u32 on = 0;
     for (u32 k = k0; k < k1; k += 64) on += (u32)__popcll(__ballot(k + lane < k1 && sBit[k + lane]));
     if (lane == 0) sOn[wave] = on;

@@ -4,64 +4,40 @@
 // |O|. What `grep -E -e expr... -b -A after -B before` prints, `--` lines counted.
 //
 // The passes, the window, (stream), (launches) and (order) are zra_grep.hip's; the selector is the regex grep's (RegexSelect), the
-// automaton in LDS, the walks and the delimiter compaction are zra_regex_tile.h's, the algebra over records whose selection is known
-// is zra_context.h's, and what joins the two, (summary), (combine) and (front), is zra_regex_context.h's. (pending) is
-// zra_grep_context.hip's, word for word. This file's own:
+// automaton in LDS, the walks and the delimiter compaction are zra_regex_tile.h's, the algebra over records whose selection is known,
+// (pending) included, is zra_context.h's, what joins the two, (summary), (combine) and (front), is zra_regex_context.h's, and the
+// carried state, the head, the end of the scan kernel and the fill's writing trip, which the literal set runs alike, are
+// zra_context_tile.h's. This file's own:
 //  (count) zra_grepxc_count_kernel: the tile's delimiters compacted into LDS, one lane per record from the start state, as the regex
 //      grep's count; the selection bits stay in LDS by delimiter, and the waves reduce a quarter of them each to a Ctx, in trips of
 //      64 COMPACTED delimiters: dm is the mask of the trip's valid lanes, sm the bits, record 0 left out. Per tile a 16-byte summary
 //      and the 64-byte head map.
 //  (scan) zra_grepxc_scan_kernel, ONE workgroup of 1,024 lanes. Forwards: every lane reduces a run of tiles with (combine), the 1,024
 //      Runs and maps are scanned in LDS (64 KiB of maps, 48 KiB of Runs), then the lane walks its run from the (front) in front of it:
-//      per tile the DFA state and the Ctx in front, and, its first record now resolved, the tile's own look. Backwards: the lanes'
-//      looks are scanned, and the lane walks its run back: per tile the look at its end and the (true count) in front. The last lane
-//      ends the record open at hi, moves the pending ranges and writes the carried state. Neither direction depends on before or
-//      after beyond the arithmetic of Ctx.
+//      per tile the DFA state and the Ctx in front, and, its first record now resolved, the tile's own look. Backwards, the end of
+//      the pass and the carried state: context_scan_tail. Neither direction depends on before or after beyond the arithmetic of Ctx.
 //  (fill) zra_grepxc_fill_kernel: the tiles with a listed or a pending record are redone. regex_select gives every delimiter's bit,
 //      the head record's from the state in the tile's head entry, so a wave's quarter reduces to a Ctx with nothing left open; the
 //      (forward) in front of a wave is the head's and the waves' in front, the (look) behind it the waves' behind and the head's. Then
-//      zra_grep_context.hip's three walks over the trips of compacted delimiters: looks, looks backwards, and the writes at prefix
-//      counts, the pending records behind the capacity.
+//      the three walks over the trips of compacted delimiters: looks, looks backwards, and the writes at prefix counts, the pending
+//      records behind the capacity.
 // Every loop is bounded by the tile's size, no workgroup waits for another one, and no tile byte beyond hi is read.
 #include "zra_record_scan.h"
 #include "zra_regex_tile.h"
 #include "zra_regex_context.h"
+#include "zra_context_tile.h"
 
 namespace {
-using zra_ctx::Ctx;
 using zra_rxc::Run;
 using zra_rxc::Front;
-constexpr u64 kSelectedBit = 1ull << 63;   // ZRA_HIP_CONTEXT_SELECTED
 
-// a tile's Run in device memory, 16 bytes, its map apart: a tile ends at most 8,192 records, so w = has (1 bit) | tail state << 1 (6)
-// | head << 7 (8) | tail << 15 (8) | sel << 23 (14) | out << 37 (14) | groups << 51 (13)
+// a tile's Run in device memory, 16 bytes, its map apart: w = has (1 bit) | tail state << 1 (6) | zra_context.h's ctx_pack above them
 struct __attribute__((aligned(16))) XCSum { u64 last, w; };
-__device__ __forceinline__ XCSum pack(const Run& r) {
-  XCSum s;
-  s.last = r.last;
-  s.w = (u64)r.has | (u64)r.tail << 1 | (u64)r.c.head << 7 | (u64)r.c.tail << 15 | r.c.sel << 23 | r.c.out << 37 | r.c.groups << 51;
-  return s;
-}
-__device__ __forceinline__ Run unpack(const XCSum& s) {
-  Run r;
-  r.last = s.last; r.has = (u32)s.w & 1; r.tail = (u32)(s.w >> 1) & 63;
-  r.c.head = (u32)(s.w >> 7) & 0xFF; r.c.tail = (u32)(s.w >> 15) & 0xFF;
-  r.c.sel = (s.w >> 23) & 0x3FFF; r.c.out = (s.w >> 37) & 0x3FFF; r.c.groups = s.w >> 51;
-  return r;
-}
-// per tile for the fill: base, open, fwd, la, cnt, pend as zra_grep_context.hip's CHead; state = the DFA state of the record open at
-// the tile's first position
-struct __attribute__((aligned(16))) XCHead { u64 base, open; u32 fwd, la, cnt, pend, state, pad[3]; };
-// the carried state: the regex grep's four words (sel = |O| so far), the Ctx of the stream so far, and the pending words of
-// zra_grep_context.hip's CState
-struct XCState { u64 start, state, sel, tail; Ctx c; u32 np, pendBase, npThis, pad; };
-struct XCTotals { XCState st[2]; u64 matches, delims; };
+__device__ __forceinline__ XCSum pack(const Run& r) { return XCSum{r.last, zra_ctx::ctx_pack((u64)r.has | (u64)r.tail << 1, r.c, 7)}; }
+__device__ __forceinline__ Run unpack(const XCSum& s) { return Run{s.last, (u32)s.w & 1, (u32)(s.w >> 1) & 63, zra_ctx::ctx_unpack(s.w, 7)}; }
+// per tile for the fill: CHead and the DFA state of the record open at the tile's first position
+struct __attribute__((aligned(16))) XCHead : CHead { u32 state, pad[3]; };
 
-// a wave's share of a tile's nD compacted delimiters: a quarter, in whole trips
-__device__ __forceinline__ void wave_share(u32 nD, u32 wave, u32* k0, u32* k1) {
-  const u32 quarter = ((nD + 255) / 256) * 64;
-  *k0 = wave * quarter; *k1 = min(nD, *k0 + quarter);
-}
 // One trip of compacted delimiters [k, k + 64) below k1: the mask of the valid lanes and their selection bits; skip0: record 0 is
 // not the tile's to decide.
 __device__ __forceinline__ void trip_bits(const u8* sBit, u32 k, u32 k1, u32 lane, bool skip0, u64* dm, u64* sm) {
@@ -84,7 +60,7 @@ __device__ __forceinline__ Ctx share_ctx(const u8* sBit, u32 k0, u32 k1, u32 lan
 
 // The run of a pass, its tiles and workgroups: zra_grep.hip's grep_count. Per tile its summary -> sums[tile] and its map -> maps[tile].
 extern "C" __global__ void __launch_bounds__(256) zra_grepxc_count_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, const RxTable* tbl, u32 delim, u32 inv,
-                                                                          u32 before, u32 after, u64 p0, XCSum* sums, u8* maps, XCTotals* tot) {
+                                                                          u32 before, u32 after, u64 p0, XCSum* sums, u8* maps, CtxTotals* tot) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
   __shared__ __attribute__((aligned(16))) Dfa sD;
   __shared__ u16 sPos[kTile];
@@ -145,14 +121,11 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepxc_count_kernel(const 
 }
 
 // One workgroup: (scan). pend = list + cap.
-extern "C" __global__ void __launch_bounds__(1024) zra_grepxc_scan_kernel(const XCSum* sums, const u8* maps, u32 nTiles, XCHead* heads, const XCState* in, XCState* out,
+extern "C" __global__ void __launch_bounds__(1024) zra_grepxc_scan_kernel(const XCSum* sums, const u8* maps, u32 nTiles, XCHead* heads, const CtxState* in, CtxState* out,
                                                                           const RxTable* tbl, u32 inv, u32 before, u32 after, u32 lastPass, u64 hi, Range* list, u64 cap,
-                                                                          XCTotals* tot) {
+                                                                          CtxTotals* tot) {
   __shared__ __attribute__((aligned(16))) u32 sMap[1024 * 16];
   __shared__ Run sR[1024];
-  __shared__ u32 sLook[1024];
-  __shared__ u32 sMove[4];                                                   // {source in pend, count, to the list?, 0}
-  __shared__ u64 sMoveTo;
   const u64 accept = tbl->accept;
   const u32 tid = threadIdx.x;
   const u32 per = (nTiles + 1023) / 1024;
@@ -209,82 +182,16 @@ extern "C" __global__ void __launch_bounds__(1024) zra_grepxc_scan_kernel(const 
     runLook = zra_ctx::look_cat(runLook, h.la);
     heads[t] = h;
   }
-  // the record open at hi, and the look behind the last tile
-  u32 tailLook = zra_ctx::look(false, 0);
+  // the record open at hi
   const bool tailRec = lastPass && f.start < hi, tailSel = zra_rxc::selected(accept, f.state, inv) != 0;
-  if (tid == 1023) {
-    if (tailRec) { tailLook = tailSel ? zra_ctx::look(true, 0) : zra_ctx::look(false, 1); matched += zra_rxc::accepts(accept, f.state); }
-    runLook = zra_ctx::look_cat(runLook, tailLook);
-  }
-  sLook[tid] = runLook;
-  __syncthreads();
-  for (u32 d = 1; d < 1024; d <<= 1) {
-    u32 b = 0;
-    const bool on = tid + d < 1024;
-    if (on) b = sLook[tid + d];
-    __syncthreads();
-    if (on) { runLook = zra_ctx::look_cat(runLook, b); sLook[tid] = runLook; }
-    __syncthreads();
-  }
-  // ---- backwards: the look behind this lane's run, then tile by tile
-  Ctx& C = f.c;
-  u32 la = tid < 1023 ? sLook[tid + 1] : tailLook;
-  u64 nextBase = C.out + zra_ctx::confirmed(zra_ctx::uncovered(C, after), la, before);
-  for (u32 t = b1; t-- > b0;) {
-    XCHead h = heads[t];
-    const u32 own = h.la;
-    h.la = la;
-    la = zra_ctx::look_cat(own, la);
-    h.pend = zra_ctx::confirmed(h.pend, la, before);
-    h.base += h.pend;
-    h.cnt = (u32)(nextBase - h.base);
-    nextBase = h.base;
-    heads[t] = h;
-  }
-  if (tid == 1023) {
-    const u32 passLook = sLook[0];                                           // the whole pass, the record open at hi included
-    const u32 npOld = in->np, d = zra_ctx::look_d(passLook);
-    u32 src = 0, cnt = 0, toList = 0, pendBase = npOld;
-    if (zra_ctx::look_has(passLook)) {
-      cnt = d < before ? min(npOld, before - d) : 0; src = npOld - cnt; toList = 1; pendBase = 0;
-    } else if (d) {
-      const u32 aOld = in->c.tail;
-      const u32 cov = in->c.sel && aOld < after ? min(after - aOld, d) : 0, u = d - cov;
-      cnt = u < before ? min(npOld, before - u) : 0; src = npOld - cnt; pendBase = cnt;
-    }
-    sMove[0] = src; sMove[1] = cnt; sMove[2] = toList; sMove[3] = 0;
-    sMoveTo = in->c.out;
-    u64 tail = 0;
-    if (tailRec) {
-      tail = 1;
-      const u64 at = C.out + (tailSel ? min(zra_ctx::uncovered(C, after), before) : 0u);
-      if ((tailSel || (C.sel && C.tail < after)) && at < cap) { Range q; q.offset = f.start; q.size = (hi - f.start) | (tailSel ? kSelectedBit : 0); list[at] = q; }
-      zra_ctx::push(C, tailSel, before, after);
-    }
-    XCState o;
-    o.start = f.start; o.state = f.state; o.sel = C.out; o.tail = tail; o.c = C;
-    o.np = lastPass ? 0 : min(zra_ctx::uncovered(C, after), before);
-    if (!zra_ctx::look_has(passLook) && !d) o.np = npOld;
-    o.pendBase = pendBase; o.npThis = o.np > pendBase ? o.np - pendBase : 0; o.pad = 0;
-    *out = o;
-  }
+  if (tid == 1023 && tailRec) matched += zra_rxc::accepts(accept, f.state);
   if (matched) atomicAdd((unsigned long long*)&tot->matches, (unsigned long long)matched);
-  __syncthreads();
-  // (pending) at most 64 entries, one wave's job; source and destination may overlap inside pend
-  const u32 cnt = sMove[1];
-  Range q; q.offset = 0; q.size = 0;
-  Range* const pend = list + cap;
-  if (tid < cnt && sMove[0] + tid < before) q = pend[sMove[0] + tid];
-  __syncthreads();
-  if (tid < cnt && sMove[0] + tid < before) {
-    if (sMove[2]) { if (sMoveTo + tid < cap) list[sMoveTo + tid] = q; }
-    else pend[tid] = q;
-  }
+  context_scan_tail(f.c, f.start, f.state, runLook, tailRec, tailSel, b0, b1, heads, in, out, list, cap, hi, lastPass, before, after);
 }
 
 // The count's workgroups redo the tiles that hold a record of O in front of the capacity, or a pending one: (fill).
 extern "C" __global__ void __launch_bounds__(256) zra_grepxc_fill_kernel(const u8* win, long long xLo, long long xHi, u64 nPos, const RxTable* tbl, u32 delim, u32 inv,
-                                                                         u32 before, u32 after, u64 p0, const XCSum* sums, const XCHead* heads, const XCState* st,
+                                                                         u32 before, u32 after, u64 p0, const XCSum* sums, const XCHead* heads, const CtxState* st,
                                                                          Range* list, u64 cap) {
   __shared__ __attribute__((aligned(16))) u32 sTile[kLdsWords];
   __shared__ __attribute__((aligned(16))) Dfa sD;
@@ -296,19 +203,14 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepxc_fill_kernel(const u
   const u32 tiles = (u32)((nPos + kTile - 1) / kTile);
   const u32 bBegin = blockIdx.x * kGroup, bEnd = min(tiles, bBegin + kGroup);
   const u32 pendBase = st->pendBase, npThis = st->npThis;
-  Range* const pend = list + cap;
-  auto wanted = [&](u32 b) {                                                 // (uniform in the workgroup)
-    const XCHead h = heads[b];
-    return (h.cnt != 0 && h.base < cap) || (npThis != 0 && (sums[b].w & 1) && !zra_ctx::look_has(h.la) && zra_ctx::look_d(h.la) < npThis);
-  };
   bool any = false;
-  for (u32 b = bBegin; b < bEnd; b++) any |= wanted(b);
+  for (u32 b = bBegin; b < bEnd; b++) any |= context_wanted(heads, sums, b, npThis, cap);
   if (!any) return;
   const u32 start = tbl->start;
   const u64 accept = tbl->accept;
   stage_dfa(tbl, &sD, tbl->classes);
   for (u32 b = bBegin; b < bEnd; b++) {
-    if (!wanted(b)) continue;
+    if (!context_wanted(heads, sums, b, npThis, cap)) continue;
     const XCHead head = heads[b];
     const u64 t0 = (u64)b * kTile;
     const u32 n = (u32)min((u64)kTile, nPos - t0);
@@ -325,7 +227,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepxc_fill_kernel(const u
     __syncthreads();
     if (k0 >= k1) continue;                                                  // (uniform in the wave; the barriers are in front)
     // (forward) in front of this wave and the (look) behind it, from the head and the four shares
-    Ctx C = Ctx{(head.fwd & zra_ctx::kLookHas) ? 1u : 0u, head.base - head.pend, 0, 0, head.fwd & ~zra_ctx::kLookHas};
+    Ctx C = context_front(head);
 #pragma unroll 1
     for (u32 w = 0; w < wave; w++) zra_ctx::append(C, sW[w], before, after);
     u32 behind = zra_ctx::look(false, 0);
@@ -342,12 +244,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepxc_fill_kernel(const u
       const u32 tl = zra_ctx::ctx_trip_look(dm, sm);
       if (lane == t) keep = tl;
     }
-#pragma unroll 1
-    for (u32 t = trips; t-- > 0;) {
-      const u32 tl = (u32)__shfl((int)keep, (int)t, 64);
-      if (lane == t) keep = la;
-      la = zra_ctx::look_cat(tl, la);
-    }
+    la = context_looks_back(keep, la, trips, lane);
     // la is now the look at the share's head: the (true count) in front of it
     u64 at = C.out + zra_ctx::confirmed(zra_ctx::uncovered(C, after), la, before);
     bool fAny = C.sel != 0;
@@ -357,27 +254,12 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepxc_fill_kernel(const u
       u64 dm, sm;
       trip_bits(sBit, k0 + t * 64, k1, lane, false, &dm, &sm);
       const u32 k = k0 + t * 64 + lane;
-      const bool isD = (dm >> lane) & 1;
-      const u32 lk = (u32)__shfl((int)keep, (int)t, 64);
-      bool inO = false, has = false;
-      u32 dist = 0;
-      if (isD) zra_ctx::ctx_member(dm, sm, lane, fAny, fTail, lk, before, after, &inO, &has, &dist);
-      const u64 om = __ballot(inO);
       Range q; q.offset = 0; q.size = 0;
-      if (isD) {
+      if ((dm >> lane) & 1) {
         q.offset = k ? p0 + t0 + sPos[k - 1] + 1 : head.open;
-        q.size = (p0 + t0 + sPos[k] - q.offset) | (((sm >> lane) & 1) ? kSelectedBit : 0);
+        q.size = p0 + t0 + sPos[k] - q.offset;
       }
-      if (inO) {
-        const u64 idx = at + (u32)__popcll(om & ((1ull << lane) - 1));
-        if (idx < cap) list[idx] = q;
-      } else if (isD && !has && dist < npThis) {
-        const u32 slot = pendBase + npThis - 1 - dist;
-        if (slot < before) pend[slot] = q;
-      }
-      at += (u32)__popcll(om);
-      if (sm) { fAny = true; const u32 ls = 63 - (u32)__builtin_clzll(sm); fTail = ls < 63 ? (u32)__popcll(dm >> (ls + 1)) : 0; }
-      else fTail = zra_ctx::sat(fTail + (u32)__popcll(dm));
+      context_write_trip(dm, sm, lane, q, (u32)__shfl((int)keep, (int)t, 64), at, fAny, fTail, list, cap, pendBase, npThis, before, after);
     }
   }
 }
@@ -387,7 +269,7 @@ extern "C" __global__ void __launch_bounds__(256) zra_grepxc_fill_kernel(const u
 // | maps[tiles]; the list scratch holds `before` pending entries behind the capacity.
 namespace {
 struct RegexContextKernels {
-  using Sum = XCSum; using Head = XCHead; using Totals = XCTotals;
+  using Sum = XCSum; using Head = XCHead; using Totals = CtxTotals;
   static constexpr size_t kMapBytes = 64;
   static constexpr bool kData = false;
   static void launch(hipStream_t s, const RegexSelect& sel, const RecordCall& c, const zra_eng::ScanPass& ps, const RecordPass<RegexContextKernels>& p, u32 parity) {
@@ -402,7 +284,7 @@ struct RegexContextKernels {
                          p.heads, p.tot->st + (parity ^ 1), p.list, (u64)p.listCap);
   }
 };
-static_assert(sizeof(XCTotals) == 176 && sizeof(XCSum) == 16 && sizeof(XCHead) == 48 && sizeof(Run) == 48, "the entries as the kernels index them");
+static_assert(sizeof(CtxTotals) == 176 && sizeof(XCSum) == 16 && sizeof(XCHead) == 48 && sizeof(Run) == 48, "the entries as the kernels index them");
 }  // namespace
 
 namespace zra_eng {

@@ -54,12 +54,9 @@ ZRA_CTX_FN bool finish(Front& f, uint64_t hi, uint64_t accept, uint32_t inv, uin
   return true;
 }
 
-// the (look) of a run with a delimiter whose first record is resolved: that record, then the run's others
-ZRA_CTX_FN uint32_t resolved_look(uint32_t sel1, const Ctx& rest) {
-  return sel1 ? zra_ctx::look(true, 0) : zra_ctx::look(rest.sel != 0, 1 + rest.head);
-}
-// the (look) of a run of resolved records
-ZRA_CTX_FN uint32_t ctx_look(const Ctx& c) { return zra_ctx::look(c.sel != 0, c.head); }
+// the (look) of a run whose first record is resolved, and of a run of resolved records: zra_context.h's
+using zra_ctx::resolved_look;
+using zra_ctx::ctx_look;
 
 // F := m o F over the 64 states, a byte each (the host's form of zra_regex_tile.h's compose)
 ZRA_CTX_FN void compose_bytes(uint8_t* F, const uint8_t* m) {

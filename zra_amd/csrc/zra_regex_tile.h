@@ -1,9 +1,10 @@
 // zra_amd — the tile of the two regex record scans (zra_grep_regex.hip: ZraHipGrepArchiveRegex; zra_extract_regex.hip:
-// ZraHipExtractRecordsRegex): the automaton in LDS, a lane's walk over a record, a tile's delimiters, the
-// composition of maps, and the two pieces the two calls run alike: the forward half of the one-workgroup scan (regex_scan_forward;
-// kBytes: the extract's two summary fields {first, bytes} ride along) and phase 1 of the fill and the copy (regex_select). The two
-// count kernels stay in their files: joined into one body they measured slower for the extract (profiles/record_scan_refactor.md). (state), (summary), (count) and (scan) are described in zra_grep_regex.hip, the two fields in
-// zra_extract_regex.hip. Device code: included by those two translation units only.
+// ZraHipExtractRecordsRegex): the automaton in LDS, a lane's walk over a record, a tile's delimiters and a wave's
+// share of them, the composition of maps, and the two pieces the two calls run alike: the forward half of the one-workgroup scan
+// (regex_scan_forward; kBytes: the extract's two summary fields {first, bytes} ride along) and phase 1 of the fill and the copy
+// (regex_select). The two count kernels stay in their files: joined into one body they measured slower for the extract
+// (profiles/record_scan_refactor.md). (state), (summary), (count) and (scan) are described in zra_grep_regex.hip, the two fields in
+// zra_extract_regex.hip. Device code: included by those two translation units and by zra_grep_regex_context.hip.
 #pragma once
 #include "zra_scan_tile.h"
 #include "zra_regex.h"
@@ -55,6 +56,12 @@ __device__ __forceinline__ u32 compact_delims(const u32* sTile, u32 d, u32 n, u3
   }
   __syncthreads();
   return all;
+}
+
+// a wave's share of a tile's nD compacted delimiters: a quarter, in whole trips
+__device__ __forceinline__ void wave_share(u32 nD, u32 wave, u32* k0, u32* k1) {
+  const u32 quarter = ((nD + 255) / 256) * 64;
+  *k0 = wave * quarter; *k1 = min(nD, *k0 + quarter);
 }
 
 // F := m o src, maps of 64 states as 16 words of four: F[s] = m[src[s]]. F lives in registers, indexed by constants only; src may be F.
