@@ -221,6 +221,11 @@ ZRA_EXPORT void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t
 /** Bring-up aid, like ZraHipDebugUpdateStageMs: HIP-event time of the last accepted scan's job-split and stage-from-cache launches,
  *  summed over its passes; 0 when none ran. archive NULL: 0. */
 ZRA_EXPORT double ZraHipDebugArchiveScanStageMs(const ZraHipArchive* archive);
+/** Bring-up aid: where the handle's arena lies, [*base, *base + *bytes) in device memory, so that a test can aim a buffer at it and
+ *  see the arena check of the calls above, of ZraHipArchiveUpdate and of the extracts through a handle refuse it. The arena is the
+ *  handle's own: nothing but the handle may write it, and the range holds until ZraHipArchiveClose. A handle without a cache, and
+ *  archive NULL, give NULL and 0; base or bytes NULL: no-op. */
+ZRA_EXPORT void ZraHipDebugArchiveArena(const ZraHipArchive* archive, const void** base, size_t* bytes);
 
 /* ---- the record index through the handle: index, locate and read records from the frame cache ----
  * ZraHipIndexRecords, ZraHipLocateRecords and ZraHipReadRecords (below) are the one read path whose caller comes back to the same frames
@@ -738,7 +743,7 @@ ZRA_EXPORT ZraStatus ZraHipCheckRecordClauses(const ZraHipRecordClause* hClauses
  *  Cost: the grep's; a trip of 64 positions in which something hit pays one lane read per hitting lane and one ballot per distinct
  *  pattern that hit in it, or, from 8 hitting lanes on, a six-step scan over the lanes: 1.01 to 1.04 times the grep's scan time on
  *  log text, 1.35 times with a hit at nearly every position (profiles/grep_where.md). The plain entry points keep their own kernels.
- *  Not covered: ZraHipExtractRecords with a predicate, per-pattern record counts, quantifiers, alternation inside a pattern, anchors (ZraHipGrepArchiveRegex, below),
+ *  The selected records' bytes: ZraHipExtractRecordsWhere, below. Not covered: per-pattern record counts, quantifiers, alternation inside a pattern, anchors (ZraHipGrepArchiveRegex, below),
  *  context lines, shards, the host-pointer API. */
 ZRA_EXPORT ZraStatus ZraHipGrepArchiveWhere(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
     const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
@@ -754,6 +759,60 @@ ZRA_EXPORT ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive,
     const ZraHipRecordClause* hClauses, size_t nClauses,
     uint64_t offset, uint64_t size, size_t stagingBytes,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords);
+
+/** The records ZraHipGrepArchiveWhere selects WITH their bytes, packed: the text `grep A | grep B | grep -v C` prints, from the one
+ *  decode pass that selects the records. The meaning is the composition of two contracts, word for word.
+ *  Selection: ZraHipGrepArchiveWhere's. 1 .. 64 patterns with their `syntax` word (0: literal bytes; ZRA_HIP_PATTERN_FOLD_CASE,
+ *  ZRA_HIP_PATTERN_CLASSES); the hit set of a record is H = { i : a match (p, i) of the multi search on [lo, hi) starts inside the
+ *  record }; a clause {all, any, none} holds for H when (H & all) == all, and any == 0 or (H & any) != 0, and (H & none) == 0; a
+ *  record is selected when one of the 1 .. ZRA_HIP_WHERE_MAX_CLAUSES clauses holds, and ZRA_HIP_GREP_INVERT, the only bit of `mode`,
+ *  complements that answer. lo and hi cut records the way delimiters do.
+ *  Result: ZraHipExtractRecordsExpr's. *nRecords = the selected records; *dataSize = the sum of (n_i + 1) over them; dData (device
+ *  memory) receives each selected record's bytes followed by one `delimiter` byte, in ascending order, the last record, which hi
+ *  ends, included. The list goes to hRecords once, after the last pass, only on Success and only when recordCapacity != 0. The
+ *  bytes of dData in [*dataSize, dataCapacity) are undefined after Success (a record open at the end of a pass is copied before its
+ *  selection is known: under a predicate that can change up to the record's last byte); no byte outside [dData, dData +
+ *  dataCapacity) is ever written, whatever the outcome.
+ *  Statuses, checked in this order:
+ *   1. ZraHipGrepArchiveWhere's rule 1 (ZraHipGrepArchiveExpr's, then every refusal of ZraHipCheckRecordClauses); dataSize NULL;
+ *      hRecords NULL with recordCapacity != 0; dData NULL with dataCapacity != 0 -> {ZStdError, 42}. Nothing is decoded.
+ *   2. dData overlaps the archive (through a handle: or the handle's arena) -> {ZStdError, 42}.
+ *   3. Header problems: ZraHipGrepArchive's rule 2.
+ *   4. The range: ZraHipGrepArchiveWhere's rule 3. The empty range is Success with 0 records and 0 bytes. In a non-empty range
+ *      shorter than the shortest pattern every record has H = {}: when the predicate, INVERT applied, is false on the empty set, the
+ *      call is Success with 0 records and 0 bytes, nothing decoded and stats {frames, 0, ...}; otherwise the range is scanned and
+ *      every record of it is selected.
+ *   5. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the extract's with 96 bytes per 8 KiB of window for the
+ *      per-tile tables in the place of 64.
+ *   6. A decoded frame that fails: ZraHipGrepArchive's rule 5.
+ *   7. OutputBufferTooSmall: ZraHipExtractRecords's rule 7, word for word: *nRecords and *dataSize then hold what the call needs,
+ *      hRecords is not written. recordCapacity 0 and dataCapacity 0 make the sizing call, which launches no copy kernel.
+ *  Zeroing of the outputs and the stats on every other status: ZraHipExtractRecords's rules.
+ *  The call writes ZraHipGetExtractStats and ZraHipDebugExtractMs as ZraHipExtractRecordsExpr does; word 7, matches, is the number
+ *  of (p, i) pairs, whatever the predicate. The grep's and the searches' stats are left alone.
+ *  Cost: ZraHipGrepArchiveWhere's, plus a second walk of the tiles that hold a copied byte: measured on 1 GiB of log lines, the call's
+ *  launches take 1.20 to 1.46 times the predicate grep's scan and 1.12 to 1.21 times ZraHipExtractRecords' under the plain predicate,
+ *  and the call 0.72 to 0.78 of the wall time of the predicate grep followed by a ZraHipDecompressRABatch of the listed ranges once
+ *  thousands of records are selected (profiles/extract_where.md).
+ *  Not covered: context records with the predicate, the predicate over regular expressions, per-pattern record counts, shards, the
+ *  host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipExtractRecordsWhere(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    const ZraHipRecordClause* hClauses, size_t nClauses,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** ZraHipExtractRecordsWhere through a ZraHipArchive handle: resident frames are staged from the cache as for
+ *  ZraHipArchiveExtractRecords, the cache is not changed, dData must overlap neither the archive nor the handle's arena (rule 2),
+ *  and the handle's scan counters (ZraHipArchiveGetScanStats) move as for ZraHipArchiveExtractRecords. */
+ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecordsWhere(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode,
+    const ZraHipRecordClause* hClauses, size_t nClauses,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
 
 /* ---- grep with context records: the records in front of and behind each selected one ----
  * `grep -A`, `-B`, `-C`. A log search wants the lines around a hit; with the calls above a caller decodes the neighbourhood of every
@@ -914,7 +973,7 @@ ZRA_EXPORT ZraStatus ZraHipArchiveGrepRegex(ZraHipArchive* archive,
  *  Cost: ZraHipGrepArchiveRegex's, plus a second walk of the tiles that hold a copied byte: measured on 1 GiB of log lines, the
  *  call's launches take 1.10 to 1.63 times the regex grep's scan, and the call 0.68 to 0.78 of the wall time of the regex grep
  *  followed by a ZraHipDecompressRABatch of the listed ranges (profiles/extract_regex.md).
- *  Not covered: ZraHipGrepArchiveWhere with bytes or with regular expressions; match offsets, spans, captures; more than
+ *  Not covered: ZraHipGrepArchiveWhere with regular expressions; match offsets, spans, captures; more than
  *  ZRA_HIP_REGEX_MAX_STATES states; context lines, output without delimiter bytes; multi-byte delimiters, shards, the host-pointer
  *  API. */
 ZRA_EXPORT ZraStatus ZraHipExtractRecordsRegex(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,

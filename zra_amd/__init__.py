@@ -163,6 +163,7 @@ def load():
         "ZraHipArchiveExtractRecords": (S, [vp, vp, ctypes.POINTER(u32), sz, ctypes.c_uint8, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p, vp, sz, u64p]),
         "ZraHipArchiveGetScanStats": (None, [vp, u64p]),
         "ZraHipDebugArchiveScanStageMs": (ctypes.c_double, [vp]),
+        "ZraHipDebugArchiveArena": (None, [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz)]),
         # the record index through the handle: likewise
         "ZraHipArchiveIndexRecords": (S, [vp, u32, ctypes.c_uint64, ctypes.c_uint64, sz, vp, sz, ctypes.POINTER(ZraHipRecordIndex)]),
         "ZraHipArchiveLocateRecords": (S, [vp, ctypes.POINTER(ZraHipRecordIndex), vp, sz, u64p, sz, sz, u64p]),
@@ -209,6 +210,11 @@ def load():
         "ZraHipCheckRecordClauses": (S, [vp, sz, sz]),
         "ZraHipGrepArchiveWhere": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
         "ZraHipArchiveGrepWhere": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p]),
+        # the extract with a record predicate: ZraHipGrepArchiveWhere's arguments, then the extract's three
+        "ZraHipExtractRecordsWhere": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
+                                          vp, sz, u64p]),
+        "ZraHipArchiveExtractRecordsWhere": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
+                                                 vp, sz, u64p]),
         # the grep with context records: before and after behind `mode`, |S| and the groups behind nRecords
         "ZraHipGrepArchiveContext": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
                                          u64p, u64p]),
@@ -300,7 +306,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipArchiveOpen", "ZraHipArchiveClose", "ZraHipArchiveRead", "ZraHipArchiveDropCache", "ZraHipArchiveGetStats",
                    "ZraHipArchiveUpdate", "ZraHipArchiveGetUpdateStats", "ZraHipDebugUpdateStageMs",
                    "ZraHipArchiveSearch", "ZraHipArchiveSearchMulti", "ZraHipArchiveGrep", "ZraHipArchiveExtractRecords", "ZraHipArchiveGetScanStats",
-                   "ZraHipDebugArchiveScanStageMs",
+                   "ZraHipDebugArchiveScanStageMs", "ZraHipDebugArchiveArena",
                    "ZraHipArchiveIndexRecords", "ZraHipArchiveLocateRecords", "ZraHipArchiveReadRecords", "ZraHipArchiveGetRecordStats",
                    "ZraHipDebugArchiveRecordStageMs",
                    "ZraHipUpdateArchive", "ZraHipGetUpdateStats", "ZraHipVerifyArchive", "ZraHipGetVerifyStats",
@@ -310,7 +316,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipExtractRecords", "ZraHipGetExtractStats", "ZraHipDebugExtractMs",
                    "ZraHipCheckPatternExpr", "ZraHipSearchArchiveMultiExpr", "ZraHipGrepArchiveExpr", "ZraHipExtractRecordsExpr",
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
-                   "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere",
+                   "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere", "ZraHipExtractRecordsWhere", "ZraHipArchiveExtractRecordsWhere",
                    "ZraHipGrepArchiveContext", "ZraHipArchiveGrepContext",
                    "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
                    "ZraHipExtractRecordsRegex", "ZraHipArchiveExtractRecordsRegex",
@@ -666,21 +672,22 @@ class Engine:
         return self.L.ZraHipDebugGrepScanMs(self.h)
 
     def extract(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0,
-                syntax=0):
+                syntax=0, where=None):
         """ZraHipExtractRecords: grep()'s selected records with their bytes, from one decode pass. For each selected record, in ascending
         order, its content and then one `delimiter` byte lie packed at d_data (data_cap bytes, device memory): the text `grep` prints.
         Returns (n_records, data_size, [(offset, size)]); the list is filled iff max_records != 0. OutputBufferTooSmall (more than
         max_records records when a list is wanted, or more than data_cap bytes) carries what the call needs in ZraError.needed_records
-        and ZraError.needed_data; d_data=0, data_cap=0 is the sizing call. syntax: search_multi's (ZraHipExtractRecordsExpr). ZraError
-        otherwise is a call that could not extract."""
+        and ZraError.needed_data; d_data=0, data_cap=0 is the sizing call. syntax: search_multi's (ZraHipExtractRecordsExpr). where:
+        grep()'s clauses (ZraHipExtractRecordsWhere): the records grep(where=...) selects, the text `grep A | grep B | grep -v C`
+        prints. ZraError otherwise is a call that could not extract."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._order()
-        fn, sx = _scan_call(self.L, "ZraHipExtractRecords", syntax)
+        fn, sx, wx = _grep_call(self.L, "ZraHipExtractRecords", syntax, where)
         st = fn(self.h, d_archive or None, size, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter,
-                GREP_INVERT if invert else 0, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
+                GREP_INVERT if invert else 0, *wx, offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr,
                 max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
         if st.zra != 0:
             e = ZraError(st.tup(), fn.__name__)
@@ -1189,16 +1196,16 @@ class Archive:
                                                   arr, max_records, ctypes.byref(n), ctypes.byref(ns), ctypes.byref(ng)), "ZraHipArchiveGrepRegexContext")
         return n.value, ns.value, ng.value, _context_list(arr, min(n.value, max_records))
 
-    def extract(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0, syntax=0):
-        """ZraHipArchiveExtractRecords (syntax != 0: ...Expr): Engine.extract through the handle; d_data must overlap neither the archive nor the cache. Returns
+    def extract(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0, syntax=0, where=None):
+        """ZraHipArchiveExtractRecords (syntax != 0: ...Expr; a non-empty where: ZraHipArchiveExtractRecordsWhere): Engine.extract through the handle; d_data must overlap neither the archive nor the cache. Returns
         (n_records, data_size, [(offset, size)]); OutputBufferTooSmall carries ZraError.needed_records and ZraError.needed_data."""
         patterns = [bytes(p) for p in patterns]
         sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
         arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
         n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self.engine._order()
-        fn, sx = _scan_call(self.L, "ZraHipArchiveExtractRecords", syntax)
-        st = fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, offset,
+        fn, sx, wx = _grep_call(self.L, "ZraHipArchiveExtractRecords", syntax, where)
+        st = fn(self.h, _cbuf(b"".join(patterns)), sizes, len(patterns), *sx, delimiter, GREP_INVERT if invert else 0, *wx, offset,
                 (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n),
                 d_data or None, data_cap, ctypes.byref(ds))
         if st.zra != 0:
@@ -1235,6 +1242,12 @@ class Archive:
     def scan_stage_ms(self):
         """bring-up: HIP-event time of the last accepted scan's job-split and stage-from-cache launches, summed over its passes."""
         return self.L.ZraHipDebugArchiveScanStageMs(self.h)
+
+    def arena_range(self):
+        """bring-up: (base, bytes) of the handle's arena in device memory, (0, 0) without a cache: for tests of the arena check."""
+        base, n = ctypes.c_void_p(0), ctypes.c_size_t(0)
+        self.L.ZraHipDebugArchiveArena(self.h, ctypes.byref(base), ctypes.byref(n))
+        return base.value or 0, n.value
 
     # ---- the record index through the handle: Engine.index_records / locate_records / read_records of the archive the handle serves,
     # without d_archive and size. A whole-frame sweep copies the resident frames it needs out of the cache and decodes only the others.

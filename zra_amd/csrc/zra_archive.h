@@ -41,6 +41,8 @@ class ArchiveCache {
   void scan_stats(uint64_t out[8]) const;
   // bring-up: HIP-event time of the last accepted scan's job-split and stage-from-cache launches, summed over its passes (0: none ran)
   double scan_stage_ms() const { return scanStageMs_; }
+  // bring-up: where the arena lies, [*base, *base + *bytes); nullptr and 0 for a handle without a cache
+  void arena_range(const void** base, size_t* bytes) const { *base = arena_; *bytes = arena_ ? (size_t)slots_ * h_.frameSize : 0; }
   // The record calls of the engine (zra_records.hip) on the archive the handle is bound to (zra_hip.h: ZraHipArchiveIndexRecords,
   // ZraHipArchiveLocateRecords, ZraHipArchiveReadRecords): a whole-frame sweep copies the resident frames it needs out of the arena and
   // decodes the others. Index and locate are not reads: they change nothing of the cache and none of stats()' words, on any status. The

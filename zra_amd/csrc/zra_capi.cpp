@@ -782,6 +782,11 @@ void ZraHipArchiveGetScanStats(const ZraHipArchive* archive, uint64_t* out8) {
   if (archive) archive->c->scan_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
 }
 double ZraHipDebugArchiveScanStageMs(const ZraHipArchive* archive) { return archive ? archive->c->scan_stage_ms() : 0.0; }
+void ZraHipDebugArchiveArena(const ZraHipArchive* archive, const void** base, size_t* bytes) {
+  if (!base || !bytes) return;
+  *base = nullptr; *bytes = 0;
+  if (archive) archive->c->arena_range(base, bytes);
+}
 ZraStatus ZraHipArchiveIndexRecords(ZraHipArchive* archive, uint32_t delimiter, uint64_t firstFrame, uint64_t frameCount, size_t stagingBytes, uint64_t* dIndex,
                                     size_t indexCapacityWords, ZraHipRecordIndex* info) {
   if (info) *info = ZraHipRecordIndex{0, 0, 0, 0, 0, 0};
@@ -1010,6 +1015,27 @@ ZraStatus ZraHipArchiveGrepWhere(ZraHipArchive* archive, const void* hPatterns, 
   if (!archive) return mk(ZStdError, 42);
   return mk(archive->c->record_scan({kRecGrepWhere, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
                                     (uint64_t*)hRecords, recordCapacity, nRecords, nullptr, 0, nullptr, hClauses, nClauses}));
+}
+// ---- the extract with a record predicate: the predicate grep's selector, kernels of its own (zra_extract_where.hip); the extract's stats row and
+// milliseconds
+ZraStatus ZraHipExtractRecordsWhere(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                                    uint32_t syntax, uint8_t delimiter, uint32_t mode, const ZraHipRecordClause* hClauses, size_t nClauses, uint64_t offset, uint64_t size,
+                                    size_t stagingBytes, ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity,
+                                    uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->record_scan({zra_eng::kRecExtractWhere, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset,
+                                    size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize, hClauses, nClauses}));
+}
+ZraStatus ZraHipArchiveExtractRecordsWhere(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                           uint32_t mode, const ZraHipRecordClause* hClauses, size_t nClauses, uint64_t offset, uint64_t size, size_t stagingBytes,
+                                           ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!archive) return mk(ZStdError, 42);
+  return mk(archive->c->record_scan({zra_eng::kRecExtractWhere, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                                     (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize, hClauses, nClauses}));
 }
 // ---- the grep with regular expressions: the compiler is zra_regex.h's, the kernels zra_grep_regex.hip's; the grep's stats row and milliseconds
 ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, int delimiter, ZraHipRegexInfo* info) {

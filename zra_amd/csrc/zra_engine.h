@@ -102,6 +102,8 @@ enum RecordKind : uint32_t {
                      // of and `after` behind each selected one. Kernels of its own; writes the grep's counters (word 4: |O|) and milliseconds
   kRecGrepRegexContext,   // ZraHipGrepArchiveRegexContext (zra_grep_regex_context.hip, zra_regex_context.h): kRecGrepRegex's selection,
                      // kRecGrepContext's outputs. Kernels of its own; writes the grep's counters (word 4: |O|, word 7: the matched records)
+  kRecExtractWhere,  // ZraHipExtractRecordsWhere (zra_extract_where.hip): kRecGrepWhere's selection, kRecExtract's outputs, in one pass. Kernels of
+                     // its own; writes the extract's counters and milliseconds
 };
 struct RecordCall {
   RecordKind kind;
@@ -115,7 +117,7 @@ struct RecordCall {
   // the extracts: each selected record's content and one delimiter byte, packed at dData (device memory); the list goes to hRecords
   // iff recordCap != 0. *dataSize: the packed bytes
   uint8_t* dData = nullptr; size_t dataCap = 0; uint64_t* dataSize = nullptr;
-  // kRecGrepWhere: a record is selected when one of the nClauses clauses {all, any, none} (ZraHipRecordClause) holds for the set of
+  // kRecGrepWhere, kRecExtractWhere: a record is selected when one of the nClauses clauses {all, any, none} (ZraHipRecordClause) holds for the set of
   // patterns that hit in it
   const void* hClauses = nullptr; size_t nClauses = 0;
   // kRecGrepContext, kRecGrepRegexContext: the context in records (each at most 64), and beside *nRecords = |O| the selected records and the groups (or null)

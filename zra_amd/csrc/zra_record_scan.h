@@ -1,7 +1,7 @@
 // zra_amd — the one call path of the record scans: ZraHipGrepArchive (zra_grep.hip), ZraHipGrepArchiveWhere (zra_grep_where.hip),
 // ZraHipGrepArchiveRegex (zra_grep_regex.hip), ZraHipExtractRecords (zra_extract.hip), ZraHipExtractRecordsRegex
-// (zra_extract_regex.hip), ZraHipGrepArchiveContext (zra_grep_context.hip), ZraHipGrepArchiveRegexContext
-// (zra_grep_regex_context.hip), their ...Expr forms and the same calls through an archive
+// (zra_extract_regex.hip), ZraHipExtractRecordsWhere (zra_extract_where.hip), ZraHipGrepArchiveContext (zra_grep_context.hip),
+// ZraHipGrepArchiveRegexContext (zra_grep_regex_context.hip), their ...Expr forms and the same calls through an archive
 // handle. They cut a content range into records at a delimiter, select records and return them as a list, the extracts with the
 // records' bytes, the two greps with context with the records around the selected ones; they take the arguments of
 // one RecordCall (zra_engine.h) and differ in two things only, which record_scan() takes as types:
@@ -9,7 +9,7 @@
 //      pattern, which the driver's (carry) and (ownership) run on; nothing(len): a range of len bytes in which no record can be
 //      selected; table_bytes() / build(): the table that heads the call's device tables; open(): the carried state of the record that
 //      opens at lo, beyond its start.
-//  a KERNEL SET (seven, each next to its kernels): Sum / Head, the two per-tile entries, kMapBytes more per tile behind them; Totals =
+//  a KERNEL SET (eight, each next to its kernels; ExtractWhereKernels is WhereSelect's second): Sum / Head, the two per-tile entries, kMapBytes more per tile behind them; Totals =
 //      {State st[2] (the ping-pong pair of zra_scan.h's (c)), matches, delims}; kData: the call packs bytes; launch(): the three
 //      launches of a pass, the third one only when a capacity asks for it.
 // record_scan() wraps its steps in ScanImpl::call for the row kData names, so the kernel set alone decides whose counters a call writes.
@@ -39,7 +39,8 @@ struct LiteralSelect {
   void build(uint8_t* dst, const RecordCall& c) const { build_pattern_table(dst, pset, c.hPat, c.hSizes, c.nPat); }
   template <class State> void open(State&) const {}
 };
-// the literal selector's patterns under a record predicate (zra_where.h): the block carries the mode
+// the literal selector's patterns under a record predicate (zra_where.h): the block carries the mode. WhereKernels lists the selected
+// records (zra_grep_where.hip), ExtractWhereKernels packs their bytes as well (zra_extract_where.hip)
 struct WhereSelect : LiteralSelect {
   zra_where::Block w;
   bool compile(const RecordCall& c) {

@@ -63,6 +63,7 @@ struct ScanImpl {
   static Status extract_regex(Engine& E, const RecordCall& c, ScanCacheView* cv);   // zra_extract_regex.hip
   static Status grep_context(Engine& E, const RecordCall& c, ScanCacheView* cv);    // zra_grep_context.hip
   static Status grep_regex_context(Engine& E, const RecordCall& c, ScanCacheView* cv);   // zra_grep_regex_context.hip
+  static Status extract_where(Engine& E, const RecordCall& c, ScanCacheView* cv);   // zra_extract_where.hip
 
   // What a call of the family leaves behind: entry_call's rule (zra_host.h). `which`: kScanSearch .. kScanExtract; out0 / out1: the
   // call's output words (either may be nullptr), kept on OutputTooSmall (the extract's rule 7, whose two words say what the call needs).
@@ -178,6 +179,7 @@ inline Status Engine::record_scan(const RecordCall& c, ScanCacheView* cv) {
     case kRecExtractRegex: return ScanImpl::extract_regex(*this, c, cv);
     case kRecGrepContext: return ScanImpl::grep_context(*this, c, cv);
     case kRecGrepRegexContext: return ScanImpl::grep_regex_context(*this, c, cv);
+    case kRecExtractWhere: return ScanImpl::extract_where(*this, c, cv);
   }
   return zerr(42);
 }

@@ -25,6 +25,8 @@
 //         must occur in the record), ?i (one of the ?-patterns must), -i (pattern i must not), i = the pattern's position on the command
 //         line from 0; a record is selected when some clause holds, -v complements that. Output and exit status of gl; a refused
 //         clause is exit status 2
+//   gxw : gxe with glw's record predicate (ZraHipExtractRecordsWhere): the text `grep A | grep B | grep -v C` prints; -w as glw, -o, -v,
+//         -d, -i, -F as gxe. Output and exit status of gx; a refused clause is exit status 2
 //   glr : gl with regular expressions (ZraHipGrepArchiveRegex): POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on top of
 //         gle's atoms (zra_hip.h: ZraHipCheckRegex); several expressions are alternatives; -i: ASCII letters match either case, -v, -d as
 //         gl; -c: only the count. Output and exit status of gl; a refused expression is exit status 2 with the reason and its index
@@ -421,13 +423,18 @@ int grep_archive_regex(const char* path, bool invert, bool fold, bool countOnly,
   return total ? 0 : 1;
 }
 
-// modes gx, (ex) gxe and (rx) gxr: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to outPath, or to
-// stdout when it is null. Nothing is written when a call fails or when nothing is selected.
-int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex, const RegexOpt* rx = nullptr) {
+// modes gx, (ex) gxe, (where) gxw and (rx) gxr: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to
+// outPath, or to stdout when it is null. Nothing is written when a call fails or when nothing is selected.
+int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex, const RegexOpt* rx = nullptr,
+                    const std::vector<ZraHipRecordClause>* where = nullptr) {
   std::string all;
   std::vector<uint32_t> sizes;
   uint32_t syntax = 0;
   if (rx ? !gather_regex(texts, n, rx->fold, delimiter, &all, &sizes, &syntax) : !gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
+  if (where && ZraHipCheckRecordClauses(where->data(), where->size(), sizes.size()).zra != Success) {
+    std::fprintf(stderr, "1 to %u clauses over the patterns 0 .. %d, none with a pattern both wanted and unwanted\n", ZRA_HIP_WHERE_MAX_CLAUSES, n - 1);
+    return 2;
+  }
   zra::Buffer arc = read_file(path);
   ZraHipEngine* eng = nullptr;
   ZraStatus st = ZraHipCreateEngine(&eng, 0);
@@ -438,6 +445,9 @@ int extract_records(const char* path, bool invert, uint8_t delimiter, const char
   uint64_t total = 0, bytes = 0;
   std::string text;
   auto extract = [&](void* dOut, size_t cap) {
+    if (where)
+      return ZraHipExtractRecordsWhere(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, where->data(), where->size(), 0, UINT64_MAX,
+                                       0, nullptr, 0, &total, dOut, cap, &bytes);
     if (rx)
       return ZraHipExtractRecordsRegex(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, 0, UINT64_MAX, 0, nullptr, 0, &total, dOut,
                                        cap, &bytes);
@@ -662,6 +672,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gme {file} {-i} {-F} {expression | hex:digits}...
 //       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
 //       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
+//       gxw {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} -w clause {-w clause}... {expression | hex:digits}...
 //       glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...
 //       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
 //       gxr {file} {-i} {-v} {-d hex byte = 0a} {-o file} {expression}...
@@ -686,6 +697,7 @@ int main(int argc, char** argv) {
                 "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}... - Grep an archive on the device: offset and size of every record (line) that holds a match, -v: that holds none (exit status 0 some, 1 none, 2 trouble)\n"
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
+                "gxw {file} {options of gxe} {-w clause}... {expression | hex:digits}... - gxe with glw's record predicate: the selected records' bytes, the text grep A | grep B | grep -v C prints; output and exit status as gx\n"
                 "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
                 "glc {file} {options of gle} {-A records} {-B records} {-C records} {expression | hex:digits}... - gle with context: up to 64 records behind (-A), in front of (-B) or around (-C) every selected record; a selected record is marked *, `--` separates groups (exit status as gl)\n"
                 "glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}... - gl with regular expressions: POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on gle's atoms, several expressions are alternatives; -c: only the count (a refused expression: exit status 2)\n"
@@ -720,8 +732,8 @@ int main(int argc, char** argv) {
     if (i >= argc) { std::fprintf(stderr, "gme {file} {-i} {-F} {expression | hex:digits}...\n"); return 2; }
     return search_archive_multi(argv[2], argv + i, argc - i, &ex);
   }
-  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw") {
-    const bool text = mode[1] == 'x', expr = mode.size() == 3, pred = mode == "glw";
+  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw" || mode == "gxw") {
+    const bool text = mode[1] == 'x', expr = mode.size() == 3, pred = mode == "glw" || mode == "gxw";
     std::vector<ZraHipRecordClause> where;
     ExprOpt ex = {false, false};
     bool invert = false;
@@ -752,6 +764,7 @@ int main(int argc, char** argv) {
                    pred ? "-w clause {-w clause}... " : "", expr ? "expression" : "pattern");
       return 2;
     }
+    if (pred && text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, &ex, nullptr, &where);
     if (pred) return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, &ex, &where);
     if (text) return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i, argc - i, expr ? &ex : nullptr);
     return grep_archive(argv[2], invert, (uint8_t)delimiter, argv + i, argc - i, expr ? &ex : nullptr);
