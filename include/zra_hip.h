@@ -814,6 +814,66 @@ ZRA_EXPORT ZraStatus ZraHipArchiveExtractRecordsWhere(ZraHipArchive* archive,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
     void* dData, size_t dataCapacity, uint64_t* dataSize);
 
+/* ---- cut records: the chosen fields of the selected records, packed ----
+ * `grep -F A | cut -d SEP -f LIST`. A log or CSV archive is rarely queried for whole lines; the extract packs whole records, and the
+ * plaintext, the record boundaries and the selection all lie in the staging window when it runs. This call adds "which field is
+ * this byte in" and packs only the chosen fields of each selected record. */
+#define ZRA_HIP_CUT_MAX_FIELD 64
+/** cut's LIST (`1,3,5-7,9-`, `-3`) as a field mask, on the host: bit j - 1 stands for field j, bit 63 for field 64 AND every later one
+ *  (cut's `64-`). Items are separated by commas; an item is N, N-M, N- or -M, numbers from 1. A range whose end lies above 64, and
+ *  N- with N >= 64, set bit 63 (and the bits of the fields below 64 they cover); a lone field above 64 is refused, because it cannot
+ *  be told from `64-`. {ZStdError, 42} with *mask = 0 (where mask is not NULL): list or mask NULL, an empty list or item, a 0, a
+ *  decreasing range, any other character. */
+ZRA_EXPORT ZraStatus ZraHipFieldMask(const char* list, uint64_t* mask);
+/** The records ZraHipExtractRecordsExpr selects, of each only the chosen fields, packed: the text `grep -F -f patterns | cut -d SEP
+ *  -f LIST` prints, from the one decode pass that selects the records.
+ *  Selection: ZraHipExtractRecordsExpr's, word for word: the patterns with their `syntax` word (0: literal bytes), `delimiter`,
+ *  `mode` (ZRA_HIP_GREP_INVERT only), the range with lo and hi cutting records the way delimiters do, stagingBytes and the passes,
+ *  whole frames with verified checksums. One addition: nPatterns == 0 selects every record, plain `cut`; hPatterns and hPatternSizes
+ *  may then be NULL, and word 7 of the stats, matches, is 0.
+ *  Fields: inside a record as reported (for a record that lo cuts: from lo) field 1 starts at the record's start; every `separator`
+ *  byte ends a field and starts the next; fields may be empty. Field j is chosen iff bit min(j, 64) - 1 of fieldMask is set. A
+ *  content byte is kept iff its field is chosen; the separator in front of field k (k >= 2) is kept iff field k is chosen and some
+ *  field j < k is. A selected record contributes its kept bytes in order and then one `delimiter` byte: the record that hi ends
+ *  included, and a record that keeps nothing, which contributes the delimiter alone.
+ *  Against `cut -d SEP -f LIST`: on every record that holds a separator the output is GNU cut's; on a record without one it is
+ *  cut's as well when field 1 is chosen, and an empty line otherwise, where cut prints the record whole (and `cut -s` nothing).
+ *  Result: *nRecords = the selected records; hRecords receives their {offset, size} in the content, exactly the extract's list (only
+ *  on Success and when recordCapacity != 0); *dataSize = the packed size; dData (device memory) holds the packed text. The bytes of
+ *  dData in [*dataSize, dataCapacity) are undefined after Success; no byte outside [dData, dData + dataCapacity) is ever written.
+ *  Statuses, checked in this order:
+ *   1. ZraHipExtractRecordsExpr's rule 1 (with nPatterns == 0 allowed); separator == delimiter; fieldMask == 0; INVERT with
+ *      nPatterns == 0 -> {ZStdError, 42}. Nothing is decoded.
+ *   2. dData overlaps the archive (through a handle: or the handle's arena) -> {ZStdError, 42}.
+ *   3. to 6. ZraHipExtractRecordsExpr's: header, range (the empty range, and without INVERT a range shorter than the shortest
+ *      pattern, are Success with 0 records, 0 bytes and nothing decoded), scratch (1,104 bytes per 8 KiB of window for the per-tile
+ *      tables: the keep flags of every position lie there), a decoded frame that fails.
+ *   7. OutputBufferTooSmall: ZraHipExtractRecords's rule 7, word for word: *nRecords and *dataSize then hold what the call needs,
+ *      hRecords is not written. recordCapacity 0 and dataCapacity 0 make the sizing call, which launches no copy kernel.
+ *  Zeroing of the outputs and the stats on every other status: ZraHipExtractRecords's rules.
+ *  The call writes ZraHipGetExtractStats (word 5: *dataSize) and ZraHipDebugExtractMs as the extracts do. The grep's and the
+ *  searches' stats are left alone.
+ *  Cost: five launches per pass (count, one-workgroup scan, keep flags, one-workgroup placement, copy); DESIGN.md §33 and
+ *  profiles/cut_scan.md say what was measured.
+ *  Not covered: regex and predicate selection; `cut -s` and cut's whole-line rule for records without a separator; `--complement`
+ *  (the caller inverts the mask); `--output-delimiter`; multi-byte separators; byte or character positions (`-b`, `-c`); shards; the
+ *  host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipCutRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint8_t separator, uint64_t fieldMask,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+/** ZraHipCutRecords through a ZraHipArchive handle: resident frames are staged from the cache as for ZraHipArchiveExtractRecords,
+ *  the cache is not changed, dData must overlap neither the archive nor the handle's arena (rule 2), and the handle's scan counters
+ *  (ZraHipArchiveGetScanStats) move as for ZraHipArchiveExtractRecords. */
+ZRA_EXPORT ZraStatus ZraHipArchiveCutRecords(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint8_t separator, uint64_t fieldMask,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
+    void* dData, size_t dataCapacity, uint64_t* dataSize);
+
 /* ---- grep with context records: the records in front of and behind each selected one ----
  * `grep -A`, `-B`, `-C`. A log search wants the lines around a hit; with the calls above a caller decodes the neighbourhood of every
  * hit a second time and cuts it at delimiters on the host. The grep pass sees every delimiter and every selection in order: this call

@@ -215,6 +215,12 @@ def load():
                                           vp, sz, u64p]),
         "ZraHipArchiveExtractRecordsWhere": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, vp, sz, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
                                                  vp, sz, u64p]),
+        # cut records: ZraHipExtractRecordsExpr's arguments with the separator and the field mask behind `mode`; the LIST parser is host only
+        "ZraHipFieldMask": (S, [ctypes.c_char_p, u64p]),
+        "ZraHipCutRecords": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz,
+                                 u64p, sz, u64p, vp, sz, u64p]),
+        "ZraHipArchiveCutRecords": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz,
+                                        u64p, sz, u64p, vp, sz, u64p]),
         # the grep with context records: before and after behind `mode`, |S| and the groups behind nRecords
         "ZraHipGrepArchiveContext": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
                                          u64p, u64p]),
@@ -317,6 +323,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipCheckPatternExpr", "ZraHipSearchArchiveMultiExpr", "ZraHipGrepArchiveExpr", "ZraHipExtractRecordsExpr",
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
                    "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere", "ZraHipExtractRecordsWhere", "ZraHipArchiveExtractRecordsWhere",
+                   "ZraHipFieldMask", "ZraHipCutRecords", "ZraHipArchiveCutRecords",
                    "ZraHipGrepArchiveContext", "ZraHipArchiveGrepContext",
                    "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
                    "ZraHipExtractRecordsRegex", "ZraHipArchiveExtractRecordsRegex",
@@ -696,6 +703,14 @@ class Engine:
         k = n.value if max_records else 0
         return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
 
+    def cut(self, d_archive, size, patterns, d_data, data_cap, *, separator, fields, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0,
+            max_records=0, syntax=0):
+        """ZraHipCutRecords: extract()'s selected records, of each only the chosen fields: the text `grep -F patterns | cut -d SEP -f LIST`
+        prints, packed at d_data from one decode pass. separator: the byte that ends a field; fields: cut's LIST as a string ("1,3,5-7,9-")
+        or a mask (field_mask()). No pattern selects every record, plain cut. Returns and raises as extract() does."""
+        return _cut_call(self.L, self.L.ZraHipCutRecords, (self.h, d_archive or None, size), self._order, patterns, d_data, data_cap, separator, fields, delimiter,
+                         invert, offset, length, staging_bytes, max_records, syntax)
+
     def extract_regex(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None,
                       staging_bytes=0, max_records=0):
         """ZraHipExtractRecordsRegex: grep_regex()'s selected records with their bytes, packed at d_data as extract() packs them: the
@@ -1006,6 +1021,35 @@ def _clauses(where):
     return (ctypes.c_uint64 * max(len(flat), 3))(*flat), len(where)
 
 
+def field_mask(text):
+    """ZraHipFieldMask: cut's LIST ("1,3,5-7,9-", "-3") as the field mask of Engine.cut: bit j - 1 for field j, bit 63 for field 64 and
+    every later one. ZraError for a list the call refuses."""
+    m = ctypes.c_uint64(0)
+    st = load().ZraHipFieldMask(text.encode() if isinstance(text, str) else bytes(text), ctypes.byref(m))
+    if st.zra != 0:
+        raise ZraError(st.tup(), "ZraHipFieldMask")
+    return m.value
+
+
+def _cut_call(L, fn, head, order, patterns, d_data, data_cap, separator, fields, delimiter, invert, offset, length, staging_bytes, max_records, syntax):
+    """Engine.cut and Archive.cut: `head` is what stands in front of hPatterns"""
+    patterns = [bytes(p) for p in patterns]
+    sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+    mask = fields if isinstance(fields, int) else field_mask(fields)
+    sep = separator if isinstance(separator, int) else bytes(separator)[0]
+    arr = (ctypes.c_uint64 * (2 * max_records))() if max_records else None
+    n, ds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    order()
+    st = fn(*head, _cbuf(b"".join(patterns)) if patterns else None, sizes if patterns else None, len(patterns), syntax, delimiter, GREP_INVERT if invert else 0, sep, mask,
+            offset, (1 << 64) - 1 if length is None else length, staging_bytes, arr, max_records, ctypes.byref(n), d_data or None, data_cap, ctypes.byref(ds))
+    if st.zra != 0:
+        e = ZraError(st.tup(), fn.__name__)
+        e.needed_records, e.needed_data = n.value, ds.value
+        raise e
+    k = n.value if max_records else 0
+    return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+
 def _grep_call(L, name, syntax, where):
     """the entry point of a grep, what goes behind nPatterns and what goes behind mode: _scan_call's without `where`, else the
     ...Where call, which takes the syntax word always and the clauses"""
@@ -1214,6 +1258,12 @@ class Archive:
             raise e
         k = n.value if max_records else 0
         return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
+
+    def cut(self, patterns, d_data, data_cap, *, separator, fields, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, max_records=0, syntax=0):
+        """ZraHipArchiveCutRecords: Engine.cut through the handle; d_data must overlap neither the archive nor the cache. Returns and raises as
+        extract() does."""
+        return _cut_call(self.L, self.L.ZraHipArchiveCutRecords, (self.h,), self.engine._order, patterns, d_data, data_cap, separator, fields, delimiter, invert,
+                         offset, length, staging_bytes, max_records, syntax)
 
     def extract_regex(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0, max_records=0):
         """ZraHipArchiveExtractRecordsRegex: Engine.extract_regex through the handle; d_data must overlap neither the archive nor the cache. Returns

@@ -1037,6 +1037,63 @@ ZraStatus ZraHipArchiveExtractRecordsWhere(ZraHipArchive* archive, const void* h
   return mk(archive->c->record_scan({zra_eng::kRecExtractWhere, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
                                      (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize, hClauses, nClauses}));
 }
+// ---- cut records: the extract's selector, where no pattern selects every record, kernels of its own (zra_cut.hip); the extract's stats row and
+// milliseconds
+ZraStatus ZraHipFieldMask(const char* list, uint64_t* mask) {
+  if (mask) *mask = 0;
+  if (!list || !mask || !*list) return mk(ZStdError, 42);
+  uint64_t m = 0;
+  const char* p = list;
+  // a number from 1, clamped to 65: everything above 64 is one case
+  auto number = [&](uint64_t* v) {
+    if (*p < '0' || *p > '9') return false;
+    for (*v = 0; *p >= '0' && *p <= '9'; p++) *v = std::min<uint64_t>(*v * 10 + (uint64_t)(*p - '0'), 65);
+    return *v != 0;
+  };
+  for (;;) {
+    uint64_t a = 1, b = 0;
+    bool range = false;
+    if (*p == '-') { range = true; p++; if (!number(&b)) return mk(ZStdError, 42); }   // -M
+    else {
+      if (!number(&a)) return mk(ZStdError, 42);
+      if (*p == '-') { range = true; p++; if (*p == ',' || !*p) b = 65; else if (!number(&b)) return mk(ZStdError, 42); }   // N- | N-M
+      else b = a;
+    }
+    if (b < a || (!range && a > 64)) return mk(ZStdError, 42);
+    for (uint64_t j = std::min<uint64_t>(a, 64); j <= std::min<uint64_t>(b, 64); j++) m |= 1ull << (j - 1);
+    if (!*p) break;
+    if (*p++ != ',') return mk(ZStdError, 42);
+  }
+  *mask = m;
+  return mk(Success, 0);
+}
+namespace {
+const uint32_t kNoPattern = 0;   // what the call path reads in the place of NULL pattern arguments when there is no pattern
+}
+ZraStatus ZraHipCutRecords(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                           uint32_t syntax, uint8_t delimiter, uint32_t mode, uint8_t separator, uint64_t fieldMask, uint64_t offset, uint64_t size, size_t stagingBytes,
+                           ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!engine) return mk(ZStdError, 42);
+  if (nPatterns == 0) { hPatterns = &kNoPattern; hPatternSizes = &kNoPattern; }
+  zra_eng::RecordCall c = {zra_eng::kRecCut, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset,
+                           size, stagingBytes, (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize};
+  c.separator = separator; c.fieldMask = fieldMask;
+  return mk(engine->e->record_scan(c));
+}
+ZraStatus ZraHipArchiveCutRecords(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                  uint32_t mode, uint8_t separator, uint64_t fieldMask, uint64_t offset, uint64_t size, size_t stagingBytes, ZraHipContentRange* hRecords,
+                                  size_t recordCapacity, uint64_t* nRecords, void* dData, size_t dataCapacity, uint64_t* dataSize) {
+  if (nRecords) *nRecords = 0;
+  if (dataSize) *dataSize = 0;
+  if (!archive) return mk(ZStdError, 42);
+  if (nPatterns == 0) { hPatterns = &kNoPattern; hPatternSizes = &kNoPattern; }
+  zra_eng::RecordCall c = {zra_eng::kRecCut, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                           (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize};
+  c.separator = separator; c.fieldMask = fieldMask;
+  return mk(archive->c->record_scan(c));
+}
 // ---- the grep with regular expressions: the compiler is zra_regex.h's, the kernels zra_grep_regex.hip's; the grep's stats row and milliseconds
 ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, int delimiter, ZraHipRegexInfo* info) {
   static_assert(sizeof(ZraHipRegexInfo) == sizeof(zra_regex::Info) && ZRA_HIP_REGEX_MAX_STATES == zra_regex::kMaxStates &&

@@ -104,6 +104,8 @@ enum RecordKind : uint32_t {
                      // kRecGrepContext's outputs. Kernels of its own; writes the grep's counters (word 4: |O|, word 7: the matched records)
   kRecExtractWhere,  // ZraHipExtractRecordsWhere (zra_extract_where.hip): kRecGrepWhere's selection, kRecExtract's outputs, in one pass. Kernels of
                      // its own; writes the extract's counters and milliseconds
+  kRecCut,           // ZraHipCutRecords (zra_cut.hip): kRecExtract's selection (no pattern: every record), of each selected record only the fields
+                     // of fieldMask, cut at `separator`. Kernels of its own; writes the extract's counters and milliseconds
 };
 struct RecordCall {
   RecordKind kind;
@@ -123,6 +125,8 @@ struct RecordCall {
   // kRecGrepContext, kRecGrepRegexContext: the context in records (each at most 64), and beside *nRecords = |O| the selected records and the groups (or null)
   uint32_t before = 0, after = 0;
   uint64_t* nSelected = nullptr, * nGroups = nullptr;
+  // kRecCut: the byte that ends a field, and the chosen fields: bit min(j, 64) - 1 for field j (no other kind reads them)
+  uint8_t separator = 0; uint64_t fieldMask = 0;
 };
 // The byte fetch of a record read through an archive handle (zra_records.hip): the located ranges as one read of the handle, a query
 // allowed to end AT the content's end. *jobs: the frames the fetch decoded.

@@ -1,15 +1,15 @@
 // zra_amd — the one call path of the record scans: ZraHipGrepArchive (zra_grep.hip), ZraHipGrepArchiveWhere (zra_grep_where.hip),
 // ZraHipGrepArchiveRegex (zra_grep_regex.hip), ZraHipExtractRecords (zra_extract.hip), ZraHipExtractRecordsRegex
 // (zra_extract_regex.hip), ZraHipExtractRecordsWhere (zra_extract_where.hip), ZraHipGrepArchiveContext (zra_grep_context.hip),
-// ZraHipGrepArchiveRegexContext (zra_grep_regex_context.hip), their ...Expr forms and the same calls through an archive
-// handle. They cut a content range into records at a delimiter, select records and return them as a list, the extracts with the
+// ZraHipGrepArchiveRegexContext (zra_grep_regex_context.hip), ZraHipCutRecords (zra_cut.hip), their ...Expr forms and the same calls
+// through an archive handle. They cut a content range into records at a delimiter, select records and return them as a list, the extracts with the
 // records' bytes, the two greps with context with the records around the selected ones; they take the arguments of
 // one RecordCall (zra_engine.h) and differ in two things only, which record_scan() takes as types:
-//  a SELECTOR (three, below; host only): what the patterns of the call become. compile(): rule 1 beyond the nulls; M: the longest
+//  a SELECTOR (three, below, and next to the cut's kernels LiteralSelect wrapped so that no pattern selects every record; host only): what the patterns of the call become. compile(): rule 1 beyond the nulls; M: the longest
 //      pattern, which the driver's (carry) and (ownership) run on; nothing(len): a range of len bytes in which no record can be
 //      selected; table_bytes() / build(): the table that heads the call's device tables; open(): the carried state of the record that
 //      opens at lo, beyond its start.
-//  a KERNEL SET (eight, each next to its kernels; ExtractWhereKernels is WhereSelect's second): Sum / Head, the two per-tile entries, kMapBytes more per tile behind them; Totals =
+//  a KERNEL SET (nine, each next to its kernels; ExtractWhereKernels is WhereSelect's second): Sum / Head, the two per-tile entries, kMapBytes more per tile behind them; Totals =
 //      {State st[2] (the ping-pong pair of zra_scan.h's (c)), matches, delims}; kData: the call packs bytes; launch(): the three
 //      launches of a pass, the third one only when a capacity asks for it.
 // record_scan() wraps its steps in ScanImpl::call for the row kData names, so the kernel set alone decides whose counters a call writes.

@@ -64,6 +64,7 @@ struct ScanImpl {
   static Status grep_context(Engine& E, const RecordCall& c, ScanCacheView* cv);    // zra_grep_context.hip
   static Status grep_regex_context(Engine& E, const RecordCall& c, ScanCacheView* cv);   // zra_grep_regex_context.hip
   static Status extract_where(Engine& E, const RecordCall& c, ScanCacheView* cv);   // zra_extract_where.hip
+  static Status cut(Engine& E, const RecordCall& c, ScanCacheView* cv);             // zra_cut.hip
 
   // What a call of the family leaves behind: entry_call's rule (zra_host.h). `which`: kScanSearch .. kScanExtract; out0 / out1: the
   // call's output words (either may be nullptr), kept on OutputTooSmall (the extract's rule 7, whose two words say what the call needs).
@@ -180,6 +181,7 @@ inline Status Engine::record_scan(const RecordCall& c, ScanCacheView* cv) {
     case kRecGrepContext: return ScanImpl::grep_context(*this, c, cv);
     case kRecGrepRegexContext: return ScanImpl::grep_regex_context(*this, c, cv);
     case kRecExtractWhere: return ScanImpl::extract_where(*this, c, cv);
+    case kRecCut: return ScanImpl::cut(*this, c, cv);
   }
   return zerr(42);
 }

@@ -27,6 +27,9 @@
 //         clause is exit status 2
 //   gxw : gxe with glw's record predicate (ZraHipExtractRecordsWhere): the text `grep A | grep B | grep -v C` prints; -w as glw, -o, -v,
 //         -d, -i, -F as gxe. Output and exit status of gx; a refused clause is exit status 2
+//   cut : gx with cut's field selection (ZraHipCutRecords): of every selected record only the fields of LIST (cut's: 1,3,5-7,9-), cut
+//         at the separator byte; both stand in front of the patterns, and no pattern at all selects every record. -o, -v, -d as gx.
+//         Output and exit status of gx; a refused separator or list is exit status 2
 //   glr : gl with regular expressions (ZraHipGrepArchiveRegex): POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on top of
 //         gle's atoms (zra_hip.h: ZraHipCheckRegex); several expressions are alternatives; -i: ASCII letters match either case, -v, -d as
 //         gl; -c: only the count. Output and exit status of gl; a refused expression is exit status 2 with the reason and its index
@@ -423,14 +426,17 @@ int grep_archive_regex(const char* path, bool invert, bool fold, bool countOnly,
   return total ? 0 : 1;
 }
 
-// modes gx, (ex) gxe, (where) gxw and (rx) gxr: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to
+struct CutOpt { uint8_t separator; uint64_t mask; };
+
+// modes gx, (ex) gxe, (where) gxw, (rx) gxr and (cut) cut: a sizing call, then the call with a buffer of exactly that size; the packed bytes go to
 // outPath, or to stdout when it is null. Nothing is written when a call fails or when nothing is selected.
 int extract_records(const char* path, bool invert, uint8_t delimiter, const char* outPath, char** texts, int n, const ExprOpt* ex, const RegexOpt* rx = nullptr,
-                    const std::vector<ZraHipRecordClause>* where = nullptr) {
+                    const std::vector<ZraHipRecordClause>* where = nullptr, const CutOpt* cut = nullptr) {
   std::string all;
   std::vector<uint32_t> sizes;
   uint32_t syntax = 0;
-  if (rx ? !gather_regex(texts, n, rx->fold, delimiter, &all, &sizes, &syntax) : !gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
+  if (cut && n == 0) {}                                                       // (every record)
+  else if (rx ? !gather_regex(texts, n, rx->fold, delimiter, &all, &sizes, &syntax) : !gather_patterns(texts, n, delimiter, ex, &all, &sizes, &syntax)) return 2;
   if (where && ZraHipCheckRecordClauses(where->data(), where->size(), sizes.size()).zra != Success) {
     std::fprintf(stderr, "1 to %u clauses over the patterns 0 .. %d, none with a pattern both wanted and unwanted\n", ZRA_HIP_WHERE_MAX_CLAUSES, n - 1);
     return 2;
@@ -445,6 +451,9 @@ int extract_records(const char* path, bool invert, uint8_t delimiter, const char
   uint64_t total = 0, bytes = 0;
   std::string text;
   auto extract = [&](void* dOut, size_t cap) {
+    if (cut)
+      return ZraHipCutRecords(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, cut->separator, cut->mask, 0, UINT64_MAX, 0, nullptr,
+                              0, &total, dOut, cap, &bytes);
     if (where)
       return ZraHipExtractRecordsWhere(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, where->data(), where->size(), 0, UINT64_MAX,
                                        0, nullptr, 0, &total, dOut, cap, &bytes);
@@ -672,6 +681,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gme {file} {-i} {-F} {expression | hex:digits}...
 //       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
 //       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
+//       cut {file} {-v} {-d hex byte = 0a} {-o file} {separator: hex byte} {list} {pattern | hex:digits}...
 //       gxw {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} -w clause {-w clause}... {expression | hex:digits}...
 //       glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...
 //       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
@@ -697,6 +707,7 @@ int main(int argc, char** argv) {
                 "gl {file} {-v} {-d hex byte = 0a} {pattern | hex:digits}... - Grep an archive on the device: offset and size of every record (line) that holds a match, -v: that holds none (exit status 0 some, 1 none, 2 trouble)\n"
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
+                "cut {file} {options of gx} {separator: hex byte} {list} {pattern | hex:digits}... - gx with cut's field selection: of every selected record only the fields of the list (1,3,5-7,9-), cut at the separator; no pattern: every record; output and exit status as gx\n"
                 "gxw {file} {options of gxe} {-w clause}... {expression | hex:digits}... - gxe with glw's record predicate: the selected records' bytes, the text grep A | grep B | grep -v C prints; output and exit status as gx\n"
                 "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
                 "glc {file} {options of gle} {-A records} {-B records} {-C records} {expression | hex:digits}... - gle with context: up to 64 records behind (-A), in front of (-B) or around (-C) every selected record; a selected record is marked *, `--` separates groups (exit status as gl)\n"
@@ -732,8 +743,8 @@ int main(int argc, char** argv) {
     if (i >= argc) { std::fprintf(stderr, "gme {file} {-i} {-F} {expression | hex:digits}...\n"); return 2; }
     return search_archive_multi(argv[2], argv + i, argc - i, &ex);
   }
-  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw" || mode == "gxw") {
-    const bool text = mode[1] == 'x', expr = mode.size() == 3, pred = mode == "glw" || mode == "gxw";
+  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw" || mode == "gxw" || mode == "cut") {
+    const bool fields = mode == "cut", text = mode[1] == 'x' || fields, expr = mode.size() == 3 && !fields, pred = mode == "glw" || mode == "gxw";
     std::vector<ZraHipRecordClause> where;
     ExprOpt ex = {false, false};
     bool invert = false;
@@ -758,6 +769,17 @@ int main(int argc, char** argv) {
         if (++i < argc) delimiter = std::strtoul(argv[i], &end, 16);
         if (i >= argc || !*argv[i] || *end || delimiter > 0xFF) { std::fprintf(stderr, "-d takes a byte as hex digits\n"); return 2; }
       } else break;
+    }
+    if (fields) {
+      CutOpt cut = {0, 0};
+      char* end = nullptr;
+      const unsigned long sep = i < argc ? std::strtoul(argv[i], &end, 16) : 0;
+      if (i + 1 >= argc || !*argv[i] || *end || sep > 0xFF || sep == delimiter || ZraHipFieldMask(argv[i + 1], &cut.mask).zra != Success) {
+        std::fprintf(stderr, "cut {file} {-v} {-d hex byte = 0a} {-o file} {separator: a byte as hex digits, not the delimiter} {list: 1,3,5-7,9-} {pattern | hex:digits}...\n");
+        return 2;
+      }
+      cut.separator = (uint8_t)sep;
+      return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i + 2, argc - i - 2, nullptr, nullptr, nullptr, &cut);
     }
     if (i >= argc || (pred && where.empty())) {
       std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s%s%s{%s | hex:digits}...\n", mode.c_str(), expr ? "{-i} {-F} " : "", text ? "{-o file} " : "",
