@@ -874,6 +874,97 @@ ZRA_EXPORT ZraStatus ZraHipArchiveCutRecords(ZraHipArchive* archive,
     ZraHipContentRange* hRecords, size_t recordCapacity, uint64_t* nRecords,
     void* dData, size_t dataCapacity, uint64_t* dataSize);
 
+/* ---- tally records: the distinct records of a packed text and their counts ----
+ * `grep A | cut -d' ' -f9 | sort | uniq -c`. The calls above return records; the question a log archive is asked next is an aggregate:
+ * how many lines per status code, per host, per user. The packed text of an extract or a cut lies in device memory when the call
+ * returns; these calls group it there and hand back a few entries where the caller would copy the text to the host and count. */
+/** the longest record that is a key; a longer one is skipped and counted in *nSkipped. It bounds every lane's loops over a record */
+#define ZRA_HIP_TALLY_MAX_KEY 4096
+/** ZraHipDebugTallyHashBits: keep no bit of the hash, every key starts probing at slot 0 */
+#define ZRA_HIP_TALLY_HASH_NONE 0xFFFFFFFFu
+/** one distinct key: where its first occurrence lies in the tallied text (without its delimiter), and how often it occurs */
+typedef struct ZraHipTallyEntry {
+  uint64_t offset;
+  uint64_t size;
+  uint64_t count;
+} ZraHipTallyEntry;
+/** The distinct records of textSize bytes at dText (device memory) and the count of each.
+ *  Records: dText is cut at `delimiter`; bytes behind the last delimiter form one more record iff there are any; empty records count,
+ *  with the empty key: the format ZraHipExtractRecords* and ZraHipCutRecords write.
+ *  Keys: two records are the same key iff their bytes are equal; the comparison is of the bytes, never of a hash. A record longer than
+ *  ZRA_HIP_TALLY_MAX_KEY is skipped: counted in *nSkipped, in no entry and in no count. *nRecords counts every record, skipped ones
+ *  included.
+ *  Result: *nDistinct = the distinct keys; hEntries[k], k < *nDistinct, is the k-th key in order of first appearance: offset and size
+ *  of its first occurrence in dText without the delimiter, and the number of its occurrences; the counts sum to *nRecords - *nSkipped.
+ *  dKeys (device memory) receives the keys in entry order, each followed by one `delimiter` byte, the text `awk '!seen[$0]++'` prints;
+ *  *keySize = its size. hEntries and dKeys may each be NULL with capacity 0. The result is a function of the input alone, byte for
+ *  byte, run after run. The bytes of dKeys in [*keySize, keyCapacity) are undefined after Success; no byte outside [dKeys, dKeys +
+ *  keyCapacity) is ever written, and dText is only read.
+ *  Statuses, checked in this order:
+ *   1. engine or one of the four result words NULL; dText NULL with textSize != 0; hEntries NULL with entryCapacity != 0; dKeys NULL
+ *      with keyCapacity != 0; [dKeys, dKeys + keyCapacity) overlaps the text; textSize >= 2^40 - 1 -> {ZStdError, 42}. Nothing is
+ *      launched.
+ *   2. textSize == 0 -> Success with four zeros.
+ *   3. scratch that cannot be allocated -> {ZStdError, 64}. The call takes 16 bytes per 4 KiB tile, a quarter of the text's size for two
+ *      bitmaps of its positions, and 24 bytes per table slot: the power of two at or above 1.5 * min(maxDistinct, *nRecords) + 64.
+ *   4. more than maxDistinct distinct keys -> OutputBufferTooSmall; *nRecords and *nSkipped are set, *nDistinct = *nRecords -
+ *      *nSkipped, a bound that is certain to suffice, *keySize = 0, and nothing is written to the buffers. maxDistinct == 0 makes no
+ *      promise: the table is sized by the record count and this status cannot occur.
+ *   5. *nDistinct > entryCapacity with entryCapacity != 0, or *keySize > keyCapacity with keyCapacity != 0 -> OutputBufferTooSmall
+ *      with the four exact words; hEntries and dKeys are not written. Both capacities 0 make the sizing call, which is Success.
+ *  On every status but Success and rules 4 and 5 the four words are zeroed.
+ *  The call writes ZraHipGetTallyStats and ZraHipDebugTallyMs and no other call's stats.
+ *  Cost: seven launches and two synchronisations (the record count sizes the table; the totals decide rules 4 and 5); DESIGN.md §34
+ *  and profiles/tally_scan.md say what was measured.
+ *  Not covered: the bytewise-sorted order and the top-k by count (the host derives both from the entries); regex and predicate
+ *  selection in the composite; sums and extrema of numeric fields; a tally that streams pass by pass without a workspace; shards; the
+ *  host-pointer API. */
+ZRA_EXPORT ZraStatus ZraHipTallyRecords(ZraHipEngine* engine, const void* dText, size_t textSize, uint8_t delimiter,
+    uint64_t maxDistinct,
+    ZraHipTallyEntry* hEntries, size_t entryCapacity,
+    void* dKeys, size_t keyCapacity,
+    uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize);
+/** ZraHipCutRecords into a workspace, then ZraHipTallyRecords of it, on the engine's stream: `grep -F A | cut -d SEP -f LIST | sort |
+ *  uniq -c` (in first-appearance order). The selection and field arguments are ZraHipCutRecords', word for word; a fieldMask of all
+ *  ones tallies whole selected records. dWork (device memory, workCapacity bytes) receives the cut's packed text, *workSize its size,
+ *  and the entries' offsets point into it. The tally's arguments and results are ZraHipTallyRecords'.
+ *  Statuses: engine, workSize or a tally result word NULL, the tally's other rule-1 refusals (with dWork's capacity as the text), and
+ *  dKeys overlapping the archive -> {ZStdError, 42}; then the cut's, in its order, with the five words zeroed as the cut zeroes its
+ *  own; its rule 7 reads "*workSize says what dWork needs" (workCapacity 0 is that sizing call), the tally's words are then zero. After
+ *  a successful cut the tally's rules 2 to 5 follow.
+ *  The cut writes ZraHipGetExtractStats as it does on its own; the tally writes ZraHipGetTallyStats, zeroed when the cut fails. */
+ZRA_EXPORT ZraStatus ZraHipTallyFields(ZraHipEngine* engine, const void* dArchive, size_t archiveSize,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint8_t separator, uint64_t fieldMask,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    void* dWork, size_t workCapacity, uint64_t* workSize,
+    uint64_t maxDistinct,
+    ZraHipTallyEntry* hEntries, size_t entryCapacity,
+    void* dKeys, size_t keyCapacity,
+    uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize);
+/** ZraHipTallyFields through a ZraHipArchive handle: the cut is ZraHipArchiveCutRecords (resident frames staged from the cache, the
+ *  cache not changed, the handle's scan counters moved); dWork and dKeys must overlap neither the archive nor the handle's arena. */
+ZRA_EXPORT ZraStatus ZraHipArchiveTallyFields(ZraHipArchive* archive,
+    const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax,
+    uint8_t delimiter, uint32_t mode, uint8_t separator, uint64_t fieldMask,
+    uint64_t offset, uint64_t size, size_t stagingBytes,
+    void* dWork, size_t workCapacity, uint64_t* workSize,
+    uint64_t maxDistinct,
+    ZraHipTallyEntry* hEntries, size_t entryCapacity,
+    void* dKeys, size_t keyCapacity,
+    uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize);
+/** the last tally of this engine: {records, distinct keys, skipped records, key bytes, table slots, longest probe (the most slots one insert
+ *  looked at, its own included), inserts into the table in device memory (the rest were combined in LDS), 0}; all zero unless it
+ *  succeeded. Words 5 and 6 depend on the order in which lanes arrive, nothing else does. */
+ZRA_EXPORT void ZraHipGetTallyStats(ZraHipEngine* engine, uint64_t* out8);
+/** bring-up: HIP-event milliseconds of the last tally's own launches */
+ZRA_EXPORT double ZraHipDebugTallyMs(ZraHipEngine* engine);
+/** bring-up, for tests: the next tallies of this engine keep only the low `bits` (1 .. 63) of the key hash; 0 restores the full hash;
+ *  ZRA_HIP_TALLY_HASH_NONE keeps no bit. With 0 to 2 bits kept every key starts probing at one of at most four slots, so that claim
+ *  races, byte-compare mismatches, long probe chains and the wrap at the table's end happen at a few hundred keys. Results do not
+ *  change, only the time. Any other value is ignored. */
+ZRA_EXPORT void ZraHipDebugTallyHashBits(ZraHipEngine* engine, uint32_t bits);
+
 /* ---- grep with context records: the records in front of and behind each selected one ----
  * `grep -A`, `-B`, `-C`. A log search wants the lines around a hit; with the calls above a caller decodes the neighbourhood of every
  * hit a second time and cuts it at delimiters on the host. The grep pass sees every delimiter and every selection in order: this call

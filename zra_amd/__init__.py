@@ -221,6 +221,16 @@ def load():
                                  u64p, sz, u64p, vp, sz, u64p]),
         "ZraHipArchiveCutRecords": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz,
                                         u64p, sz, u64p, vp, sz, u64p]),
+        # tally records: the primitive over packed text in device memory; the composites take the cut's arguments up to stagingBytes, then the workspace, then
+        # the primitive's from maxDistinct on
+        "ZraHipTallyRecords": (S, [vp, vp, sz, ctypes.c_uint8, ctypes.c_uint64, u64p, sz, vp, sz, u64p, u64p, u64p, u64p]),
+        "ZraHipTallyFields": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz,
+                                  vp, sz, u64p, ctypes.c_uint64, u64p, sz, vp, sz, u64p, u64p, u64p, u64p]),
+        "ZraHipArchiveTallyFields": (S, [vp, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, sz,
+                                         vp, sz, u64p, ctypes.c_uint64, u64p, sz, vp, sz, u64p, u64p, u64p, u64p]),
+        "ZraHipGetTallyStats": (None, [vp, u64p]),
+        "ZraHipDebugTallyMs": (ctypes.c_double, [vp]),
+        "ZraHipDebugTallyHashBits": (None, [vp, u32]),
         # the grep with context records: before and after behind `mode`, |S| and the groups behind nRecords
         "ZraHipGrepArchiveContext": (S, [vp, vp, sz, vp, ctypes.POINTER(u32), sz, u32, ctypes.c_uint8, u32, u32, u32, ctypes.c_uint64, ctypes.c_uint64, sz, u64p, sz, u64p,
                                          u64p, u64p]),
@@ -324,6 +334,7 @@ HIP_ABI_SYMBOLS = ["ZraHipDeviceCount", "ZraHipCreateEngine", "ZraHipDestroyEngi
                    "ZraHipArchiveSearchMultiExpr", "ZraHipArchiveGrepExpr", "ZraHipArchiveExtractRecordsExpr",
                    "ZraHipCheckRecordClauses", "ZraHipGrepArchiveWhere", "ZraHipArchiveGrepWhere", "ZraHipExtractRecordsWhere", "ZraHipArchiveExtractRecordsWhere",
                    "ZraHipFieldMask", "ZraHipCutRecords", "ZraHipArchiveCutRecords",
+                   "ZraHipTallyRecords", "ZraHipTallyFields", "ZraHipArchiveTallyFields", "ZraHipGetTallyStats", "ZraHipDebugTallyMs", "ZraHipDebugTallyHashBits",
                    "ZraHipGrepArchiveContext", "ZraHipArchiveGrepContext",
                    "ZraHipCheckRegex", "ZraHipGrepArchiveRegex", "ZraHipArchiveGrepRegex",
                    "ZraHipExtractRecordsRegex", "ZraHipArchiveExtractRecordsRegex",
@@ -711,6 +722,41 @@ class Engine:
         return _cut_call(self.L, self.L.ZraHipCutRecords, (self.h, d_archive or None, size), self._order, patterns, d_data, data_cap, separator, fields, delimiter,
                          invert, offset, length, staging_bytes, max_records, syntax)
 
+    def tally_text(self, d_text, size, *, delimiter=0x0A, max_distinct=0, d_keys=0, key_cap=0, max_entries=1 << 16):
+        """ZraHipTallyRecords: the distinct records of `size` bytes of packed text at d_text (device memory; what extract() and cut() write),
+        cut at `delimiter`, in order of first appearance, each with its count: `sort | uniq -c` in the order of `awk '!seen[$0]++'`.
+        Returns (n_records, n_skipped, [(offset, size, count)]): offset and size locate the key's first occurrence in the text; a record
+        longer than TALLY_MAX_KEY is skipped. d_keys / key_cap (optional): the keys as text, each with its delimiter; its size and the other
+        words of the call are in self.last_tally. max_distinct: a promise that sizes the hash table (0: none). ZraError for a refused call;
+        OutputBufferTooSmall carries n_records, n_skipped, needed_entries and needed_keys."""
+        return _tally_call(self, lambda tail: self.L.ZraHipTallyRecords(self.h, d_text or None, size, delimiter, *tail), "ZraHipTallyRecords", None, max_distinct,
+                           d_keys, key_cap, max_entries)
+
+    def tally(self, d_archive, size, patterns, d_work, work_cap, *, separator, fields, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, syntax=0,
+              max_distinct=0, d_keys=0, key_cap=0, max_entries=1 << 16):
+        """ZraHipTallyFields: cut() into the workspace d_work (device memory, work_cap bytes), then tally_text() of what it packed: the counts
+        `grep -F patterns | cut -d SEP -f LIST | sort | uniq -c` prints. Arguments as cut() and tally_text(); fields=(1 << 64) - 1 tallies
+        whole records. Returns as tally_text(), the offsets pointing into d_work; self.last_tally["work_size"] is the cut's packed size,
+        also when it says what d_work needs (ZraError.needed_work)."""
+        return _tally_call(self, None, "ZraHipTallyFields", (self.L.ZraHipTallyFields, (self.h, d_archive or None, size), patterns, separator, fields, delimiter, invert,
+                                                             offset, length, staging_bytes, syntax, d_work, work_cap), max_distinct, d_keys, key_cap, max_entries)
+
+    def tally_stats(self):
+        """Counters of the last tally_text() / tally() on this engine (all zero unless it succeeded), keyed by TALLY_STATS. longest_probe
+        and table_inserts depend on the order in which lanes arrive; nothing else does."""
+        a = (ctypes.c_uint64 * 8)()
+        self.L.ZraHipGetTallyStats(self.h, a)
+        return dict(zip(TALLY_STATS, (int(v) for v in a)))
+
+    def tally_ms(self):
+        """bring-up: HIP-event time of the last tally's own launches."""
+        return self.L.ZraHipDebugTallyMs(self.h)
+
+    def debug_tally_hash_bits(self, bits):
+        """bring-up (ZraHipDebugTallyHashBits): the next tallies keep only the low `bits` bits of the key hash; 0 keeps none (every key
+        starts probing at slot 0), None restores the full hash."""
+        self.L.ZraHipDebugTallyHashBits(self.h, 0 if bits is None else (TALLY_HASH_NONE if bits == 0 else bits))
+
     def extract_regex(self, d_archive, size, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None,
                       staging_bytes=0, max_records=0):
         """ZraHipExtractRecordsRegex: grep_regex()'s selected records with their bytes, packed at d_data as extract() packs them: the
@@ -1050,6 +1096,31 @@ def _cut_call(L, fn, head, order, patterns, d_data, data_cap, separator, fields,
     return n.value, ds.value, [(int(arr[2 * i]), int(arr[2 * i + 1])) for i in range(k)]
 
 
+def _tally_call(engine, plain, name, composite, max_distinct, d_keys, key_cap, max_entries):
+    """Engine.tally_text (plain: the call with the primitive's tail), Engine.tally and Archive.tally (composite: the cut's arguments)"""
+    arr = (ctypes.c_uint64 * (3 * max_entries))() if max_entries else None
+    w = [ctypes.c_uint64(0) for _ in range(5)]                               # records, distinct, skipped, key size; the workspace's size
+    tail = (max_distinct, arr, max_entries, d_keys or None, key_cap) + tuple(ctypes.byref(x) for x in w[:4])
+    engine._order()
+    if composite is None:
+        st = plain(tail)
+    else:
+        fn, head, patterns, separator, fields, delimiter, invert, offset, length, staging_bytes, syntax, d_work, work_cap = composite
+        patterns = [bytes(p) for p in patterns]
+        sizes = (ctypes.c_uint32 * max(len(patterns), 1))(*(len(p) for p in patterns))
+        mask = fields if isinstance(fields, int) else field_mask(fields)
+        sep = separator if isinstance(separator, int) else bytes(separator)[0]
+        st = fn(*head, _cbuf(b"".join(patterns)) if patterns else None, sizes if patterns else None, len(patterns), syntax, delimiter, GREP_INVERT if invert else 0, sep,
+                mask, offset, (1 << 64) - 1 if length is None else length, staging_bytes, d_work or None, work_cap, ctypes.byref(w[4]), *tail)
+    engine.last_tally = {"records": w[0].value, "distinct": w[1].value, "skipped": w[2].value, "key_size": w[3].value, "work_size": w[4].value}
+    if st.zra != 0:
+        e = ZraError(st.tup(), name)
+        e.n_records, e.needed_entries, e.n_skipped, e.needed_keys, e.needed_work = (x.value for x in w)
+        raise e
+    k = w[1].value if max_entries else 0
+    return w[0].value, w[2].value, [(int(arr[3 * i]), int(arr[3 * i + 1]), int(arr[3 * i + 2])) for i in range(k)]
+
+
 def _grep_call(L, name, syntax, where):
     """the entry point of a grep, what goes behind nPatterns and what goes behind mode: _scan_call's without `where`, else the
     ...Where call, which takes the syntax word always and the clauses"""
@@ -1081,6 +1152,9 @@ def check_regex(patterns, fold_case=False, delimiter=0x0A):
         e.info = d
         raise e
     return d
+TALLY_MAX_KEY = 4096                         # ZRA_HIP_TALLY_MAX_KEY
+TALLY_HASH_NONE = 0xFFFFFFFF                 # ZRA_HIP_TALLY_HASH_NONE
+TALLY_STATS = ("records", "distinct", "skipped", "key_bytes", "table_slots", "longest_probe", "table_inserts")
 EXTRACT_STATS = ("frames", "decoded", "content_bytes", "records", "selected", "packed_bytes", "passes", "matches")
 
 COMPARE_DECODE_ALL = 1                       # ZRA_HIP_COMPARE_DECODE_ALL
@@ -1264,6 +1338,14 @@ class Archive:
         extract() does."""
         return _cut_call(self.L, self.L.ZraHipArchiveCutRecords, (self.h,), self.engine._order, patterns, d_data, data_cap, separator, fields, delimiter, invert,
                          offset, length, staging_bytes, max_records, syntax)
+
+    def tally(self, patterns, d_work, work_cap, *, separator, fields, delimiter=0x0A, invert=False, offset=0, length=None, staging_bytes=0, syntax=0, max_distinct=0,
+              d_keys=0, key_cap=0, max_entries=1 << 16):
+        """ZraHipArchiveTallyFields: Engine.tally through the handle; d_work and d_keys must overlap neither the archive nor the cache. Returns
+        and raises as Engine.tally; the words of the call are in self.engine.last_tally."""
+        return _tally_call(self.engine, None, "ZraHipArchiveTallyFields", (self.L.ZraHipArchiveTallyFields, (self.h,), patterns, separator, fields, delimiter, invert,
+                                                                           offset, length, staging_bytes, syntax, d_work, work_cap), max_distinct, d_keys, key_cap,
+                           max_entries)
 
     def extract_regex(self, patterns, d_data, data_cap, *, delimiter=0x0A, invert=False, fold_case=False, offset=0, length=None, staging_bytes=0, max_records=0):
         """ZraHipArchiveExtractRecordsRegex: Engine.extract_regex through the handle; d_data must overlap neither the archive nor the cache. Returns

@@ -43,6 +43,9 @@ class ArchiveCache {
   double scan_stage_ms() const { return scanStageMs_; }
   // bring-up: where the arena lies, [*base, *base + *bytes); nullptr and 0 for a handle without a cache
   void arena_range(const void** base, size_t* bytes) const { *base = arena_; *bytes = arena_ ? (size_t)slots_ * h_.frameSize : 0; }
+  // the composite calls (ZraHipArchiveTallyFields): the engine the handle runs on, and where the archive it serves lies
+  Engine* engine() const { return e_; }
+  void archive_range(const void** base, size_t* bytes) const { *base = dArc_; *bytes = arcSize_; }
   // The record calls of the engine (zra_records.hip) on the archive the handle is bound to (zra_hip.h: ZraHipArchiveIndexRecords,
   // ZraHipArchiveLocateRecords, ZraHipArchiveReadRecords): a whole-frame sweep copies the resident frames it needs out of the arena and
   // decodes the others. Index and locate are not reads: they change nothing of the cache and none of stats()' words, on any status. The

@@ -13,6 +13,7 @@
 #include "zra_where.h"
 #include "zra_regex.h"
 
+#include <functional>
 #include <atomic>
 #include <algorithm>
 #include <cstdlib>
@@ -1093,6 +1094,74 @@ ZraStatus ZraHipArchiveCutRecords(ZraHipArchive* archive, const void* hPatterns,
                            (uint64_t*)hRecords, recordCapacity, nRecords, (uint8_t*)dData, dataCapacity, dataSize};
   c.separator = separator; c.fieldMask = fieldMask;
   return mk(archive->c->record_scan(c));
+}
+// ---- tally records: the primitive is zra_tally.hip's; the composites are the cut above into the caller's workspace and the primitive on what it packed,
+// each with its own stats row
+ZraStatus ZraHipTallyRecords(ZraHipEngine* engine, const void* dText, size_t textSize, uint8_t delimiter, uint64_t maxDistinct, ZraHipTallyEntry* hEntries,
+                             size_t entryCapacity, void* dKeys, size_t keyCapacity, uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize) {
+  static_assert(sizeof(ZraHipTallyEntry) == 24 && ZRA_HIP_TALLY_MAX_KEY == zra_eng::kTallyMaxKey, "three 64-bit words per entry; the cap the kernels are built with");
+  for (uint64_t* w : {nRecords, nDistinct, nSkipped, keySize}) if (w) *w = 0;
+  if (!engine) return mk(ZStdError, 42);
+  return mk(engine->e->tally_records((const uint8_t*)dText, textSize, delimiter, maxDistinct, (uint64_t*)hEntries, entryCapacity, (uint8_t*)dKeys, keyCapacity, nRecords,
+                                     nDistinct, nSkipped, keySize));
+}
+namespace {
+struct TallyOut {
+  uint64_t maxDistinct; ZraHipTallyEntry* hEntries; size_t entryCapacity; void* dKeys; size_t keyCapacity; uint64_t* nRecords, * nDistinct, * nSkipped, * keySize;
+};
+// the composite behind both entry points: rule 1 of the tally, the cut `cut` makes of c, the tally of what it packed. arc / arena: what dKeys may not overlap
+ZraStatus tally_fields(Engine* e, zra_eng::RecordCall c, const TallyOut& t, const void* arc, size_t arcBytes, const void* arena, size_t arenaBytes,
+                       const std::function<zra_eng::Status(const zra_eng::RecordCall&)>& cut) {
+  if (!c.dataSize || !t.nRecords || !t.nDistinct || !t.nSkipped || !t.keySize || (!t.hEntries && t.entryCapacity) || (!t.dKeys && t.keyCapacity)) return mk(ZStdError, 42);
+  auto overlaps = [&](const void* p, size_t n) { return t.keyCapacity && n && (uintptr_t)t.dKeys < (uintptr_t)p + n && (uintptr_t)p < (uintptr_t)t.dKeys + t.keyCapacity; };
+  if (overlaps(c.dData, c.dataCap) || overlaps(arc, arcBytes) || overlaps(arena, arenaBytes)) return mk(ZStdError, 42);
+  uint64_t selected = 0;
+  c.nRecords = &selected;
+  const zra_eng::Status st = cut(c);
+  if (st.zra) { e->tally_clear(); return mk(st); }
+  return mk(e->tally_records(c.dData, (size_t)*c.dataSize, c.delimiter, t.maxDistinct, (uint64_t*)t.hEntries, t.entryCapacity, (uint8_t*)t.dKeys, t.keyCapacity, t.nRecords,
+                             t.nDistinct, t.nSkipped, t.keySize));
+}
+}  // namespace
+ZraStatus ZraHipTallyFields(ZraHipEngine* engine, const void* dArchive, size_t archiveSize, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns,
+                            uint32_t syntax, uint8_t delimiter, uint32_t mode, uint8_t separator, uint64_t fieldMask, uint64_t offset, uint64_t size, size_t stagingBytes,
+                            void* dWork, size_t workCapacity, uint64_t* workSize, uint64_t maxDistinct, ZraHipTallyEntry* hEntries, size_t entryCapacity, void* dKeys,
+                            size_t keyCapacity, uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize) {
+  for (uint64_t* w : {workSize, nRecords, nDistinct, nSkipped, keySize}) if (w) *w = 0;
+  if (!engine) return mk(ZStdError, 42);
+  if (nPatterns == 0) { hPatterns = &kNoPattern; hPatternSizes = &kNoPattern; }
+  zra_eng::RecordCall c = {zra_eng::kRecCut, (const uint8_t*)dArchive, archiveSize, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset,
+                           size, stagingBytes, nullptr, 0, nullptr, (uint8_t*)dWork, workCapacity, workSize};
+  c.separator = separator; c.fieldMask = fieldMask;
+  Engine* const e = engine->e;
+  return tally_fields(e, c, {maxDistinct, hEntries, entryCapacity, dKeys, keyCapacity, nRecords, nDistinct, nSkipped, keySize}, dArchive, archiveSize, nullptr, 0,
+                      [&](const zra_eng::RecordCall& rc) { return e->record_scan(rc); });
+}
+ZraStatus ZraHipArchiveTallyFields(ZraHipArchive* archive, const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, uint8_t delimiter,
+                                   uint32_t mode, uint8_t separator, uint64_t fieldMask, uint64_t offset, uint64_t size, size_t stagingBytes, void* dWork,
+                                   size_t workCapacity, uint64_t* workSize, uint64_t maxDistinct, ZraHipTallyEntry* hEntries, size_t entryCapacity, void* dKeys,
+                                   size_t keyCapacity, uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize) {
+  for (uint64_t* w : {workSize, nRecords, nDistinct, nSkipped, keySize}) if (w) *w = 0;
+  if (!archive) return mk(ZStdError, 42);
+  if (nPatterns == 0) { hPatterns = &kNoPattern; hPatternSizes = &kNoPattern; }
+  zra_eng::RecordCall c = {zra_eng::kRecCut, nullptr, 0, (const uint8_t*)hPatterns, hPatternSizes, nPatterns, syntax, delimiter, mode, offset, size, stagingBytes,
+                           nullptr, 0, nullptr, (uint8_t*)dWork, workCapacity, workSize};
+  c.separator = separator; c.fieldMask = fieldMask;
+  const void* arc, * arena; size_t arcBytes, arenaBytes;
+  archive->c->archive_range(&arc, &arcBytes); archive->c->arena_range(&arena, &arenaBytes);
+  return tally_fields(archive->c->engine(), c, {maxDistinct, hEntries, entryCapacity, dKeys, keyCapacity, nRecords, nDistinct, nSkipped, keySize}, arc, arcBytes, arena,
+                      arenaBytes, [&](const zra_eng::RecordCall& rc) { return archive->c->record_scan(rc); });
+}
+void ZraHipGetTallyStats(ZraHipEngine* engine, uint64_t* out8) {
+  if (!out8) return;
+  if (engine) engine->e->tally_stats(out8); else for (int i = 0; i < 8; i++) out8[i] = 0;
+}
+double ZraHipDebugTallyMs(ZraHipEngine* engine) { return engine ? engine->e->tally_ms() : 0.0; }
+void ZraHipDebugTallyHashBits(ZraHipEngine* engine, uint32_t bits) {
+  if (!engine) return;
+  if (bits == 0) engine->e->set_tally_keep(~0ull);
+  else if (bits == ZRA_HIP_TALLY_HASH_NONE) engine->e->set_tally_keep(0);
+  else if (bits < 64) engine->e->set_tally_keep((1ull << bits) - 1);
 }
 // ---- the grep with regular expressions: the compiler is zra_regex.h's, the kernels zra_grep_regex.hip's; the grep's stats row and milliseconds
 ZraStatus ZraHipCheckRegex(const void* hPatterns, const uint32_t* hPatternSizes, size_t nPatterns, uint32_t syntax, int delimiter, ZraHipRegexInfo* info) {

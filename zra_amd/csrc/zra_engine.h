@@ -52,7 +52,9 @@ struct ArchiveView {
 // The index of a device-archive call's counters and milliseconds (Engine::callStats_, callMs_): the range scans (search, multi-pattern
 // search, grep, extract; one host driver, zra_scan.h) first, then the calls on whole frames (zra_framepass.h, zra_verify.hip)
 enum : int { kScanSearch = 0, kScanMulti, kScanGrep, kScanExtract, kScanCalls,
-             kCallCompare = kScanCalls, kCallDiff, kCallSign, kCallSigDiff, kCallIndex, kCallLocate, kCallRead, kCallVerify, kCalls };
+             kCallCompare = kScanCalls, kCallDiff, kCallSign, kCallSigDiff, kCallIndex, kCallLocate, kCallRead, kCallVerify, kCallTally, kCalls };
+// the tally (zra_tally.hip): the positions of one workgroup, and ZRA_HIP_TALLY_MAX_KEY, the longest record that is a key
+constexpr uint32_t kTallyTile = 4096, kTallyMaxKey = 4096;
 // the code a failing frame is reported with: 255 (the decoder's own "regenerated another size than its slot") is corruption_detected
 __host__ __device__ inline int reported_code(unsigned long long firstError) { const int c = (int)(firstError & 0xFF); return c == 255 ? 20 : c; }
 // An update through an archive handle (zra_archive.hip, ZraHipArchiveUpdate): what the handle lends to Engine::update_archive and what
@@ -371,6 +373,20 @@ class Engine {
   // bring-up: HIP-event time of the last read's locate-sweep launches, summed over its passes (its read sweep: kernel_stats)
   double read_records_ms() const { return callMs_[kCallRead]; }
 
+  // ---- tally (zra_tally.hip): the distinct records of textSize bytes of packed text at dText (device memory), cut at `delimiter`, in
+  // order of first appearance, as {offset, size, count} triples in hEntries and as text at dKeys (device memory), each key followed by
+  // one delimiter byte. A record longer than kTallyMaxKey is skipped. Statuses and their order: zra_hip.h, ZraHipTallyRecords.
+  Status tally_records(const uint8_t* dText, size_t textSize, uint32_t delimiter, uint64_t maxDistinct, uint64_t* hEntries, size_t entryCap, uint8_t* dKeys, size_t keyCap,
+                       uint64_t* nRecords, uint64_t* nDistinct, uint64_t* nSkipped, uint64_t* keySize);
+  // the last tally_records: {records, distinct keys, skipped records, key bytes, table slots, longest probe, inserts into the table in
+  // HBM, 0}; all zero unless it succeeded. Words 5 and 6 depend on the order in which lanes arrive; nothing else does
+  void tally_stats(uint64_t out[8]) const { call_stats(kCallTally, out); }
+  // bring-up: HIP-event time of the last tally's own launches (count, insert, mark, sum, scan, emit, copy)
+  double tally_ms() const { return callMs_[kCallTally]; }
+  void tally_clear();                        // the row as a failed tally leaves it (the composite, when its cut fails)
+  // bring-up (ZraHipDebugTallyHashBits): the bits of the key hash the next tallies keep; ~0: all
+  void set_tally_keep(uint64_t mask) { tallyKeep_ = mask; }
+
   // ---- host-pointer helpers (H2D -> kernels -> D2H) behind the reference-compatible C/C++ API (zra_hostpipe.hip; compress_frames_host: zra_encode.hip)
   Status compress_host(const uint8_t* hIn, size_t n, uint8_t* hOut, size_t* outSize, int level, uint32_t frameSize, bool checksum);
   Status compress_frames_host(const uint8_t* hIn, size_t n, uint8_t* hBody, std::vector<uint64_t>& sizes, size_t* bodySize,
@@ -484,12 +500,16 @@ class Engine {
   // record index (zra_records.hip): the header words + frame counts, prefix, slots and tile prefixes of a call; the record numbers,
   // boundaries and positions of a locate
   struct RecScratch { DevBuf tables, ranges; } rec_;
+  // tally (zra_tally.hip): the call's words; the tiles' table, the two bitmaps of the text's positions and the hash table; the entries
+  struct TallyScratch { DevBuf hdr, tables, entries; } tally_;
+  uint64_t tallyKeep_ = ~0ull;
   friend struct EncodeImpl;
   friend struct UpdateImpl;        // the update drives the walk's pinned tuples, the decoder's job arrays and the encoder (zra_update.hip)
   friend struct VerifyImpl;        // the verifier drives the decoder's job arrays and reads its per-job status words (zra_verify.hip)
   friend struct ScanImpl;          // the range scans drive the decoder's job arrays as the verifier does (zra_scan.h, zra_record_scan.h and the seven calls' files)
   friend struct FramePasses;       // the one pass driver of compare, diff, sign, signature diff and index: scratch, job arrays, call events (zra_framepass.h)
   friend struct RecordsImpl;       // the locate sweep drives the decoder's job arrays of the needed frames on its own (zra_records.hip)
+  friend struct TallyImpl;         // the tally uses the call events (zra_tally.hip)
   friend class ArchiveCache;       // the archive handle drives the random-access scratch and the decoder of its engine (zra_archive.hip)
 };
 

@@ -158,7 +158,7 @@ void Engine::free_scratch() {
     b->release();
   for (auto& x : encCtx_) for (DevBuf* b : {&x.tables, &x.seqs, &x.lits, &x.work, &x.slots, &x.misc, &x.ck, &x.sizes, &x.rec}) b->release();
   for (DevBuf* b : {&upd_.plan, &upd_.packed, &upd_.encSizes, &upd_.frames, &upd_.table, &upd_.copies}) b->release();
-  for (DevBuf* b : {&vfy_.plan, &vfy_.faults, &scan_.tables, &scan_.list, &fp_.flags, &fp_.dirty, &fp_.tables, &fp_.list, &rec_.tables, &rec_.ranges}) b->release();
+  for (DevBuf* b : {&vfy_.plan, &vfy_.faults, &scan_.tables, &scan_.list, &fp_.flags, &fp_.dirty, &fp_.tables, &fp_.list, &rec_.tables, &rec_.ranges, &tally_.hdr, &tally_.tables, &tally_.entries}) b->release();
 }
 
 Status Engine::release_scratch() {

@@ -30,6 +30,8 @@
 //   cut : gx with cut's field selection (ZraHipCutRecords): of every selected record only the fields of LIST (cut's: 1,3,5-7,9-), cut
 //         at the separator byte; both stand in front of the patterns, and no pattern at all selects every record. -o, -v, -d as gx.
 //         Output and exit status of gx; a refused separator or list is exit status 2
+//   tally : cut, counted (ZraHipTallyFields): one line per distinct value of the cut's output in order of first appearance, `count key`:
+//         the counts `cut ... | sort | uniq -c` prints. Separator, list and patterns as cut; -v, -d as gx. Exit status of gx
 //   glr : gl with regular expressions (ZraHipGrepArchiveRegex): POSIX extended expressions over bytes, * + ? {n,m} ( ) | ^ $ on top of
 //         gle's atoms (zra_hip.h: ZraHipCheckRegex); several expressions are alternatives; -i: ASCII letters match either case, -v, -d as
 //         gl; -c: only the count. Output and exit status of gl; a refused expression is exit status 2 with the reason and its index
@@ -490,6 +492,60 @@ int extract_records(const char* path, bool invert, uint8_t delimiter, const char
   return 0;
 }
 
+// mode tally: the cut's selection into a workspace of exactly the size a first call names (ZraHipTallyFields), then the sizes of the tally
+// and the tally itself on that workspace (ZraHipTallyRecords); one line per distinct key in order of first appearance: the count, a
+// space, the key, the delimiter. Nothing goes to stdout when a call fails.
+int tally_fields(const char* path, bool invert, uint8_t delimiter, const CutOpt& cut, char** texts, int n) {
+  std::string all;
+  std::vector<uint32_t> sizes;
+  uint32_t syntax = 0;
+  if (n && !gather_patterns(texts, n, delimiter, nullptr, &all, &sizes, &syntax)) return 2;
+  zra::Buffer arc = read_file(path);
+  ZraHipEngine* eng = nullptr;
+  ZraStatus st = ZraHipCreateEngine(&eng, 0);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: no engine: %s\n", path, ZraGetErrorString(st)); return 2; }
+  void* dArc = nullptr; void* dWork = nullptr; void* dKeys = nullptr;
+  if (!to_device(path, arc, &dArc)) { ZraHipDestroyEngine(eng); return 2; }
+  const uint32_t mode = invert ? ZRA_HIP_GREP_INVERT : 0u;
+  uint64_t work = 0, records = 0, distinct = 0, skipped = 0, keyBytes = 0;
+  std::vector<ZraHipTallyEntry> entries;
+  std::string keys;
+  auto fields = [&](void* w, size_t cap) {
+    return ZraHipTallyFields(eng, dArc, arc.size(), all.data(), sizes.data(), sizes.size(), syntax, delimiter, mode, cut.separator, cut.mask, 0, UINT64_MAX, 0, w, cap, &work,
+                             0, nullptr, 0, nullptr, 0, &records, &distinct, &skipped, &keyBytes);
+  };
+  st = fields(nullptr, 0);
+  if (st.zra == OutputBufferTooSmall && work) {
+    const uint64_t need = work;
+    if (hipMalloc(&dWork, need) != hipSuccess) { dWork = nullptr; st.zra = ZStdError; st.zstd = 64; }
+    else st = fields(dWork, need);                                            // (both capacities 0: the tally's sizes)
+    if (st.zra == Success && distinct) {
+      entries.resize(distinct); keys.resize(keyBytes);
+      if (hipMalloc(&dKeys, keyBytes) != hipSuccess) { dKeys = nullptr; st.zra = ZStdError; st.zstd = 64; }
+      else {
+        st = ZraHipTallyRecords(eng, dWork, work, delimiter, 0, entries.data(), entries.size(), dKeys, keyBytes, &records, &distinct, &skipped, &keyBytes);
+        if (st.zra == Success && hipMemcpy(&keys[0], dKeys, keyBytes, hipMemcpyDeviceToHost) != hipSuccess) { st.zra = ZStdError; st.zstd = 1; }
+      }
+    }
+  }
+  if (dArc) (void)hipFree(dArc);
+  if (dWork) (void)hipFree(dWork);
+  if (dKeys) (void)hipFree(dKeys);
+  ZraHipDestroyEngine(eng);
+  if (st.zra != Success) { std::fprintf(stderr, "%s: cannot tally: %s\n", path, ZraGetErrorString(st)); return 2; }
+  if (skipped) std::fprintf(stderr, "%s: %llu records longer than %u bytes are not counted\n", path, (unsigned long long)skipped, ZRA_HIP_TALLY_MAX_KEY);
+  if (!distinct) return 1;
+  std::string out;
+  size_t at = 0;
+  for (const ZraHipTallyEntry& e : entries) {                                 // (the keys lie in entry order, each with its delimiter)
+    out += std::to_string(e.count); out += ' ';
+    out.append(keys, at, (size_t)e.size + 1);
+    at += (size_t)e.size + 1;
+  }
+  if (std::fwrite(out.data(), 1, out.size(), stdout) != out.size() || std::fflush(stdout) != 0) { std::fprintf(stderr, "cannot write to stdout\n"); return 2; }
+  return 0;
+}
+
 // mode cmp. Nothing goes to stdout when the call fails.
 int compare_archives(const char* pathA, const char* pathB) {
   zra::Buffer a = read_file(pathA), b = read_file(pathB);
@@ -682,6 +738,7 @@ int index_records(const char* path, uint8_t delimiter, bool read, uint64_t first
 //       gle {file} {-v} {-d hex byte = 0a} {-i} {-F} {expression | hex:digits}...
 //       gxe {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} {expression | hex:digits}...
 //       cut {file} {-v} {-d hex byte = 0a} {-o file} {separator: hex byte} {list} {pattern | hex:digits}...
+//       tally {file} {-v} {-d hex byte = 0a} {separator: hex byte} {list} {pattern | hex:digits}...
 //       gxw {file} {-v} {-d hex byte = 0a} {-i} {-F} {-o file} -w clause {-w clause}... {expression | hex:digits}...
 //       glc {file} {-v} {-d hex byte = 0a} {-i} {-F} {-A records} {-B records} {-C records} {expression | hex:digits}...
 //       glr {file} {-i} {-v} {-c} {-d hex byte = 0a} {expression}...
@@ -708,6 +765,7 @@ int main(int argc, char** argv) {
                 "gx {file} {-v} {-d hex byte = 0a} {-o file} {pattern | hex:digits}... - Extract from an archive on the device: the text of the records gl lists, each with its delimiter, to stdout or to a file (exit status as gl)\n"
                 "gme | gle | gxe {file} {options of gm | gl | gx} {-i} {-F} {expression | hex:digits}... - gm, gl and gx with pattern expressions of fixed length: . [set] [^set] \\escape; -i: letters match either case, -F: literal patterns (a refused expression: exit status 2)\n"
                 "cut {file} {options of gx} {separator: hex byte} {list} {pattern | hex:digits}... - gx with cut's field selection: of every selected record only the fields of the list (1,3,5-7,9-), cut at the separator; no pattern: every record; output and exit status as gx\n"
+                "tally {file} {-v} {-d hex byte = 0a} {separator: hex byte} {list} {pattern | hex:digits}... - cut, counted: one line `count key` per distinct value of cut's output, in order of first appearance (exit status as gl)\n"
                 "gxw {file} {options of gxe} {-w clause}... {expression | hex:digits}... - gxe with glw's record predicate: the selected records' bytes, the text grep A | grep B | grep -v C prints; output and exit status as gx\n"
                 "glw {file} {options of gle} {-w clause}... {expression | hex:digits}... - gle with a record predicate: a clause is comma-separated +i (pattern i occurs), ?i (one of these occurs), -i (pattern i does not), i counted from 0; a record is selected when some clause holds (a refused clause: exit status 2)\n"
                 "glc {file} {options of gle} {-A records} {-B records} {-C records} {expression | hex:digits}... - gle with context: up to 64 records behind (-A), in front of (-B) or around (-C) every selected record; a selected record is marked *, `--` separates groups (exit status as gl)\n"
@@ -743,8 +801,8 @@ int main(int argc, char** argv) {
     if (i >= argc) { std::fprintf(stderr, "gme {file} {-i} {-F} {expression | hex:digits}...\n"); return 2; }
     return search_archive_multi(argv[2], argv + i, argc - i, &ex);
   }
-  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw" || mode == "gxw" || mode == "cut") {
-    const bool fields = mode == "cut", text = mode[1] == 'x' || fields, expr = mode.size() == 3 && !fields, pred = mode == "glw" || mode == "gxw";
+  if (mode == "gl" || mode == "gx" || mode == "gle" || mode == "gxe" || mode == "glw" || mode == "gxw" || mode == "cut" || mode == "tally") {
+    const bool counted = mode == "tally", fields = mode == "cut" || counted, text = mode[1] == 'x' || fields, expr = mode.size() == 3 && !fields, pred = mode == "glw" || mode == "gxw";
     std::vector<ZraHipRecordClause> where;
     ExprOpt ex = {false, false};
     bool invert = false;
@@ -775,10 +833,12 @@ int main(int argc, char** argv) {
       char* end = nullptr;
       const unsigned long sep = i < argc ? std::strtoul(argv[i], &end, 16) : 0;
       if (i + 1 >= argc || !*argv[i] || *end || sep > 0xFF || sep == delimiter || ZraHipFieldMask(argv[i + 1], &cut.mask).zra != Success) {
-        std::fprintf(stderr, "cut {file} {-v} {-d hex byte = 0a} {-o file} {separator: a byte as hex digits, not the delimiter} {list: 1,3,5-7,9-} {pattern | hex:digits}...\n");
+        std::fprintf(stderr, "%s {file} {-v} {-d hex byte = 0a} %s{separator: a byte as hex digits, not the delimiter} {list: 1,3,5-7,9-} {pattern | hex:digits}...\n",
+                     mode.c_str(), counted ? "" : "{-o file} ");
         return 2;
       }
       cut.separator = (uint8_t)sep;
+      if (counted) return tally_fields(argv[2], invert, (uint8_t)delimiter, cut, argv + i + 2, argc - i - 2);
       return extract_records(argv[2], invert, (uint8_t)delimiter, outPath, argv + i + 2, argc - i - 2, nullptr, nullptr, nullptr, &cut);
     }
     if (i >= argc || (pred && where.empty())) {
