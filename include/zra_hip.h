@@ -43,7 +43,8 @@ ZRA_EXPORT ZraStatus ZraHipReleaseScratch(ZraHipEngine* engine);
 ZRA_EXPORT void* ZraHipGetStream(ZraHipEngine* engine);
 
 /** CompressBuffer with device-resident input/output. dOut must hold ZraGetCompressedOutputBufferSize(inSize, frameSize) bytes.
- *  Output is byte-identical to the reference at the same level (zstd 1.4.9 semantics). Synchronous. */
+ *  Output is byte-identical to the reference at the same level (zstd 1.4.9 semantics). Synchronous. *outSize is written on Success
+ *  only: on any other status ({ZStdError, 64} when scratch cannot be allocated) it is not touched. */
 ZRA_EXPORT ZraStatus ZraHipCompressBuffer(ZraHipEngine* engine, const void* dIn, size_t inSize, void* dOut, size_t* outSize,
                                           int8_t compressionLevel, uint32_t frameSize, bool checksum);
 
@@ -111,7 +112,8 @@ ZRA_EXPORT ZraStatus ZraHipArchiveRead(ZraHipArchive* archive, void* dOut, const
 /** Forgets every resident frame (the counters stay). */
 ZRA_EXPORT ZraStatus ZraHipArchiveDropCache(ZraHipArchive* archive);
 /** out8 = {cache slots, frames resident now, reads accepted, frame hits, frame misses (= frames decoded), evictions,
- *  uncompressed size, frame size}; counters 2-5 are cumulative since the handle was opened. */
+ *  uncompressed size, frame size}; counters 2-5 are cumulative since the handle was opened. A read refused with OutOfBoundsAccess is
+ *  not accepted; nor is, on a handle without slots, one refused with {ZStdError, 64}: it decoded and wrote nothing. */
 ZRA_EXPORT void ZraHipArchiveGetStats(const ZraHipArchive* archive, uint64_t* out8);
 /** ZraHipUpdateArchive (below) through the handle: the archive the handle is bound to is updated into dOut, the handle is bound to the
  *  result, and its cache stays coherent and warm. Synchronous; stream ordering as the other compute calls (ZraHipWaitStream).
@@ -330,6 +332,7 @@ ZRA_EXPORT double ZraHipDebugArchiveRecordStageMs(const ZraHipArchive* archive);
  *   7. header + body >= 2^40 -> CompressedSizeTooLarge (ZraHipCompressBuffer's rule).
  *   8. outCapacity smaller than the result -> OutputBufferTooSmall, and *outSize holds the size needed. (ZraGetCompressedOutputBufferSize(U',
  *      frameSize) + the meta size is always enough for the touched frames; carried frames keep the size they have.)
+ *  *outSize is written on Success and by rule 8 and on no other status: it is not touched then (the same through ZraHipArchiveUpdate).
  *   9. Scratch that cannot be allocated -> {ZStdError, 64}. Scratch is the engine's: plaintext staging of at most 65,536 frames or 4 GiB
  *      (more touched frames go through several decode / encode passes), the newly encoded frames, 29 bytes per frame of tables;
  *      ZraHipReleaseScratch returns it.

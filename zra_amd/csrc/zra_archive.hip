@@ -338,7 +338,8 @@ Status ArchiveCache::read(uint8_t* dOut, const uint64_t* hOff, const uint64_t* h
     // no cache: the batch call itself, header read and checked at open
     E.set_ra_verify_whole_frames(wholeFramesOpt);
     Status st = E.ra_batch_body(view(), dOut, hOff, hSize, hOutOff, nq, endInclusive, jobsOut);
-    if (st.zra == kOutOfBounds) return st;
+    // (a read refused for its bounds or for lack of scratch decoded nothing and wrote nothing: it is not counted)
+    if (st.zra == kOutOfBounds || (st.zra == kZStdError && st.zstd == 64)) return st;
     reads_++;
     const uint64_t fs = h_.frameSize;
     if (fs && nFrames_) {
@@ -366,11 +367,18 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
   if (nq == 0) { reads_++; return ok(); }
   uint64_t nSlices = 0;
   { Status st = E.ra_walk_queries(a, hOff, hSize, hOutOff, nq, &nSlices, endInclusive); if (st.zra) return st; }
+  // the batch's planner scratch (the lookup's two result words inside its totals), then seen[nFrames]: one memset; and the job arrays a
+  // miss will need, a few bytes per frame and per slice: all of it in front of the lookup, which copies the hits to dOut and is counted,
+  // so that a read refused for lack of these tables ({ZStdError, 64}) has written and counted nothing
+  const size_t planWords = RaPlan::words(nF);
+  if (nSlices && (!E.raPlan_.reserve((planWords + nF) * 4) || !E.frameOff_.reserve(((size_t)nF + 1) * 16) || !E.outOff_.reserve((size_t)nF * 8) ||
+                  !E.expect_.reserve((size_t)nF * 4) || !E.raLimit_.reserve((size_t)nF * 4) || !E.raPieceBase_.reserve(((size_t)nF + 1) * 4) ||
+                  !E.raPieces_.reserve((size_t)nSlices * sizeof(ZraRaPiece) + 64))) {
+    (void)hipStreamSynchronize(s);                    // (the tuples' copy)
+    return zerr(64);
+  }
   reads_++;
   if (nSlices == 0) { HIPCHK_CLR(hipStreamSynchronize(s)); return ok(); }
-  // the batch's planner scratch (the lookup's two result words inside its totals), then seen[nFrames]: one memset
-  const size_t planWords = RaPlan::words(nF);
-  if (!E.raPlan_.reserve((planWords + nF) * 4)) return zerr(64);
   uint32_t* plan = E.raPlan_.as<uint32_t>();
   const RaPlan P = RaPlan::over(plan, nF);
   uint32_t* const seen = plan + planWords, * const words = P.lookup_words();
@@ -385,10 +393,8 @@ Status ArchiveCache::read_cached(uint8_t* dOut, const uint64_t* hOff, const uint
   hits_ += hit; misses_ += missed;
   if (!missed) return ok();
 
-  // ---- misses: whole frames into CLOCK victims, passes of at most maxPass_ frames through the batch's planner and decoder
-  if (!E.frameOff_.reserve(((size_t)nF + 1) * 16) || !E.outOff_.reserve((size_t)nF * 8) || !E.expect_.reserve((size_t)nF * 4) ||
-      !E.raLimit_.reserve((size_t)nF * 4) || !E.raPieceBase_.reserve(((size_t)nF + 1) * 4) || !E.raPieces_.reserve((size_t)nSlices * sizeof(ZraRaPiece) + 64))
-    return zerr(64);
+  // ---- misses: whole frames into CLOCK victims, passes of at most maxPass_ frames through the batch's planner and decoder (their job
+  // arrays: reserved above)
   const uint32_t V = std::min(missed, maxPass_);
   hipLaunchKernelGGL(zra_cache_victims_kernel, dim3(1), dim3(1024), 0, s, slotOf_, frameOf_, ref_, hand_, dctr_, slots_, V, victim_, 0u);
   uint32_t totals[2];

@@ -96,6 +96,7 @@ Status Engine::compress_impl(const uint8_t* dIn, size_t inSize, uint8_t* dBody, 
                              size_t* bodySize, int level, uint32_t frameSize, bool checksum) {
   encCounters_ = nullptr; encCountersBytes_ = 0;
   mfTele_.clear(); mfTeleDev_ = nullptr;               // (a call that takes another path, or fails, leaves no telemetry of an earlier launch behind)
+  dbgB_ = 0;                                           // (nor debug_read_seqs a stride into scratch a failed reservation has emptied)
   Status s = compress_impl_body(dIn, inSize, dBody, bodyBase0, dEntries, dSizes, bodySize, level, frameSize, checksum);
   if (s.zra) drain_after_error();
   return s;

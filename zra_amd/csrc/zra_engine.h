@@ -19,7 +19,10 @@ inline Status zerr(int code) { return {kZStdError, (int)(int8_t)code}; }   // i8
 // grow-only device allocation
 struct DevBuf {
   void* p = nullptr; size_t cap = 0;
-  bool reserve(size_t n);
+  // true: cap >= n (the buffer may have MOVED, and its old contents are gone: the old one is freed before the new one is asked for,
+  // to keep the peak low). false: no memory, and on `false` the buffer is EMPTY (p == nullptr, cap == 0): every pointer taken from
+  // it before is dead, and so is host state that describes its contents. The result decides the caller's status ({ZStdError, 64}).
+  [[nodiscard]] bool reserve(size_t n);
   void release();
   template <typename T> T* as() const { return (T*)p; }
 };

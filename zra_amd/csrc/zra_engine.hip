@@ -167,6 +167,7 @@ Status Engine::release_scratch() {
   HIPCHK(hipStreamSynchronize(stream2_));
   free_scratch();
   mfTeleDev_ = nullptr;                                // (lived inside encScan_)
+  dbgB_ = 0;                                           // (debug_read_seqs: the batch it would read lived in encCtx_[0])
   decCountersClean_ = false;
   return ok();
 }
@@ -353,8 +354,10 @@ Status Engine::decode_launch(const ZraDecodeArgs& a0, const uint32_t* dExpect, u
         !decBlkLists_.reserve((size_t)(2 * nb + n) * 4 + 64) || !decLits_.reserve(litAll + 64) || !decSeqs_.reserve(seqAll * 8 + 64)) {
       (void)hipGetLastError();
       fmb = false;                                      // (no memory for it: the rounds)
-    }
-    a.lits = decLits_.as<uint8_t>(); a.seqs = decSeqs_.as<uint64_t>();       // (the buffers may have moved)
+      // a failed reserve leaves its buffer EMPTY (zra_engine.h), and the one before it may have moved: the rounds' scratch is sized again,
+      // so that a.lits / a.litCap / a.seqs / a.seqCap describe live buffers (they fitted a moment ago; if they do not now, a status)
+      { Status st = decode_scratch(a, maxFrameBytes); if (st.zra) return st; }
+    } else { a.lits = decLits_.as<uint8_t>(); a.seqs = decSeqs_.as<uint64_t>(); }       // (the buffers may have moved)
     if (fmb) {
       ZraDecodeArgs x = a;
       x.bpf = bpf; x.blkRecs = decBlkRecs_.as<ZraDecFrame>(); x.blkTables = decBlkTables_.as<uint32_t>();
